@@ -8,15 +8,22 @@ uses exactly 5); fp64; inputs resident in HBM before the timed region.  A "step"
 (> 256 MiB of inputs in total) so that no step can be served from the Infinity Cache.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5] [--rays R]
+                    [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a child
 `python -m torch.distributed.run`, before this process has touched the GPU); under a launcher (WORLD_SIZE set) the
 process is one rank.  cfg 2 / cfg 3 scale weakly (every rank traces the config's full size); cfg 4 / cfg 5 name a
 TOTAL (6.4e8 ray-wavelength pairs, 1e8 rays) that is sharded over the ranks (`"scaling": "strong"`).  No
 collective in the data path; the single end-of-job gather of the per-ray final state over RCCL is timed
-separately (`gather_ms`).  The default N = 1 run also measures the other BASELINE configs at the size one GPU sees
-(`configs`), a >= 6 s sustained loop (`sustained`), the cold-start figure (`cold`), call latencies at the
-reference's own sizes (`latency`) and the CPU baseline.
+separately (`gather_ms`).
+
+A plain run sets up, pre-loads, picks the output layout on the timed buffers, warms up, times the K steps and prints
+the line.  `--dump-outputs DIR` writes what the last timed step computed (a fixed, seeded sample of its rays:
+`dump_outputs`).  `--full` also measures everything beside the headline: the cold-start figure (`cold`), the
+per-launch kernel time and the stream ceiling of the roofline, the other slot layout (`other_layout`), a >= 6 s
+sustained loop (`sustained`), with N = 1 the other BASELINE configs at the size one GPU sees (`configs`), call
+latencies at the reference's own sizes (`latency`) and the CPU baseline, and with N > 1 the configs BASELINE quotes
+multi-GPU (`sharded_configs`).
 
 Prints ONE JSON line on rank 0.
 """
@@ -54,10 +61,15 @@ def parse_args(argv=None):
     ap.add_argument("--rays", type=int, default=None, help="rays per GPU (default: from the workload and the world size)")
     ap.add_argument("--workload", default="cfg2", choices=["cfg2", "cfg3", "cfg4", "cfg5"],
                     help="cfg2 = the bench line; the others are the remaining BASELINE configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the segments the last timed step computed as DIR/<field>.npy (a fixed, seeded sample of <= 60 MiB, finite values)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: cold start, per-launch kernel time, stream ceiling, the other "
+                         "layout, the sustained loop, the other configs, latencies, the CPU baseline, the sharded configs (N > 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the cfg3/cfg4/cfg5 survey of the default run")
+    ap.add_argument("--no-configs", action="store_true", help="skip the cfg3/cfg4/cfg5 survey of a --full run")
     ap.add_argument("--no-sustained", action="store_true")
-    ap.add_argument("--no-latency", action="store_true", help="skip the small-N call latencies of the default run")
+    ap.add_argument("--no-latency", action="store_true", help="skip the small-N call latencies of a --full run")
     ap.add_argument("--sustained-seconds", type=float, default=6.0, help="length of the back-to-back loop after the timed region")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU time spent on the oracle baseline (bounded sample)")
     ap.add_argument("--sharded-configs", default="auto",
@@ -192,6 +204,45 @@ def sample_device_clocks(out):
 def kernel_name(scene, wl):
     heavy = scene.n_nodes >= 24
     return ("k_trace_rolling" if heavy else "k_trace_fused") + ("<double>" if wl.precision == "f64" else "<float>")
+
+
+def dump_outputs(out, n_rays, max_seg, path, budget_bytes=60 << 20):
+    """What one step hands its caller (the segment records of `out`, slots or tiled layout) as `path/<field>.npy`: the 12 real
+    fields and `ray` / `surface` as [max_seg, m] (segment k of sampled ray j), `count.npy` and `ray_index.npy` as [m].  The m rays
+    are all of them when they fit `budget_bytes`, else a fixed, seeded sample (sorted).  Every value written is finite: slots a ray
+    did not use (k >= |count|) hold 0 (their memory is never written), and a non-finite value of a used slot (`length` is +inf
+    for a ray's last, unbounded segment) is written as 0 with its code in `<field>_nonfinite.npy` [max_seg, m] (1 = +inf,
+    -1 = -inf, 2 = NaN, 0 = finite), present only for fields that have one.  Reals keep the trace's precision; the int32
+    fields and the codes are written as float64 / float32 (exact)."""
+    import numpy as np
+    import torch
+    from optable_amd import abi
+
+    assert out.layout in ("slots", "tiled"), out.layout
+    real = np.float64 if out.precision == "f64" else np.float32
+    # per ray: 12 reals + 2 ints as float64 + (at most) a float32 code per field and slot, + count and ray index
+    per_ray = max_seg * (12 * np.dtype(real).itemsize + 2 * 8 + 14 * 4) + 2 * 8
+    m = min(n_rays, budget_bytes // per_ray)
+    idx = np.arange(n_rays) if m == n_rays else np.sort(np.random.default_rng(0).choice(n_rays, m, replace=False))
+    sel = torch.from_numpy(idx).to(out.count.device)
+    flat = torch.arange(max_seg, device=sel.device)[:, None] * n_rays + sel[None, :]  # slot k * n_rays + ray
+    count = out.count[sel]
+    unused = (torch.arange(max_seg, device=sel.device)[:, None] >= count.abs()[None, :]).cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    for f in abi.SEG_FIELDS + ("ray", "surface"):
+        t = out.field(f)
+        v = (t[flat // 64, flat % 64] if out.tiled else t[flat]).cpu().numpy()
+        v = v.astype(real if v.dtype.kind == "f" else np.float64)
+        v[unused] = 0
+        bad = ~np.isfinite(v)
+        if bad.any():
+            code = np.where(np.isnan(v), 2, np.sign(np.where(bad, v, 0))).astype(np.float32)
+            np.save(os.path.join(path, f"{f}_nonfinite.npy"), code)
+            v[bad] = 0
+        np.save(os.path.join(path, f"{f}.npy"), v)
+    np.save(os.path.join(path, "count.npy"), count.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "ray_index.npy"), idx.astype(np.float64))
+    return m
 
 
 def committed_counters(name):
@@ -561,6 +612,8 @@ def real_example_latency(oa):
 
 def main():
     args = parse_args()
+    if args.dump_outputs and args.dry_run:
+        sys.exit("bench.py: --dump-outputs needs a real trace, not --dry-run")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -653,18 +706,19 @@ def main():
         def step(s):
             eng.trace(batches[s % n_inputs], MAX_SEG, out=outs[s % n_inputs], layout=layout)
 
-        # cold: what a caller sees right after the upload — one launch to load the code object, then the next 20
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        step(0)
-        torch.cuda.synchronize()
-        ev0.record()
-        for s in range(20):
-            step(s)
-        ev1.record()
-        torch.cuda.synchronize()
-        extra["cold"] = {"us_per_step": ev0.elapsed_time(ev1) / 20 * 1e3, "steps": 20,
-                         "note": "first 20 launches after one code-object-loading launch, no pre-load: the chip is still "
-                                 "below its steady clocks"}
+        if args.full:
+            # cold: what a caller sees right after the upload — one launch to load the code object, then the next 20
+            step(0)
+            torch.cuda.synchronize()
+            ev0.record()
+            for s in range(20):
+                step(s)
+            ev1.record()
+            torch.cuda.synchronize()
+            extra["cold"] = {"us_per_step": ev0.elapsed_time(ev1) / 20 * 1e3, "steps": 20,
+                             "note": "first 20 launches after one code-object-loading launch, no pre-load: the chip is still "
+                                     "below its steady clocks"}
         # The chip takes tens of milliseconds of sustained load to reach its steady clocks (kernel time 122 -> 109 us
         # between 5 and 300 launches of pre-load on the same device): load it for ~60 ms, then the W warmup steps.
         preload = 0
@@ -727,23 +781,27 @@ def main():
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         region_ms = ev0.elapsed_time(ev1)
-        # the same K launches again with a HIP event pair around every launch (library timing): the pure kernel
-        # duration, the number rocprofv3 reports
-        eng.timing(True)
-        for s in range(args.steps):
-            step(s)
-        kernel_ms, launches = eng.timing_read()
-        eng.timing_reset()
+        if args.dump_outputs and rank == 0:  # before anything else writes into the output buffers
+            extra["dumped_rays"] = dump_outputs(outs[(args.steps - 1) % n_inputs], n, MAX_SEG, args.dump_outputs)
+        kernel_ms, launches = 0.0, 0
         ceil_ms, ceil_n = 0.0, 0
-        if scene.n_nodes < 24:  # the HBM-bound workloads: the same streams with no tracing (every ray fills its K slots)
-            for s in range(3):  # (untimed: the first launch of a kernel loads its code object)
-                eng.stream_ceiling(batches[s % n_inputs], MAX_SEG, outs[s % n_inputs])
+        if args.full:
+            # the same K launches again with a HIP event pair around every launch (library timing): the pure kernel
+            # duration, the number rocprofv3 reports
+            eng.timing(True)
+            for s in range(args.steps):
+                step(s)
+            kernel_ms, launches = eng.timing_read()
             eng.timing_reset()
-            for s in range(10 if wl.name == "cfg2" else 3):
-                eng.stream_ceiling(batches[s % n_inputs], MAX_SEG, outs[s % n_inputs])
-            ceil_ms, ceil_n = eng.timing_read()
-        eng.timing(False)
-        if not heavy_wl and world == 1:
+            if scene.n_nodes < 24:  # the HBM-bound workloads: the same streams with no tracing (every ray fills its K slots)
+                for s in range(3):  # (untimed: the first launch of a kernel loads its code object)
+                    eng.stream_ceiling(batches[s % n_inputs], MAX_SEG, outs[s % n_inputs])
+                eng.timing_reset()
+                for s in range(10 if wl.name == "cfg2" else 3):
+                    eng.stream_ceiling(batches[s % n_inputs], MAX_SEG, outs[s % n_inputs])
+                ceil_ms, ceil_n = eng.timing_read()
+            eng.timing(False)
+        if args.full and not heavy_wl and world == 1:
             # the same K launches into the OTHER slot layout (the one the probe did not choose), for comparison
             other = "slots" if layout == "tiled" else "tiled"
             outs_o = cand.get(other) or [SegmentBatch(n * MAX_SEG, prec, batches[0].device, tiled=(other == "tiled")) for _ in range(n_inputs)]
@@ -768,7 +826,7 @@ def main():
             cand.pop(other, None)
             del outs_o
             torch.cuda.empty_cache()
-        if world == 1 and not args.no_sustained:
+        if args.full and world == 1 and not args.no_sustained:
             # >= 6 s of back-to-back launches: long enough for any outside sampler (the driver polls the card every few seconds)
             # to see the GPU busy, and the figure a long job gets
             clocks = {}
@@ -836,7 +894,7 @@ def main():
 
     # The configs BASELINE quotes on several GPUs, at their quoted totals: cfg 4 on 2 and 4 ranks, cfg 5 on 8 (every rank takes part)
     sharded = []
-    if distributed and world > 1 and not args.dry_run and wl.name == "cfg2" and args.sharded_configs != "none" \
+    if args.full and distributed and world > 1 and not args.dry_run and wl.name == "cfg2" and args.sharded_configs != "none" \
             and (args.sharded_configs != "auto" or args.rays is None):
         names = (["cfg4"] if world in (2, 4) else []) + (["cfg5"] if world == 8 else []) if args.sharded_configs == "auto" \
             else [c for c in args.sharded_configs.split(",") if c]
@@ -882,7 +940,7 @@ def main():
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
                          "kernel": kernel_name(scene, wl), "kernel_us": avg_kernel_s * 1e6,
-                         "kernel_us_per_launch_events": per_launch_us, "algorithmic_bytes_per_launch": alg_bytes,
+                         "kernel_us_per_launch_events": per_launch_us if launches else None, "algorithmic_bytes_per_launch": alg_bytes,
                          "stream_ceiling_gbs": (alg_bytes / (ceil_ms / ceil_n / 1e3) / 1e9) if ceil_n else None},
         }
         if heavy:
@@ -921,7 +979,7 @@ def main():
             line["ranks"] = ranks_info
             line["comm"] = {"backend": "rccl" if use_nccl else "gloo",
                             "rccl_version": ".".join(str(v) for v in torch.cuda.nccl.version()) if use_nccl else None}
-        if world == 1 and not args.dry_run and wl.name == "cfg2" and not args.no_configs and args.rays is None:
+        if args.full and world == 1 and not args.dry_run and wl.name == "cfg2" and not args.no_configs and args.rays is None:
             # the other BASELINE configs, at the size one GPU sees in the configuration they are quoted on
             del batches, outs
             torch.cuda.empty_cache()
@@ -937,13 +995,13 @@ def main():
                 line["configs"].append({"workload": "cfg4 branching", "error": f"{type(exc).__name__}: {exc}"})
             batches = [make_batch(oa, wl, min(n, 200_000), rank, device)]
             eng.upload(scene)
-        if world == 1 and not args.dry_run and wl.name == "cfg2" and not args.no_latency and args.rays is None:
+        if args.full and world == 1 and not args.dry_run and wl.name == "cfg2" and not args.no_latency and args.rays is None:
             try:
                 line["latency"] = survey_latency(oa)
             except Exception as exc:  # noqa: BLE001
                 line["latency"] = [{"error": f"{type(exc).__name__}: {exc}"}]
             eng.upload(scene)
-        if world == 1 and not args.no_cpu_baseline and not args.dry_run:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.dry_run:
             try:
                 line["cpu_baseline"] = cpu_baseline(table, batches[0].slice(0, min(n, 200_000)).to_host(), MAX_SEG, S_LEAVES,
                                                     wl.name, budget_s=args.cpu_seconds)

@@ -106,3 +106,34 @@ def example_rays_host(gold):
     host["id"] = gold["in_class"].astype(np.int32)
     host["wavelength"] = host["wavelength"] * gold["in_unit_scale"]
     return host
+
+
+def scene_tables(scene):
+    """The device tables of a CompiledScene as plain arrays: `node/<field>` for every column of the node table,
+    `mat/<field>` for every material field (one row per material), `aux` and `scalars` = (n_materials, max_children,
+    root_grid, number of count slots).  What tests/golden/g28_adapter.npz records for scenes built with the reference's
+    own classes (tools/make_golden.py adapter_fixture)."""
+    nodes = scene.node_table()
+    out = {f"node/{f}": np.asarray(nodes[f]) for f in nodes.dtype.names}
+    for f, _ in abi.OtMaterial._fields_:
+        rows = [getattr(scene.materials[k], f) for k in range(scene.n_materials)]
+        out[f"mat/{f}"] = np.array([np.array(x[:] if hasattr(x, "__len__") else x) for x in rows])
+    out["aux"] = np.ctypeslib.as_array(scene.aux)[: scene.n_aux].copy()
+    out["scalars"] = np.array([scene.n_materials, scene.max_children, scene.root_grid, len(scene.limited)])
+    return out
+
+
+def assert_same_tables(theirs, mine):
+    """Two `scene_tables` agree: integer columns exactly, reals to 1e-12 (materials to 1e-15)."""
+    assert sorted(theirs) == sorted(mine)
+    assert len(theirs["node/kind"]) == len(mine["node/kind"])
+    for key in sorted(k for k in mine if k.startswith("node/")):
+        if mine[key].dtype.kind == "f":
+            np.testing.assert_allclose(theirs[key], mine[key], rtol=0, atol=1e-12, err_msg=key)
+        else:
+            np.testing.assert_array_equal(theirs[key], mine[key], err_msg=key)
+    assert theirs["scalars"][0] == mine["scalars"][0]
+    for key in sorted(k for k in mine if k.startswith("mat/")):
+        np.testing.assert_allclose(theirs[key], mine[key], atol=1e-15, err_msg=key)
+    np.testing.assert_allclose(theirs["aux"], mine["aux"], atol=1e-12)
+    assert theirs["scalars"].tolist() == mine["scalars"].tolist()

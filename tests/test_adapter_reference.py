@@ -1,6 +1,7 @@
-"""CPU, build container only: scenes built with the ORIGINAL optable classes compile (through
-optable_amd.adapter's duck typing) to exactly the same device tables as the same scenes built with this
-package's classes.  Skipped where /root/reference does not exist (e.g. the GPU box)."""
+"""CPU: scenes built with the ORIGINAL optable classes compile (through optable_amd.adapter's duck typing) to exactly the
+same device tables as the same scenes built with this package's classes.  What the reference's objects compile to is recorded
+in tests/golden/g28_adapter.npz (tools/make_golden.py adapter_fixture), so those comparisons run everywhere; where the reference
+package itself can be imported they run on its live objects too, and the tests that need its classes run only there."""
 import os
 import sys
 
@@ -10,13 +11,31 @@ import pytest
 import scenes
 import optable_amd as oa
 from optable_amd import abi
+from helpers import assert_same_tables, golden, scene_tables
 
 REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "optable")), reason="reference not present")
+HAVE_REF = os.path.isdir(os.path.join(REF, "optable"))
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return golden("g28_adapter")
+
+
+@pytest.fixture(scope="module")
+def live_ref():
+    """The reference package where it can be imported, else None (the recorded tables stand in for its objects)."""
+    return _import_reference() if HAVE_REF else None
 
 
 @pytest.fixture(scope="module")
 def ref():
+    if not HAVE_REF:
+        pytest.skip("needs the reference package's own classes, which are not part of the repository")
+    return _import_reference()
+
+
+def _import_reference():
     os.environ.setdefault("MPLBACKEND", "Agg")
     sys.dont_write_bytecode = True
     sys.path.insert(0, REF)
@@ -32,42 +51,33 @@ ADAPTABLE = sorted(scenes.SCENES)  # incl. g16: Block with a hole = the referenc
 
 
 @pytest.mark.parametrize("name", ADAPTABLE)
-def test_reference_objects_compile_to_the_same_tables(name, ref):
+def test_reference_objects_compile_to_the_same_tables(name, live_ref, gold):
     np.random.seed(12345)
-    theirs = oa.compile_scene(scenes.SCENES[name](ref)["components"])
-    np.random.seed(12345)
-    mine = oa.compile_scene(scenes.SCENES[name](oa)["components"])
-    a, b = theirs.node_table(), mine.node_table()
-    assert len(a) == len(b)
-    for field in a.dtype.names:
-        if a[field].dtype.kind == "f":
-            np.testing.assert_allclose(a[field], b[field], rtol=0, atol=1e-12, err_msg=field)
-        else:
-            np.testing.assert_array_equal(a[field], b[field], err_msg=field)
-    assert theirs.n_materials == mine.n_materials
-    for k in range(mine.n_materials):
-        for field, _ in abi.OtMaterial._fields_:
-            x, y = getattr(theirs.materials[k], field), getattr(mine.materials[k], field)
-            np.testing.assert_allclose(np.array(x[:] if hasattr(x, "__len__") else x), np.array(y[:] if hasattr(y, "__len__") else y), atol=1e-15)
-    np.testing.assert_allclose(np.ctypeslib.as_array(theirs.aux)[: theirs.n_aux], np.ctypeslib.as_array(mine.aux)[: mine.n_aux], atol=1e-12)
-    assert (theirs.max_children, theirs.root_grid, len(theirs.limited)) == (mine.max_children, mine.root_grid, len(mine.limited))
+    mine = scene_tables(oa.compile_scene(scenes.SCENES[name](oa)["components"]))
+    assert_same_tables({k[len(name) + 1:]: v for k, v in gold.items() if k.startswith(name + "/")}, mine)
+    if live_ref is not None:
+        np.random.seed(12345)
+        assert_same_tables(scene_tables(oa.compile_scene(scenes.SCENES[name](live_ref)["components"])), mine)
 
 
-def test_reference_boolean_apertures_are_recovered_from_their_closures(ref):
+def test_reference_boolean_apertures_are_recovered_from_their_closures(live_ref, gold):
     """The reference builds Plane.union / subtract as closures (surfaces.py:100-136); the adapter reads the
     operands from the closure cells, MEASURES the operator and checks the recovered program on a grid."""
-    from optable_amd import shapes
+    from optable_amd import adapter, shapes
 
-    hole = ref.Block([4, 0, 0], hole=ref.Circle(0.3), width=2, height=2)
     mine = oa.Block([4, 0, 0], hole=oa.Circle(0.3), width=2, height=2)
-    a, b = oa.compile_scene([hole]), oa.compile_scene([mine])
-    np.testing.assert_array_equal(np.ctypeslib.as_array(a.aux)[: a.n_aux], np.ctypeslib.as_array(b.aux)[: b.n_aux])
-    assert a.node_table()["shape"][0] == shapes.CSG
+    b = oa.compile_scene([mine])
     # nested: (rectangle - circle) | small rectangle
-    nested_ref = ref.Rectangle(2, 2).subtract(ref.Circle(0.5)).union(ref.Rectangle(0.2, 3.0))
     nested_mine = oa.Rectangle(2, 2).subtract(oa.Circle(0.5)).union(oa.Rectangle(0.2, 3.0))
-    from optable_amd import adapter
-    assert adapter.lower_surface(nested_ref).aux == nested_mine.lower().aux
+    theirs = [(gold["boolean/hole_aux"], int(gold["boolean/hole_shape"]), gold["boolean/nested_aux"].tolist())]
+    if live_ref is not None:
+        a = oa.compile_scene([live_ref.Block([4, 0, 0], hole=live_ref.Circle(0.3), width=2, height=2)])
+        nested_ref = live_ref.Rectangle(2, 2).subtract(live_ref.Circle(0.5)).union(live_ref.Rectangle(0.2, 3.0))
+        theirs.append((np.ctypeslib.as_array(a.aux)[: a.n_aux], a.node_table()["shape"][0], adapter.lower_surface(nested_ref).aux))
+    for hole_aux, hole_shape, nested_aux in theirs:
+        np.testing.assert_array_equal(hole_aux, np.ctypeslib.as_array(b.aux)[: b.n_aux])
+        assert hole_shape == shapes.CSG
+        assert nested_aux == nested_mine.lower().aux
 
 
 def test_unrecognisable_surface_is_rejected_loudly(ref):
@@ -126,12 +136,16 @@ def test_reference_ray_objects_round_trip_through_pack_and_scatter(ref):
     assert per_ray[0][0].origin[0] == 0.0                                        # the returned list is independent
 
 
-def test_reference_objects_with_user_functions_get_the_same_series(ref):
+def test_reference_objects_with_user_functions_get_the_same_series(live_ref, gold):
     """ASphericLens(f_asphere = callable) and Material(n = callable) built with the REFERENCE's classes lower to the same
     Chebyshev records as this package's own (optable_amd/cheb.py through adapter.py)."""
-    a = oa.compile_scene(scenes.g24_callables(ref)["components"])
     b = oa.compile_scene(scenes.g24_callables(oa)["components"])
-    assert a.n_aux == b.n_aux > 100
-    np.testing.assert_array_equal(np.ctypeslib.as_array(a.aux)[: a.n_aux], np.ctypeslib.as_array(b.aux)[: b.n_aux])
-    assert [m.kind for m in a.materials[: a.n_materials]] == [m.kind for m in b.materials[: b.n_materials]]
-    assert list(a.node_table()["shape"]) == list(b.node_table()["shape"]) and 10 in a.node_table()["shape"]
+    theirs = [(gold["callables/aux"], gold["callables/material_kinds"].tolist(), gold["callables/shape"].tolist())]
+    if live_ref is not None:
+        a = oa.compile_scene(scenes.g24_callables(live_ref)["components"])
+        theirs.append((np.ctypeslib.as_array(a.aux)[: a.n_aux], [m.kind for m in a.materials[: a.n_materials]], list(a.node_table()["shape"])))
+    for aux, kinds, shape in theirs:
+        assert len(aux) == b.n_aux > 100
+        np.testing.assert_array_equal(aux, np.ctypeslib.as_array(b.aux)[: b.n_aux])
+        assert kinds == [m.kind for m in b.materials[: b.n_materials]]
+        assert shape == list(b.node_table()["shape"]) and 10 in shape

@@ -11,9 +11,9 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*extra):
+def _run(*extra, full=True):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "1",
-                          "--sustained-seconds", "1", *extra],
+                          "--sustained-seconds", "1", *(("--full",) if full else ()), *extra],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -52,6 +52,54 @@ def test_bench_line_contract(workload, rays):
     assert nb * rays * rec >= 256 * 2**20 or nb == 4
     if roof["traffic"] is not None:
         assert "profiles/" in roof["traffic_source"]
+
+
+def test_plain_run_is_lean_and_dumps_what_its_last_step_computed(tmp_path, oracle):
+    """Without --full the line holds the headline alone; --dump-outputs writes the segments of the LAST timed step (a seeded
+    sample of its rays, float arrays, <= 64 MiB), and they are what the oracle computes for the same input rays."""
+    import numpy as np
+
+    import optable_amd as oa
+    from optable_amd import abi
+    from optable_amd import workloads as W
+    from optable_amd.batch import RayBatch
+
+    n, steps = 200_000, 3
+    line = _run("--rays", str(n), "--dump-outputs", str(tmp_path), full=False)
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and line["dtype"] == "f64"
+    for key in ("cold", "sustained", "other_layout", "configs", "latency", "cpu_baseline"):
+        assert key not in line, key
+    paths = sorted(tmp_path.glob("*.npy"))
+    assert sum(p.stat().st_size for p in paths) <= 64 << 20
+    dump = {p.stem: np.load(p) for p in paths}
+    fields = abi.SEG_FIELDS + ("ray", "surface")
+    codes = {k for k in dump if k.endswith("_nonfinite")}
+    assert set(dump) - codes == set(fields) | {"count", "ray_index"} and codes <= {f + "_nonfinite" for f in fields}
+    assert all(np.isfinite(v).all() for v in dump.values())
+    assert all(dump[k].dtype == np.float64 for k in dump if k not in codes)
+    for k in codes:  # what was not finite, back in place (1 = +inf, -1 = -inf, 2 = NaN)
+        f, c = k[: -len("_nonfinite")], dump[k]
+        dump[f] = np.select([c == 1, c == -1, c == 2], [np.inf, -np.inf, np.nan], dump[f])
+    assert "length_nonfinite" in codes  # every ray of cfg 2 ends on an unbounded segment
+    idx = dump["ray_index"].astype(np.int64)
+    assert line["dumped_rays"] == len(idx) and 0 < len(idx) < n and np.all(np.diff(idx) > 0)
+    assert np.all(dump["count"] == 5) and dump["ray"].shape == (5, len(idx))
+    # the last step traced input batch (steps - 1) % rotated of the rotation (bench.make_batch: seed shifted by 1000 per batch)
+    shift = 1000 * ((steps - 1) % line["config"]["input_batches_rotated"])
+    o, d, lam = W.baseline_workloads(oa)["cfg2"].rays(n, shift)
+    table = oa.OpticalTable()
+    table.add_components(W.cfg2_components(oa))
+    host = RayBatch.from_arrays(o[idx], d[idx], wavelength=lam, q=1j * np.pi * W.W0**2 / lam, ids=idx, device="cpu").to_host()
+    scene = table.compile()
+    ref = oracle.trace(scene, host, max_trace_num=5)
+    got = {f: dump[f].T.reshape(-1) for f in fields}  # [k][ray] -> ray-major, as the oracle
+    np.testing.assert_array_equal(got["ray"], idx[ref["ray"]])  # (the oracle numbers rays by their place in the sample)
+    np.testing.assert_array_equal(got["surface"], ref["surface"])
+    for f in abi.SEG_FIELDS:
+        if f not in ("q_re", "q_im"):
+            np.testing.assert_allclose(got[f], ref[f], rtol=1e-9, atol=1e-9, err_msg=f)
+    qtol, _ = oracle.q_tolerance(scene, host, ref, 5)
+    assert np.all(np.hypot(got["q_re"] - ref["q_re"], got["q_im"] - ref["q_im"]) <= qtol)
 
 
 def test_two_ranks_on_one_card_gloo_rehearsal():

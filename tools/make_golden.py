@@ -350,10 +350,36 @@ def calibrate_fixture():
     print("g22_calibrate:", {k: np.round(v, 5).tolist() if v.size <= 4 else v.shape for k, v in out.items()})
 
 
+def adapter_fixture():
+    """g28: the device tables that scenes built with the REFERENCE's classes compile to through optable_amd.adapter
+    (tests/test_adapter_reference.py compares this package's own scenes with them): every parity scene, the boolean
+    apertures the reference builds as closures, and the Chebyshev records of its user functions."""
+    import optable_amd as oa
+    from optable_amd import adapter
+    from helpers import scene_tables
+
+    out = {}
+    for nm in sorted(scenes.SCENES):
+        np.random.seed(12345)
+        for key, val in scene_tables(oa.compile_scene(scenes.SCENES[nm](ref)["components"])).items():
+            out[f"{nm}/{key}"] = val
+    hole = oa.compile_scene([ref.Block([4, 0, 0], hole=ref.Circle(0.3), width=2, height=2)])
+    out["boolean/hole_aux"] = np.ctypeslib.as_array(hole.aux)[: hole.n_aux].copy()
+    out["boolean/hole_shape"] = np.array(hole.node_table()["shape"][0])
+    nested = ref.Rectangle(2, 2).subtract(ref.Circle(0.5)).union(ref.Rectangle(0.2, 3.0))
+    out["boolean/nested_aux"] = np.array(adapter.lower_surface(nested).aux, dtype=np.float64)
+    cal = oa.compile_scene(scenes.g24_callables(ref)["components"])
+    out["callables/aux"] = np.ctypeslib.as_array(cal.aux)[: cal.n_aux].copy()
+    out["callables/material_kinds"] = np.array([m.kind for m in cal.materials[: cal.n_materials]])
+    out["callables/shape"] = np.array(cal.node_table()["shape"])
+    np.savez_compressed(os.path.join(OUT, "g28_adapter.npz"), **out)
+    print("g28_adapter:", len(out), "arrays")
+
+
 if __name__ == "__main__":
     names = sys.argv[1:] or list(scenes.SCENES) + list(scenes.HOOKED_SCENES)
     for nm in names:
-        if nm in ("g14_slab", "g17_abcd", "g20_interact", "g22_calibrate", "g23_exports", "g27_real_example", "examples"):
+        if nm in ("g14_slab", "g17_abcd", "g20_interact", "g22_calibrate", "g23_exports", "g27_real_example", "g28_adapter", "examples"):
             continue
         np.random.seed(12345)
         run(nm)
@@ -374,3 +400,5 @@ if __name__ == "__main__":
     if not sys.argv[1:] or "g20_interact" in sys.argv[1:]:
         np.random.seed(12345)
         interact_fixture()
+    if not sys.argv[1:] or "g28_adapter" in sys.argv[1:]:
+        adapter_fixture()
