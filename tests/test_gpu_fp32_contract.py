@@ -16,7 +16,7 @@ import optable_amd as oa
 from optable_amd import abi
 from optable_amd import workloads as W
 from optable_amd.batch import RayBatch
-from optable_amd.fp32_audit import audit
+from optable_amd.fp32_audit import assert_explained, audit, audit_traces
 
 pytestmark = pytest.mark.gpu
 EDGE = 1e-4   # model units (scene size ~30): hit point within this of an aperture edge ...
@@ -38,6 +38,10 @@ def test_fp32_leaves_the_fp64_path_only_at_edge_cases(name, n):
     assert rep["same"].mean() >= 0.9995, rep["same"].mean()
     edge = (rep["margin"] < EDGE) | (np.minimum(rep["len64"], rep["len32"]) < SHORT)
     assert edge.all(), [(int(r), int(k), float(m)) for r, k, m in zip(rep["ray"][~edge], rep["kstar"][~edge], rep["margin"][~edge])]
+    # and the general audit: the records before the divergence agree, and the cause is marginal in the fp64 trace
+    host = RayBatch.from_arrays(o, d, wavelength=lam, q=q, device="cpu").to_host()
+    assert_explained(audit_traces(table.compile(), s64.to_host(reference_order=True), s32.to_host(reference_order=True),
+                                  prec="f32", tol=2e-3, rays=host))
     # on the rays that agree, every segment start agrees to 2e-3 (20-50 bounces, coordinates ~30, fp32 ulp 2e-6)
     c64 = np.abs(s64.count.cpu().numpy())
     valid = (np.arange(K)[:, None] < c64[None, :]) & rep["same"][None, :]

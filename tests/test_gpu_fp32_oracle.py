@@ -18,7 +18,7 @@ from optable_amd import abi
 from optable_amd import workloads as W
 from optable_amd.batch import RayBatch, SegmentBatch
 from optable_amd.engine import get_engine
-from optable_amd.fp32_audit import audit
+from optable_amd.fp32_audit import assert_explained, audit, audit_traces
 
 pytestmark = pytest.mark.gpu
 EDGE, SHORT = 1e-4, 1e-4
@@ -81,6 +81,8 @@ def test_fp32_production_kernel_matches_oracle(name, n, oracle):
     host = RayBatch.from_arrays(o, d, wavelength=lam, q=q, device="cpu").to_host()
     ref = oracle.trace(scene, host, max_trace_num=K)
     rep = check_against(scene, slots_from_reference_order(ref, n, K), s32, n, K)
+    # the general audit reads the oracle's records directly: prefix check, every cause (polygons, cylinders, TIR, ties)
+    assert_explained(audit_traces(scene, ref, s32.to_host(reference_order=True), prec="f32", tol=2e-3, rays=host))
     # the [k][ray] slots are the same computation: identical records (tests/test_gpu_append.py) — spot-check the count here
     slots = table.trace_batch(b32, max_segments=K, layout="slots")
     np.testing.assert_array_equal(slots.count.cpu().numpy(), s32.count.cpu().numpy())
@@ -114,6 +116,7 @@ def test_fp32_against_reference_fixture(fixture):
         fix["o" + ax], fix["d" + ax] = gold["seg_origin"][:, k], gold["seg_direction"][:, k]
     fix["length"], fix["intensity"], fix["pathlength"], fix["n"] = gold["seg_length"], gold["seg_intensity"], gold["seg_pathlength"], gold["seg_n"]
     check_against(scene, slots_from_reference_order(fix, n, K), s32, n, K)
+    assert_explained(audit_traces(scene, ref, s32.to_host(reference_order=True), prec="f32", tol=2e-3, rays=host))
     # fields beyond the positions, on the rays that agree, at what 20-50 fp32 bounces leave: 2e-3 relative
     got = s32.to_host(reference_order=True)
     if len(got["ray"]) == len(gold["seg_tree"]) and np.array_equal(got["ray"], gold["seg_tree"]):

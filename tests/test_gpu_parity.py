@@ -10,6 +10,7 @@ import pytest
 import helpers
 import scenes
 from optable_amd import abi
+from optable_amd.fp32_audit import assert_explained, audit_traces
 
 pytestmark = pytest.mark.gpu
 
@@ -577,6 +578,8 @@ def test_fp32_heavy_scenes_track_fp64(case, min_same):
     valid = np.arange(K)[:, None] < c64[None, :]
     same = (c64 == c32) & np.all((surf64 == surf32) | ~valid, axis=0)
     assert same.mean() >= min_same, same.mean()
+    assert_explained(audit_traces(table.compile(), s64.to_host(reference_order=True), s32.to_host(reference_order=True), prec="f32",
+                                  tol=2e-3, rays=RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q, device="cpu").to_host()))
     for f in ("ox", "oy", "oz"):
         a = s64.field(f).cpu().numpy().reshape(K, n)
         b = s32.field(f).cpu().numpy().reshape(K, n).astype(np.float64)
@@ -757,6 +760,8 @@ def test_fp32_ray_trees_track_fp64():
     seq = lambda x: [tuple(x["surface"][x["ray"] == i].tolist()) for i in range(n)]
     same = np.array([u == v for u, v in zip(seq(a), seq(b))])
     assert same.mean() > 0.995, same.mean()            # a ray grazing an edge may fall on the other side in float
+    assert_explained(audit_traces(table.compile(), s64.to_host(reference_order=True), s32.to_host(reference_order=True), prec="f32",
+                                  tol=2e-4, rays=RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q, device="cpu").to_host()))
     ka, kb = same[a["ray"]], same[b["ray"]]
     for f in ("ox", "oy", "oz", "dx", "dy", "dz", "intensity"):
         assert np.abs(a[f][ka].astype(np.float64) - b[f][kb]).max() < 2e-4, f
@@ -1083,6 +1088,7 @@ def test_very_large_scene_image(oracle):
     seq = lambda x: [tuple(x["surface"][x["ray"] == i].tolist()) for i in range(n)]
     same = np.array([a == b for a, b in zip(seq(g32), seq(ref))])
     assert same.mean() > 0.9, same.mean()
+    assert_explained(audit_traces(scene, ref, g32, prec="f32", tol=2e-3, rays=batch.to_host()))
 
 
 @pytest.mark.filterwarnings("ignore:Maximum number of iterations")  # the 50-iteration cap is upstream's own setting
@@ -1207,6 +1213,7 @@ def test_repeated_hits_on_one_curved_surface(shape, oracle):
     c64, c32 = out["f64"].count.cpu().numpy(), out["f32"].count.cpu().numpy()
     assert np.median(c64) > min_repeats            # the rays really do come back to the surface they left
     assert (c64 == c32).mean() >= 0.99, (c64 == c32).mean()
+    assert_explained(audit_traces(table.compile(), got, out["f32"].to_host(reference_order=True), prec="f32", tol=2e-3, rays=host))
 
 
 @pytest.mark.parametrize("prec", ["f64", "f32"])

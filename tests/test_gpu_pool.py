@@ -8,6 +8,7 @@ import torch
 
 import scenes
 from optable_amd import abi
+from optable_amd.fp32_audit import assert_explained, audit_traces
 
 pytestmark = pytest.mark.gpu
 
@@ -77,6 +78,7 @@ def test_block_pool_against_the_oracle(oracle):
     np.testing.assert_array_equal(got["ray"], ref["ray"])
     same = got["surface"] == ref["surface"]
     assert same.mean() > 0.999
+    assert_explained(audit_traces(table.compile(), ref, got, prec="f32", tol=2e-3, rays=b64.to_host()))
     np.testing.assert_allclose(got["ox"][same], ref["ox"][same], atol=2e-3)
 
 

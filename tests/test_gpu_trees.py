@@ -11,6 +11,7 @@ from optable_amd import abi
 from optable_amd import workloads as W
 from optable_amd.batch import RayBatch
 from optable_amd.engine import get_engine
+from optable_amd.fp32_audit import assert_explained, audit_traces
 
 pytestmark = pytest.mark.gpu
 Q = 1j * np.pi * W.W0**2 / W.WL
@@ -322,6 +323,7 @@ def test_trees_in_a_scene_of_grids_and_curved_optics(precision, oracle):
         seq = lambda x: [[int(s) for r, s in zip(x["ray"], x["surface"]) if r == i] for i in range(small.n)]
         same = np.array([a == b for a, b in zip(seq(mine), seq(ref))])
         assert (~same).mean() <= 0.01  # (a hit within an ulp of a micro-mirror's edge may fall to either side)
+        assert_explained(audit_traces(scene, ref, mine, prec="f64", tol=1e-9, rays=small.to_host()))
         keep_m, keep_r = same[mine["ray"]], same[ref["ray"]]
         for f in ("ox", "oy", "oz", "dx", "dy", "dz", "intensity", "pathlength"):
             np.testing.assert_allclose(mine[f][keep_m], ref[f][keep_r], rtol=1e-9, atol=1e-9, err_msg=f)
