@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define OT_ABI_VERSION 13  /* 13: OT_OPT_TREES_GLOBAL_IMAGE, tree kernels for scenes beyond the LDS; 12: OT_OPT_GEN_PARENT_INDEX; 11: OT_OPT_GEN_AHEAD, ot_trace_trees_*, ot_trace_trees_append_*, OT_OPT_TREES_LDS_ENTRIES, OT_OPT_TREES_REFILL_AT, OT_OPT_TREES_FLAT; 10: ot_trace_plan, ot_probe_layouts, ot_runtime_info, OT_OPT_REFILL, OT_OPT_REFILL_TICKET, OT_OPT_POOL_JITTER, OT_OPT_GEN_ONEPASS; 9: ot_trace_tree_*, OT_OPT_BLOCK_POOL, OT_OPT_GEN_DROP_DOOMED, ot_trace_append_* holes per workgroup chunk; 8: OT_SHAPE_ASPHERE_CHEB, OT_MAT_CHEB, OT_NODE_BOX_TRUSTED, ot_trace_tiled_*, ot_bench_stream_tiled_*; 3: ot_trace_generation_f32; 4: ot_bench_stream_f32; 5: OT_OPT_LIST_CAP, ray flags bits 8..31, ot_debug_generation_mismatches; 6: ot_debug_last_launch, OT_OPT_FLAT_QUEUE, OT_OPT_LDS_RECORDS; 7: ot_trace_append_*, ot_segment_block, OT_OPT_APPEND_CHUNK, OT_OPT_INSTANCING */
+#define OT_ABI_VERSION 14  /* 14: OT_SHAPE_IMPLICIT_CHEB and its record; 13: OT_OPT_TREES_GLOBAL_IMAGE, tree kernels for scenes beyond the LDS; 12: OT_OPT_GEN_PARENT_INDEX; 11: OT_OPT_GEN_AHEAD, ot_trace_trees_*, ot_trace_trees_append_*, OT_OPT_TREES_LDS_ENTRIES, OT_OPT_TREES_REFILL_AT, OT_OPT_TREES_FLAT; 10: ot_trace_plan, ot_probe_layouts, ot_runtime_info, OT_OPT_REFILL, OT_OPT_REFILL_TICKET, OT_OPT_POOL_JITTER, OT_OPT_GEN_ONEPASS; 9: ot_trace_tree_*, OT_OPT_BLOCK_POOL, OT_OPT_GEN_DROP_DOOMED, ot_trace_append_* holes per workgroup chunk; 8: OT_SHAPE_ASPHERE_CHEB, OT_MAT_CHEB, OT_NODE_BOX_TRUSTED, ot_trace_tiled_*, ot_bench_stream_tiled_*; 3: ot_trace_generation_f32; 4: ot_bench_stream_f32; 5: OT_OPT_LIST_CAP, ray flags bits 8..31, ot_debug_generation_mismatches; 6: ot_debug_last_launch, OT_OPT_FLAT_QUEUE, OT_OPT_LDS_RECORDS; 7: ot_trace_append_*, ot_segment_block, OT_OPT_APPEND_CHUNK, OT_OPT_INSTANCING */
 
 /* ---- status codes ------------------------------------------------------------------- */
 enum ot_status {
@@ -66,10 +66,25 @@ enum ot_shape_kind {
     OT_SHAPE_CYLINDER = 7,   /* surfaces.py:212-281   p[0]=R p[1]=height/2 p[2]=theta0 p[3]=theta1  */
     OT_SHAPE_POINT = 8,      /* surfaces.py:68-86     never hit                                     */
     OT_SHAPE_CSG = 9,        /* Plane.union/subtract  surfaces.py:100-136: aux -> postfix program   */
-    OT_SHAPE_ASPHERE_CHEB = 10 /* ASphere with an arbitrary sag F(r) (component_group.py:1014-1055), given as a verified
+    OT_SHAPE_ASPHERE_CHEB = 10, /* ASphere with an arbitrary sag F(r) (component_group.py:1014-1055), given as a verified
                                 Chebyshev series: p[0]=aperture radius, aux -> [N, lo, hi, c[N], c'[N], c''[N]]: F, dF/dr and
                                 d2F/dr2 as series in t = (2r - lo - hi) / (hi - lo); [lo, hi] covers -2h .. radius*sqrt2 + 2h,
                                 h = 1e-4 radius (the reference's finite-difference step, surfaces.py:355-369)            */
+    OT_SHAPE_IMPLICIT_CHEB = 11 /* a user's implicit surface f(P) = 0 (surfaces.py:5-65), given as a verified tensor Chebyshev
+                                series over its local box: aux -> implicit record (below)                                 */
+};
+
+/* Implicit record (OT_SHAPE_IMPLICIT_CHEB): a header of OT_IMPLICIT_HEADER reals, then four blocks of nx*ny*nz coefficients —
+   f, df/dx, df/dy, df/dz — each indexed [(i * ny + j) * nz + k] for T_i(tx) T_j(ty) T_k(tz), t = (x - centre) * (1 / half width).
+   header: [0..2] nx ny nz (terms per axis, 1..64)   [3..5] centre of the box   [6..8] 1 / half widths (formed on the host)
+           [9] normal sign s (normal = s grad f / |grad f|)   [10] aperture kind (OT_APERTURE_*)   [11] aperture radius^2
+           [12..17] aperture box x0 x1 y0 y1 z0 z1   [18] measured max error of f / max|f|   [19] max|f| over the box */
+#define OT_IMPLICIT_HEADER 20
+enum ot_implicit_aperture {
+    OT_APERTURE_BOX = 0,   /* the (slightly widened) local box                          */
+    OT_APERTURE_DISC = 1,  /* (y - cy)^2 + (z - cz)^2 <= R^2, the disc inscribed in the box's yz face */
+    OT_APERTURE_RECT = 2,  /* the rectangle of the box's yz face                        */
+    OT_APERTURE_BALL = 3   /* |P| <= R (the 3-norm form of Circle, surfaces.py:144-145)  */
 };
 
 /* interaction kinds (what interact_local does) */

@@ -253,33 +253,51 @@ def _surface_state(surf):
     return (type(surf), tuple(items))
 
 
-def _measured(surf):
-    """`_recognise_user_surface`, remembered on the object while its state stands: the measurement is ~1,500 calls of the user's
-    methods and a series fit (20-60 ms), and `table.ray_tracing` compiles the scene on every call."""
-    state = _surface_state(surf)
+def _lower_user_surface(surf, implicit):
+    """`_recognise_user_surface`; where that refuses a NON-planar surface and the scene asked for `implicit_surfaces`, the
+    verified 3-D series of its f (implicit.py) — or that module's refusal, which names what was measured."""
+    try:
+        return _recognise_user_surface(surf)
+    except AdapterError as exc:
+        if bool(getattr(surf, "planar", True)):
+            raise
+        if not implicit:
+            raise AdapterError(f"{exc}; set implicit_surfaces=True to trace it as a verified 3-D series") from exc
+    from . import implicit as _implicit
+
+    return _implicit.lower(surf)
+
+
+def _measured(surf, implicit=False):
+    """`_lower_user_surface`, remembered on the object while its state (and the scene's `implicit_surfaces` switch) stands: the
+    measurement is ~1,500 calls of the user's methods and a series fit (20-60 ms; a 3-D series: ~0.1-1 s), and
+    `table.ray_tracing` compiles the scene on every call."""
+    key = (_surface_state(surf), bool(implicit))
     memo = surf.__dict__.get("_ot_lowered")
-    if memo is None or memo[0] != state:
-        memo = (state, _recognise_user_surface(surf))
+    if memo is None or memo[0] != key:
+        memo = (key, _lower_user_surface(surf, bool(implicit)))
         surf.__dict__["_ot_lowered"] = memo
     return memo[1]
 
 
-def lower_surface(surf):
+def lower_surface(surf, implicit=False):
+    """Device form of a surface.  implicit: user surfaces that no built-in shape reproduces may become verified 3-D series
+    (OpticalTable.implicit_surfaces, compile_scene(..., implicit_surfaces=True))."""
     if _user_overrides(surf):
-        return _measured(surf)  # measured, never assumed from the base class (see _recognise_user_surface)
+        return _measured(surf, implicit)  # measured, never assumed from the base class (see _recognise_user_surface)
     if hasattr(surf, "lower"):
         try:
             return surf.lower()
         except NotImplementedError:
             if type(surf).lower is not shapes.Surface.lower:
                 raise
-            return _measured(surf)  # a user's subclass of this package's Surface: measured (see _recognise_user_surface)
+            return _measured(surf, implicit)  # a user's subclass of this package's Surface: measured (see _recognise_user_surface)
     fn = _SURFACES.get(type(surf).__name__)
     if fn is None:
         if _closure_operands(surf) is not None:  # the closure-based Plane.union / subtract of the reference
             return _boolean_plane(surf)
         if all(callable(getattr(surf, m, None)) for m in ("f", "normal", "within_boundary", "get_bbox_local")):
-            return _measured(surf)  # a user's subclass of the reference's Surface
+            return _measured(surf, implicit)  # a user's subclass of the reference's Surface
         raise AdapterError(f"surface {type(surf).__name__} has no device form")
     return fn(surf)
 
@@ -403,7 +421,8 @@ def install(optable_module):
     def compile_(self):
         from .scene import compile_scene
 
-        return compile_scene(self.components, getattr(self, "unit", 1e-2))
+        return compile_scene(self.components, getattr(self, "unit", 1e-2),
+                             implicit_surfaces=getattr(self, "implicit_surfaces", False))
 
     OT.ray_tracing, OT.compile, Mon.record = ray_tracing, compile_, record
 

@@ -330,6 +330,9 @@ __global__ __launch_bounds__(256, MINW) void k_trace_trees(SceneBlob blob, T uni
                                                            int32_t* counts, int32_t n_classes, int32_t refill_at, int32_t flat_cap) {
     constexpr bool APPEND = std::is_same<OUT, SegPlanes<T>>::value;
     static_assert(IMG == 1 || (F & F_FLAT) == 0, "the pair queue reads the image from LDS");
+    // IMG = 2 (records in LDS, aux tables in L2) without the implicit-series surfaces: their search costs this kernel spills, and the
+    // host gives scenes with such surfaces the IMG = 0 kernel instead (optable_hip.hip trees_plan)
+    constexpr uint32_t FX = IMG == 2 ? (F | F_NOIMPL) : F;
     extern __shared__ __align__(16) uint32_t lds[];
     const uint32_t* base = blob.words;
     size_t img_bytes = 0;
@@ -505,7 +508,7 @@ __global__ __launch_bounds__(256, MINW) void k_trace_trees(SceneBlob blob, T uni
             h = flat_grid_hit<T, F, GATE_PLAIN>(sc, flat_grid, r, active, gate, flat, lane);
 #endif
         } else {
-            h = nearest_hit<T, F, GATE_PLAIN>(sc, r, active, gate);
+            h = nearest_hit<T, FX, GATE_PLAIN>(sc, r, active, gate);
         }
         const int64_t slot = place(active, (int64_t)k * n + i);
         if (active) {
@@ -535,7 +538,7 @@ __global__ __launch_bounds__(256, MINW) void k_trace_trees(SceneBlob blob, T uni
                 if (slot >= 0) store_segment<T, false>(out, slot, r, r.len, i, -1);
             } else {
                 if (slot >= 0) store_segment<T, false>(out, slot, r, h.t, i, leaf_id_of<T, F>(sc, h.node));
-                interact<T, F, 2, decltype(push)>(sc, r, h, nullptr, mc, &push);
+                interact<T, FX, 2, decltype(push)>(sc, r, h, nullptr, mc, &push);
             }
             if ((qs & 0xff00ff00u) != 0 && left > 0 && !overflow) {
                 if (llen() > 0) {

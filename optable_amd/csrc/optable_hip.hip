@@ -53,6 +53,7 @@ struct ot_ctx {
     size_t lds_limit = 64 * 1024;
     // scene
     bool has_scene = false;
+    bool has_implicit = false;  // a leaf is OT_SHAPE_IMPLICIT_CHEB (the IMG = 2 tree kernel lacks its normal: kernels.h k_trace_trees)
     void *blob64 = nullptr, *blob32 = nullptr;
     size_t bytes64 = 0, bytes32 = 0;
     size_t head64 = 0, head32 = 0;  // node + material records at the front of the image (k_trace_trees IMG = 2 keeps these in LDS)
@@ -353,7 +354,7 @@ static uint32_t scene_features(const ot_scene_desc* s) {
         if (nd.shape != OT_SHAPE_CIRCLE && nd.shape != OT_SHAPE_RECT && nd.shape != OT_SHAPE_POLYGON2D &&
             nd.shape != OT_SHAPE_CSG)
             f |= F_CURVED;
-        if (nd.shape == OT_SHAPE_ASPHERE_CHEB) f |= F_MISC;
+        if (nd.shape == OT_SHAPE_ASPHERE_CHEB || nd.shape == OT_SHAPE_IMPLICIT_CHEB) f |= F_MISC;
         if (nd.shape == OT_SHAPE_POLYGON3D) f |= F_POLY | F_MISC;
         if (nd.shape == OT_SHAPE_CYLINDER) f |= F_MISC;
         if (nd.interaction == OT_INT_REFRACT) f |= F_REFRACT;
@@ -410,6 +411,22 @@ static int64_t series_record_len(const ot_scene_desc* s, int64_t off, int blocks
     return off + len <= s->n_aux ? len : -1;
 }
 
+// implicit record: [OT_IMPLICIT_HEADER | 4 blocks x nx*ny*nz coefficients] (trace_core.h cheb3_eval); returns its length or -1
+static int64_t implicit_record_len(const ot_scene_desc* s, int64_t off) {
+    if (off < 0 || off + OT_IMPLICIT_HEADER > s->n_aux) return -1;
+    const double* h = s->aux + off;
+    int64_t n = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (!(h[a] >= 1 && h[a] <= 64) || h[a] != (double)(int)h[a]) return -1;
+        if (!(h[6 + a] > 0) || !(h[6 + a] < 1e300)) return -1;  // 1 / half width: positive and finite
+        n *= (int64_t)h[a];
+    }
+    const int ap = (int)h[10];
+    if (h[10] != (double)ap || ap < OT_APERTURE_BOX || ap > OT_APERTURE_BALL || !(h[9] == 1.0 || h[9] == -1.0)) return -1;
+    const int64_t len = OT_IMPLICIT_HEADER + 4 * n;
+    return off + len <= s->n_aux ? len : -1;
+}
+
 // CSG record: [ntok | ntok x (kind, len, body[len])], postfix over a 32-deep bit stack (trace_core.h csg_inside)
 static int validate_csg(const ot_scene_desc* s, int64_t off) {
     if (off < 0 || off + 1 > s->n_aux) return fail(OT_ERR_INVALID, "CSG program out of range");
@@ -457,9 +474,11 @@ static int validate_scene(const ot_scene_desc* s) {
         if (nd.end <= i || nd.end > s->n_nodes) return fail(OT_ERR_INVALID, "node.end out of range at " + std::to_string(i));
         if (nd.kind == OT_NODE_LEAF) {
             if (nd.end != i + 1) return fail(OT_ERR_INVALID, "leaf.end must be index+1");
-            if (nd.shape < 0 || nd.shape > OT_SHAPE_ASPHERE_CHEB) return fail(OT_ERR_UNSUPPORTED, "unknown shape kind");
+            if (nd.shape < 0 || nd.shape > OT_SHAPE_IMPLICIT_CHEB) return fail(OT_ERR_UNSUPPORTED, "unknown shape kind");
             if (nd.shape == OT_SHAPE_ASPHERE_CHEB && series_record_len(s, nd.aux, 3) < 0)
                 return fail(OT_ERR_INVALID, "asphere series record out of range at node " + std::to_string(i));
+            if (nd.shape == OT_SHAPE_IMPLICIT_CHEB && implicit_record_len(s, nd.aux) < 0)
+                return fail(OT_ERR_INVALID, "implicit series record malformed or out of range at node " + std::to_string(i));
             if (nd.interaction < 0 || nd.interaction > OT_INT_BLOCK) return fail(OT_ERR_UNSUPPORTED, "unknown interaction kind");
             if (nd.interaction == OT_INT_REFRACT &&
                 (nd.mat1 < 0 || nd.mat1 >= s->n_materials || nd.mat2 < 0 || nd.mat2 >= s->n_materials))
@@ -606,6 +625,9 @@ int ot_scene_upload(ot_ctx* c, const ot_scene_desc* s) {
     c->n_nodes = s->n_nodes; c->n_mats = s->n_materials; c->n_aux = s->n_aux;
     c->n_slots = s->n_count_slots; c->max_children = s->max_children; c->unit = s->unit;
     c->features = scene_features(s);
+    c->has_implicit = false;
+    for (int i = 0; i < s->n_nodes; ++i)
+        if (s->nodes[i].kind == OT_NODE_LEAF && s->nodes[i].shape == OT_SHAPE_IMPLICIT_CHEB) c->has_implicit = true;
     c->root_grid = s->root_grid;
     c->root_pack = packable_cells(s) > 0 ? s->n_aux : -1;
     c->cache_mat = -1;
@@ -1233,7 +1255,7 @@ template <class T> static bool trees_plan(const ot_ctx* c, int32_t cap, int64_t 
         // ... and the node and material records alone in LDS when they leave room for the queues (instanced runs fold thousands of
         // lattice members into a few records: the walk's dependent reads then come from LDS, only poses and grids from L2)
         const size_t head = ((size_t)(sizeof(T) == 8 ? c->head64 : c->head32) + 16 * (size_t)c->n_runs + 15) & ~(size_t)15;  // records + the run table
-        if (head > 0 && head + 4 * 3 * entry <= room / 2 && c->opt_trees_global != 2 && tree_kernel<T, SegPlanes<T>>(4, 2)) { p->img_global = 2; img = head; }
+        if (head > 0 && head + 4 * 3 * entry <= room / 2 && c->opt_trees_global != 2 && !c->has_implicit && tree_kernel<T, SegPlanes<T>>(4, 2)) { p->img_global = 2; img = head; }
     }
     const int64_t need = ((int64_t)cap + 1) / 2, fit = (int64_t)((room - img) / (4 * entry));
     // entries in LDS: two under small caps (queues stay short: a third workgroup per CU is worth more than the third entry —

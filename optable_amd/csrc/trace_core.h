@@ -49,8 +49,10 @@ enum : uint32_t {
     F_MISC = 256,    // the rarer curved shapes: cylinder walls, polygons in a tilted plane (needs F_CURVED)
     F_SUBTREE = 512, // cells of the top-level grid may list whole groups (stale boxes, gridded groups) besides leaves
     F_ALL = 1023,
-    F_FLAT = 1024    // (not part of F_ALL) planar scenes under a top-level grid: candidates go through a wave-wide
+    F_FLAT = 1024,   // (not part of F_ALL) planar scenes under a top-level grid: candidates go through a wave-wide
                      // queue of (ray, leaf) pairs and are tested with full lanes (flat_grid_hit)
+    F_NOIMPL = 2048  // (not part of F_ALL) without the implicit-series surfaces: the lane-per-tree kernel that keeps its records in
+                     // LDS and its aux tables in global memory (IMG = 2), which the host never gives such a scene
 };
 
 template <class T> struct Num;
@@ -306,6 +308,38 @@ template <class T> __device__ __forceinline__ T cheb_eval(const T* rec, T x, int
     return c[0] + T(0.5) * t2 * b1 - b2;
 }
 
+// A user's implicit surface as a tensor series (optable_amd/implicit.py; record layout: include/optable_hip.h, OT_IMPLICIT_HEADER).
+// Block b of sum_ijk c_ijk T_i(tx) T_j(ty) T_k(tz) as three nested Clenshaw recurrences: the innermost over the contiguous
+// k run of one (i, j), the outer two kept as loops (#pragma unroll 1) so that an inlined copy costs a dozen registers and
+// not nx * ny copies of the inner loop.  Each level runs the uniform step down to k = 0 and ends with b0 - t b1.
+template <class T> __device__ __forceinline__ T cheb3_eval(const T* rec, int block, T x, T y, T z) {
+    const int nx = (int)rec[0], ny = (int)rec[1], nz = (int)rec[2];
+    const T tx = (x - rec[3]) * rec[6], ty = (y - rec[4]) * rec[7], tz = (z - rec[5]) * rec[8];
+    const T* c = rec + OT_IMPLICIT_HEADER + (block * nx * ny + nx * ny - 1) * nz;  // the last (i, j) run of the block
+    T ax1 = T(0), ax2 = T(0);
+#pragma unroll 1
+    for (int i = nx - 1; i >= 0; --i) {
+        T ay1 = T(0), ay2 = T(0);
+#pragma unroll 1
+        for (int j = ny - 1; j >= 0; --j, c -= nz) {
+            T az1 = T(0), az2 = T(0);
+#pragma unroll 1
+            for (int k = nz - 1; k >= 0; --k) {
+                const T b0 = c[k] + T(2) * tz * az1 - az2;
+                az2 = az1;
+                az1 = b0;
+            }
+            const T b0 = (az1 - tz * az2) + T(2) * ty * ay1 - ay2;
+            ay2 = ay1;
+            ay1 = b0;
+        }
+        const T b0 = (ay1 - ty * ay2) + T(2) * tx * ax1 - ax2;
+        ax2 = ax1;
+        ax1 = b0;
+    }
+    return ax1 - tx * ax2;
+}
+
 template <class T, uint32_t F> __device__ __forceinline__ T material_index(const Scene<T>& sc, const DMat<T>& m, T wavelength_m) {
     if (m.kind == OT_MAT_CONST) return m.n;
     if constexpr ((F & F_MISC) != 0) {
@@ -509,6 +543,21 @@ __device__ __forceinline__ bool curved_boundary(const Scene<T>& sc, const DNode<
             return nd.p[2] <= th && th <= nd.p[3] && -nd.p[1] <= Pz && Pz <= nd.p[1];
         }
         if (nd.shape == OT_SHAPE_ASPHERE_CHEB) return sqrt_t(Py * Py + Pz * Pz) <= nd.p[0] + T(1e-12);  // surfaces.py:375-378
+        if (nd.shape == OT_SHAPE_IMPLICIT_CHEB) {  // the aperture family measured from the user's within_boundary
+            // fp32: the bounds widened by 1e-6 relative — a hit ON a bound of the box (a cylinder wall at |x| = R) rounds to
+            // either side of it, where fp64 has the record's 1e-12 slack
+            const T* rec = sc.aux + nd.aux;
+            const int ap = (int)rec[10];
+            const T rel = sizeof(T) == 4 ? T(1e-6) : T(0);
+            if (ap == OT_APERTURE_DISC || ap == OT_APERTURE_BALL) {
+                const T u = ap == OT_APERTURE_BALL ? Px : T(0), v = ap == OT_APERTURE_BALL ? Py : Py - rec[4];
+                const T w = ap == OT_APERTURE_BALL ? Pz : Pz - rec[5];
+                return u * u + v * v + w * w <= rec[11] * (T(1) + T(2) * rel);
+            }
+            auto in = [&](T lo, T hi, T v) { const T e = rel * max_t(abs_t(lo), abs_t(hi)); return lo - e <= v && v <= hi + e; };
+            const bool yz = in(rec[14], rec[15], Py) && in(rec[16], rec[17], Pz);
+            return ap == OT_APERTURE_RECT ? yz : (yz && in(rec[12], rec[13], Px));
+        }
     }
     switch (nd.shape) {
         case OT_SHAPE_SPHERE:
@@ -524,9 +573,12 @@ __device__ __forceinline__ bool curved_boundary(const Scene<T>& sc, const DNode<
 }
 
 // Implicit function g(t) = f(o + t d) of the non-planar shapes and its derivative.
-template <class T, uint32_t F>
+// IMPL: the implicit series (OT_SHAPE_IMPLICIT_CHEB) and nothing else.  hit_leaf searches that shape on a path of its own
+// (hit_implicit), so that the shapes' common path does not carry the registers of its loop nest.
+template <class T, uint32_t F, bool IMPL = false>
 __device__ __forceinline__ T surf_g(const Scene<T>& sc, const DNode<T>& nd, T ox, T oy, T oz, T dx, T dy, T dz, T t, T* dg) {
     const T Px = ox + t * dx, Py = oy + t * dy, Pz = oz + t * dz;
+    if constexpr (IMPL) return cheb3_eval(sc.aux + nd.aux, 0, Px, Py, Pz);  // (no slope: hit_implicit's polish takes none, dg unused)
     if constexpr (F & F_MISC) {
         if (nd.shape == OT_SHAPE_CYLINDER) {
             if (dg) *dg = T(2) * (Px * dx + Py * dy);
@@ -560,14 +612,32 @@ __device__ __forceinline__ T surf_g(const Scene<T>& sc, const DNode<T>& nd, T ox
 // Root of g inside a bracket with a sign change: Newton steps kept inside the shrinking
 // bracket, bisection when a step leaves it (the reference polishes the same bracket with
 // scipy brentq to xtol 2e-12; both converge on the same root).
-template <class T, uint32_t F>
+template <class T, uint32_t F, bool IMPL = false>
 __device__ __forceinline__ T polish_root(const Scene<T>& sc, const DNode<T>& nd, T ox, T oy, T oz, T dx, T dy, T dz, T a, T b,
                                          T ga, T gb) {
     T t = a - qd(ga * (b - a), gb - ga);  // false-position start
     if (!(t > a && t < b)) t = T(0.5) * (a + b);
+    if constexpr (IMPL) {
+        // The implicit series: false position with the Illinois weight (superlinear, no gradient series — three more loop nests
+        // per step cost the all-features kernels spills), bisection when a step leaves the bracket, to the same tolerance.
+        int side = 0;
+#pragma unroll 1
+        for (int it = 0; it < 96; ++it) {
+            const T g = surf_g<T, F, true>(sc, nd, ox, oy, oz, dx, dy, dz, t, (T*)nullptr);
+            if (g == T(0)) return t;
+            if ((g < T(0)) == (ga < T(0))) { a = t; ga = g; if (side == -1) gb *= T(0.5); side = -1; }
+            else { b = t; gb = g; if (side == 1) ga *= T(0.5); side = 1; }
+            if (b - a <= Num<T>::root_tol() * abs_t(t) + Num<T>::tiny()) break;
+            T tn = a - qd(ga * (b - a), gb - ga);
+            if (!(tn > a && tn < b)) tn = T(0.5) * (a + b);
+            if (tn == t || !(tn > a && tn < b)) break;  // the bracket is two neighbouring reals
+            t = tn;
+        }
+        return t;
+    }
     for (int it = 0; it < 48; ++it) {
         T dg;
-        const T g = surf_g<T, F>(sc, nd, ox, oy, oz, dx, dy, dz, t, &dg);
+        const T g = surf_g<T, F, IMPL>(sc, nd, ox, oy, oz, dx, dy, dz, t, &dg);
         if (g == T(0)) return t;
         if ((g < T(0)) == (ga < T(0))) { a = t; ga = g; } else { b = t; gb = g; }
         T tn = t - qd(g, dg);
@@ -580,6 +650,42 @@ __device__ __forceinline__ T polish_root(const Scene<T>& sc, const DNode<T>& nd,
         if (b - a <= Num<T>::root_tol() * abs_t(t)) break;
     }
     return t;
+}
+
+// hit_leaf's search for a user's implicit surface given as a series (OT_SHAPE_IMPLICIT_CHEB): the same ten samples of the
+// same interval [a, b], the same brackets, the same polish and filters as hit_leaf below — only rolled, so
+// that the instruction stream holds one copy of the series evaluator instead of ten.
+template <class T, uint32_t F>
+__device__ __forceinline__ bool hit_implicit(const Scene<T>& sc, const DNode<T>& nd, T ox, T oy, T oz, T dx, T dy, T dz, T len,
+                                             T a, T b, T step, T& t_out, T& Px, T& Py, T& Pz) {
+    const T EPS = Num<T>::eps_t();
+    auto sample = [&](T t) { return surf_g<T, F, true>(sc, nd, ox, oy, oz, dx, dy, dz, t, (T*)nullptr); };
+    uint32_t crossings = 0;
+    T gl = sample(a);
+#pragma unroll 1
+    for (int i = 1; i < 10; ++i) {
+        const T gr = sample((i == 9) ? b : a + T(i) * step);
+        const bool crossing = sizeof(T) == 4 ? ((gl < T(0)) != (gr < T(0))) : (gl * gr < T(0));
+        if (crossing) crossings |= 1u << i;
+        gl = gr;
+    }
+#pragma unroll 1
+    while (crossings) {
+        const int i = __builtin_ctz(crossings);
+        crossings &= crossings - 1;
+        const T tl = (i == 1) ? a : a + T(i - 1) * step, tr = (i == 9) ? b : a + T(i) * step;
+        // (no start-point shortcut: f has the user's scale, so "grazing" has no fixed threshold; the root at the start point
+        // of a ray that left this surface is polished and dropped by the |t| < EPS filter, as the reference does)
+        const T t = polish_root<T, F, true>(sc, nd, ox, oy, oz, dx, dy, dz, tl, tr, sample(tl), sample(tr));
+        if (t >= T(0) && abs_t(t) >= EPS && t <= len) {
+            const T X = ox + t * dx, Y = oy + t * dy, Z = oz + t * dz;
+            if (curved_boundary<T, F>(sc, nd, X, Y, Z)) {
+                t_out = t; Px = X; Py = Y; Pz = Z;
+                return true;
+            }
+        }
+    }
+    return false;
 }
 
 // intersect_point_local, non-planar branch (optical_component.py:197-233), ray already in the
@@ -631,6 +737,12 @@ __device__ __forceinline__ bool hit_leaf(const Scene<T>& sc, const DNode<T>& nd,
                 }
             }
             return false;
+        }
+        // F_NOIMPL (the IMG = 2 tree kernel) has no branch for this shape: an implicit leaf would fall through to the generic
+        // path below and be searched as another shape.  trees_plan (optable_hip.hip) never gives that kernel a scene with one
+        // (tests/test_gpu_implicit.py checks the launch); even a one-compare guard here costs the kernel 10 spilled registers.
+        if constexpr ((F & F_MISC) != 0 && (F & F_NOIMPL) == 0) {
+            if (nd.shape == OT_SHAPE_IMPLICIT_CHEB) return hit_implicit<T, F>(sc, nd, ox, oy, oz, dx, dy, dz, len, a, b, step, t_out, Px, Py, Pz);
         }
         // sign samples: aspheres through the division-free form (same sign, and the polish below only uses
         // the bracket values for its starting guess)
@@ -1475,6 +1587,20 @@ template <class T> __device__ __forceinline__ void cdiv(T ar, T ai, T br, T bi, 
     ci = (ai * br - ar * bi) * inv;
 }
 
+// s grad f / |grad f| of an implicit series, s the sign measured against the user's normal.
+template <class T> __device__ __forceinline__ void implicit_normal(const T* rec, T Px, T Py, T Pz, T& nx, T& ny, T& nz) {
+    T gx = T(0), gy = T(0), gz = T(0);
+#pragma unroll 1
+    for (int b = 1; b < 4; ++b) {
+        const T v = cheb3_eval(rec, b, Px, Py, Pz);
+        if (b == 1) gx = v;
+        else if (b == 2) gy = v;
+        else gz = v;
+    }
+    const T inv = rec[9] * rsqrt_t(gx * gx + gy * gy + gz * gz);
+    nx = gx * inv; ny = gy * inv; nz = gz * inv;
+}
+
 template <class T, uint32_t F>
 __device__ __forceinline__ void surf_normal(const Scene<T>& sc, const DNode<T>& nd, T Px, T Py, T Pz, T& nx, T& ny, T& nz) {
     nx = T(1); ny = T(0); nz = T(0);  // Plane._normal
@@ -1482,6 +1608,12 @@ __device__ __forceinline__ void surf_normal(const Scene<T>& sc, const DNode<T>& 
         if (nd.shape == OT_SHAPE_POLYGON2D) {
             const T* rec = sc.aux + nd.aux;
             nx = rec[1]; ny = rec[2]; nz = rec[3];
+        }
+    }
+    if constexpr ((F & F_MISC) != 0 && (F & F_NOIMPL) == 0) {
+        if (nd.shape == OT_SHAPE_IMPLICIT_CHEB) {
+            implicit_normal(sc.aux + nd.aux, Px, Py, Pz, nx, ny, nz);
+            return;
         }
     }
     if constexpr (F & F_CURVED) {

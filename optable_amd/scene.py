@@ -15,8 +15,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import abi
-from .components import MIRROR, REFRACT, LENS, ROC_INF
+from . import abi, shapes
+from .components import MIRROR, REFRACT, LENS, ROC_INF, ROC_ASPHERE
 from .materials import Material
 
 
@@ -40,6 +40,7 @@ class CompiledScene:
         self.n_aux = len(aux)
         self.leaves = leaves        # leaf_id -> component
         self.hooks = {}             # leaf_id -> component whose interact_local is the user's Python (adapter.host_hook)
+        self.implicit = {}          # leaf_id -> (component, aux record): user surfaces traced as 3-D series (implicit.py)
         self.limited = limited      # count_slot -> component
         self.max_children = max_children
         self.unit = unit
@@ -87,7 +88,7 @@ class CompiledScene:
         sc.n_aux = len(aux)
         sc.leaves = [None] * n_leaves
         sc.limited = [types.SimpleNamespace(max_interact_count=int(m), _interact_count={}) for m in tables["limited_max"]]
-        sc.hooks = {}
+        sc.hooks, sc.implicit = {}, {}
         sc.max_children, sc.unit, sc.root_grid = max_children, float(tables["unit"][0]), root_grid
         sc.always_branches, sc.wavelength_range = bool(always), None
         return sc
@@ -98,8 +99,10 @@ class CompiledScene:
 
 
 class _Builder:
-    def __init__(self, accelerate=True):
+    def __init__(self, accelerate=True, implicit_surfaces=False):
         self.accelerate = accelerate
+        self.implicit_surfaces = implicit_surfaces
+        self.implicit = {}    # leaf_id -> (component, aux record) of the leaves traced as 3-D series (table.ray_tracing checks their hits)
         self.nodes, self.materials, self.aux = [], [], []
         self.mat_index = {}
         self.leaves, self.limited, self.hooks = [], [], {}
@@ -249,10 +252,13 @@ class _Builder:
             raise SceneError(f"{type(comp).__name__} is not an optical component")
         surf = comp.surface
         try:
-            low = adapter.lower_surface(surf)
+            low = adapter.lower_surface(surf, implicit=self.implicit_surfaces)
             inter = adapter.lower_interaction(comp)
         except NotImplementedError as exc:
             raise SceneError(f"{type(comp).__name__}: {exc}") from exc
+        if low.kind == shapes.IMPLICIT_CHEB and inter.get("roc_kind") == ROC_ASPHERE:
+            raise SceneError(f"{type(comp).__name__}: a callable roc on the implicit surface {type(surf).__name__} has no device "
+                             "form; give the component a number (or no roc: infinity)")
         node = abi.OtNode()
         node.kind, node.end = abi.NODE_LEAF, len(self.nodes) + 1
         node.flags = abi.NODE_CHECK_AABB if in_group else 0
@@ -285,6 +291,8 @@ class _Builder:
         node.leaf_id = len(self.leaves)
         if inter.get("host_hook"):
             self.hooks[node.leaf_id] = comp
+        if low.kind == shapes.IMPLICIT_CHEB:
+            self.implicit[node.leaf_id] = (comp, low.aux)
         self.leaves.append(comp)
         self.leaf_pose.append((np.asarray(comp.transform_matrix, dtype=float), np.asarray(comp.origin, dtype=float),
                                np.asarray(surf.get_bbox_local(), dtype=float)))
@@ -492,8 +500,10 @@ def _root_grid(b, tops):
     return offset
 
 
-def compile_scene(components, unit=1e-2, accelerate=True) -> CompiledScene:
-    b = _Builder(accelerate)
+def compile_scene(components, unit=1e-2, accelerate=True, implicit_surfaces=False) -> CompiledScene:
+    """implicit_surfaces: a non-planar user surface that no built-in shape reproduces is traced as a verified 3-D Chebyshev
+    series of its f (implicit.py) instead of being refused."""
+    b = _Builder(accelerate, implicit_surfaces)
     tops = []
     for comp in components:
         tops.append(len(b.nodes))
@@ -509,4 +519,5 @@ def compile_scene(components, unit=1e-2, accelerate=True) -> CompiledScene:
     scene = CompiledScene(b.nodes, b.materials, b.aux, b.leaves, b.limited, b.max_children, unit, root, b.always_branches,
                           b.wavelength_range)
     scene.hooks = b.hooks
+    scene.implicit = b.implicit
     return scene

@@ -14,7 +14,7 @@ from .geometry import Base, unit_vector
 from .slab import solve_ray_bboxes_intersections
 
 # shape kinds == ot_shape_kind
-CIRCLE, RECT, POLYGON2D, POLYGON3D, SPHERE, ASPHERE_PARAM, ASPHERE_EXACT, CYLINDER, POINT, CSG, ASPHERE_CHEB = range(11)
+CIRCLE, RECT, POLYGON2D, POLYGON3D, SPHERE, ASPHERE_PARAM, ASPHERE_EXACT, CYLINDER, POINT, CSG, ASPHERE_CHEB, IMPLICIT_CHEB = range(12)
 # CSG postfix opcodes (aux program): operand kinds reuse CIRCLE/RECT/POLYGON2D
 CSG_OR, CSG_ANDNOT = 100, 101
 

@@ -81,10 +81,14 @@ class OpticalTable:
         return self._bbox
 
     accelerate = True  # attach the acceleration grids (scene.py); results do not depend on it
+    # trace non-planar user surfaces that no built-in shape reproduces as verified 3-D Chebyshev series of their f (implicit.py)
+    # instead of refusing them.  ray_tracing checks every hit on such a surface against the user's within_boundary and f;
+    # trace_batch does not, and opting in is the user's acceptance of the measured aperture there.
+    implicit_surfaces = False
 
     def compile(self):
         """Flatten the current components into device tables (poses are read now)."""
-        return compile_scene(self.components, self.unit, accelerate=self.accelerate)
+        return compile_scene(self.components, self.unit, accelerate=self.accelerate, implicit_surfaces=self.implicit_surfaces)
 
     # -- the hot path ---------------------------------------------------------------------------
     def ray_tracing(self, rays: Union[Ray, List[Ray]], perfomance_limit=None):
@@ -414,6 +418,7 @@ class OpticalTable:
                     per_tree = np.bincount(host_segs["ray"], minlength=len(sub))
                     self._last_trace_num = int(per_tree[segs.capped.cpu().numpy()].max())
             total_capped += capped
+            check_implicit_hits(scene, host_segs)
             _scatter_segments(host_segs, sub, pick, per_ray)
         if scene.limited:
             host = counts.cpu().numpy()
@@ -589,6 +594,33 @@ def _fused_capped(host_segs, cap):
     each processed a ray, so `exit_flag` was never set (optical_table.py:93-98, 138-143) — i.e.
     the tree filled all `cap` slots, whether or not a queued ray was actually dropped."""
     return int(np.sum(host_segs["count"] >= cap))
+
+
+def check_implicit_hits(scene, segs):
+    """Run-time check of the surfaces traced as 3-D series (scene.implicit): every segment that ends on one is taken into the
+    leaf's frame and asked of the user's own methods — within_boundary must hold and |f| must be within what a hit point off
+    by 1e-7 of the scene scale along grad f gives.  The aperture family was measured on a few thousand surface points at
+    compile time (implicit.py); a feature smaller than that sampling resolves (a hole of ~1 % of the aperture) shows here."""
+    from . import implicit
+    from .scene import SceneError
+
+    leaves = getattr(scene, "implicit", None)
+    if not leaves:
+        return
+    surface = np.asarray(segs["surface"])
+    for s in np.nonzero(np.isin(surface, list(leaves)))[0]:
+        comp, rec = leaves[int(surface[s])]
+        P = (np.array([segs["ox"][s], segs["oy"][s], segs["oz"][s]], dtype=float)
+             + float(segs["length"][s]) * np.array([segs["dx"][s], segs["dy"][s], segs["dz"][s]], dtype=float))
+        loc = np.asarray(comp.transform_matrix, dtype=float).T @ (P - np.asarray(comp.origin, dtype=float))
+        surf = comp.surface
+        inside, fv = bool(surf.within_boundary(loc)), float(surf.f(loc))
+        tol = float(np.linalg.norm(implicit.record_gradient(rec, loc))) * 1e-7 * max(1.0, float(np.abs(loc).max())) + 4 * implicit.REL_TOL * rec[19]
+        if not inside or not abs(fv) <= tol:
+            what = "its within_boundary(P) is False" if not inside else f"its f(P) = {fv:.3e} (allowed {tol:.1e})"
+            raise SceneError(f"{type(comp).__name__} with implicit surface {type(surf).__name__}: the device hit it at local "
+                             f"P = {loc.tolist()}, but {what}: the aperture or surface measured at compile time does not hold "
+                             "there (a feature finer than the measurement's sampling)")
 
 
 def _scatter_segments(host_segs, sources, pick, per_ray):

@@ -21,6 +21,7 @@ sys.path.insert(2, ROOT)  # tests/scenes.py takes the BASELINE generators from o
 import numpy as np  # noqa: E402
 import optable as ref  # noqa: E402  (the reference)
 import scenes  # noqa: E402
+import implicit_scenes  # noqa: E402
 
 assert ref.__file__.startswith("/root/reference"), ref.__file__
 OUT = os.path.join(ROOT, "tests", "golden")
@@ -60,7 +61,7 @@ def ray_rows(rays):
 
 
 def run(name):
-    sc = {**scenes.SCENES, **scenes.HOOKED_SCENES}[name](ref)
+    sc = {**scenes.SCENES, **scenes.HOOKED_SCENES, **implicit_scenes.IMPLICIT_SCENES}[name](ref)
     table = ref.OpticalTable()
     table.add_components(sc["components"])
     table.add_monitors(sc["monitors"])
@@ -377,7 +378,7 @@ def adapter_fixture():
 
 
 if __name__ == "__main__":
-    names = sys.argv[1:] or list(scenes.SCENES) + list(scenes.HOOKED_SCENES)
+    names = sys.argv[1:] or list(scenes.SCENES) + list(scenes.HOOKED_SCENES) + list(implicit_scenes.IMPLICIT_SCENES)
     for nm in names:
         if nm in ("g14_slab", "g17_abcd", "g20_interact", "g22_calibrate", "g23_exports", "g27_real_example", "g28_adapter", "examples"):
             continue
