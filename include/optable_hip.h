@@ -399,7 +399,8 @@ int ot_debug_generation_mismatches(ot_ctx* ctx, int64_t* count);
  * scratch ring), [1] threads per workgroup, [2] workgroups per CU the occupancy
  * query allowed, [3] workgroups launched, [4] dynamic LDS bytes per workgroup, [5] list capacity per wave (rolling),
  * [6] 1 = mixed generations, [7] bit 0 = candidate pair queue (OT_OPT_FLAT_QUEUE took effect), bit 1 = records in LDS,
- * bit 2 = append layout, bit 3 = tiled layout, bit 4 = workgroup-wide block pool (OT_OPT_BLOCK_POOL; [5] = its slots). */
+ * bit 2 = append layout, bit 3 = tiled layout, bit 4 = workgroup-wide block pool (OT_OPT_BLOCK_POOL; [5] = its slots),
+ * bit 5 = rays in registers, refilled in place (OT_OPT_REFILL: reported as kernel 2; [5] = rays per ticket). */
 int ot_debug_last_launch(ot_ctx* ctx, int32_t info[8]);
 
 /* Monitor.record (monitor.py:183-193): intersect finished segments with a rectangular

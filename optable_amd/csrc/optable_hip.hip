@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <tuple>
 #include <chrono>
 #include <vector>
 
@@ -46,19 +47,58 @@ struct Scratch {
     }
 };
 
+// The uploaded scene in one precision (fill_blob): [0] single, [1] double in ot_ctx, image_of<T>() picks
+struct SceneImage {
+    void* blob = nullptr;
+    size_t bytes = 0;
+    size_t head = 0;        // node + material records at the front of the image (k_trace_trees IMG = 2 keeps these in LDS)
+    int32_t runs_word = 0;  // instanced runs folded by fill_blob (trace_core.h NodeRef)
+};
+
+// Shape of a launch as ot_debug_last_launch reports it (include/optable_hip.h), in the order of info[0..7]
+enum : int32_t { LL_PAIR_QUEUE = 1, LL_REC_LDS = 2, LL_APPEND = 4, LL_TILES = 8, LL_POOL = 16, LL_REFILL = 32 };  // bits of info[7]
+struct LaunchShape {
+    int32_t kernel, threads, per_cu, grid, lds_bytes;
+    int32_t cap;    // rolling lists: list capacity per wave; refill: rays per ticket; pool: its slots; lane per tree: queue entries in LDS
+    int32_t mixed;  // 1 = mixed generations; lane per tree: queue entries in the scratch ring
+    int32_t flags;  // LL_*
+};
+
+// Heavy scenes (launch_rolling): what classify_rolling makes of the scene and the options, ...
+struct RollingScene {
+    int fr = 0;                                // preset of k_trace_rolling / k_trace_refill / k_trace_pool (tables.h): 0 FR, 1 FC, 2 FD, 3 F_ALL, 4 FRP
+    bool mix = false;                          // lists mix generations
+    bool img_fits = false;                     // the image goes to LDS next to the lists; else: read from L2, by the all-features preset
+    bool flat_ok = false;                      // candidates through the wave-wide pair queue (flat_grid_hit) ...
+    int32_t flat_cap = 0;                      // ... of at most this many pairs a round
+    size_t img = 0, entry = 0, rec_bytes = 0;  // bytes: the image in whole 16, a list entry, the record of a live ray
+    int32_t cap0 = 0;                          // list capacity asked for
+    auto tie() const { return std::tie(fr, mix, img, img_fits, flat_ok, flat_cap, entry, rec_bytes, cap0); }
+};
+// ... everything plan_rolling may read (it sees no ot_ctx, so no option can move a plan without being part of this key), ...
+struct RollingPlanArgs {
+    RollingScene scene;
+    int32_t opt_rec_lds = -1;  // OT_OPT_LDS_RECORDS
+    bool sweep_room = false;   // the pair queue's room is the plan's to choose (OT_OPT_FLAT_QUEUE = 1)
+    uint64_t upload = 0;       // serial of the ot_scene_upload the scene came with (0: no plan yet)
+    bool operator==(const RollingPlanArgs& o) const { return scene.tie() == o.scene.tie() && opt_rec_lds == o.opt_rec_lds && sweep_room == o.sweep_room && upload == o.upload; }
+};
+// ... one placement of image and records with the waves per CU it allows (rolling_occupancy; waves = 0: none fits), ...
+struct RollingTry { int waves = 0, wpb = 0, per_cu = 0; int32_t cap = 0, capl = 0; size_t lds = 0; bool lds_img = false; };  // capl > 0: the records of the first `capl` list positions in LDS
+// ... and the launch plan (a dozen occupancy queries): kept per precision and output layout, reused while its arguments compare equal
+struct RollingPlan { RollingPlanArgs args; RollingTry at; int32_t flat_cap = 0; };
+
 struct ot_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     int n_cus = 256;
-    size_t lds_limit = 64 * 1024;
     // scene
     bool has_scene = false;
     bool has_implicit = false;  // a leaf is OT_SHAPE_IMPLICIT_CHEB (the IMG = 2 tree kernel lacks its normal: kernels.h k_trace_trees)
-    void *blob64 = nullptr, *blob32 = nullptr;
-    size_t bytes64 = 0, bytes32 = 0;
-    size_t head64 = 0, head32 = 0;  // node + material records at the front of the image (k_trace_trees IMG = 2 keeps these in LDS)
+    SceneImage image[2];
+    uint64_t uploads = 0;  // ot_scene_upload calls that replaced the images
     int32_t n_nodes = 0, n_mats = 0, n_aux = 0, n_slots = 0, max_children = 0;
-    int32_t n_phys = 0, n_runs = 0, runs_word64 = 0, runs_word32 = 0;  // instanced runs folded by fill_blob (trace_core.h NodeRef)
+    int32_t n_phys = 0, n_runs = 0;  // instanced runs folded by fill_blob (trace_core.h NodeRef)
     int32_t opt_append_chunk = 512;  // append layout: slots per claim
     int32_t opt_instancing = 1;      // fold lattice children into instanced runs at upload
     bool opt_gen_parent = false;     // ot_trace_generation_*: next_tree[] = index of the parent ray (OT_OPT_GEN_PARENT_INDEX)
@@ -84,10 +124,7 @@ struct ot_ctx {
     int32_t opt_lds_limit_kb = 64;
     int32_t opt_kernel = 0;  // 0 auto, 1 fused (lane per ray), 2 rolling lists (the heavy-scene kernel)
     int32_t last_launch[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // ot_debug_last_launch
-    // heavy-scene launch plan per precision (a dozen occupancy queries): recomputed after an upload or an option change
-    struct RollingPlan { uint64_t epoch = 0; int wpb = 4, per_cu = 1; int32_t cap = 128, capl = 0, flat_cap = 0; bool lds = false, rec_lds = false; size_t lds_bytes = 0; };
     RollingPlan plan[2][2];  // [precision][output layout]
-    uint64_t plan_epoch = 1;
     int32_t opt_refill = 0;      // mixed scenes: rays in registers, refilled in place (k_trace_refill): 0 never (the lists; default: the two tie on cfg 3
                                  // in the append layout, 2.08-2.11 ms, and the lists win into [k][ray] slots, 3.7 against 4.7 ms), 1 whenever a kernel exists
     int32_t opt_refill_ticket = 0;  // rays per ticket of k_trace_refill (0 = by batch size)
@@ -118,6 +155,17 @@ struct ot_ctx {
     int64_t* pinned_state = nullptr;             // ot_trace_tree_*: page-locked landing place of the per-generation read-back
 };
 
+// derived scene facts, one definition each
+template <class T> static const SceneImage& image_of(const ot_ctx* c) { return c->image[sizeof(T) == 8 ? 1 : 0]; }
+// the generation, lane-per-ray and one-pass kernels stage the whole image in LDS (OT_OPT_LDS_LIMIT_KB), else read it from L2
+template <class T> static bool in_lds(const ot_ctx* c) { return image_of<T>(c).bytes <= (size_t)c->opt_lds_limit_kb * 1024; }
+// heavy scenes keep the count pass's decision per ray for the emit pass (kernels.h k_gen_pass); OT_OPT_GEN_REUSE: -1 auto
+static bool gen_reuse(const ot_ctx* c) { return c->opt_gen_reuse < 0 ? c->n_nodes >= 12 : c->opt_gen_reuse != 0; }
+static void set_last_launch(ot_ctx* c, const LaunchShape& s) {
+    const int32_t info[8] = {s.kernel, s.threads, s.per_cu, s.grid, s.lds_bytes, s.cap, s.mixed, s.flags};
+    memcpy(c->last_launch, info, sizeof info);
+}
+
 static int flush_events(ot_ctx* c) {
     if (c->events_used == 0) return 0;
     HIP_TRY(hipEventSynchronize(c->events[c->events_used - 1].second));
@@ -130,19 +178,20 @@ static int flush_events(ot_ctx* c) {
     c->events_used = 0;
     return 0;
 }
+// room for one more event pair at events[events_used]
+static int next_event_pair(ot_ctx* c) {
+    if (c->events_used < c->events.size()) return 0;
+    if (c->events.size() >= 1024) return flush_events(c);
+    hipEvent_t a, b;
+    HIP_TRY(hipEventCreate(&a));
+    HIP_TRY(hipEventCreate(&b));
+    c->events.push_back({a, b});
+    return 0;
+}
 static int timing_begin(ot_ctx* c) {
     if (!c->timing) return 0;
-    if (c->events_used == c->events.size()) {
-        if (c->events.size() >= 1024) {
-            int rc = flush_events(c);
-            if (rc) return rc;
-        } else {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a));
-            HIP_TRY(hipEventCreate(&b));
-            c->events.push_back({a, b});
-        }
-    }
+    const int rc = next_event_pair(c);
+    if (rc) return rc;
     HIP_TRY(hipEventRecord(c->events[c->events_used].first, c->stream));
     return 0;
 }
@@ -151,17 +200,8 @@ static int timing_begin(ot_ctx* c) {
 static int timing_pair(ot_ctx* c, hipEvent_t* start, hipEvent_t* stop) {
     *start = *stop = nullptr;
     if (!c->timing) return 0;
-    if (c->events_used == c->events.size()) {
-        if (c->events.size() >= 1024) {
-            int rc = flush_events(c);
-            if (rc) return rc;
-        } else {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a));
-            HIP_TRY(hipEventCreate(&b));
-            c->events.push_back({a, b});
-        }
-    }
+    const int rc = next_event_pair(c);
+    if (rc) return rc;
     *start = c->events[c->events_used].first;
     *stop = c->events[c->events_used].second;
     c->events_used += 1;
@@ -257,7 +297,7 @@ static std::vector<NodeRun> find_runs(const ot_scene_desc* s) {
 }
 
 template <class T> static void fill_blob(const ot_scene_desc* s, const std::vector<NodeRun>& runs_in, std::vector<uint8_t>& out, int32_t& n_phys,
-                                         int32_t& runs_word) {
+                                         SceneImage& im) {
     std::vector<NodeRun> runs = runs_in;
     const int64_t pack = packable_cells(s);
     int folded = 0, geo_reals = 0;
@@ -337,7 +377,8 @@ template <class T> static void fill_blob(const ot_scene_desc* s, const std::vect
             for (int k = 0; k < 6; ++k) aux[geo++] = (T)h.aabb[k];
         }
     }
-    runs_word = (int32_t)((nb + mb + ab) / 4);
+    im.head = nb + mb;
+    im.runs_word = (int32_t)((nb + mb + ab) / 4);
     int32_t* rt = reinterpret_cast<int32_t*>(out.data() + nb + mb + ab);
     for (size_t k = 0; k < runs.size(); ++k) { rt[4 * k] = runs[k].first; rt[4 * k + 1] = runs[k].count; rt[4 * k + 2] = runs[k].pnode; rt[4 * k + 3] = runs[k].geo; }
 }
@@ -553,10 +594,7 @@ int ot_ctx_create(int device, void* stream, ot_ctx** out) {
     c->device = device;
     c->stream = (hipStream_t)stream;  // NULL is the device's default (null) stream, e.g. torch's default
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
-        c->n_cus = prop.multiProcessorCount;
-        c->lds_limit = prop.maxSharedMemoryPerMultiProcessor ? prop.maxSharedMemoryPerMultiProcessor : prop.sharedMemPerBlock;
-    }
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cus = prop.multiProcessorCount;
     *out = c;
     return 0;
 }
@@ -566,19 +604,14 @@ int ot_ctx_destroy(ot_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     for (auto& e : c->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    if (c->blob64) (void)hipFree(c->blob64);
-    if (c->blob32) (void)hipFree(c->blob32);
+    for (SceneImage& im : c->image)
+        if (im.blob) (void)hipFree(im.blob);
     if (c->slot_max) (void)hipFree(c->slot_max);
-    if (c->gen.p) (void)hipFree(c->gen.p);
-    if (c->gen_rem.p) (void)hipFree(c->gen_rem.p);
-    if (c->gen_ahead.p) (void)hipFree(c->gen_ahead.p);
-    if (c->trees.p) (void)hipFree(c->trees.p);
+    for (Scratch* s : {&c->gen, &c->gen_rem, &c->gen_ahead, &c->trees, &c->scan_tmp, &c->mon, &c->blocked})
+        if (s->p) (void)hipFree(s->p);
     if (c->gen_mismatch) (void)hipFree(c->gen_mismatch);
     if (c->gen_chain) (void)hipFree(c->gen_chain);
     if (c->pinned_state) (void)hipHostFree(c->pinned_state);
-    if (c->scan_tmp.p) (void)hipFree(c->scan_tmp.p);
-    if (c->mon.p) (void)hipFree(c->mon.p);
-    if (c->blocked.p) (void)hipFree(c->blocked.p);
     delete c;
     return 0;
 }
@@ -605,23 +638,20 @@ int ot_scene_upload(ot_ctx* c, const ot_scene_desc* s) {
     rc = validate_root_grid(s);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    std::vector<uint8_t> b64, b32;
+    std::vector<uint8_t> host[2];
     const std::vector<NodeRun> runs = c->opt_instancing ? find_runs(s) : std::vector<NodeRun>();
-    int32_t n_phys = 0;
-    fill_blob<double>(s, runs, b64, n_phys, c->runs_word64);
-    fill_blob<float>(s, runs, b32, n_phys, c->runs_word32);
-    c->n_phys = n_phys;
+    fill_blob<float>(s, runs, host[0], c->n_phys, c->image[0]);
+    fill_blob<double>(s, runs, host[1], c->n_phys, c->image[1]);
     c->n_runs = (int32_t)runs.size();
     HIP_TRY(hipStreamSynchronize(c->stream));  // previous launches may still read the old scene
-    if (c->blob64) { (void)hipFree(c->blob64); c->blob64 = nullptr; }
-    if (c->blob32) { (void)hipFree(c->blob32); c->blob32 = nullptr; }
-    HIP_TRY(hipMalloc(&c->blob64, b64.size() ? b64.size() : 16));
-    HIP_TRY(hipMalloc(&c->blob32, b32.size() ? b32.size() : 16));
-    if (!b64.empty()) HIP_TRY(hipMemcpy(c->blob64, b64.data(), b64.size(), hipMemcpyHostToDevice));
-    if (!b32.empty()) HIP_TRY(hipMemcpy(c->blob32, b32.data(), b32.size(), hipMemcpyHostToDevice));
-    c->bytes64 = b64.size(); c->bytes32 = b32.size();
-    c->head64 = sizeof(DNode<double>) * (size_t)n_phys + sizeof(DMat<double>) * (size_t)s->n_materials;
-    c->head32 = sizeof(DNode<float>) * (size_t)n_phys + sizeof(DMat<float>) * (size_t)s->n_materials;
+    ++c->uploads;
+    for (int p = 0; p < 2; ++p) {
+        SceneImage& im = c->image[p];
+        if (im.blob) { (void)hipFree(im.blob); im.blob = nullptr; }
+        HIP_TRY(hipMalloc(&im.blob, host[p].size() ? host[p].size() : 16));
+        if (!host[p].empty()) HIP_TRY(hipMemcpy(im.blob, host[p].data(), host[p].size(), hipMemcpyHostToDevice));
+        im.bytes = host[p].size();
+    }
     c->n_nodes = s->n_nodes; c->n_mats = s->n_materials; c->n_aux = s->n_aux;
     c->n_slots = s->n_count_slots; c->max_children = s->max_children; c->unit = s->unit;
     c->features = scene_features(s);
@@ -657,7 +687,6 @@ int ot_scene_upload(ot_ctx* c, const ot_scene_desc* s) {
         HIP_TRY(hipMemcpy(c->slot_max, smax.data(), sizeof(int32_t) * smax.size(), hipMemcpyHostToDevice));
     }
     c->has_scene = true;
-    ++c->plan_epoch;
     return 0;
 }
 
@@ -696,10 +725,10 @@ template <class T> static int32_t pair_ok(const ot_ctx* c, const ot_segments* s,
 }
 
 template <class T> static SceneBlob make_blob(const ot_ctx* c) {
-    constexpr bool f64 = sizeof(T) == 8;
+    const SceneImage& im = image_of<T>(c);
     SceneBlob blob;
-    blob.words = (const uint32_t*)(f64 ? c->blob64 : c->blob32);
-    blob.n_words = (int32_t)((f64 ? c->bytes64 : c->bytes32) / 4);
+    blob.words = (const uint32_t*)im.blob;
+    blob.n_words = (int32_t)(im.bytes / 4);
     blob.n_nodes = c->n_nodes;
     blob.n_phys = c->n_phys;
     blob.n_mats = c->n_mats;
@@ -707,244 +736,254 @@ template <class T> static SceneBlob make_blob(const ot_ctx* c) {
     blob.root_pack = c->root_pack;
     blob.cache_mat = c->cache_mat;
     blob.n_runs = c->n_runs;
-    blob.runs_word = f64 ? c->runs_word64 : c->runs_word32;
+    blob.runs_word = im.runs_word;
     return blob;
 }
 
-// Heavy scenes: persistent waves with their own lists of live rays (k_trace_rolling).  OUT = SegsT<T>: the [k][ray] slots of
-// ot_trace_*; SegPlanes<T>: the append layout of ot_trace_append_*.
-template <class T, class OUT>
-static int launch_rolling(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const OUT& out, const AppendCtl& ac, int32_t* seg_count,
-                          int32_t* counts, int32_t n_classes) {
+// One kernel launch with everything that goes with it: the ticket words of the persistent kernels and the append cursor zeroed,
+// the timing pair attached to the dispatch, the error checked, the shape recorded for ot_debug_last_launch.  `ticket`, `cursor`:
+// NULL where the kernel has none.  Grid, workgroup size and dynamic LDS are the shape's.
+#ifdef OT_STAMP
+constexpr size_t TICKET_WORDS = 24;  // the counter + the phase stamps (ot_debug_stamps)
+#else
+constexpr size_t TICKET_WORDS = 1;
+#endif
+template <class... P>
+static int launch_kernel(ot_ctx* c, void (*kern)(P...), const LaunchShape& s, unsigned long long* ticket, unsigned long long* cursor,
+                         typename std::common_type<P>::type... args) {
+    if (s.lds_bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, s.lds_bytes));
+    if (ticket) HIP_TRY(hipMemsetAsync(ticket, 0, TICKET_WORDS * sizeof(unsigned long long), c->stream));
+    if (cursor) HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(unsigned long long), c->stream));
+    hipEvent_t ev0, ev1;
+    const int rc = timing_pair(c, &ev0, &ev1);
+    if (rc) return rc;
+    hipExtLaunchKernelGGL(kern, dim3(s.grid), dim3(s.threads), (uint32_t)s.lds_bytes, c->stream, ev0, ev1, 0u, args...);
+    HIP_TRY(hipGetLastError());
+    set_last_launch(c, s);
+    return 0;
+}
+// The ticket counter of the persistent kernels: TICKET_WORDS behind `scratch_bytes` of per-wave scratch in c->blocked (NULL: no memory)
+static unsigned long long* ticket_counter(ot_ctx* c, size_t scratch_bytes) {
+    if (c->blocked.ensure(scratch_bytes + 256)) return nullptr;
+    c->blocked_queue_off = scratch_bytes;
+    return (unsigned long long*)((uint8_t*)c->blocked.p + scratch_bytes);
+}
+
+// The planar presets of scenes under a top-level grid: 0 = FR, 1 = FRP, -1 = neither (k_trace_rolling numbers them 0 / 4, k_trace_trees 5 / 6)
+static int planar_grid_preset(const ot_ctx* c) {
     using namespace preset;  // tables.h
-    constexpr bool f64 = sizeof(T) == 8, append = std::is_same<OUT, SegPlanes<T>>::value;
-    const SceneBlob blob = make_blob<T>(c);
-    const size_t bytes = f64 ? c->bytes64 : c->bytes32;
-    const uint32_t need = c->features;
-    // Scenes under a top-level grid (many separate components, rays of a wave unrelated after the first bounce)
-    // mix generations in a list and top it up continuously.  Scenes whose rays all run through the same sequence
-    // of surfaces (cfg 5) keep generation-pure lists: mixing costs them more than the tails do (cfg 5 fp32:
-    // 36.6 vs 31.6 ms; cfg 3 fp32: 5.1 vs 5.5 ms).
-    const bool mix = c->opt_mix < 0 ? c->root_grid >= 0 : (c->opt_mix != 0 && c->root_grid >= 0);
-    const size_t img = ((bytes + 15) / 16) * 16;
-    const bool img_fits = c->opt_lds_limit_kb != 0 && img <= 140 * 1024;  // else: read from L2, by the all-features preset
-    const int fr = !img_fits ? 3 : ((c->root_grid >= 0 && (need & ~FR) == 0) ? 0 : ((c->root_grid >= 0 && (need & ~FRP) == 0) ? 4 : ((need & ~FC) == 0 ? 1 : ((need & ~FD) == 0 ? 2 : 3))));
-    // planar scenes under a top-level grid of leaves: candidates through a wave-wide pair queue (flat_grid_hit)
+    if (c->root_grid < 0) return -1;
+    return (c->features & ~FR) == 0 ? 0 : ((c->features & ~FRP) == 0 ? 1 : -1);
+}
+// LDS bytes of a pair queue with room for `room` pairs, per wave (kernels.h)
+template <class T> static size_t flat_lds_bytes(int32_t room) { return ((size_t)(FlatLds<T>::fixed_bytes + (size_t)room * 2) + 15) & ~(size_t)15; }
+// planar scenes under a top-level grid of leaves: candidates through a wave-wide pair queue (flat_grid_hit).  Returns the pairs a
+// round of the queue can hold, 0 when the scene does not qualify.  `planar`: the caller's kernel is one of the planar presets and
+// has nothing else against the queue (the callers differ there: classify_rolling, trees_flat_cap).
+static int32_t pair_queue_room(const ot_ctx* c, bool planar) {
     // pairs a round of the pair queue can hold: 512, not the worst case of 64 lanes x the fullest cells (cfg 3: 1152) — a round
     // that would overflow defers lanes (flat_grid_hit), and the 1.3 KB per wave are what lets 16 waves per CU run instead of 12
     const int32_t flat_full = 64 * FLAT_CELLS * (c->root_max_items > 0 ? c->root_max_items : 1);
     const int32_t flat_room = c->opt_flat > 1 ? c->opt_flat : 512;  // (>= one lane's worst case: 2 * FLAT_CELLS * 42 items = 168)
     const int32_t flat_cap = flat_full < flat_room ? flat_full : flat_room;
-    const bool flat_ok = c->opt_flat && mix && (fr == 0 || fr == 4) && c->root_pack >= 0 && flat_cap <= 8192 && c->n_runs == 0;  // queue entry = lane << 10 | index into the grid's item list
-    // Where the scene image and the records of the live rays live, and how many waves share an image.  The waves never
-    // synchronise after staging, so the workgroup size is only packaging: take what keeps most waves resident per CU
-    // (registers and LDS decide).  Preference: image + records in LDS (a pass then waits for nothing in global memory)
-    // when enough waves still fit; else image in LDS, records in the per-wave global scratch (L2); images beyond what
-    // LDS holds next to the lists are read from L2 (all-features preset only).
-    const size_t entry = mix ? 8 : 4;  // list entry: (ray index | segment index << 32), or the ray index alone (kernels.h)
-    const size_t flat_bytes = flat_ok ? (((size_t)(FlatLds<T>::fixed_bytes + (size_t)flat_cap * 2) + 15) & ~(size_t)15) : 0;  // per wave (kernels.h)
-    const size_t rec_bytes = 12 * sizeof(T) + 4 * (fr == 3 ? 2 : 1);  // per record of a live ray (kernels.h rec_int_words: the all-features preset keeps the count class)
+    const bool ok = c->opt_flat && planar && c->root_pack >= 0 && flat_cap <= 8192 && c->n_runs == 0;  // queue entry = lane << 10 | index into the grid's item list
+    return ok ? flat_cap : 0;
+}
+
+// Heavy scenes: persistent waves with their own lists of live rays (k_trace_rolling).  OUT = SegsT<T>: the [k][ray] slots of
+// ot_trace_*; SegPlanes<T>: the append layout of ot_trace_append_*.  Three steps: classify_rolling (the scene and the options),
+// plan_rolling (the occupancy search of the lists), and one launcher per kernel: launch_refill, launch_pool, launch_lists.
+template <class T> static RollingScene classify_rolling(const ot_ctx* c) {
+    using namespace preset;  // tables.h
+    RollingScene s;
+    const uint32_t need = c->features;
+    // Scenes under a top-level grid (many separate components, rays of a wave unrelated after the first bounce)
+    // mix generations in a list and top it up continuously.  Scenes whose rays all run through the same sequence
+    // of surfaces (cfg 5) keep generation-pure lists: mixing costs them more than the tails do (cfg 5 fp32:
+    // 36.6 vs 31.6 ms; cfg 3 fp32: 5.1 vs 5.5 ms).
+    s.mix = c->opt_mix < 0 ? c->root_grid >= 0 : (c->opt_mix != 0 && c->root_grid >= 0);
+    s.img = ((image_of<T>(c).bytes + 15) / 16) * 16;
+    s.img_fits = c->opt_lds_limit_kb != 0 && s.img <= 140 * 1024;  // else: read from L2, by the all-features preset
+    const int planar = planar_grid_preset(c);
+    s.fr = !s.img_fits ? 3 : (planar == 0 ? 0 : (planar == 1 ? 4 : ((need & ~FC) == 0 ? 1 : ((need & ~FD) == 0 ? 2 : 3))));
+    s.flat_cap = pair_queue_room(c, s.mix && (s.fr == 0 || s.fr == 4));  // (generation-pure lists have no pair-queue kernel)
+    s.flat_ok = s.flat_cap > 0;
+    s.entry = s.mix ? 8 : 4;  // list entry: (ray index | segment index << 32), or the ray index alone (kernels.h)
+    s.rec_bytes = 12 * sizeof(T) + 4 * (s.fr == 3 ? 2 : 1);  // per record of a live ray (kernels.h rec_int_words: the all-features preset keeps the count class)
     // List capacity.  Mixed lists (rings, a power of two): 128 (256: +4 %, 512: +25 % on cfg 3).  Generation-pure lists: the
     // longer the better for the lanes (a list shrinks as its rays die and every round ends in a partial pass: 45 lanes per
     // pass at 128 entries, 53 at 256, 58 at 512 on cfg 5), but only the first 128 positions keep their records in LDS and a
     // pass over the global part waits for its loads behind the segment stores of the pass before (one in-order counter):
     // cfg 5 fp32, append layout, 16 waves per CU: 14.9 ms at 128, 13.5 at 256, 16+ at 384 and beyond.
-    // Mixed scenes: the live rays in registers, refilled in place (k_trace_refill) — no list, no records, 1.5 KB of LDS per wave
-    // (pair queue) + 1.5 KB (the parked ride-along fields), so registers alone decide how many waves share a CU.
-    if (mix && img_fits && c->opt_refill > 0) {
-        const auto kf = refill_kernel<T, OUT>(fr, flat_ok);
-        if (kf) {
-            const int threads = refill_max_threads<T>(fr, flat_ok), waves = threads / 64;
-            const size_t park_bytes = flat_ok ? 6 * 64 * sizeof(T) : 0;
-            const size_t lds_f = img + (size_t)waves * (flat_bytes + park_bytes);
-            int per_cu = 0;
-            if (lds_f <= 158 * 1024) {
-                if (lds_f > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kf, threads, lds_f) != hipSuccess) per_cu = 0;
-            }
-            if (per_cu >= 1) {
-                if (c->opt_blocks_per_cu > 0) per_cu = c->opt_blocks_per_cu;
-                const int64_t want = (n + 64 * (int64_t)waves - 1) / (64 * (int64_t)waves);
-                const int64_t capf = (int64_t)c->n_cus * per_cu;
-                const int gridf = (int)(want < capf ? want : capf);
-                // rays per ticket (one atomic on the device-wide queue each): 256, less when the batch is small enough that
-                // whole tickets would leave waves without work
-                int64_t per_wave4 = n / ((int64_t)gridf * waves * 4);
-                int32_t ticket = c->opt_refill_ticket > 0 ? c->opt_refill_ticket : (int32_t)(per_wave4 >= 256 ? 256 : (per_wave4 < 64 ? 64 : (per_wave4 / 64) * 64));
-                if (c->blocked.ensure(256)) return fail(OT_ERR_HIP, "hipMalloc of the ticket counter failed");
-                c->blocked_queue_off = 0;
-                unsigned long long* queue = (unsigned long long*)c->blocked.p;
-#ifdef OT_STAMP
-                HIP_TRY(hipMemsetAsync(queue, 0, 24 * sizeof(unsigned long long), c->stream));
-#else
-                HIP_TRY(hipMemsetAsync(queue, 0, sizeof(unsigned long long), c->stream));
-#endif
-                if (append) HIP_TRY(hipMemsetAsync(ac.cursor, 0, sizeof(unsigned long long), c->stream));
-                hipEvent_t ev0, ev1;
-                int rc = timing_pair(c, &ev0, &ev1);
-                if (rc) return rc;
-                WaveScratch<T> ws = {nullptr, 0};
-                hipExtLaunchKernelGGL(kf, dim3(gridf), dim3(threads), (uint32_t)lds_f, c->stream, ev0, ev1, 0u, blob, (T)c->unit, view<T>(rays), n, K, out,
-                                      ac, seg_count, counts, n_classes, ws, ticket, 0, queue, 1, flat_ok ? flat_cap : 0);
-                HIP_TRY(hipGetLastError());
-                const int32_t shape[8] = {2, threads, per_cu, gridf, (int32_t)lds_f, ticket, 1, (flat_ok ? 1 : 0) | (append ? 4 : 0) | 32};  // bit 5: rays in registers
-                for (int q = 0; q < 8; ++q) c->last_launch[q] = shape[q];
-                return 0;
-            }
-        }
+    s.cap0 = s.mix ? c->opt_list_cap : (c->opt_list_cap_pure > 0 ? c->opt_list_cap_pure : 256);
+    return s;
+}
+
+// Where the scene image and the records of the live rays live, and how many waves share an image.  The waves never
+// synchronise after staging, so the workgroup size is only packaging: take what keeps most waves resident per CU
+// (registers and LDS decide).  Preference: image + records in LDS (a pass then waits for nothing in global memory)
+// when enough waves still fit; else image in LDS, records in the per-wave global scratch (L2); images beyond what
+// LDS holds next to the lists are read from L2 (all-features preset only).
+// most waves per CU for one placement: image in LDS or not, the first `capl` records of every list in LDS
+template <class T, class OUT>
+static int rolling_occupancy(const RollingScene& s, size_t flat_b, bool lds_img, int32_t CAP, int32_t CAPL, RollingTry* best) {
+    *best = RollingTry();
+    const void* k = (const void*)rolling_kernel<T, OUT>(s.fr, s.flat_ok, lds_img, CAPL > 0);
+    if (!k) return 0;
+    const size_t per_wave = (size_t)CAP * s.entry + flat_b + s.rec_bytes * CAPL;
+    for (int wpb = 4; wpb * 64 <= rolling_max_threads<T>(s.fr, s.flat_ok, CAPL > 0); wpb += 4) {
+        const size_t lds_b = (lds_img ? s.img : 0) + (size_t)wpb * per_wave;
+        if (lds_b > 158 * 1024) continue;
+        if (lds_b > 48 * 1024) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 64 * wpb, lds_b) != hipSuccess) per_cu = 0;
+        if (per_cu * wpb > best->waves) *best = RollingTry{per_cu * wpb, wpb, per_cu, CAP, CAPL, lds_b, lds_img};
     }
-    const int32_t cap0 = mix ? c->opt_list_cap : (c->opt_list_cap_pure > 0 ? c->opt_list_cap_pure : 256);
-    // Generation-pure scenes of the curved-surface preset, single precision, append layout: the workgroup-wide block pool
-    // (k_trace_pool) when at least 24 blocks of 64 records fit next to the image (cfg 5: 15 KB image, 41 blocks; 12.1 ms
-    // against 13.8 with the per-wave lists).  Not for the [k][ray] slots unless asked for (OT_OPT_BLOCK_POOL = 1): blocks
-    // that merge mix rays of many tickets, a pass then stores 64 scattered elements per plane instead of runs (20 ms
-    // against 14.4).
-    if (!mix && !f64 && img_fits && (c->opt_pool > 0 || (c->opt_pool < 0 && append)) && c->opt_rec_lds != 0 && K < (1 << 20)) {  // (a block's generation has 20 bits)
-        const auto kp = pool_kernel<T, OUT>(fr);
-        const size_t fixed = img + (64 + 16) * sizeof(uint32_t);
-        const int64_t nb_fit = fixed < 158 * 1024 ? (int64_t)((158 * 1024 - fixed) / (POOL_BLOCK_WORDS * 4)) : 0;
-        const int32_t NB = (int32_t)(nb_fit > 64 ? 64 : nb_fit);
-        if (kp && NB >= (c->opt_pool > 0 ? 16 : 24)) {
-            const size_t lds_p = fixed + (size_t)NB * POOL_BLOCK_WORDS * 4;
-            HIP_TRY(hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-            const int64_t want = (n + 1023) / 1024;
-            const int gridp = (int)(want < c->n_cus ? want : c->n_cus);
-            if (c->blocked.ensure(256)) return fail(OT_ERR_HIP, "hipMalloc of the ticket counter failed");
-            c->blocked_queue_off = 0;
-            unsigned long long* queue = (unsigned long long*)c->blocked.p;
-#ifdef OT_STAMP
-            HIP_TRY(hipMemsetAsync(queue, 0, 24 * sizeof(unsigned long long), c->stream));
-#else
-            HIP_TRY(hipMemsetAsync(queue, 0, sizeof(unsigned long long), c->stream));
-#endif
-            if (append) HIP_TRY(hipMemsetAsync(ac.cursor, 0, sizeof(unsigned long long), c->stream));
-            hipEvent_t ev0, ev1;
-            int rc = timing_pair(c, &ev0, &ev1);
-            if (rc) return rc;
-            WaveScratch<T> ws = {nullptr, 0};
-            hipExtLaunchKernelGGL(kp, dim3(gridp), dim3(1024), (uint32_t)lds_p, c->stream, ev0, ev1, 0u, blob, (T)c->unit, view<T>(rays), n, K, out,
-                                  ac, seg_count, counts, n_classes, ws, NB, 0, queue, 0, c->opt_pool_jitter);
-            HIP_TRY(hipGetLastError());
-            const int32_t shape[8] = {2, 1024, 1, gridp, (int32_t)lds_p, NB * 64, 0, 2 | 16 | (append ? 4 : 0)};  // bit 4: block pool
-            for (int q = 0; q < 8; ++q) c->last_launch[q] = shape[q];
-            return 0;
-        }
+    return 0;
+}
+// the placement policy for one room of the pair queue (`room` pairs; ignored without the queue)
+template <class T, class OUT> static int rolling_placement(const RollingPlanArgs& a, int32_t room, RollingTry* chosen) {
+    const RollingScene& s = a.scene;
+    const size_t flat_b = s.flat_ok ? flat_lds_bytes<T>(room) : 0;
+    *chosen = RollingTry();
+    // (1) image in LDS, records in LDS: all of them (mixed lists) or the front of the list (generation-pure lists).
+    //     Taken when at least 12 waves per CU still fit (OT_OPT_LDS_RECORDS = 1: whenever it fits at all).
+    const int rec_lds_min_waves = a.opt_rec_lds > 0 ? 4 : 12;
+    if (s.img_fits && a.opt_rec_lds != 0) {
+        // (the LDS part of a list is REC_LDS_POSITIONS = 128 entries, a compile-time constant of the kernels: a mixed list
+        // is then exactly that long, a generation-pure one keeps the rest of its cap0 entries in global scratch)
+        const int rc = rolling_occupancy<T, OUT>(s, flat_b, true, s.mix || s.cap0 < REC_LDS_POSITIONS ? REC_LDS_POSITIONS : s.cap0, REC_LDS_POSITIONS, chosen);
+        if (rc) return rc;
+        if (chosen->waves < rec_lds_min_waves) *chosen = RollingTry();
     }
-    ot_ctx::RollingPlan& plan = c->plan[f64 ? 1 : 0][append ? 1 : 0];
-    if (plan.epoch != c->plan_epoch) {
-        struct Try { int waves = 0, wpb = 0, per_cu = 0; int32_t cap = 0, capl = 0; size_t lds = 0; };
-        // most waves per CU for one placement: image in LDS or not, the first `capl` records of every list in LDS
-        size_t flat_b = flat_bytes;  // per wave, for the queue room under evaluation (below)
-        auto evaluate = [&](bool lds_img, int32_t CAP, int32_t CAPL, Try& best) -> int {
-            const void* k = (const void*)rolling_kernel<T, OUT>(fr, flat_ok, lds_img, CAPL > 0);
-            if (!k) return 0;
-            const size_t per_wave = (size_t)CAP * entry + flat_b + rec_bytes * CAPL;
-            for (int wpb = 4; wpb * 64 <= rolling_max_threads<T>(fr, flat_ok, CAPL > 0); wpb += 4) {
-                const size_t lds_b = (lds_img ? img : 0) + (size_t)wpb * per_wave;
-                if (lds_b > 158 * 1024) continue;
-                if (lds_b > 48 * 1024) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
-                int per_cu = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 64 * wpb, lds_b) != hipSuccess) per_cu = 0;
-                if (per_cu * wpb > best.waves) { best.waves = per_cu * wpb; best.wpb = wpb; best.per_cu = per_cu; best.cap = CAP; best.capl = CAPL; best.lds = lds_b; }
-            }
-            return 0;
-        };
-        Try chosen;
-        bool lds_img = false;
-        int32_t room_sel = flat_cap;
-        // The pair queue's room is LDS that every wave holds: 512 pairs are 1 KB, and with the records of the live rays in LDS the
-        // sixteenth wave of a CU can hang on the last few hundred bytes (cfg 3's scene under grids whose fullest cell holds four or
-        // five leaves instead of three: 12 waves per CU instead of 16, 2.6-3.0 ms instead of 2.15-2.25 — tools/sweep_root_grid.py).
-        // A round that overflows a smaller queue defers lanes and costs little (cfg 3 with room for 192 pairs where its worst case is
-        // 384: 2.165 against 2.13-2.17 ms at 256 ... 512); a lost quarter of the waves costs 25 %.
-        // So the room is the largest of 512, 448, ... 192 (>= one lane's worst case of 168) that keeps the most waves resident;
-        // OT_OPT_FLAT_QUEUE > 1 still sets it by hand.
-        auto choose = [&]() -> int {
-        chosen = Try();
-        lds_img = false;
-        // (1) image in LDS, records in LDS: all of them (mixed lists) or the front of the list (generation-pure lists).
-        //     Taken when at least 12 waves per CU still fit (OT_OPT_LDS_RECORDS = 1: whenever it fits at all).
-        const int rec_lds_min_waves = c->opt_rec_lds > 0 ? 4 : 12;
-        if (img_fits && c->opt_rec_lds != 0) {
-            Try t;
-            // (the LDS part of a list is REC_LDS_POSITIONS = 128 entries, a compile-time constant of the kernels: a mixed list
-            // is then exactly that long, a generation-pure one keeps the rest of its cap0 entries in global scratch)
-            const int rc = evaluate(true, mix || cap0 < REC_LDS_POSITIONS ? REC_LDS_POSITIONS : cap0, REC_LDS_POSITIONS, t);
-            if (rc) return rc;
-            if (t.waves >= rec_lds_min_waves) { chosen = t; lds_img = true; }
-        }
-        // (2) image in LDS, records in global scratch
-        if (!chosen.waves && img_fits) {
-            for (int32_t CAP = cap0; CAP >= 128 && !chosen.waves; CAP >>= 1) {
-                const int rc = evaluate(true, CAP, 0, chosen);
-                if (rc) return rc;
-            }
-            lds_img = chosen.waves > 0;
-        }
-        // (3) image read from L2
-        if (!chosen.waves) {
-            const int rc = evaluate(false, cap0, 0, chosen);
-            if (rc) return rc;
-        }
-        return 0;
-        };
-        int rc_choose = choose();
-        if (rc_choose) return rc_choose;
-        if (flat_ok && c->opt_flat == 1 && flat_cap > 192) {
-            const Try first = chosen;
-            const bool first_img = lds_img;
-            Try best_t = first;
-            bool best_img = first_img;
-            for (int32_t room = flat_cap - 64; room >= 192; room -= 64) {
-                flat_b = ((size_t)(FlatLds<T>::fixed_bytes + (size_t)room * 2) + 15) & ~(size_t)15;
-                rc_choose = choose();
-                if (rc_choose) return rc_choose;
-                // (the policy of choose() first — records in LDS when at least 12 waves fit — then the number of waves)
-                const bool rec_new = chosen.capl > 0, rec_old = best_t.capl > 0;
-                if ((rec_new && !rec_old) || (rec_new == rec_old && chosen.waves > best_t.waves)) { best_t = chosen; best_img = lds_img; room_sel = room; }
-            }
-            chosen = best_t;
-            lds_img = best_img;
-        }
-        if (!chosen.waves) return fail(OT_ERR_UNSUPPORTED, "no k_trace_rolling launch configuration fits this scene image");
-        plan.flat_cap = room_sel;
-        plan.epoch = c->plan_epoch; plan.wpb = chosen.wpb; plan.per_cu = chosen.per_cu; plan.cap = chosen.cap; plan.capl = chosen.capl; plan.lds = lds_img;
-        plan.rec_lds = chosen.capl > 0; plan.lds_bytes = chosen.lds;
+    // (2) image in LDS, records in global scratch
+    for (int32_t CAP = s.cap0; s.img_fits && CAP >= 128 && !chosen->waves; CAP >>= 1) {
+        const int rc = rolling_occupancy<T, OUT>(s, flat_b, true, CAP, 0, chosen);
+        if (rc) return rc;
     }
-    const int wpb = plan.wpb;
-    const int32_t CAP = plan.cap;
-    const auto kr = rolling_kernel<T, OUT>(fr, flat_ok, plan.lds, plan.rec_lds);
+    // (3) image read from L2
+    if (!chosen->waves) return rolling_occupancy<T, OUT>(s, flat_b, false, s.cap0, 0, chosen);
+    return 0;
+}
+template <class T, class OUT> static int plan_rolling(const RollingPlanArgs& a, RollingPlan* plan) {
+    const RollingScene& s = a.scene;
+    RollingTry best;
+    int32_t room_sel = s.flat_cap;
+    int rc = rolling_placement<T, OUT>(a, s.flat_cap, &best);
+    if (rc) return rc;
+    // The pair queue's room is LDS that every wave holds: 512 pairs are 1 KB, and with the records of the live rays in LDS the
+    // sixteenth wave of a CU can hang on the last few hundred bytes (cfg 3's scene under grids whose fullest cell holds four or
+    // five leaves instead of three: 12 waves per CU instead of 16, 2.6-3.0 ms instead of 2.15-2.25 — tools/sweep_root_grid.py).
+    // A round that overflows a smaller queue defers lanes and costs little (cfg 3 with room for 192 pairs where its worst case is
+    // 384: 2.165 against 2.13-2.17 ms at 256 ... 512); a lost quarter of the waves costs 25 %.
+    // So the room is the largest of 512, 448, ... 192 (>= one lane's worst case of 168) that keeps the most waves resident;
+    // OT_OPT_FLAT_QUEUE > 1 still sets it by hand.
+    for (int32_t room = s.flat_cap - 64; a.sweep_room && room >= 192; room -= 64) {
+        RollingTry t;
+        rc = rolling_placement<T, OUT>(a, room, &t);
+        if (rc) return rc;
+        // (the policy of rolling_placement first — records in LDS when at least 12 waves fit — then the number of waves)
+        const bool rec_new = t.capl > 0, rec_old = best.capl > 0;
+        if ((rec_new && !rec_old) || (rec_new == rec_old && t.waves > best.waves)) { best = t; room_sel = room; }
+    }
+    if (!best.waves) return fail(OT_ERR_UNSUPPORTED, "no k_trace_rolling launch configuration fits this scene image");
+    *plan = RollingPlan{a, best, room_sel};
+    return 0;
+}
+
+// what the caller of launch_rolling passed, for the launchers
+template <class T, class OUT> struct RollingCall {
+    const ot_rays* rays; int64_t n; int32_t K; const OUT& out; const AppendCtl& ac; int32_t *seg_count, *counts; int32_t n_classes;
+    static constexpr bool append = std::is_same<OUT, SegPlanes<T>>::value;
+};
+template <class T, class OUT>
+static int launch_rolling_kernel(ot_ctx* c, RollingKern<T, OUT> k, const LaunchShape& shape, const RollingCall<T, OUT>& a, WaveScratch<T> ws,
+                                 int32_t cap, int32_t capl, unsigned long long* queue, int32_t mix, int32_t last) {
+    return launch_kernel(c, k, shape, queue, a.append ? a.ac.cursor : nullptr, make_blob<T>(c), (T)c->unit, view<T>(a.rays), a.n, a.K, a.out, a.ac,
+                         a.seg_count, a.counts, a.n_classes, ws, cap, capl, queue, mix, last);
+}
+// Mixed scenes: the live rays in registers, refilled in place (k_trace_refill) — no list, no records, 1.5 KB of LDS per wave
+// (pair queue) + 1.5 KB (the parked ride-along fields), so registers alone decide how many waves share a CU.
+// *done = false: no kernel or no room for this scene, the lists take it.
+template <class T, class OUT> static int launch_refill(ot_ctx* c, const RollingScene& s, const RollingCall<T, OUT>& a, bool* done) {
+    const auto kf = s.mix && s.img_fits && c->opt_refill > 0 ? refill_kernel<T, OUT>(s.fr, s.flat_ok) : nullptr;
+    if (!kf) return 0;
+    const int threads = refill_max_threads<T>(s.fr, s.flat_ok), waves = threads / 64;
+    const size_t park_bytes = s.flat_ok ? 6 * 64 * sizeof(T) : 0;
+    const size_t lds_f = s.img + (size_t)waves * ((s.flat_ok ? flat_lds_bytes<T>(s.flat_cap) : 0) + park_bytes);
+    if (lds_f > 158 * 1024) return 0;
+    int per_cu = 0;
+    if (lds_f > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kf, threads, lds_f) != hipSuccess || per_cu < 1) return 0;
+    if (c->opt_blocks_per_cu > 0) per_cu = c->opt_blocks_per_cu;
+    const int64_t want = (a.n + 64 * (int64_t)waves - 1) / (64 * (int64_t)waves);
+    const int64_t capf = (int64_t)c->n_cus * per_cu;
+    const int gridf = (int)(want < capf ? want : capf);
+    // rays per ticket (one atomic on the device-wide queue each): 256, less when the batch is small enough that
+    // whole tickets would leave waves without work
+    const int64_t per_wave4 = a.n / ((int64_t)gridf * waves * 4);
+    const int32_t ticket = c->opt_refill_ticket > 0 ? c->opt_refill_ticket : (int32_t)(per_wave4 >= 256 ? 256 : (per_wave4 < 64 ? 64 : (per_wave4 / 64) * 64));
+    unsigned long long* queue = ticket_counter(c, 0);
+    if (!queue) return fail(OT_ERR_HIP, "hipMalloc of the ticket counter failed");
+    *done = true;
+    const LaunchShape shape = {2, threads, per_cu, gridf, (int32_t)lds_f, ticket, 1, (s.flat_ok ? LL_PAIR_QUEUE : 0) | (a.append ? LL_APPEND : 0) | LL_REFILL};
+    return launch_rolling_kernel<T, OUT>(c, kf, shape, a, WaveScratch<T>{nullptr, 0}, ticket, 0, queue, 1, s.flat_cap);
+}
+// Generation-pure scenes of the curved-surface preset, single precision, append layout: the workgroup-wide block pool
+// (k_trace_pool) when at least 24 blocks of 64 records fit next to the image (cfg 5: 15 KB image, 41 blocks; 12.1 ms
+// against 13.8 with the per-wave lists).  Not for the [k][ray] slots unless asked for (OT_OPT_BLOCK_POOL = 1): blocks
+// that merge mix rays of many tickets, a pass then stores 64 scattered elements per plane instead of runs (20 ms
+// against 14.4).
+template <class T, class OUT> static int launch_pool(ot_ctx* c, const RollingScene& s, const RollingCall<T, OUT>& a, bool* done) {
+    if (s.mix || sizeof(T) == 8 || !s.img_fits || !(c->opt_pool > 0 || (c->opt_pool < 0 && a.append)) || c->opt_rec_lds == 0 || a.K >= (1 << 20)) return 0;  // (a block's generation has 20 bits)
+    const auto kp = pool_kernel<T, OUT>(s.fr);
+    const size_t fixed = s.img + (64 + 16) * sizeof(uint32_t);
+    const int64_t nb_fit = fixed < 158 * 1024 ? (int64_t)((158 * 1024 - fixed) / (POOL_BLOCK_WORDS * 4)) : 0;
+    const int32_t NB = (int32_t)(nb_fit > 64 ? 64 : nb_fit);
+    if (!kp || NB < (c->opt_pool > 0 ? 16 : 24)) return 0;
+    const size_t lds_p = fixed + (size_t)NB * POOL_BLOCK_WORDS * 4;
+    const int64_t want = (a.n + 1023) / 1024;
+    const int gridp = (int)(want < c->n_cus ? want : c->n_cus);
+    unsigned long long* queue = ticket_counter(c, 0);
+    if (!queue) return fail(OT_ERR_HIP, "hipMalloc of the ticket counter failed");
+    *done = true;
+    const LaunchShape shape = {2, 1024, 1, gridp, (int32_t)lds_p, NB * 64, 0, LL_REC_LDS | LL_POOL | (a.append ? LL_APPEND : 0)};
+    return launch_rolling_kernel<T, OUT>(c, kp, shape, a, WaveScratch<T>{nullptr, 0}, NB, 0, queue, 0, c->opt_pool_jitter);
+}
+template <class T, class OUT> static int launch_lists(ot_ctx* c, const RollingScene& s, const RollingCall<T, OUT>& a) {
+    RollingPlan& plan = c->plan[sizeof(T) == 8 ? 1 : 0][a.append ? 1 : 0];
+    const RollingPlanArgs args = {s, c->opt_rec_lds, s.flat_ok && c->opt_flat == 1, c->uploads};
+    if (!(plan.args == args)) {
+        const int rc = plan_rolling<T, OUT>(args, &plan);
+        if (rc) return rc;
+    }
+    const RollingTry& at = plan.at;
+    const int wpb = at.wpb;
+    const auto kr = rolling_kernel<T, OUT>(s.fr, s.flat_ok, at.lds_img, at.capl > 0);
     if (!kr) return fail(OT_ERR_UNSUPPORTED, "no k_trace_rolling instantiation for this scene / option combination");
-    const size_t lds_r = plan.lds_bytes;
-    if (lds_r > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r));
-    int per_cu_r = plan.per_cu;
-    if (c->opt_blocks_per_cu > 0) per_cu_r = c->opt_blocks_per_cu;
-    const int64_t want = (n + 64 * (int64_t)wpb - 1) / (64 * (int64_t)wpb);  // one ticket per wave at least
+    const int per_cu_r = c->opt_blocks_per_cu > 0 ? c->opt_blocks_per_cu : at.per_cu;
+    const int64_t want = (a.n + 64 * (int64_t)wpb - 1) / (64 * (int64_t)wpb);  // one ticket per wave at least
     const int64_t capr = (int64_t)c->n_cus * per_cu_r;
     const int gridr = (int)(want < capr ? want : capr);
     // per-wave record scratch (by list position) + the ticket counter
-    const int32_t CAPL = plan.capl;
-    const size_t wave_bytes = align_up((size_t)(CAP - CAPL) * rec_bytes);  // what the lists keep outside LDS
-    const size_t scratch_bytes = wave_bytes * (size_t)gridr * wpb;
-    if (c->blocked.ensure(scratch_bytes + 256)) return fail(OT_ERR_HIP, "hipMalloc of rolling-trace scratch failed");
-    c->blocked_queue_off = scratch_bytes;
-    WaveScratch<T> ws = {(uint8_t*)c->blocked.p, (int64_t)wave_bytes};
-    unsigned long long* queue = (unsigned long long*)((uint8_t*)c->blocked.p + scratch_bytes);
-#ifdef OT_STAMP
-    HIP_TRY(hipMemsetAsync(queue, 0, 24 * sizeof(unsigned long long), c->stream));
-#else
-    HIP_TRY(hipMemsetAsync(queue, 0, sizeof(unsigned long long), c->stream));
-#endif
-    if (append) HIP_TRY(hipMemsetAsync(ac.cursor, 0, sizeof(unsigned long long), c->stream));
-    hipEvent_t ev0, ev1;
-    int rc = timing_pair(c, &ev0, &ev1);
-    if (rc) return rc;
-    hipExtLaunchKernelGGL(kr, dim3(gridr), dim3(64 * wpb), (uint32_t)lds_r, c->stream, ev0, ev1, 0u, blob, (T)c->unit, view<T>(rays), n,
-                          K, out, ac, seg_count, counts, n_classes, ws, CAP, CAPL, queue, mix ? 1 : 0, flat_ok ? plan.flat_cap : 0);
-    HIP_TRY(hipGetLastError());
-    const int32_t shape[8] = {2, 64 * wpb, per_cu_r, gridr, (int32_t)lds_r, CAP, mix ? 1 : 0, (flat_ok ? 1 : 0) | (plan.rec_lds ? 2 : 0) | (append ? 4 : 0)};
-    for (int q = 0; q < 8; ++q) c->last_launch[q] = shape[q];
-    return 0;
+    const size_t wave_bytes = align_up((size_t)(at.cap - at.capl) * s.rec_bytes);  // what the lists keep outside LDS
+    unsigned long long* queue = ticket_counter(c, wave_bytes * (size_t)gridr * wpb);
+    if (!queue) return fail(OT_ERR_HIP, "hipMalloc of rolling-trace scratch failed");
+    const LaunchShape shape = {2, 64 * wpb, per_cu_r, gridr, (int32_t)at.lds, at.cap, s.mix ? 1 : 0,
+                               (s.flat_ok ? LL_PAIR_QUEUE : 0) | (at.capl > 0 ? LL_REC_LDS : 0) | (a.append ? LL_APPEND : 0)};
+    return launch_rolling_kernel<T, OUT>(c, kr, shape, a, WaveScratch<T>{(uint8_t*)c->blocked.p, (int64_t)wave_bytes}, at.cap, at.capl, queue, s.mix ? 1 : 0,
+                                         s.flat_ok ? plan.flat_cap : 0);
+}
+template <class T, class OUT>
+static int launch_rolling(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const OUT& out, const AppendCtl& ac, int32_t* seg_count,
+                          int32_t* counts, int32_t n_classes) {
+    const RollingScene s = classify_rolling<T>(c);
+    const RollingCall<T, OUT> call = {rays, n, K, out, ac, seg_count, counts, n_classes};
+    bool done = false;
+    int rc = launch_refill<T, OUT>(c, s, call, &done);
+    if (!rc && !done) rc = launch_pool<T, OUT>(c, s, call, &done);
+    if (!rc && !done) rc = launch_lists<T, OUT>(c, s, call);
+    return rc;
 }
 
 static int check_trace_args(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const int32_t* seg_count, const int32_t* counts, int32_t n_classes) {
@@ -967,26 +1006,18 @@ static int fused_preset(uint32_t need) {  // smallest lane-per-ray preset that c
     return (need & ~FA) == 0 ? 0 : ((need & ~FB) == 0 ? 1 : ((need & ~FE) == 0 ? 2 : ((need & ~FM) == 0 ? 3 : 4)));
 }
 template <class T> static bool wants_rolling(const ot_ctx* c, int32_t K) {
-    using namespace preset;
     const bool f64 = sizeof(T) == 8;
-    const int fi = fused_preset(c->features);
-    const size_t bytes = f64 ? c->bytes64 : c->bytes32;
-    const bool in_lds = bytes <= (size_t)c->opt_lds_limit_kb * 1024;
-    return c->opt_kernel == 2 || (c->opt_kernel == 0 && c->n_nodes >= 24 && K > 2) || (f64 && (fi == 4 || !in_lds));
+    return c->opt_kernel == 2 || (c->opt_kernel == 0 && c->n_nodes >= 24 && K > 2) || (f64 && (fused_preset(c->features) == 4 || !in_lds<T>(c)));
 }
 
 // one lane per ray (k_trace_fused); OUT = SegsT<T> or SegTiles<T>
 template <class T, class OUT>
 static int launch_fused(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const OUT& out, int32_t pair, int32_t* seg_count, int32_t* counts,
                         int32_t n_classes) {
-    int rc = 0;
-    using namespace preset;  // tables.h
     const bool f64 = sizeof(T) == 8;
-    const uint32_t need = c->features;
-    const int fi = fused_preset(need);
-    const size_t bytes = f64 ? c->bytes64 : c->bytes32;
-    const bool in_lds = bytes <= (size_t)c->opt_lds_limit_kb * 1024;
-    const SceneBlob blob = make_blob<T>(c);
+    const int fi = fused_preset(c->features);
+    const size_t bytes = image_of<T>(c).bytes;
+    const bool lds = in_lds<T>(c);
     const int block = 256;
     const int64_t blocks_needed = (n + block - 1) / block;
     // Grid: small scenes (staging the blob costs nothing) get up to 256 blocks per CU, i.e. one ray per
@@ -994,29 +1025,20 @@ static int launch_fused(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, co
     // balances better than 16 long-lived blocks per CU (cfg 4, 1.6e8 rays: 12.7 -> 11.8 ms fp64; flat from
     // 64 per CU on).  Scenes with a large LDS image run persistent, as many blocks per CU as the image allows.
     int per_cu = 256;
-    if (in_lds && bytes > 16 * 1024) {  // beyond 64 B of staging per ray a short-lived workgroup no longer pays
+    if (lds && bytes > 16 * 1024) {  // beyond 64 B of staging per ray a short-lived workgroup no longer pays
         const int fit = (int)((160 * 1024) / (bytes + 512));
         per_cu = fit < 1 ? 1 : (fit > 8 ? 8 : fit);
     }
     if (c->opt_blocks_per_cu > 0) per_cu = c->opt_blocks_per_cu;
     const int64_t cap = (int64_t)c->n_cus * per_cu;
     const int grid = (int)(blocks_needed < cap ? blocks_needed : cap);
-    hipEvent_t ev0, ev1;
-    rc = timing_pair(c, &ev0, &ev1);
-    if (rc) return rc;
     // smallest instantiation that covers the scene's features; the 128-register cap pays for the mirror / lens kernel
     // and the fp32 Snell kernel only (the fp64 Snell kernel would spill: 145 VGPRs)
     const bool mw = c->opt_minw == 4 && (fi == 0 || (fi == 1 && !f64));
-    FusedKern<T, OUT> kern = fused_kernel<T, OUT>(fi, in_lds, mw, c->opt_nt != 0);
+    FusedKern<T, OUT> kern = fused_kernel<T, OUT>(fi, lds, mw, c->opt_nt != 0);
     if (!kern) return fail(OT_ERR_UNSUPPORTED, "no kernel instantiation for this scene / option combination");
-    const size_t lds_bytes = in_lds ? bytes : 0;
-    if (lds_bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipExtLaunchKernelGGL(kern, dim3(grid), dim3(block), (uint32_t)lds_bytes, c->stream, ev0, ev1, 0u, blob, (T)c->unit, view<T>(rays), n, K,
-                          out, seg_count, counts, n_classes, pair);
-    HIP_TRY(hipGetLastError());
-    const int32_t shape[8] = {1, (int32_t)block, 0, (int32_t)grid, (int32_t)lds_bytes, 0, 0, std::is_same<OUT, SegTiles<T>>::value ? 8 : 0};
-    for (int q = 0; q < 8; ++q) c->last_launch[q] = shape[q];
-    return 0;
+    const LaunchShape shape = {1, block, 0, grid, (int32_t)(lds ? bytes : 0), 0, 0, std::is_same<OUT, SegTiles<T>>::value ? LL_TILES : 0};
+    return launch_kernel(c, kern, shape, nullptr, nullptr, make_blob<T>(c), (T)c->unit, view<T>(rays), n, K, out, seg_count, counts, n_classes, pair);
 }
 
 template <class T>
@@ -1053,15 +1075,21 @@ static int trace_tiled(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, voi
     return launch_fused<T, SegTiles<T>>(c, rays, n, K, SegTiles<T>{(uint8_t*)tiles}, pair, seg_count, counts, n_classes);
 }
 
+// the segment block of the append layout (ot_trace_append_*, ot_trace_trees_append_*)
+template <class T> static int check_append_block(const ot_segment_block* out, const int64_t* n_slots) {
+    if (!out || !out->base || out->capacity < 0 || !n_slots) return fail(OT_ERR_INVALID, "bad segment block / n_slots");
+    if ((uintptr_t)out->base % 16 || out->capacity % 64) return fail(OT_ERR_INVALID, "segment block: base must be 16-byte aligned, capacity a multiple of 64");
+    if (out->capacity >= ((int64_t)1 << 30) / (int64_t)(sizeof(T) / 4)) return fail(OT_ERR_INVALID, "segment block: capacity must stay below 2^30 slots (2^29 in double precision) per launch");
+    return 0;
+}
 // Append layout: always the rolling lists (a light scene takes the planar preset FC).
 template <class T>
 static int trace_append(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segment_block* out, int64_t* n_slots,
                         int32_t* seg_count, int32_t* counts, int32_t n_classes) {
     int rc = check_trace_args(c, rays, n, K, seg_count, counts, n_classes);
     if (rc) return rc;
-    if (!out || !out->base || out->capacity < 0 || !n_slots) return fail(OT_ERR_INVALID, "bad segment block / n_slots");
-    if ((uintptr_t)out->base % 16 || out->capacity % 64) return fail(OT_ERR_INVALID, "segment block: base must be 16-byte aligned, capacity a multiple of 64");
-    if (out->capacity >= ((int64_t)1 << 30) / (int64_t)(sizeof(T) / 4)) return fail(OT_ERR_INVALID, "segment block: capacity must stay below 2^30 slots (2^29 in double precision) per launch");
+    rc = check_append_block<T>(out, n_slots);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (n == 0) {
         HIP_TRY(hipMemsetAsync(n_slots, 0, sizeof(int64_t), c->stream));
@@ -1140,8 +1168,7 @@ static int trace_generation(ot_ctx* c, const ot_rays* rays, const int32_t* tree,
     const size_t sz_tot = align_up(sizeof(int64_t) * 4);
     const int64_t n_waves = (n + 63) / 64;
     const size_t sz_code = align_up((size_t)n), sz_wave = align_up(sizeof(unsigned long long) * n_waves);
-    // heavy scenes keep the count pass's decision per ray for the emit pass (kernels.h k_gen_pass); OT_OPT_GEN_REUSE: -1 auto
-    const bool reuse = (c->opt_gen_reuse < 0 ? c->n_nodes >= 12 : c->opt_gen_reuse != 0) && !ahead_in;
+    const bool reuse = gen_reuse(c) && !ahead_in;
     const size_t sz_hn = reuse ? align_up(sizeof(int32_t) * n) : 0, sz_ht = reuse ? align_up(sizeof(T) * n) : 0;
     const size_t total = sz_tot + sz_code + 2 * sz_wave + (ns > 0 ? 3 * sz_slot : 0) + sz_hn + sz_ht;
     if (c->gen.ensure(total)) return fail(OT_ERR_HIP, "hipMalloc of generation scratch failed");
@@ -1172,15 +1199,13 @@ static int trace_generation(ot_ctx* c, const ot_rays* rays, const int32_t* tree,
         HIP_TRY(hipMemsetAsync(c->gen_mismatch, 0, sizeof(unsigned long long), c->stream));
     }
     mismatch = c->gen_mismatch;  // lives with the ctx: accumulated over all generations (ot_debug_generation_mismatches)
-    constexpr bool f64 = sizeof(T) == 8;
-    const size_t bytes = f64 ? c->bytes64 : c->bytes32;
     const SceneBlob blob = make_blob<T>(c);
-    const bool in_lds = bytes <= (size_t)c->opt_lds_limit_kb * 1024;
-    const size_t lds_bytes = in_lds ? bytes : 0;
+    const bool lds = in_lds<T>(c);
+    const size_t lds_bytes = lds ? image_of<T>(c).bytes : 0;
     const int fg = gen_preset(c->features);  // smallest generation preset that covers the scene (tables.h)
-    const ProbeKern<T> k_probe = probe_kernel<T>(fg, in_lds);
-    const GenKern<T> k_count = gen_kernel<T>(fg, in_lds, false);
-    const GenKern<T> k_emit = ahead_out ? gen_ahead_kernel<T>(fg, in_lds) : gen_kernel<T>(fg, in_lds, true);
+    const ProbeKern<T> k_probe = probe_kernel<T>(fg, lds);
+    const GenKern<T> k_count = gen_kernel<T>(fg, lds, false);
+    const GenKern<T> k_emit = ahead_out ? gen_ahead_kernel<T>(fg, lds) : gen_kernel<T>(fg, lds, true);
     if (!k_emit) return fail(OT_ERR_UNSUPPORTED, "no look-ahead emit kernel for this scene");
     if (ahead_in) code = ahead_in;  // rewritten in place by k_gen_recount
     if (lds_bytes > 48 * 1024) {
@@ -1225,26 +1250,23 @@ static int trace_generation(ot_ctx* c, const ot_rays* rays, const int32_t* tree,
 // on small trees (full = 0).
 struct TreesPlan { int32_t QL, QG, full, groups_per_cu, grid, chunk, preset, flat_cap, img_global; size_t lds_bytes; };
 // Planar scenes under a top-level grid of leaves search through the wave-wide pair queue of the heavy non-branching kernel
-// (launch_rolling's flat_ok, flat_grid_hit): the tree kernel's presets 5 (FR) / 6 (FRP).  0: the scene does not qualify.
+// (pair_queue_room, flat_grid_hit): the tree kernel's presets 5 (FR) / 6 (FRP).  0: the scene does not qualify.
 static int32_t trees_flat_cap(const ot_ctx* c, int* preset) {
-    using namespace preset;
-    const uint32_t need = c->features;
-    const int fr = (c->root_grid >= 0 && (need & ~FR) == 0) ? 5 : ((c->root_grid >= 0 && (need & ~FRP) == 0) ? 6 : 0);
-    const int32_t flat_full = 64 * FLAT_CELLS * (c->root_max_items > 0 ? c->root_max_items : 1);
-    const int32_t flat_room = c->opt_flat > 1 ? c->opt_flat : 512;
-    const int32_t flat_cap = flat_full < flat_room ? flat_full : flat_room;
-    if (!c->opt_flat || !fr || c->root_pack < 0 || flat_cap > 8192 || c->n_runs != 0 || c->n_slots > 0) return 0;
-    *preset = fr;
+    const int planar = planar_grid_preset(c);
+    // (a tree is one lane's: no mixed lists to ask for, and the queue is tried whether or not the image will fit — trees_plan
+    // drops it again when it does not; the presets 5 / 6 have no count gates)
+    const int32_t flat_cap = pair_queue_room(c, planar >= 0 && c->n_slots == 0);
+    if (flat_cap) *preset = 5 + planar;
     return flat_cap;
 }
 template <class T> static bool trees_plan(const ot_ctx* c, int32_t cap, int64_t n, TreesPlan* p) {
-    const size_t image = sizeof(T) == 8 ? c->bytes64 : c->bytes32;
+    const size_t image = image_of<T>(c).bytes;
     *p = TreesPlan{};
     if (!c->has_scene || c->max_children > 2 || cap < 1) return false;
     p->preset = gen_preset(c->features);
     p->flat_cap = c->opt_trees_flat ? trees_flat_cap(c, &p->preset) : 0;
     if (!tree_kernel<T, SegPlanes<T>>(p->preset)) return false;
-    const size_t flat_bytes = p->flat_cap ? (((size_t)(FlatLds<T>::fixed_bytes + (size_t)p->flat_cap * 2) + 15) & ~(size_t)15) : 0;  // per wave (kernels.h)
+    const size_t flat_bytes = p->flat_cap ? flat_lds_bytes<T>(p->flat_cap) : 0;
     const size_t room = 160 * 1024 - 1024, entry = (size_t)tree_entry_bytes<T>();
     size_t img = ((image + 15) & ~(size_t)15) + 4 * flat_bytes;
     if (img + 4 * entry > room || c->opt_trees_global) {  // (OT_OPT_TREES_GLOBAL_IMAGE: test knob, every scene takes this path)
@@ -1254,7 +1276,7 @@ template <class T> static bool trees_plan(const ot_ctx* c, int32_t cap, int64_t 
         img = 0;
         // ... and the node and material records alone in LDS when they leave room for the queues (instanced runs fold thousands of
         // lattice members into a few records: the walk's dependent reads then come from LDS, only poses and grids from L2)
-        const size_t head = ((size_t)(sizeof(T) == 8 ? c->head64 : c->head32) + 16 * (size_t)c->n_runs + 15) & ~(size_t)15;  // records + the run table
+        const size_t head = (image_of<T>(c).head + 16 * (size_t)c->n_runs + 15) & ~(size_t)15;  // records + the run table
         if (head > 0 && head + 4 * 3 * entry <= room / 2 && c->opt_trees_global != 2 && !c->has_implicit && tree_kernel<T, SegPlanes<T>>(4, 2)) { p->img_global = 2; img = head; }
     }
     const int64_t need = ((int64_t)cap + 1) / 2, fit = (int64_t)((room - img) / (4 * entry));
@@ -1302,23 +1324,13 @@ static int launch_trees(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t cap, 
     HIP_TRY(hipSetDevice(c->device));
     const TreeKern<T, OUT> kern = tree_kernel<T, OUT>(p.preset, p.img_global == 0 ? 1 : (p.img_global == 2 ? 2 : 0));
     if (!kern) return fail(OT_ERR_UNSUPPORTED, "this scene's tree kernel writes the append layout only (ot_trace_trees_append_*)");
-    const SceneBlob blob = make_blob<T>(c);
-    const int grid = p.grid;  // persistent: the scratch is per workgroup
-    const size_t scratch = (size_t)grid * 4 * (size_t)p.QG * 64 * (sizeof(T) == 8 ? 96 : 48);
+    const size_t scratch = (size_t)p.grid * 4 * (size_t)p.QG * 64 * (sizeof(T) == 8 ? 96 : 48);  // (the grid is persistent: the scratch is per workgroup)
     if (c->trees.ensure(scratch + 256)) return fail(OT_ERR_HIP, "hipMalloc of the tree queues failed");
-    if (ac.cursor) HIP_TRY(hipMemsetAsync(ac.cursor, 0, sizeof(unsigned long long), c->stream));
     AppendCtl ctl = ac;
     if (ac.cursor) ctl.chunk = p.chunk;
-    hipEvent_t ev0, ev1;
-    int rc = timing_pair(c, &ev0, &ev1);
-    if (rc) return rc;
-    if (p.lds_bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
-    hipExtLaunchKernelGGL(kern, dim3(grid), dim3(256), (uint32_t)p.lds_bytes, c->stream, ev0, ev1, 0u, blob, (T)c->unit, view<T>(rays), n, cap, p.QL, p.QG,
-                          (uint8_t*)c->trees.p, out, ctl, seg_count, counts, n_classes, c->opt_trees_refill_at, p.flat_cap);
-    HIP_TRY(hipGetLastError());
-    const int32_t shape[8] = {4, 256, p.groups_per_cu, (int32_t)grid, (int32_t)p.lds_bytes, p.QL, p.QG, (std::is_same<OUT, SegPlanes<T>>::value ? 4 : 0) | (p.flat_cap ? 1 : 0)};
-    for (int q = 0; q < 8; ++q) c->last_launch[q] = shape[q];
-    return 0;
+    const LaunchShape shape = {4, 256, p.groups_per_cu, p.grid, (int32_t)p.lds_bytes, p.QL, p.QG, (std::is_same<OUT, SegPlanes<T>>::value ? LL_APPEND : 0) | (p.flat_cap ? LL_PAIR_QUEUE : 0)};
+    return launch_kernel(c, kern, shape, nullptr, ac.cursor, make_blob<T>(c), (T)c->unit, view<T>(rays), n, cap, p.QL, p.QG, (uint8_t*)c->trees.p, out, ctl, seg_count, counts,
+                         n_classes, c->opt_trees_refill_at, p.flat_cap);
 }
 template <class T>
 static int trace_trees(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t cap, const ot_segments* out, int32_t* seg_count, int32_t* counts,
@@ -1335,9 +1347,8 @@ static int trace_trees_append(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t
                               int32_t* counts, int32_t n_classes) {
     int rc = check_trace_args(c, rays, n, cap, seg_count, counts, n_classes);
     if (rc) return rc;
-    if (!out || !out->base || out->capacity < 0 || !n_slots) return fail(OT_ERR_INVALID, "bad segment block / n_slots");
-    if ((uintptr_t)out->base % 16 || out->capacity % 64) return fail(OT_ERR_INVALID, "segment block: base must be 16-byte aligned, capacity a multiple of 64");
-    if (out->capacity >= ((int64_t)1 << 30) / (int64_t)(sizeof(T) / 4)) return fail(OT_ERR_INVALID, "segment block: capacity must stay below 2^30 slots (2^29 in double precision) per launch");
+    rc = check_append_block<T>(out, n_slots);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (n == 0) {
         HIP_TRY(hipMemsetAsync(n_slots, 0, sizeof(int64_t), c->stream));
@@ -1354,7 +1365,6 @@ template <class T>
 static int trace_generation_one(ot_ctx* c, const ot_rays* rays, const int32_t* tree, const int32_t* rem, int64_t n, int32_t* budget, const ot_segments* out,
                                 int64_t out_capacity, int64_t* state, const ot_rays* next, int32_t* next_tree, int32_t* next_rem, int64_t next_capacity,
                                 int32_t* counts, int32_t n_classes, const int64_t* n_in = nullptr, int64_t* n_out = nullptr) {
-    constexpr bool f64 = sizeof(T) == 8;
     const int64_t n_tiles = (n + 63) / 64, n_groups = (n + 255) / 256;  // a tile = the 64 rays of one wave
     const size_t sz_desc = align_up(sizeof(unsigned long long) * n_tiles + 8);
     // (at least 64 KB: growing the scratch frees it, which waits for the device — not between the launches of a chain)
@@ -1364,12 +1374,11 @@ static int trace_generation_one(ot_ctx* c, const ot_rays* rays, const int32_t* t
     int rc = timing_begin(c);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(desc, 0, sizeof(unsigned long long) * n_tiles + 8, c->stream));
-    const size_t bytes = f64 ? c->bytes64 : c->bytes32;
     const SceneBlob blob = make_blob<T>(c);
-    const bool in_lds = bytes <= (size_t)c->opt_lds_limit_kb * 1024;
-    const size_t lds_bytes = in_lds ? bytes : 0;
+    const bool lds = in_lds<T>(c);
+    const size_t lds_bytes = lds ? image_of<T>(c).bytes : 0;
     const int fg = gen_preset(c->features);
-    const GenOneKern<T> k = gen_one_kernel<T>(fg, in_lds);
+    const GenOneKern<T> k = gen_one_kernel<T>(fg, lds);
     if (lds_bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     hipLaunchKernelGGL(k, dim3((unsigned)n_groups), dim3(256), lds_bytes, c->stream, blob, (T)c->unit, view<T>(rays), tree, rem, n, budget, state, view<T>(out),
                        out_capacity, view_out<T>(next), next_tree, next_rem, next_capacity, desc, ticket, counts, n_classes, c->opt_gen_drop ? 1 : 0, n_in, n_out);
@@ -1403,10 +1412,7 @@ static int trace_tree(ot_ctx* c, const ot_rays* rays, const int32_t* tree, int64
     // One pass per generation (k_gen_one) where OT_OPT_GEN_ONEPASS allows it and the scene has no count-limited leaves (their
     // gate needs the scans between a probe pass and the trace).  Its per-ray budgets live in the library: seeded from budget[]
     // for the first generation of this call, two buffers of buf_capacity for the children.
-    const bool one_pass_kernel = [&] {
-        const size_t image = sizeof(T) == 8 ? c->bytes64 : c->bytes32;
-        return gen_one_kernel<T>(gen_preset(c->features), image <= (size_t)c->opt_lds_limit_kb * 1024) != nullptr;
-    }();
+    const bool one_pass_kernel = gen_one_kernel<T>(gen_preset(c->features), in_lds<T>(c)) != nullptr;
     // OT_OPT_GEN_ONEPASS: 1 every generation, 0 none, -1 (default) the SMALL ones: a generation of a few thousand rays is a
     // handful of tiles that are all resident at once — nothing to wait for in the look-back — and one launch instead of six
     // (count, three scan kernels, totals, emit) is what a tree of six rays costs: 1.08 -> ms per table.ray_tracing call.
@@ -1428,12 +1434,8 @@ static int trace_tree(ot_ctx* c, const ot_rays* rays, const int32_t* tree, int64
     // children that child will have; the next two-pass generation replaces its count pass over the rays by k_gen_recount over
     // those bytes.  Light scenes (no decision reuse: their search is a few planes) without count gates whose generation
     // buffers carry no `len`; two byte arrays of buf_capacity used in turn.
-    const bool ahead_ok = [&] {
-        const size_t image = sizeof(T) == 8 ? c->bytes64 : c->bytes32;
-        const bool reuse = c->opt_gen_reuse < 0 ? c->n_nodes >= 12 : c->opt_gen_reuse != 0;
-        return c->opt_gen_ahead != 0 && c->n_slots == 0 && !reuse && !buf_a->length && !buf_b->length &&
-               gen_ahead_kernel<T>(gen_preset(c->features), image <= (size_t)c->opt_lds_limit_kb * 1024) != nullptr;
-    }();
+    const bool ahead_ok = c->opt_gen_ahead != 0 && c->n_slots == 0 && !gen_reuse(c) && !buf_a->length && !buf_b->length &&
+                          gen_ahead_kernel<T>(gen_preset(c->features), in_lds<T>(c)) != nullptr;
     uint8_t *ahead_a = nullptr, *ahead_b = nullptr, *ahead_cur = nullptr;  // ahead_cur: the bytes of the CURRENT generation, if its producer left them
     if (ahead_ok) {
         const size_t each = align_up((size_t)buf_capacity + 64);
@@ -1719,14 +1721,13 @@ extern "C" {
 
 int ot_set_option(ot_ctx* c, int32_t option, int32_t value) {
     if (!c) return fail(OT_ERR_INVALID, "ctx is NULL");
-    ++c->plan_epoch;  // launch plans depend on the options
     switch (option) {
         case OT_OPT_NT_STORES: c->opt_nt = value != 0; return 0;
         case OT_OPT_PAIR_STORES: c->opt_pair = value != 0; return 0;
         case OT_OPT_MIX_GENERATIONS: c->opt_mix = value < 0 ? -1 : (value != 0); return 0;
         case OT_OPT_FLAT_QUEUE:
             if (value < 0 || (value > 1 && (value < 192 || value > 8192 || value % 64))) return fail(OT_ERR_INVALID, "OT_OPT_FLAT_QUEUE takes 0, 1, or the pairs a round may hold: a multiple of 64, 192..8192");
-            c->opt_flat = value; ++c->plan_epoch; return 0;
+            c->opt_flat = value; return 0;
         case OT_OPT_MIN_WAVES: 
             if (value != 0 && value != 4) return fail(OT_ERR_INVALID, "OT_OPT_MIN_WAVES takes 0 or 4");
             c->opt_minw = value; return 0;
