@@ -13,6 +13,7 @@
 //                        again, ordered slots); k_gen_probe / k_gen_rank / k_gen_counts keep interact-count gates
 //                        FIFO-exact; k_gen_totals publishes the generation's totals between the two passes.
 //   k_mon_*              Monitor.record over a segment stream (monitor.py:183-193).
+// The persistent lane-per-ray kernels' shared pieces (argument-segment layout, OT_KARG, value helpers) are one block behind load_ray.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -220,6 +221,89 @@ template <class T> __device__ __forceinline__ RayState<T> load_ray(const RaysT<T
 }
 
 // ------------------------------------------------------------------------------------------
+// Building blocks of the persistent lane-per-ray kernels (k_trace_trees, k_trace_rolling, k_trace_refill, k_trace_pool).
+// Every one is forced inline and keeps the dataflow of the code it was lifted from — what a kernel computes outside its pass
+// loop is passed in, the opaque-pointer asm sits where it sat — so these register-tight kernels compile to the instructions they
+// had with the blocks written out (tools/isa_equal.py is the check).
+// Still written out, and what was tried, one helper at a time against the parent's code objects ("changes" = other register
+// numbers and lane-spill slots, the same instructions otherwise).  Append chunk claim: struct-in / struct-out claim() + mark_tail()
+// changes every fp32 append k_trace_rolling (fp64 not built), every append k_trace_trees and one k_trace_refill; with member functions and
+// by-reference accessors (k_trace_refill only): all four.  Record loads and stores with the ray by value (r = rec_load_geom(r, ..),
+// rec_store(.., child, wl, meta)): changes every fp32 k_trace_rolling that keeps records and both k_trace_pool (fp64 not built; by
+// reference not tried there).  Interaction block, as advance() returning {child, used, survive}, with out-references, or as no
+// more than material cache + interact: each changes all four k_trace_refill (not tried elsewhere).  Search fork by reference:
+// changes k_trace_refill and k_trace_trees (by value not tried).  decode_lead_flags(fl, sc, r) by reference: changes k_trace_refill.
+struct AppendCtl {
+    unsigned long long* cursor;  // slots claimed so far (device); the caller reads it back as *n_slots
+    int64_t capacity;
+    int32_t chunk;               // slots per claim, a multiple of 64
+};
+template <class T> struct WaveScratch {
+    uint8_t* base;
+    int64_t wave_bytes;  // bytes per wave: CAP * record bytes, rounded up
+};
+// The parameter list of k_trace_rolling, k_trace_refill and k_trace_pool, in order = the layout of their kernel-argument segment,
+// each at its natural alignment (tests/test_build_resources.py compares the offsets).  CAP is CAP, TICKET or NB by kernel.
+template <class T, class OUT> struct LeadArgs {
+    SceneBlob blob; T unit; RaysT<T> in; int64_t n; int32_t K; OUT out; AppendCtl ac; int32_t* seg_count; int32_t* counts;
+    int32_t n_classes; WaveScratch<T> ws; int32_t CAP; int32_t capl; unsigned long long* queue; int32_t mix; int32_t flat_cap;
+};
+// one kernel argument, loaded from the kernel-argument segment HERE (the asm keeps the load from being hoisted and kept live)
+template <class V> __device__ __forceinline__ V karg(size_t offset) {
+    typedef const __attribute__((address_space(4))) V* ArgPtr;
+    ArgPtr p = (ArgPtr)((uintptr_t)__builtin_amdgcn_kernarg_segment_ptr() + offset);
+    asm volatile("" : "+s"(p));
+    return *p;
+}
+// OT_KARG(field): that field of the running kernel's argument segment (k_trace_rolling, k_trace_refill, k_trace_pool: each names
+// its layout first, `using Args = LeadArgs<T, OUT>;`), for arguments a pass needs once or less: a scalar live across the search
+// is spilled into a vector lane and read back (a VALU instruction each way, per pass); one loaded when needed costs a scalar load.
+#define OT_KARG(field) karg<decltype(Args::field)>(offsetof(Args, field))
+typedef const __attribute__((address_space(4))) uint64_t* ArgWords;
+__device__ __forceinline__ ArgWords karg_words(size_t offset) { return (ArgWords)((uintptr_t)__builtin_amdgcn_kernarg_segment_ptr() + offset); }
+// A struct of pointers out of the argument segment through a pointer made opaque HERE: loaded where used, not hoisted out of the loop
+static_assert(sizeof(RaysT<float>) == 15 * sizeof(uint64_t) && sizeof(RaysT<double>) == 15 * sizeof(uint64_t), "RaysT is fifteen pointers");
+static_assert(sizeof(SegsT<float>) == 14 * sizeof(uint64_t) && sizeof(SegsT<double>) == 14 * sizeof(uint64_t), "SegsT is fourteen pointers");
+template <class S> __device__ __forceinline__ S karg_struct(ArgWords p) {
+    constexpr int N = (int)(sizeof(S) / sizeof(uint64_t));
+    asm volatile("" : "+s"(p));
+    uint64_t words[N];
+#pragma unroll
+    for (int w = 0; w < N; ++w) words[w] = p[w];
+    S s;
+    __builtin_memcpy(&s, words, sizeof(s));
+    return s;
+}
+// a 64-bit value of the first active lane to the whole wave (scalar registers)
+__device__ __forceinline__ unsigned long long uniform64(unsigned long long v) {
+    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+           (uint32_t)__builtin_amdgcn_readfirstlane((int)(v & 0xffffffffull));
+}
+// The pair queue of one wave at `fb` (flat_grid_hit): key table, node table (fp64), marker queue.  The caller zeroes the markers.
+template <class T> __device__ __forceinline__ FlatLds<T> flat_lds_at(uint8_t* fb, int flat_cap) {
+    FlatLds<T> flat = {nullptr, nullptr, nullptr, 0};
+    flat.key = reinterpret_cast<unsigned long long*>(fb);
+    if constexpr (sizeof(T) == 8) flat.node = reinterpret_cast<int32_t*>(fb + 64 * 8);
+    flat.queue = reinterpret_cast<uint16_t*>(fb + FlatLds<T>::fixed_bytes);
+    flat.queue_cap = flat_cap;
+    return flat;
+}
+// a caller's ray: the node its flag word names (bits 8..31: node it was emitted on, plus one), -1 where that is no node of this scene
+__device__ __forceinline__ int32_t lead_last(int32_t fl, int32_t n_nodes) {
+    const int32_t last = (int32_t)((uint32_t)fl >> 8) - 1;
+    return (uint32_t)last >= (uint32_t)n_nodes ? -1 : last;
+}
+// metadata word of a live ray's record: HAS_Q | (start node + 1) << 8  (a dead ray never gets a record: no other flag bit)
+__device__ __forceinline__ int32_t rec_meta(int32_t has_q, int32_t last) { return (has_q ? OT_RAY_HAS_Q : 0) | ((last + 1) << 8); }
+__device__ __forceinline__ int32_t rec_meta_last(int32_t meta) { return (meta >> 8) - 1; }
+__device__ __forceinline__ int32_t rec_meta_has_q(int32_t meta) { return meta & OT_RAY_HAS_Q; }
+// a pass entry's segment record: length, and surface — a leaf, escaped (-1), dead on arrival and returned as it came (-2)
+template <class T> __device__ __forceinline__ T seg_len(bool hit, T t, T len) { return hit ? t : len; }
+template <class T, uint32_t F> __device__ __forceinline__ int32_t seg_surface(const Scene<T>& sc, bool hit, bool active, int32_t node) {
+    return hit ? leaf_id_of<T, F>(sc, node) : (active ? -1 : -2);
+}
+
+// ------------------------------------------------------------------------------------------
 // k_trace_fused: the hot kernel
 // OUT: SegsT<T> (the [k][ray] slots of ot_trace_*: 14 arrays) or SegTiles<T> (the same slots in 64-slot tiles, ot_trace_tiled_*)
 template <class T, uint32_t F, bool SCENE_IN_LDS, int MINW, bool NT, class OUT>
@@ -309,11 +393,6 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
 // reference's order; seg_count[i] = rays processed (== cap: the cap cut the tree short or the tree ended exactly there,
 // as `budget <= 0` on the generation path).  Count-limited leaves: one column of the counts table per tree (rays that share
 // an id are the caller's successive launches, as for ot_trace_*).
-struct AppendCtl {
-    unsigned long long* cursor;  // slots claimed so far (device); the caller reads it back as *n_slots
-    int64_t capacity;
-    int32_t chunk;               // slots per claim, a multiple of 64
-};
 template <class T> constexpr int tree_entry_bytes() { return 64 * (11 * (int)sizeof(T) + 4); }
 // OUT = SegsT<T>: the [k][tree] slots described above.  OUT = SegPlanes<T>: the append layout of ot_trace_append_* — the records of a
 // step go to consecutive slots of the wave's current chunk (claimed from a device-wide cursor, `ac`), whatever trees and
@@ -363,8 +442,9 @@ __global__ __launch_bounds__(256, MINW) void k_trace_trees(SceneBlob blob, T uni
     FlatLds<T> flat = {nullptr, nullptr, nullptr, 0};
     FlatGrid<T> flat_grid = {};
     if constexpr ((F & F_FLAT) != 0) {
-        const int per_wave = (FlatLds<T>::fixed_bytes + flat_cap * 2 + 15) & ~15;
+        const int per_wave = flat_lds_bytes<T>(flat_cap);
         uint8_t* fb = reinterpret_cast<uint8_t*>(lds) + img_bytes + (size_t)(blockDim.x >> 6) * QL * EB + (size_t)wave * per_wave;
+        // (written out: through flat_lds_at the register allocation of the two fp32 pair-queue instantiations changes)
         flat.key = reinterpret_cast<unsigned long long*>(fb);
         if constexpr (sizeof(T) == 8) flat.node = reinterpret_cast<int32_t*>(fb + 64 * 8);
         flat.queue = reinterpret_cast<uint16_t*>(fb + FlatLds<T>::fixed_bytes);
@@ -458,8 +538,7 @@ __global__ __launch_bounds__(256, MINW) void k_trace_trees(SceneBlob blob, T uni
             int64_t fresh_pos = 0;
             if (need > chunk_left) {  // wave-uniform: claim the next chunk; the step may straddle the two
                 const unsigned long long c0 = lane == 0 ? atomicAdd(ac.cursor, (unsigned long long)ac.chunk) : 0ull;
-                fresh_pos = (int64_t)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(c0 >> 32)) << 32) |
-                                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(c0 & 0xffffffffull)));
+                fresh_pos = (int64_t)uniform64(c0);
             }
             const int64_t slot = rank < chunk_left ? chunk_pos + rank : fresh_pos + (rank - chunk_left);
             if (need > chunk_left) { chunk_pos = fresh_pos + (need - chunk_left); chunk_left = ac.chunk - (need - chunk_left); }
@@ -603,18 +682,7 @@ __global__ __launch_bounds__(256, MINW) void k_trace_trees(SceneBlob blob, T uni
 // 4 cells per pass (every extra pass pays the pass's load -> trace -> store latency again); lists worked off in rounds
 // with a remainder pass instead of the FIFO ring (44 instead of 62 lanes per pass).
 static constexpr int REC_LDS_POSITIONS = 128;  // REC_LDS kernels: the first 128 positions of every wave's list keep their records in LDS
-template <class T> struct WaveScratch {
-    uint8_t* base;
-    int64_t wave_bytes;  // bytes per wave: CAP * record bytes, rounded up
-};
 template <uint32_t F> constexpr int rec_int_words() { return (F & F_LIMIT) ? 2 : 1; }
-// one kernel argument, loaded from the kernel-argument segment HERE (the asm keeps the load from being hoisted and kept live)
-template <class V> __device__ __forceinline__ V karg(size_t offset) {
-    typedef const __attribute__((address_space(4))) V* ArgPtr;
-    ArgPtr p = (ArgPtr)((uintptr_t)__builtin_amdgcn_kernarg_segment_ptr() + offset);
-    asm volatile("" : "+s"(p));
-    return *p;
-}
 
 // Largest workgroup an instantiation may be launched with, and the workgroups per CU the compiler has to leave registers
 // for.  The waves never synchronise after staging, so the workgroup size only decides how many waves share one image:
@@ -650,20 +718,10 @@ __global__ __launch_bounds__((rolling_threads<T, F, REC_LDS>()), (rolling_minw<T
     // The caller's 15 array pointers are needed once per ray, for its first segment — and as a by-value kernel argument
     // they would sit in 30 of the 102 scalar registers for the whole pass loop (the kernel spills scalars into vector lanes
     // as it is).  They are read from the kernel-argument segment where they are used instead; `in` itself is never touched.
-    // (The segment is laid out like a struct of the parameters in order, each at its natural alignment: LeadArgs below;
-    // tools/kernel_resources.sh --args prints the offsets the code object records.)
-    struct LeadArgs {  // the kernel's parameter list, in order: the layout of the kernel-argument segment
-        SceneBlob blob; T unit; RaysT<T> in; int64_t n; int32_t K; OUT out; AppendCtl ac; int32_t* seg_count; int32_t* counts;
-        int32_t n_classes; WaveScratch<T> ws; int32_t CAP; int32_t capl; unsigned long long* queue; int32_t mix; int32_t flat_cap;
-    };
-    // ... and so are the arguments a pass needs once or less: the ticket queue, the append cursor and its
-    // bounds, seg_count.  A scalar that is live across the nearest-hit search is spilled into a vector lane before it
-    // and read back after it (one VALU instruction each way, per pass); one that is loaded from the argument segment
-    // when it is needed costs a scalar load.
-#define OT_KARG(field) karg<decltype(LeadArgs::field)>(offsetof(LeadArgs, field))
+    // (LeadArgs, above, is the layout of the segment.)  ... and so are the arguments a pass needs once or less: OT_KARG.
+    using Args = LeadArgs<T, OUT>;
     (void)ac; (void)seg_count; (void)queue;
-    typedef const __attribute__((address_space(4))) RaysT<T>* RaysArgPtr;
-    const RaysArgPtr in_arg = (RaysArgPtr)((uintptr_t)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(LeadArgs, in));
+    const ArgWords in_arg = karg_words(offsetof(Args, in));
     (void)in;
     extern __shared__ __align__(16) uint32_t lds[];
     const uint32_t* base = blob.words;
@@ -683,12 +741,9 @@ __global__ __launch_bounds__((rolling_threads<T, F, REC_LDS>()), (rolling_minw<T
     // F_FLAT: per-wave key table and pair queue of flat_grid_hit, behind the lists of all waves
     FlatLds<T> flat = {nullptr, nullptr, nullptr, 0};
     if constexpr ((F & F_FLAT) != 0) {
-        const int per_wave = (FlatLds<T>::fixed_bytes + flat_cap * 2 + 15) & ~15;
+        const int per_wave = flat_lds_bytes<T>(flat_cap);
         uint8_t* fb = lds_next + wave * per_wave;
-        flat.key = reinterpret_cast<unsigned long long*>(fb);
-        if constexpr (sizeof(T) == 8) flat.node = reinterpret_cast<int32_t*>(fb + 64 * 8);
-        flat.queue = reinterpret_cast<uint16_t*>(fb + FlatLds<T>::fixed_bytes);
-        flat.queue_cap = flat_cap;
+        flat = flat_lds_at<T>(fb, flat_cap);
         for (int q = lane; q < flat_cap; q += 64) flat.queue[q] = 0;  // markers only; every round leaves it zeroed again
         lds_next += n_waves * per_wave;
     }
@@ -727,8 +782,7 @@ __global__ __launch_bounds__((rolling_threads<T, F, REC_LDS>()), (rolling_minw<T
     auto draw_ticket = [&]() -> unsigned long long {
         unsigned long long first = 0;
         if (lane == 0) first = atomicAdd(OT_KARG(queue), 64ull);
-        return ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(first >> 32)) << 32) |
-               (uint32_t)__builtin_amdgcn_readfirstlane((int)(first & 0xffffffffull));
+        return uniform64(first);
     };
 
     for (;;) {
@@ -793,17 +847,7 @@ __global__ __launch_bounds__((rolling_threads<T, F, REC_LDS>()), (rolling_minw<T
             auto load_part = [&](const bool geom) {
                 if (!entry) return;
                 if (k == 0) {  // first segment: the caller's arrays (a ticket is 64 consecutive rays)
-                    RaysArgPtr ip = in_arg;
-                    asm volatile("" : "+s"(ip));  // opaque here: the pointers are loaded now, not hoisted out of the pass loop
-                    RaysT<T> in_now;
-                    {
-                        static_assert(sizeof(RaysT<T>) == 15 * sizeof(uint64_t), "RaysT is fifteen pointers");
-                        const __attribute__((address_space(4))) uint64_t* src = (const __attribute__((address_space(4))) uint64_t*)ip;
-                        uint64_t words[15];
-#pragma unroll
-                        for (int w = 0; w < 15; ++w) words[w] = src[w];
-                        __builtin_memcpy(&in_now, words, sizeof(in_now));
-                    }
+                    const RaysT<T> in_now = karg_struct<RaysT<T>>(in_arg);
                     if (geom) {
                         fl = in_now.flags[i];
                         if constexpr ((F & F_LIMIT) != 0) cls = in_now.id[i];
@@ -811,8 +855,7 @@ __global__ __launch_bounds__((rolling_threads<T, F, REC_LDS>()), (rolling_minw<T
                         r.dx = ld_once(in_now.dx + i); r.dy = ld_once(in_now.dy + i); r.dz = ld_once(in_now.dz + i);
                         r.len = in_now.len ? in_now.len[i] : Num<T>::inf();
                         r.has_q = (fl & OT_RAY_HAS_Q) != 0;
-                        r.last = (int32_t)((uint32_t)fl >> 8) - 1;  // bits 8..31: node the ray was emitted on, plus one (generation buffers; 0 for a caller's ray)
-                        if ((uint32_t)r.last >= (uint32_t)sc.n_nodes) r.last = -1;  // ... that name no node of this scene
+                        r.last = lead_last(fl, sc.n_nodes);
                         fl &= 0xff;
                     } else {
                         r.wl = ld_once(in_now.wl + i); r.qr = ld_once(in_now.qr + i); r.qi = ld_once(in_now.qi + i);
@@ -824,8 +867,8 @@ __global__ __launch_bounds__((rolling_threads<T, F, REC_LDS>()), (rolling_minw<T
                         r.dx = lrec[p + 3 * CAPL]; r.dy = lrec[p + 4 * CAPL]; r.dz = lrec[p + 5 * CAPL];
                         const int32_t meta = lint[p];
                         if constexpr ((F & F_LIMIT) != 0) cls = lint[p + CAPL];
-                        r.last = (meta >> 8) - 1;
-                        r.has_q = meta & OT_RAY_HAS_Q;  // (a dead ray never gets a record: the flag word of a record is HAS_Q or nothing)
+                        r.last = rec_meta_last(meta);
+                        r.has_q = rec_meta_has_q(meta);
                         r.len = Num<T>::inf();
                     } else {
                         r.qr = lrec[p + 6 * CAPL]; r.qi = lrec[p + 7 * CAPL]; r.I = lrec[p + 8 * CAPL];
@@ -838,8 +881,8 @@ __global__ __launch_bounds__((rolling_threads<T, F, REC_LDS>()), (rolling_minw<T
                         r.dx = grec[g + 3 * CAPG]; r.dy = grec[g + 4 * CAPG]; r.dz = grec[g + 5 * CAPG];
                         const int32_t meta = gint[g];
                         if constexpr ((F & F_LIMIT) != 0) cls = gint[g + CAPG];
-                        r.last = (meta >> 8) - 1;
-                        r.has_q = meta & OT_RAY_HAS_Q;
+                        r.last = rec_meta_last(meta);
+                        r.has_q = rec_meta_has_q(meta);
                         r.len = Num<T>::inf();
                     } else {
                         r.qr = grec[g + 6 * CAPG]; r.qi = grec[g + 7 * CAPG]; r.I = grec[g + 8 * CAPG];
@@ -873,8 +916,7 @@ __global__ __launch_bounds__((rolling_threads<T, F, REC_LDS>()), (rolling_minw<T
                 int64_t fresh_pos = 0;
                 if (need > chunk_left) {  // wave-uniform: claim the next chunk; the pass may straddle the two
                     const unsigned long long c0 = lane == 0 ? atomicAdd(OT_KARG(ac.cursor), (unsigned long long)OT_KARG(ac.chunk)) : 0ull;
-                    fresh_pos = (int64_t)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(c0 >> 32)) << 32) |
-                                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(c0 & 0xffffffffull)));
+                    fresh_pos = (int64_t)uniform64(c0);
                 }
                 slot = rank < chunk_left ? chunk_pos + rank : fresh_pos + (rank - chunk_left);
                 if (need > chunk_left) { chunk_pos = fresh_pos + (need - chunk_left); chunk_left = OT_KARG(ac.chunk) - (need - chunk_left); }
@@ -882,18 +924,18 @@ __global__ __launch_bounds__((rolling_threads<T, F, REC_LDS>()), (rolling_minw<T
                 room = slot < OT_KARG(ac.capacity);  // an output that is too small loses records, never writes outside (the cursor tells)
             }
             if constexpr (APPEND) {
-                if (entry && room) store_segment<T, NT>(out, slot, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : (active ? -1 : -2));
+                if (entry && room) store_segment<T, NT>(out, slot, r, seg_len(hit, h.t, r.len), (int32_t)i, seg_surface<T, F>(sc, hit, active, h.node));
             } else {  // the fourteen [k][ray] array pointers: from the kernel-argument segment, like the caller's ray pointers
-                typedef const __attribute__((address_space(4))) uint64_t* ArgWords;
-                ArgWords src = (ArgWords)((uintptr_t)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(LeadArgs, out));
+                // (written out: through karg_struct the register allocation of the <float, FD, REC_LDS, SegsT> instantiation changes)
+                ArgWords src = karg_words(offsetof(Args, out));
                 asm volatile("" : "+s"(src));
-                static_assert(sizeof(SegsT<T>) == 14 * sizeof(uint64_t), "SegsT is fourteen pointers");
-                uint64_t words[14];
+                constexpr int N = (int)(sizeof(SegsT<T>) / sizeof(uint64_t));
+                uint64_t words[N];
 #pragma unroll
-                for (int w = 0; w < 14; ++w) words[w] = src[w];
+                for (int w = 0; w < N; ++w) words[w] = src[w];
                 SegsT<T> out_now;
                 __builtin_memcpy(&out_now, words, sizeof(out_now));
-                if (entry) store_segment<T, NT>(out_now, slot, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : (active ? -1 : -2));
+                if (entry) store_segment<T, NT>(out_now, slot, r, seg_len(hit, h.t, r.len), (int32_t)i, seg_surface<T, F>(sc, hit, active, h.node));
             }
             bool survive = false;
             RayState<T> child = {};
@@ -916,7 +958,7 @@ __global__ __launch_bounds__((rolling_threads<T, F, REC_LDS>()), (rolling_minw<T
                 const int q = (tail + __popcll(mk & ((1ull << lane) - 1ull))) & M;
                 if (mix) ring64[q] = ((unsigned long long)(uint32_t)(k + 1) << 32) | (unsigned long long)(uint32_t)i;
                 else ring32[q] = (uint32_t)i;
-                const int32_t meta = (r.has_q ? OT_RAY_HAS_Q : 0) | ((child.last + 1) << 8);
+                const int32_t meta = rec_meta(r.has_q, child.last);
                 if (REC_LDS && (!OVERFLOW || q < CAPL)) {
                     lrec[q] = child.ox; lrec[q + CAPL] = child.oy; lrec[q + 2 * CAPL] = child.oz;
                     lrec[q + 3 * CAPL] = child.dx; lrec[q + 4 * CAPL] = child.dy; lrec[q + 5 * CAPL] = child.dz;
@@ -998,25 +1040,18 @@ __global__ __launch_bounds__((refill_threads<T, F>()), (refill_minw<T, F>())) vo
     SceneBlob blob, T unit, RaysT<T> in, int64_t n, int32_t K, OUT out, AppendCtl ac, int32_t* __restrict__ seg_count, int32_t* counts,
     int32_t n_classes, WaveScratch<T> ws, int32_t TICKET, int32_t capl_arg, unsigned long long* queue, int32_t mix, int32_t flat_cap) {
     constexpr bool APPEND = std::is_same<OUT, SegPlanes<T>>::value;
-    struct LeadArgs {  // the parameter list: the layout of the kernel-argument segment (see k_trace_rolling)
-        SceneBlob blob; T unit; RaysT<T> in; int64_t n; int32_t K; OUT out; AppendCtl ac; int32_t* seg_count; int32_t* counts;
-        int32_t n_classes; WaveScratch<T> ws; int32_t CAP; int32_t capl; unsigned long long* queue; int32_t mix; int32_t flat_cap;
-    };
+    using Args = LeadArgs<T, OUT>;  // (TICKET is its CAP)
     (void)ac; (void)seg_count; (void)queue; (void)in; (void)ws; (void)capl_arg; (void)mix;
-    typedef const __attribute__((address_space(4))) RaysT<T>* RaysArgPtr;
-    const RaysArgPtr in_arg = (RaysArgPtr)((uintptr_t)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(LeadArgs, in));
+    const ArgWords in_arg = karg_words(offsetof(Args, in));
     extern __shared__ __align__(16) uint32_t lds[];
     for (int w = threadIdx.x; w < blob.n_words; w += blockDim.x) lds[w] = blob.words[w];
     uint32_t* const lds_tail = lds + ((blob.n_words + 3) & ~3);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     FlatLds<T> flat = {nullptr, nullptr, nullptr, 0};
     if constexpr ((F & F_FLAT) != 0) {
-        const int per_wave = (FlatLds<T>::fixed_bytes + flat_cap * 2 + 15) & ~15;
+        const int per_wave = flat_lds_bytes<T>(flat_cap);
         uint8_t* fb = reinterpret_cast<uint8_t*>(lds_tail) + wave * per_wave;
-        flat.key = reinterpret_cast<unsigned long long*>(fb);
-        if constexpr (sizeof(T) == 8) flat.node = reinterpret_cast<int32_t*>(fb + 64 * 8);
-        flat.queue = reinterpret_cast<uint16_t*>(fb + FlatLds<T>::fixed_bytes);
-        flat.queue_cap = flat_cap;
+        flat = flat_lds_at<T>(fb, flat_cap);
         for (int q = lane; q < flat_cap; q += 64) flat.queue[q] = 0;  // markers only; every round leaves it zeroed again
     }
     // PARK: what only rides along to the interaction and the next record (wavelength, q, intensity, index, path length) waits
@@ -1025,8 +1060,7 @@ __global__ __launch_bounds__((refill_threads<T, F>()), (refill_minw<T, F>())) vo
     constexpr bool PARK = (F & F_FLAT) != 0;
     T* park = nullptr;
     if constexpr (PARK) {
-        const int per_wave_flat = (FlatLds<T>::fixed_bytes + flat_cap * 2 + 15) & ~15;
-        park = reinterpret_cast<T*>(reinterpret_cast<uint8_t*>(lds_tail) + (blockDim.x >> 6) * per_wave_flat) + wave * (6 * 64) + lane;
+        park = reinterpret_cast<T*>(reinterpret_cast<uint8_t*>(lds_tail) + (blockDim.x >> 6) * flat_lds_bytes<T>(flat_cap)) + wave * (6 * 64) + lane;
     }
     __syncthreads();  // the only workgroup barrier: the scene image is staged
     const Scene<T> sc = bind_scene<T>(lds, blob, unit);
@@ -1058,8 +1092,7 @@ __global__ __launch_bounds__((refill_threads<T, F>()), (refill_minw<T, F>())) vo
         if (tk_next == tk_end) {
             unsigned long long first = 0;
             if (lane == 0) first = atomicAdd(OT_KARG(queue), (unsigned long long)TICKET);
-            first = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(first >> 32)) << 32) |
-                    (uint32_t)__builtin_amdgcn_readfirstlane((int)(first & 0xffffffffull));
+            first = uniform64(first);
             const unsigned long long n_now = (unsigned long long)n;
             if (first >= n_now) { exhausted = true; return; }
             tk_next = (uint32_t)first;
@@ -1069,17 +1102,7 @@ __global__ __launch_bounds__((refill_threads<T, F>()), (refill_minw<T, F>())) vo
         const int rank = rank_below(freem);
         if (((freem >> lane) & 1ull) && rank < take) {
             fi = (int32_t)(tk_next + (uint32_t)rank);
-            RaysArgPtr ip = in_arg;
-            asm volatile("" : "+s"(ip));  // opaque here: the pointers are loaded now, not hoisted out of the pass loop
-            RaysT<T> in_now;
-            {
-                static_assert(sizeof(RaysT<T>) == 15 * sizeof(uint64_t), "RaysT is fifteen pointers");
-                const __attribute__((address_space(4))) uint64_t* src = (const __attribute__((address_space(4))) uint64_t*)ip;
-                uint64_t words[15];
-#pragma unroll
-                for (int w = 0; w < 15; ++w) words[w] = src[w];
-                __builtin_memcpy(&in_now, words, sizeof(in_now));
-            }
+            const RaysT<T> in_now = karg_struct<RaysT<T>>(in_arg);
             // (plain loads: the fresh rays of a pass are a dozen consecutive records, a fraction of a cache line per field — the
             // rest of the line is wanted a pass or two later and should still be in L2 then; non-temporal loads fetched every
             // line three times: 1.55 GB read for 0.52 GB of rays)
@@ -1105,8 +1128,7 @@ __global__ __launch_bounds__((refill_threads<T, F>()), (refill_minw<T, F>())) vo
             r.wl = fwl; r.qr = fqr; r.qi = fqi; r.I = fI; r.n = fn; r.pl = fpl; r.len = flen;
             i = fi; k = 0; cls = fcls;
             r.has_q = (ffl & OT_RAY_HAS_Q) != 0;
-            r.last = (int32_t)((uint32_t)ffl >> 8) - 1;  // bits 8..31: node the ray was emitted on, plus one (generation buffers; 0 for a caller's ray)
-            if ((uint32_t)r.last >= (uint32_t)sc.n_nodes) r.last = -1;  // ... that name no node of this scene
+            r.last = lead_last(ffl, sc.n_nodes);
             fl = ffl & 0xff;
             busy = true;
             pending = false;
@@ -1162,25 +1184,16 @@ __global__ __launch_bounds__((refill_threads<T, F>()), (refill_minw<T, F>())) vo
             int64_t fresh_pos = 0;
             if (need > chunk_left) {  // wave-uniform: claim the next chunk; the pass may straddle the two
                 const unsigned long long c0 = lane == 0 ? atomicAdd(OT_KARG(ac.cursor), (unsigned long long)OT_KARG(ac.chunk)) : 0ull;
-                fresh_pos = (int64_t)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(c0 >> 32)) << 32) |
-                                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(c0 & 0xffffffffull)));
+                fresh_pos = (int64_t)uniform64(c0);
             }
             slot = rank < chunk_left ? chunk_pos + rank : fresh_pos + (rank - chunk_left);
             if (need > chunk_left) { chunk_pos = fresh_pos + (need - chunk_left); chunk_left = OT_KARG(ac.chunk) - (need - chunk_left); }
             else { chunk_pos += need; chunk_left -= need; }
             room = slot < OT_KARG(ac.capacity);  // an output that is too small loses records, never writes outside (the cursor tells)
-            if (entry && room) store_segment<T, NT>(out, slot, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : (active ? -1 : -2));
+            if (entry && room) store_segment<T, NT>(out, slot, r, seg_len(hit, h.t, r.len), (int32_t)i, seg_surface<T, F>(sc, hit, active, h.node));
         } else {  // the fourteen [k][ray] array pointers: from the kernel-argument segment, like the caller's ray pointers
-            typedef const __attribute__((address_space(4))) uint64_t* ArgWords;
-            ArgWords src = (ArgWords)((uintptr_t)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(LeadArgs, out));
-            asm volatile("" : "+s"(src));
-            static_assert(sizeof(SegsT<T>) == 14 * sizeof(uint64_t), "SegsT is fourteen pointers");
-            uint64_t words[14];
-#pragma unroll
-            for (int w = 0; w < 14; ++w) words[w] = src[w];
-            SegsT<T> out_now;
-            __builtin_memcpy(&out_now, words, sizeof(out_now));
-            if (entry) store_segment<T, NT>(out_now, slot, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : (active ? -1 : -2));
+            const SegsT<T> out_now = karg_struct<SegsT<T>>(karg_words(offsetof(Args, out)));
+            if (entry) store_segment<T, NT>(out_now, slot, r, seg_len(hit, h.t, r.len), (int32_t)i, seg_surface<T, F>(sc, hit, active, h.node));
         }
         if (entry && !survive) OT_KARG(seg_count)[i] = used;
         if (survive) { r = child; ++k; }  // (child.wl, .has_q are the parent's; .len = inf, .last = the node it was emitted on)
@@ -1244,13 +1257,9 @@ __global__ __launch_bounds__(1024, 1) void k_trace_pool(
     static_assert(sizeof(T) == 4, "a double-precision record is 100 bytes: too few blocks would fit");
     static_assert((F & (F_LIMIT | F_FLAT)) == 0, "no count classes, no pair queue");
     constexpr bool APPEND = std::is_same<OUT, SegPlanes<T>>::value;
-    struct LeadArgs {  // the parameter list: the layout of the kernel-argument segment (see k_trace_rolling)
-        SceneBlob blob; T unit; RaysT<T> in; int64_t n; int32_t K; OUT out; AppendCtl ac; int32_t* seg_count; int32_t* counts;
-        int32_t n_classes; WaveScratch<T> ws; int32_t CAP; int32_t capl; unsigned long long* queue; int32_t mix; int32_t flat_cap;
-    };
+    using Args = LeadArgs<T, OUT>;  // (NB is its CAP)
     (void)ac; (void)seg_count; (void)queue; (void)in; (void)ws; (void)capl_arg; (void)mix;  // (flat_cap: the jitter period of the protocol test, 0 = off)
-    typedef const __attribute__((address_space(4))) RaysT<T>* RaysArgPtr;
-    const RaysArgPtr in_arg = (RaysArgPtr)((uintptr_t)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(LeadArgs, in));
+    const ArgWords in_arg = karg_words(offsetof(Args, in));
     extern __shared__ __align__(16) uint32_t lds[];
     for (int w = threadIdx.x; w < blob.n_words; w += blockDim.x) lds[w] = blob.words[w];
     uint32_t* const state = lds + ((blob.n_words + 3) & ~3);   // [64] block states, then [4] control words
@@ -1313,6 +1322,7 @@ __global__ __launch_bounds__(1024, 1) void k_trace_pool(
                 }
                 unsigned long long nb = 0;
                 if (lane == 0) nb = atomicAdd(OT_KARG(ac.cursor), (unsigned long long)wg_chunk);
+                // (the two halves are wanted apart: not uniform64)
                 const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(nb & 0xffffffffull)), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(nb >> 32));
                 if (lane == 0) {
                     __hip_atomic_store(&ctl[4 + 2 * ((epoch + 1u) & 3u)], lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1362,8 +1372,7 @@ __global__ __launch_bounds__(1024, 1) void k_trace_pool(
                 if (m > 0) {
                     unsigned long long first = 0;
                     if (lane == 0) first = atomicAdd(OT_KARG(queue), 64ull * (unsigned long long)m);
-                    first = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(first >> 32)) << 32) |
-                            (uint32_t)__builtin_amdgcn_readfirstlane((int)(first & 0xffffffffull));
+                    first = uniform64(first);
                     const unsigned long long n_now = (unsigned long long)n;
                     unsigned long long left = gm;
                     int j = 0;
@@ -1435,15 +1444,14 @@ __global__ __launch_bounds__(1024, 1) void k_trace_pool(
             if (entry) {
                 i = (int32_t)src[0];
                 if (k == 0) {  // first segment: the caller's arrays
-                    RaysArgPtr ip = in_arg;
+                    ArgWords ip = in_arg;  // (written out: through karg_struct the register allocation of the append instantiation changes)
                     asm volatile("" : "+s"(ip));
                     RaysT<T> in_now;
                     {
-                        static_assert(sizeof(RaysT<T>) == 15 * sizeof(uint64_t), "RaysT is fifteen pointers");
-                        const __attribute__((address_space(4))) uint64_t* w = (const __attribute__((address_space(4))) uint64_t*)ip;
-                        uint64_t words[15];
+                        constexpr int N = (int)(sizeof(RaysT<T>) / sizeof(uint64_t));
+                        uint64_t words[N];
 #pragma unroll
-                        for (int q = 0; q < 15; ++q) words[q] = w[q];
+                        for (int q = 0; q < N; ++q) words[q] = ip[q];
                         __builtin_memcpy(&in_now, words, sizeof(in_now));
                     }
                     fl = in_now.flags[i];
@@ -1451,8 +1459,7 @@ __global__ __launch_bounds__(1024, 1) void k_trace_pool(
                     r.dx = ld_once(in_now.dx + i); r.dy = ld_once(in_now.dy + i); r.dz = ld_once(in_now.dz + i);
                     r.len = in_now.len ? in_now.len[i] : Num<T>::inf();
                     r.has_q = (fl & OT_RAY_HAS_Q) != 0;
-                    r.last = (int32_t)((uint32_t)fl >> 8) - 1;
-                    if ((uint32_t)r.last >= (uint32_t)sc.n_nodes) r.last = -1;
+                    r.last = lead_last(fl, sc.n_nodes);
                     fl &= 0xff;
                     r.wl = ld_once(in_now.wl + i); r.qr = ld_once(in_now.qr + i); r.qi = ld_once(in_now.qi + i);
                     r.I = ld_once(in_now.I + i); r.n = ld_once(in_now.n + i); r.pl = ld_once(in_now.pl + i);
@@ -1463,8 +1470,8 @@ __global__ __launch_bounds__(1024, 1) void k_trace_pool(
                     r.qr = rec[7 * 64]; r.qi = rec[8 * 64]; r.I = rec[9 * 64];
                     r.n = rec[10 * 64]; r.pl = rec[11 * 64]; r.wl = rec[12 * 64];
                     const int32_t meta = (int32_t)src[13 * 64];
-                    r.last = (meta >> 8) - 1;
-                    r.has_q = meta & OT_RAY_HAS_Q;
+                    r.last = rec_meta_last(meta);
+                    r.has_q = rec_meta_has_q(meta);
                     r.len = Num<T>::inf();
                 }
             }
@@ -1483,18 +1490,11 @@ __global__ __launch_bounds__(1024, 1) void k_trace_pool(
             bool room = true;
             if constexpr (APPEND) {
                 slot = claim(take) + lane;  // the entries of a pass are its first `take` lanes
+                // (length and surface written out: through seg_len / seg_surface the register allocation of the SegsT instantiation changes)
                 room = slot < OT_KARG(ac.capacity);
                 if (entry && room) store_segment<T, NT>(out, slot, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : (active ? -1 : -2));
             } else {
-                typedef const __attribute__((address_space(4))) uint64_t* ArgWords;
-                ArgWords w = (ArgWords)((uintptr_t)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(LeadArgs, out));
-                asm volatile("" : "+s"(w));
-                static_assert(sizeof(SegsT<T>) == 14 * sizeof(uint64_t), "SegsT is fourteen pointers");
-                uint64_t words[14];
-#pragma unroll
-                for (int q = 0; q < 14; ++q) words[q] = w[q];
-                SegsT<T> out_now;
-                __builtin_memcpy(&out_now, words, sizeof(out_now));
+                const SegsT<T> out_now = karg_struct<SegsT<T>>(karg_words(offsetof(Args, out)));
                 if (entry) store_segment<T, NT>(out_now, slot, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : (active ? -1 : -2));
             }
             bool survive = false;
@@ -1519,7 +1519,7 @@ __global__ __launch_bounds__(1024, 1) void k_trace_pool(
                 rec[4 * 64] = child.dx; rec[5 * 64] = child.dy; rec[6 * 64] = child.dz;
                 rec[7 * 64] = child.qr; rec[8 * 64] = child.qi; rec[9 * 64] = child.I;
                 rec[10 * 64] = child.n; rec[11 * 64] = child.pl; rec[12 * 64] = r.wl;
-                dst[13 * 64] = (uint32_t)((r.has_q ? OT_RAY_HAS_Q : 0) | ((child.last + 1) << 8));
+                dst[13 * 64] = (uint32_t)rec_meta(r.has_q, child.last);
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             jitter(3);

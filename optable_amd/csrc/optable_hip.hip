@@ -775,8 +775,6 @@ static int planar_grid_preset(const ot_ctx* c) {
     if (c->root_grid < 0) return -1;
     return (c->features & ~FR) == 0 ? 0 : ((c->features & ~FRP) == 0 ? 1 : -1);
 }
-// LDS bytes of a pair queue with room for `room` pairs, per wave (kernels.h)
-template <class T> static size_t flat_lds_bytes(int32_t room) { return ((size_t)(FlatLds<T>::fixed_bytes + (size_t)room * 2) + 15) & ~(size_t)15; }
 // planar scenes under a top-level grid of leaves: candidates through a wave-wide pair queue (flat_grid_hit).  Returns the pairs a
 // round of the queue can hold, 0 when the scene does not qualify.  `planar`: the caller's kernel is one of the planar presets and
 // has nothing else against the queue (the callers differ there: classify_rolling, trees_flat_cap).

@@ -1126,9 +1126,11 @@ template <class T> struct FlatLds {
     int32_t* node;             // [64]  fp64 only: lowest node index among the candidates at the key's t
     uint16_t* queue;           // [queue_cap]
     int32_t queue_cap;
-    // bytes per wave, without the queue (kernels.h and the host size the LDS with this)
+    // bytes per wave, without the queue
     static constexpr int fixed_bytes = sizeof(T) == 4 ? 64 * 8 : 64 * (8 + 4);
 };
+// LDS bytes of one wave's pair queue with room for `flat_cap` pairs: the kernels carve it with this, the host sizes the launch with it
+template <class T> __host__ __device__ constexpr int flat_lds_bytes(int flat_cap) { return (FlatLds<T>::fixed_bytes + flat_cap * 2 + 15) & ~15; }
 // exclusive add-scan over the 64 lanes in six DPP adds (row_shr 1 / 2 / 4 / 8 inside the rows of 16, then row_bcast 15 /
 // 31 across the rows) — no LDS crossbar round trips; the wave total comes back in a scalar register.  Called with all 64
 // lanes enabled.

@@ -1,6 +1,7 @@
 """CPU: the code objects of the last build (optable_amd/csrc/build/*.o, cross-compiled for gfx950) — no kernel uses
 scratch memory or spills a vector register, the library stays small, and the kernel-argument layout that
-k_trace_rolling reads its ray pointers from (kernels.h: LeadArgs) is what the code object records."""
+k_trace_rolling reads its ray pointers from (kernels.h: LeadArgs<T, OUT>, one struct for the three kernels) is what the
+code object records."""
 import glob
 import os
 import re
