@@ -3,8 +3,10 @@
 Everything that touches rays goes through liboptable_hip.so; this module only moves
 pointers.  If the library or a GPU is missing the constructor raises — there is no CPU path.
 """
+import contextlib
 import ctypes as C
 import threading
+import time
 
 import torch
 
@@ -14,19 +16,83 @@ from .batch import RayBatch, SegmentBatch
 _engines = {}
 
 
+# -- how large an append-layout block has to be: every rule in one place, plain integers in and out -------------------
+# Per-wave lists: every wave claims `chunk` slots at a time (OT_OPT_APPEND_CHUNK) and may leave the tail of its last chunk
+# unused.  Block pool (bit 4 of `pair_queue`): a workgroup fills one chunk of `_wg_chunk(chunk)` slots at a time, loses at most
+# 63 slots where a pass crosses into the next chunk (`_pool_holes`) and leaves the tail of its last chunk unused.
+def _wg_chunk(chunk):
+    return min(16 * chunk, 1 << 19)
+
+
+def _pool_holes(n_records, wg_chunk):
+    return 64 * (n_records // (wg_chunk - 64) + 1)
+
+
+def _round64(slots):
+    return (slots + 63) // 64 * 64
+
+
 def append_slots(n_records, launch, chunk=512):
     """Slots an append-layout block needs for `n_records` segment records written by a launch of shape `launch`
-    (`Engine.last_launch()`), holes included.  Per-wave lists: every wave may leave the tail of its last chunk unused.
-    Block pool (bit 4 of `pair_queue`): a workgroup fills one chunk of 16 x chunk slots at a time, loses at most 63 slots
-    where a pass crosses into the next chunk and leaves the tail of its last chunk unused.  A multiple of 64."""
+    (`Engine.last_launch()`), holes included, per-wave lists or block pool as the launch was.  A multiple of 64."""
     n_records, chunk = int(n_records), int(chunk)
     if launch["kernel"] == 2 and launch["pair_queue"] & 16:
-        wg_chunk = min(16 * chunk, 1 << 19)
-        slots = n_records + 64 * (n_records // (wg_chunk - 64) + 1) + (wg_chunk + 64) * max(launch["workgroups"], 1)
+        wg_chunk = _wg_chunk(chunk)
+        slots = n_records + _pool_holes(n_records, wg_chunk) + (wg_chunk + 64) * max(launch["workgroups"], 1)
     else:
         waves = max(launch["workgroups"] * launch["threads"] // 64, 1) if launch["kernel"] == 2 else 256 * 16
         slots = n_records + chunk * waves
-    return (slots + 63) // 64 * 64
+    return _round64(slots)
+
+
+def append_worst_case(n, K, chunk, max_waves, pool=True):
+    """Slots that hold the records of ANY trace of n rays capped at K records each, holes included, before the launch shape is
+    known.  `max_waves`: most waves the launch can have.  pool=True (ot_trace_append_*, which picks per-wave lists or the block
+    pool itself): the tail of every wave's last chunk (one wave per ticket of 64 rays at most) or, with the pool (curved
+    scenes, fp32), 63 slots per workgroup chunk and the last chunk of every workgroup, whichever is more.  pool=False
+    (ot_trace_trees_append_*): per-wave lists only, and `max_waves` is the launch's own wave count (`Engine.trees_plan`)."""
+    if not pool:
+        return n * K + chunk * max_waves
+    wg_chunk = _wg_chunk(chunk)
+    waves = min(max_waves, (n + 63) // 64 + 1)
+    return n * K + _pool_holes(n * K, wg_chunk) + max(chunk * waves, (wg_chunk + 64) * min((n + 1023) // 1024, 512))
+
+
+def append_estimate(n, K, records_per_ray, chunk, max_waves, pool=True):
+    """Slots for a trace of n rays that a sample says writes `records_per_ray`: 15 % over that, plus the slack of a full launch
+    (pool=True: one more slot per 128 records for the pool's crossings), never more than the worst case.  A multiple of 64."""
+    records = int(n * records_per_ray * 1.15)
+    slack = records // 128 + max(chunk * max_waves, (_wg_chunk(chunk) + 64) * 256) if pool else chunk * max_waves
+    return _round64(min(records + slack, append_worst_case(n, K, chunk, max_waves, pool)))
+
+
+def _width(precision):
+    return 8 if precision == "f64" else 4
+
+
+def _counts_table(scene, counts, columns, device):
+    """The interact-count table of a launch as (table, its address, its columns): the caller's, else a zeroed one of `columns`
+    columns when the scene has count-limited surfaces, else none."""
+    if counts is None:
+        if not scene.limited:
+            return None, None, 0
+        counts = torch.zeros((len(scene.limited), columns), dtype=torch.int32, device=device)
+    return counts, counts.data_ptr(), counts.shape[1]
+
+
+# What a whole-trace launch writes, by library call: (the SegmentBatch made when the caller passes none, what makes a passed
+# one of the right precision unusable for `slots` = n x cap records, how the error says so)
+_APPEND_OUT = ({"block": True}, lambda out, slots: out.block is None or out.tiled,
+               "append layout needs a SegmentBatch(block=True) of the rays' precision")
+_OUT = {
+    "ot_trace": ({}, lambda out, slots: out.capacity < slots, "output SegmentBatch too small or of the wrong precision"),
+    "ot_trace_tiled": ({"tiled": True}, lambda out, slots: not out.tiled or out.capacity < slots,
+                       "tiled layout needs a SegmentBatch(tiled=True) of the rays' precision with max_segments * n slots"),
+    "ot_trace_append": _APPEND_OUT,
+    "ot_trace_trees": ({}, lambda out, slots: out.capacity < slots or out.tiled or out.block is not None,
+                       "out: plain slot arrays of max_trace_num * n_rays slots in the rays' precision"),
+    "ot_trace_trees_append": _APPEND_OUT,
+}
 
 
 class Engine:
@@ -42,7 +108,6 @@ class Engine:
         self.scene = None
         self.append_chunk = 512  # OT_OPT_APPEND_CHUNK as last set through set_option (the library's default)
         self.trees_refill_at = 16  # OT_OPT_TREES_REFILL_AT likewise
-        self._policy_sets_refill = False
         self._records_per_ray = {}  # (scene, cap, precision) -> records per ray seen in a sample trace (append capacity estimates)
         self._layout_choice = {}    # (scene, precision) -> "slots" | "tiled" measured on the workload itself (tune_layout)
         # An ot_ctx holds one scene and one set of scratch buffers: calls on it are serialised (include/
@@ -99,7 +164,7 @@ class Engine:
         fastest (include/optable_hip.h: ot_trace_plan).  The first call for a light scene measures the device's stream rate in
         both slot layouts (ot_probe_layouts: ~15 ms, once per engine and precision)."""
         info = (C.c_int32 * 8)()
-        abi.check(self.lib.ot_trace_plan(self._ctx, 8 if precision == "f64" else 4, int(n_rays), int(max_segments), C.byref(info)), self.lib)
+        abi.check(self.lib.ot_trace_plan(self._ctx, _width(precision), int(n_rays), int(max_segments), C.byref(info)), self.lib)
         return {"kernel": int(info[0]), "tiled_ok": bool(info[1]), "append_limit": 1 << int(info[2]),
                 "layout": ("slots", "tiled", "append")[int(info[3])], "probe_us": (info[5] / 100.0, info[6] / 100.0)}
 
@@ -148,20 +213,79 @@ class Engine:
     def probe_layouts(self, precision="f64"):
         """(microseconds per launch into the 14 slot arrays, into 64-slot tiles) of cfg 2's streams on this device."""
         a, b = C.c_double(), C.c_double()
-        abi.check(self.lib.ot_probe_layouts(self._ctx, 8 if precision == "f64" else 4, C.byref(a), C.byref(b)), self.lib)
+        abi.check(self.lib.ot_probe_layouts(self._ctx, _width(precision), C.byref(a), C.byref(b)), self.lib)
         return a.value, b.value
+
+    # -- whole traces: one launch preparation for trace and trace_trees ---------------------------
+    def _fn(self, name, precision):
+        return getattr(self.lib, name + ("_f64" if precision == "f64" else "_f32"))
+
+    def _out_for(self, name, rays, K, out, capacity, reuse_count):
+        """The SegmentBatch the library call `name` writes for `rays` capped at K: a new one (append layout: of `capacity` slots),
+        or the caller's if it is of the kind, size and precision the call takes; with `count`, `n_rays` and the layout flags set."""
+        kind, unfit, message = _OUT[name]
+        n = rays.n
+        if out is None:
+            out = SegmentBatch(capacity if "block" in kind else n * K, rays.precision, rays.device, **kind)
+        elif out.precision != rays.precision or unfit(out, n * K):
+            raise ValueError(message)
+        if not reuse_count or out.count is None or out.count.numel() != n:
+            out.count = torch.empty(n, dtype=torch.int32, device=rays.device)
+        out.n_rays = n
+        if "block" in kind:
+            out.append, out.n_valid = True, 0
+            out.tiled = False  # (forced, though the check above has just refused a tiled `out` and a new block is not tiled)
+        return out
+
+    def _launch(self, name, rays, K, out, counts_ptr, n_classes, skip=False):
+        """The library call `name`_f64 / _f32 on the whole batch, `out` handed over the way its layout wants.  skip: everything
+        but the call itself (the append cursor is still made, zeroed and attached)."""
+        kind = _OUT[name][0]
+        rs = rays.c_struct()
+        if "block" in kind:
+            cursor = torch.zeros(1, dtype=torch.int64, device=rays.device)
+            blk = out.block_struct()
+            where = (C.byref(blk), cursor.data_ptr())
+        elif "tiled" in kind:
+            where = (out.block.data_ptr(), out.capacity)
+        else:
+            ss = out.c_struct()
+            where = (C.byref(ss),)
+        if not skip:
+            abi.check(self._fn(name, rays.precision)(self._ctx, C.byref(rs), rays.n, K, *where, out.count.data_ptr(), counts_ptr, n_classes),
+                      self.lib)
+        if "block" in kind:
+            out.cursor, out.n_valid = cursor, None  # device scalar: read lazily (n_valid) so that back-to-back launches do not synchronise
+
+    def _until_it_fits(self, launch, capacity, internal_bound_ends, forget_rate):
+        """An append trace into an ESTIMATED block: `launch(capacity)` -> SegmentBatch; its cursor (one 8-byte read-back) says what
+        the launch needed, and a launch that needed more is repeated into that x 1.02 + 2^20 slots (room for the holes to fall
+        differently: which wave claims which chunk is not the same from run to run), three times at most; the last launch is
+        handed back unread (its `n_valid` raises if even that did not fit).  What the two callers do differently is passed in:
+        internal_bound_ends: a cursor of 2^62 or more (the kernel stopped at an internal bound: `n_valid` says so) ends the loop
+        instead of sizing the next block; forget_rate: `_records_per_ray` is cleared before a repeat (the next batch samples anew)."""
+        out = launch(capacity)
+        for _ in range(3):
+            need = int(out.cursor.item())
+            if need <= out.capacity or (internal_bound_ends and need >= 1 << 62):
+                break
+            if forget_rate:
+                self._records_per_ray = {}
+            del out  # (the block that was too small goes before the larger one is made)
+            out = launch(_round64(int(need * 1.02) + (1 << 20)))
+        return out
 
     # -- non-branching trace ---------------------------------------------------------------
     def trace(self, rays: RayBatch, max_segments, out: SegmentBatch = None, counts=None, layout="slots", capacity=None):
         """All segments of every ray in one launch; returns the SegmentBatch.
-        layout="slots": [k][ray] slots (ot_trace_*).  layout="auto": what the library recommends for this scene, batch and
+        layout="slots": [k][ray] slots (ot_trace_*).  layout="tiled": the same slots in 64-slot tiles (ot_trace_tiled_*): light
+        scenes, the layout the HBM streams like best.  layout="auto": what the library recommends for this scene, batch and
         device (`plan`): "append" for scenes that take the rolling-list / block-pool kernels, for light ones "tiled" or
         "slots", whichever this device streams faster — every reader of a SegmentBatch (to_host, monitors, exports,
         final_state) takes all layouts.  layout="append": a dense list in append order (ot_trace_append_*,
-        include/optable_hip.h) — `capacity` slots; default: estimated from a 1 % sample of the batch (records per ray x
-        1.15 + the launch's chunk slack; the rare batch that needs more is traced again into a block of the size the
-        first launch reported); pass what the job needs to skip the estimate: if that turns out too small a RuntimeError
-        names the size that fits."""
+        include/optable_hip.h) — `capacity` slots; default: estimated from a 1 % sample of the batch (`append_estimate`; the
+        rare batch that needs more is traced again into a block of the size the first launch reported); pass what the job
+        needs to skip the estimate: if that turns out too small a RuntimeError names the size that fits."""
         self._refuse_hooks()
         if self.scene is None:
             raise RuntimeError("upload a scene first")
@@ -172,80 +296,48 @@ class Engine:
             tuned = self._layout_choice.get((id(self.scene), rays.precision))
             plan = self.plan(rays.precision, n, K) if n else None
             layout = "slots" if plan is None else (tuned if (tuned and plan["kernel"] == 1 and plan["tiled_ok"]) else plan["layout"])
-        if layout == "append":
-            return self._trace_append(rays, K, out, counts, capacity)
-        if layout == "tiled":
-            return self._trace_tiled(rays, K, out, counts)
-        if layout != "slots":
+        if layout not in ("slots", "tiled", "append"):
             raise ValueError(f"unknown layout {layout!r}")
-        if out is None:
-            out = SegmentBatch(n * K, rays.precision, rays.device)
-        elif out.capacity < n * K or out.precision != rays.precision:
-            raise ValueError("output SegmentBatch too small or of the wrong precision")
-        if out.count is None or out.count.numel() != n:
-            out.count = torch.empty(n, dtype=torch.int32, device=rays.device)
-        out.n_rays = n
-        out.counts_table = counts
-        if n == 0:  # nothing to launch (zero-size tensors have no address to hand over)
-            return out
-        n_slots = len(self.scene.limited)
-        if n_slots and counts is None:
-            counts = torch.zeros((n_slots, n), dtype=torch.int32, device=rays.device)
-        n_classes = 0 if counts is None else counts.shape[1]
-        fn = self.lib.ot_trace_f64 if rays.precision == "f64" else self.lib.ot_trace_f32
-        rs, ss = rays.c_struct(), out.c_struct()
-        abi.check(fn(self._ctx, C.byref(rs), n, K, C.byref(ss), out.count.data_ptr(),
-                     None if counts is None else counts.data_ptr(), n_classes), self.lib)
-        out.counts_table = counts
-        return out
+        if layout != "append" or out is not None or capacity is not None:
+            return self._trace("ot_trace" if layout == "slots" else "ot_trace_" + layout, rays, K, out, counts, capacity)
+        capacity, rpr = self._append_estimate(rays, K, counts)
+        if rpr is None:
+            return self._trace("ot_trace_append", rays, K, None, counts, capacity)
+        # an estimated block can be too small.  (The table of a scene with limited surfaces is made here, once: a repeated launch
+        # goes on counting in the table the launch before it left, as it always has.)
+        counts = _counts_table(self.scene, counts, n, rays.device)[0]
+        return self._until_it_fits(lambda slots: self._trace("ot_trace_append", rays, K, None, counts, slots), capacity,
+                                   internal_bound_ends=True, forget_rate=True)
 
-    def _trace_tiled(self, rays, K, out, counts):
-        """[k][ray] slots in 64-slot tiles (ot_trace_tiled_*): light scenes, the layout the HBM streams like best."""
-        n = rays.n
-        if out is None:
-            out = SegmentBatch(n * K, rays.precision, rays.device, tiled=True)
-        elif not out.tiled or out.capacity < n * K or out.precision != rays.precision:
-            raise ValueError("tiled layout needs a SegmentBatch(tiled=True) of the rays' precision with max_segments * n slots")
-        if out.count is None or out.count.numel() != n:
-            out.count = torch.empty(n, dtype=torch.int32, device=rays.device)
-        out.n_rays, out.counts_table = n, counts
-        if n == 0:
-            return out
-        n_slots_table = len(self.scene.limited)
-        if n_slots_table and counts is None:
-            counts = torch.zeros((n_slots_table, n), dtype=torch.int32, device=rays.device)
-        n_classes = 0 if counts is None else counts.shape[1]
-        fn = self.lib.ot_trace_tiled_f64 if rays.precision == "f64" else self.lib.ot_trace_tiled_f32
-        rs = rays.c_struct()
-        abi.check(fn(self._ctx, C.byref(rs), n, K, out.block.data_ptr(), out.capacity, out.count.data_ptr(),
-                     None if counts is None else counts.data_ptr(), n_classes), self.lib)
+    def _trace(self, name, rays, K, out, counts, capacity):
+        # (a `count` of the right length is written over, not replaced: a caller who passes `out` again and again allocates nothing)
+        out = self._out_for(name, rays, K, out, capacity, reuse_count=True)
+        out.counts_table = counts
+        if rays.n == 0:  # nothing to launch (zero-size tensors have no address to hand over); `counts_table` is then what the caller
+            return out   # passed, None included: the zeroed table of a scene with limited surfaces is made for a launch only
+        counts, counts_ptr, n_classes = _counts_table(self.scene, counts, rays.n, rays.device)
+        self._launch(name, rays, K, out, counts_ptr, n_classes)
         out.counts_table = counts
         return out
 
     def append_capacity(self, n_records):
-        """Slots an append-layout block needs for `n_records` segment records on this device: every wave of the launch
-        may leave the tail of its last chunk (512 slots) unused.  Call after a trace of the same scene (the launch shape
-        is taken from it); `sum(|count|)` of that trace is the record count."""
+        """Slots an append-layout block needs for `n_records` segment records on this device (`append_slots` for the shape of the
+        last launch and the chunk in force).  Call after a trace of the same scene (the launch shape is taken from it);
+        `sum(|count|)` of that trace is the record count."""
         return append_slots(n_records, self.last_launch(), self.append_chunk)
 
     MAX_WAVES = 256 * 32  # most waves a launch can have resident (256 CUs x 8 per SIMD): each may leave one chunk's tail unused
 
     def _append_worst_case(self, n, K):
-        """Slots that hold the records of ANY trace of n rays capped at K segments, holes included: the tail of every wave's last
-        chunk (one wave per ticket of 64 rays at most); with the block pool (curved scenes, fp32) 63 slots per workgroup chunk
-        and the last chunk of every workgroup."""
-        wg_chunk = min(16 * self.append_chunk, 1 << 19)
-        waves = min(self.MAX_WAVES, (n + 63) // 64 + 1)
-        return (n * K + 64 * (n * K // (wg_chunk - 64) + 1)
-                + max(self.append_chunk * waves, (wg_chunk + 64) * min((n + 1023) // 1024, 512)))
+        return append_worst_case(n, K, self.append_chunk, self.MAX_WAVES)
 
     def _append_estimate(self, rays, K, counts):
-        """Capacity for an append trace without tracing the batch twice: records per ray from a strided 1 % sample (its own
-        small trace), x 1.15, plus the slack of the launch; remembered per scene and cap, so the next batch skips the sample."""
+        """(capacity, records per ray) for an append trace without tracing the batch twice: records per ray from a strided 1 %
+        sample (its own small trace) into `append_estimate`; remembered per scene and cap, so the next batch skips the sample.
+        (worst case, None) where no estimate is made."""
         n = rays.n
-        worst = self._append_worst_case(n, K)
         if n * K <= 1 << 22 or counts is not None:  # small: the worst case costs nothing; count tables: one ray per id per launch, never sampled
-            return worst, None
+            return self._append_worst_case(n, K), None
         key = (id(self.scene), K, rays.precision)
         rpr = self._records_per_ray.get(key)
         if rpr is None:
@@ -254,52 +346,7 @@ class Engine:
             sample = self.trace(rays.take(idx), K, layout="append", capacity=self._append_worst_case(int(idx.numel()), K))
             rpr = float(sample.count.abs().sum().item()) / float(idx.numel())
             self._records_per_ray = {key: rpr}  # (one scene at a time)
-        wg_chunk = min(16 * self.append_chunk, 1 << 19)
-        slack = max(self.append_chunk * self.MAX_WAVES, (wg_chunk + 64) * 256)
-        est = int(n * rpr * 1.15) + int(n * rpr * 1.15) // 128 + slack
-        return (min(est, worst) + 63) // 64 * 64, rpr
-
-    def _trace_append(self, rays, K, out, counts, capacity):
-        n = rays.n
-        estimated = False
-        if capacity is None and out is None:
-            capacity, rpr = self._append_estimate(rays, K, counts)
-            estimated = rpr is not None
-        elif capacity is None:
-            capacity = out.capacity
-        if out is None:
-            out = SegmentBatch(capacity, rays.precision, rays.device, block=True)
-        elif out.block is None or out.tiled or out.precision != rays.precision:
-            raise ValueError("append layout needs a SegmentBatch(block=True) of the rays' precision")
-        out.tiled = False
-        if out.count is None or out.count.numel() != n:
-            out.count = torch.empty(n, dtype=torch.int32, device=rays.device)
-        out.n_rays, out.append, out.n_valid, out.counts_table = n, True, 0, counts
-        if n == 0:
-            return out
-        n_slots_table = len(self.scene.limited)
-        if n_slots_table and counts is None:
-            counts = torch.zeros((n_slots_table, n), dtype=torch.int32, device=rays.device)
-        n_classes = 0 if counts is None else counts.shape[1]
-        fn = self.lib.ot_trace_append_f64 if rays.precision == "f64" else self.lib.ot_trace_append_f32
-        cursor = torch.zeros(1, dtype=torch.int64, device=rays.device)
-        rs, blk = rays.c_struct(), out.block_struct()
-        abi.check(fn(self._ctx, C.byref(rs), n, K, C.byref(blk), cursor.data_ptr(), out.count.data_ptr(),
-                     None if counts is None else counts.data_ptr(), n_classes), self.lib)
-        out.cursor = cursor  # device scalar: read lazily (n_valid) so that back-to-back launches do not synchronise
-        out.n_valid = None
-        out.counts_table = counts
-        if estimated:  # an estimated block can be too small: look (one 8-byte read-back), and trace again into what the launch asked for
-            for _ in range(3):
-                need = int(cursor.item())
-                if need <= out.capacity or need >= 1 << 62:
-                    break
-                # (plus room for the holes to fall differently: which wave claims which chunk is not the same from run to run)
-                self._records_per_ray = {}
-                del out
-                out = self._trace_append(rays, K, None, counts, (int(need * 1.02) + (1 << 20) + 63) // 64 * 64)
-                cursor = out.cursor
-        return out
+        return append_estimate(n, K, rpr, self.append_chunk, self.MAX_WAVES), rpr
 
     # -- branching trace: breadth-first, one generation per launch ------------------------------
     def trees_plan(self, precision, max_trace_num, n_rays=0):
@@ -307,7 +354,7 @@ class Engine:
         per lane would a cap of `max_trace_num` get for a batch of `n_rays` trees (0: one that fills the device), and is that
         enough for every possible tree."""
         info = (C.c_int32 * 8)()
-        abi.check(self.lib.ot_trace_trees_plan(self._ctx, 8 if precision == "f64" else 4, int(max_trace_num), int(n_rays), info), self.lib)
+        abi.check(self.lib.ot_trace_trees_plan(self._ctx, _width(precision), int(max_trace_num), int(n_rays), info), self.lib)
         return {"kernel": bool(info[0] & 1), "slots": bool(info[0] & 2), "queue": int(info[1]), "full": bool(info[2]), "lds_entries": int(info[3]),
                 "chunk": int(info[4]), "waves": int(info[5])}
 
@@ -324,41 +371,18 @@ class Engine:
         if self.scene is None:
             raise RuntimeError("upload a scene first")
         self._check_wavelengths(rays)
-        prec, n, K = rays.precision, rays.n, int(max_trace_num)
-        n_slots = len(self.scene.limited)
-        if n_slots and counts is None:
-            counts = torch.zeros((n_slots, max(n, 1)), dtype=torch.int32, device=rays.device)
-        n_classes = 0 if counts is None else counts.shape[1]
-        cp = None if counts is None else counts.data_ptr()
-        rs = rays.c_struct()
-        if layout == "append":
-            if out is None:
-                if capacity is None:  # every tree at its cap + the tail of every wave's last chunk
-                    plan = self.trees_plan(prec, K, n)
-                    capacity = (n * K + plan["chunk"] * plan["waves"] + 63) // 64 * 64
-                out = SegmentBatch(capacity, prec, rays.device, block=True)
-            elif out.block is None or out.tiled or out.precision != prec:
-                raise ValueError("append layout needs a SegmentBatch(block=True) of the rays' precision")
-            out.count = torch.empty(n, dtype=torch.int32, device=rays.device)
-            out.n_rays, out.append, out.tiled = n, True, False
-            cursor = torch.zeros(1, dtype=torch.int64, device=rays.device)
-            if n:
-                fn = self.lib.ot_trace_trees_append_f64 if prec == "f64" else self.lib.ot_trace_trees_append_f32
-                blk = out.block_struct()
-                abi.check(fn(self._ctx, C.byref(rs), n, K, C.byref(blk), cursor.data_ptr(), out.count.data_ptr(), cp, n_classes), self.lib)
-            out.cursor, out.n_valid = cursor, None  # device scalar: read lazily (n_valid)
-        elif layout == "slots":
-            if out is None:
-                out = SegmentBatch(n * K, prec, rays.device)
-            if out.capacity < n * K or out.precision != prec or out.tiled or out.block is not None:
-                raise ValueError("out: plain slot arrays of max_trace_num * n_rays slots in the rays' precision")
-            out.count = torch.empty(n, dtype=torch.int32, device=rays.device)
-            out.n_rays = n
-            fn = self.lib.ot_trace_trees_f64 if prec == "f64" else self.lib.ot_trace_trees_f32
-            ss = out.c_struct()
-            abi.check(fn(self._ctx, C.byref(rs), n, K, C.byref(ss), out.count.data_ptr(), cp, n_classes), self.lib)
-        else:
+        n, K = rays.n, int(max_trace_num)
+        # (a column per tree, one for a batch of none: unlike `trace`, a call for no trees makes and returns a table)
+        counts, counts_ptr, n_classes = _counts_table(self.scene, counts, max(n, 1), rays.device)
+        if layout not in ("slots", "append"):
             raise ValueError("layout: 'slots' or 'append'")
+        name = "ot_trace_trees" if layout == "slots" else "ot_trace_trees_append"
+        if layout == "append" and out is None and capacity is None:  # every tree at its cap + the tail of every wave's last chunk
+            plan = self.trees_plan(rays.precision, K, n)
+            capacity = append_worst_case(n, K, plan["chunk"], plan["waves"], pool=False)
+        out = self._out_for(name, rays, K, out, capacity, reuse_count=False)  # (unlike `trace`: a new `count` per call, whatever `out` brings)
+        # (the slots call is made for a batch of no trees too; the append call is not, it only leaves a zeroed cursor)
+        self._launch(name, rays, K, out, counts_ptr, n_classes, skip=(n == 0 and layout == "append"))
         out.capped = out.count >= K
         out.timed_out = False
         out.counts_table = counts
@@ -374,9 +398,9 @@ class Engine:
     TREES_SPECULATIVE_SLOTS = 1 << 22  # (440 MB of records in double precision; 40 rays under the reference's largest example's cap of 1e5)
 
     def _trees_estimate(self, rays, K):
-        """Rays per tree of a large batch, and how its waves should refill, from a strided 1 % sample (a lane-per-tree launch of
-        its own), remembered per scene, cap and precision.  Rays per tree sizes the append block (x 1.15 + the launch's slack
-        instead of every tree at its cap).  The spread of the tree sizes picks OT_OPT_TREES_REFILL_AT:
+        """(rays per tree of a large batch, how its waves should refill) from a strided 1 % sample (a lane-per-tree launch of
+        its own), remembered per scene, cap and precision.  Rays per tree sizes the append block (`append_estimate` instead of
+        every tree at its cap).  The spread of the tree sizes picks OT_OPT_TREES_REFILL_AT (set by the caller: `_refill_at`):
         trees that differ moderately (standard deviation below 0.35 of the mean: cfg 4 with R = 0.2 without a binding cap, 13-30
         rays) are traced 64 to a wave, in step — 1.9 instead of 2.6 ms on 3.2e6 of them; batches of mostly tiny trees, or of trees of
         every size up to the cap, keep their lanes busy one by one (1.33 vs 2.13 and 3.2 vs 3.8 ms) (kernels.h)."""
@@ -391,12 +415,17 @@ class Engine:
             even = float(sizes.std(unbiased=False).item()) < 0.35 * rpr
             known = (rpr, 64 if even else 16)
             self._records_per_ray = {key: known}  # (one scene at a time)
-        self._policy_sets_refill = True
+        return known
+
+    @contextlib.contextmanager
+    def _refill_at(self, value):
+        """OT_OPT_TREES_REFILL_AT = `value` while one batch of `trace_branching` is traced (its own choice for that batch), then
+        again what the caller last asked for through `set_option` (the default for calls that do not sample)."""
+        abi.check(self.lib.ot_set_option(self._ctx, abi.OPT_TREES_REFILL_AT, value), self.lib)
         try:
-            self.set_option(abi.OPT_TREES_REFILL_AT, known[1])
+            yield
         finally:
-            self._policy_sets_refill = False
-        return known[0]
+            self.set_option(abi.OPT_TREES_REFILL_AT, self.trees_refill_at)
 
     def trace_branching(self, rays: RayBatch, max_trace_num, counts=None, max_trace_time=None, distinct_ids=None):
         """Ray trees by whichever path the scene and the cap allow: ONE launch with a lane per tree (`trace_trees`) when the
@@ -422,27 +451,16 @@ class Engine:
                 elif n * K <= 1 << 22 or self.scene.limited:  # small: the worst case costs nothing; count tables are never sampled
                     segs = self.trace_trees(rays, K, counts=counts, layout="append")
                 else:
-                    rpr = self._trees_estimate(rays, K)  # (also sets how the waves of this batch refill)
-                    if plan["slots"] and rays.precision == "f32" and rpr >= 0.9 * K:
-                        # nearly every tree runs into the cap: lanes stay in step, [k][tree] rows are whole lines and cost no claims — in
-                        # single precision, where a step is short: 0.29 vs 0.42 ms on 1e6 bushy trees under a cap of 12 (double: 0.57
-                        # either way, cfg 4 R = 0.2 4.29 vs 4.07 for the dense list)
-                        try:
+                    rpr, refill_at = self._trees_estimate(rays, K)
+                    with self._refill_at(refill_at):
+                        if plan["slots"] and rays.precision == "f32" and rpr >= 0.9 * K:
+                            # nearly every tree runs into the cap: lanes stay in step, [k][tree] rows are whole lines and cost no claims — in
+                            # single precision, where a step is short: 0.29 vs 0.42 ms on 1e6 bushy trees under a cap of 12 (double: 0.57
+                            # either way, cfg 4 R = 0.2 4.29 vs 4.07 for the dense list)
                             return self.trace_trees(rays, K, layout="slots")
-                        finally:
-                            self.set_option(abi.OPT_TREES_REFILL_AT, self.trees_refill_at)
-                    slack = plan["chunk"] * plan["waves"]
-                    capacity = min(int(n * rpr * 1.15) + slack, n * K + slack)
-                    try:
-                        for _ in range(3):
-                            segs = self.trace_trees(rays, K, layout="append", capacity=(capacity + 63) // 64 * 64)
-                            need = int(segs.cursor.item())
-                            if need <= segs.capacity:
-                                break
-                            del segs
-                            capacity = int(need * 1.02) + (1 << 20)  # (holes fall differently from run to run)
-                    finally:
-                        self.set_option(abi.OPT_TREES_REFILL_AT, self.trees_refill_at)  # (the default for calls that do not sample)
+                        segs = self._until_it_fits(lambda slots: self.trace_trees(rays, K, layout="append", capacity=slots),
+                                                   append_estimate(n, K, rpr, plan["chunk"], plan["waves"], pool=False),
+                                                   internal_bound_ends=False, forget_rate=False)
                 if plan["full"] or not bool((segs.count < 0).any()):
                     return segs
                 del segs
@@ -458,14 +476,11 @@ class Engine:
         the whole batch, and once it has run out the rays still queued are dropped, as the reference drops a
         tree's queue (`:138-144`); the trees they belonged to are reported in `capped` (`timed_out` says why)."""
         self._refuse_hooks()
-        import time
-
         t_start = time.time()
         if self.scene is None:
             raise RuntimeError("upload a scene first")
         prec = rays.precision
         self._check_wavelengths(rays)
-        gen_fn = self.lib.ot_trace_generation_f64 if prec == "f64" else self.lib.ot_trace_generation_f32
         dev, n = rays.device, rays.n
         if n == 0:
             out = SegmentBatch(0, prec, dev)
@@ -480,17 +495,17 @@ class Engine:
         budget = torch.full((n,), int(max_trace_num), dtype=torch.int32, device=dev)
         state = torch.zeros(2, dtype=torch.int64, device=dev)  # [segment cursor, rays in the next generation]
         tree = torch.arange(n, dtype=torch.int32, device=dev)
-        n_slots = len(self.scene.limited)
-        if n_slots and counts is None:
-            counts = torch.zeros((n_slots, n), dtype=torch.int32, device=dev)
-        n_classes = 0 if counts is None else counts.shape[1]
+        counts, counts_ptr, n_classes = _counts_table(self.scene, counts, n, dev)
         # The generation loop runs inside the library (ot_trace_tree_*: one 16-byte read-back per generation); it comes back
         # when the queue is empty, when the time is up, or when the pending generation needs more room — then the
         # buffers are grown here and the call repeated with that generation as input.
-        tree_fn = self.lib.ot_trace_tree_f64 if prec == "f64" else self.lib.ot_trace_tree_f32
-        cap = max(n * fan, 1024)
-        bufs = [RayBatch(cap, prec, dev, initialise=False), RayBatch(cap, prec, dev, initialise=False)]
-        trees = [torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev)]
+        tree_fn = self._fn("ot_trace_tree", prec)
+
+        def buffer_pair(cap):  # two generations' rays and the tree of each ray
+            return ([RayBatch(cap, prec, dev, initialise=False) for _ in range(2)],
+                    [torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(2)])
+
+        bufs, trees = buffer_pair(max(n * fan, 1024))
         result = (C.c_int64 * 5)()
         cur, cur_n, written = rays, n, 0
         timed_out = None
@@ -503,7 +518,7 @@ class Engine:
             rs, ss, sa, sb = cur.c_struct(), out.c_struct(), bufs[0].c_struct(), bufs[1].c_struct()
             abi.check(tree_fn(self._ctx, C.byref(rs), tree.data_ptr(), cur_n, budget.data_ptr(), C.byref(ss), out.capacity,
                               state.data_ptr(), C.byref(sa), trees[0].data_ptr(), C.byref(sb), trees[1].data_ptr(), bufs[0].n,
-                              None if counts is None else counts.data_ptr(), n_classes, left, result), self.lib)
+                              counts_ptr, n_classes, left, result), self.lib)
             written, cur_n, where, _, reason = (int(x) for x in result)
             if where:  # the pending generation sits in one of the buffers
                 cur, tree = bufs[where - 1].slice(0, cur_n), trees[where - 1][:cur_n]
@@ -523,10 +538,8 @@ class Engine:
             if reason == 1:
                 out = _grow(out, max(written + cur_n, 2 * out.capacity), written)
             elif reason == 2:  # new, larger buffers; the pending generation stays where it is until the next call has read it
-                cap = max(cur_n * fan, 2 * bufs[0].n)
                 keep = (cur, tree)  # noqa: F841 - holds the old buffer alive across the call
-                bufs = [RayBatch(cap, prec, dev, initialise=False), RayBatch(cap, prec, dev, initialise=False)]
-                trees = [torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev)]
+                bufs, trees = buffer_pair(max(cur_n * fan, 2 * bufs[0].n))
         out.n_valid = int(written)
         out.counts_table = counts
         out.capped = budget <= 0  # cap reached: queued rays were dropped (optical_table.py:138-144)
@@ -547,7 +560,6 @@ class Engine:
             raise RuntimeError("upload a scene first")
         prec = rays.precision
         self._check_wavelengths(rays)
-        gen_fn = self.lib.ot_trace_generation_f64 if prec == "f64" else self.lib.ot_trace_generation_f32
         dev, n = rays.device, rays.n
         out = SegmentBatch(n, prec, dev)
         out.n_valid = 0
@@ -565,17 +577,14 @@ class Engine:
             budget = torch.full((int(tree[-1]) + 1,), n + 1, dtype=torch.int32, device=dev)  # (every ray processed, children wanted)
         nxt = RayBatch(n * fan, prec, dev, initialise=False)
         nxt_tree = torch.empty(n * fan, dtype=torch.int32, device=dev)
-        n_slots = len(self.scene.limited)
-        if n_slots and counts is None:
-            counts = torch.zeros((n_slots, n), dtype=torch.int32, device=dev)
-        n_classes = 0 if counts is None else counts.shape[1]
+        counts, counts_ptr, n_classes = _counts_table(self.scene, counts, n, dev)
         rs, ss, ns = rays.c_struct(), out.c_struct(), nxt.c_struct()
         self.set_option(abi.OPT_GEN_PARENT_INDEX, 1)  # nxt_tree = the parent's index, whatever `tree` groups
         try:
-            abi.check(gen_fn(
+            abi.check(self._fn("ot_trace_generation", prec)(
                 self._ctx, C.byref(rs), tree.data_ptr(), n, budget.data_ptr(), C.byref(ss), out.capacity,
                 state.data_ptr(), C.byref(ns), nxt_tree.data_ptr(), nxt.n, state.data_ptr() + 8,
-                None if counts is None else counts.data_ptr(), n_classes), self.lib)
+                counts_ptr, n_classes), self.lib)
         finally:
             self.set_option(abi.OPT_GEN_PARENT_INDEX, 0)
         written, n_next = state.tolist()
@@ -632,22 +641,20 @@ class Engine:
         abi.check(self.lib.ot_set_option(self._ctx, option, value), self.lib)
         if option == abi.OPT_APPEND_CHUNK:
             self.append_chunk = int(value)  # (the capacity estimates of the append layout count holes in chunks)
-        if option == abi.OPT_TREES_REFILL_AT and not self._policy_sets_refill:
-            self.trees_refill_at = int(value)  # (what the caller asked for: trace_branching's own choice for a batch is undone after it)
+        if option == abi.OPT_TREES_REFILL_AT:
+            self.trees_refill_at = int(value)  # (what the caller asked for: trace_branching's own choice for a batch, `_refill_at`, does not come through here)
 
     def stream_ceiling(self, rays: RayBatch, max_segments, out: SegmentBatch):
         """Same bytes as `trace` with no tracing (roofline companion), in the layout of `out` (slots or tiled)."""
         if out.count is None or out.count.numel() != rays.n:
             out.count = torch.empty(rays.n, dtype=torch.int32, device=rays.device)
         if out.tiled:
-            fn = self.lib.ot_bench_stream_tiled_f64 if rays.precision == "f64" else self.lib.ot_bench_stream_tiled_f32
             rs = rays.c_struct()
-            abi.check(fn(self._ctx, C.byref(rs), rays.n, int(max_segments), out.block.data_ptr(), out.capacity, out.count.data_ptr()), self.lib)
+            abi.check(self._fn("ot_bench_stream_tiled", rays.precision)(self._ctx, C.byref(rs), rays.n, int(max_segments), out.block.data_ptr(), out.capacity, out.count.data_ptr()), self.lib)
             return
         rs, ss = rays.c_struct(), out.c_struct()
-        fn = self.lib.ot_bench_stream_f64 if rays.precision == "f64" else self.lib.ot_bench_stream_f32
-        abi.check(fn(self._ctx, C.byref(rs), rays.n, int(max_segments), C.byref(ss),
-                                               out.count.data_ptr()), self.lib)
+        abi.check(self._fn("ot_bench_stream", rays.precision)(self._ctx, C.byref(rs), rays.n, int(max_segments), C.byref(ss),
+                                                              out.count.data_ptr()), self.lib)
 
     def last_launch(self):
         """Shape of the last trace launch (include/optable_hip.h: ot_debug_last_launch) as a dict."""
