@@ -365,7 +365,8 @@ int ot_trace_trees_plan(ot_ctx* ctx, int32_t real_bytes, int32_t max_trace_num, 
  * pending generation (0: finished), [2] where they are (0: the caller's `rays`, 1: buf_a, 2: buf_b), [3] generations run by
  * this call, [4] why it stopped: 0 queue empty, 1 the segment arrays cannot take the pending generation, 2 the buffers
  * cannot take its children (max_children x rays), 3 max_seconds (>= 0) ran out.  After 1 or 2 the caller provides more
- * room and calls again with the pending generation as `rays` / `rays_tree` (and the same state and budget). */
+ * room and calls again with the pending generation as `rays` / `rays_tree` (and the same state and budget).  The arguments
+ * are checked once, at entry, as ot_trace_generation_* checks its own, whichever kernels the generations then take. */
 int ot_trace_tree_f64(ot_ctx* ctx, const ot_rays* rays, const int32_t* rays_tree, int64_t n_rays, int32_t* budget,
                       const ot_segments* out, int64_t out_capacity, int64_t* state, const ot_rays* buf_a, int32_t* tree_a,
                       const ot_rays* buf_b, int32_t* tree_b, int64_t buf_capacity, int32_t* counts, int32_t n_count_classes,

@@ -13,6 +13,7 @@
 #include <chrono>
 #include <vector>
 
+#include "gen_host.h"
 #include "kernels.h"
 #include "misc_kernels.h"
 #include "tables.h"
@@ -709,8 +710,6 @@ static int check_segs(const ot_segments* s) {
     return 0;
 }
 
-static size_t align_up(size_t x) { return (x + 255) / 256 * 256; }
-
 // paired segment stores (kernels.h store_segment_paired): slot k*n + i is even on even lanes iff n is even, and every
 // segment array must be aligned to two elements
 // fp64 only: measured on cfg 4 (1.6e8 pairs) 12.73 -> 12.08 ms (5230 -> 5510 GB/s, 97 % of the stream ceiling), cfg 2
@@ -1135,57 +1134,74 @@ static int gen_preset(uint32_t need) {  // 0 FB (planar, no count gates), 1 FC (
     return (need & ~FB) == 0 ? 0 : ((need & ~FC) == 0 ? 1 : ((need & ~FE) == 0 ? 2 : ((need & ~FM) == 0 ? 3 : 4)));
 }
 
-template <class T>
-static int trace_generation(ot_ctx* c, const ot_rays* rays, const int32_t* tree, int64_t n, int32_t* budget,
-                            const ot_segments* out, int64_t out_capacity, int64_t* seg_cursor, const ot_rays* next,
-                            int32_t* next_tree, int64_t next_capacity, int64_t* n_next, int32_t* counts,
-                            int32_t n_classes, uint8_t* ahead_in = nullptr, uint8_t* ahead_out = nullptr, bool parent_index = false) {
-    // parent_index (OT_OPT_GEN_PARENT_INDEX, the single-generation entry points only): next_tree[] receives the input index of each
-    // child's parent instead of its tree id.
-    // ahead_in: the bytes the emit pass of the generation before left for these rays (children per ray if processed): no count
-    // pass over the rays, k_gen_recount instead.  ahead_out: where this emit pass leaves them for the next generation (of
-    // next_capacity bytes); NULL: plain emit.  Both live outside c->gen, which may be reallocated between generations.
+// What one ot_trace_tree_* / ot_trace_generation_* call launches its generations with, worked out once: the scene image, the
+// LDS it takes (0: the kernels read it from L2), and the kernels of the scene's preset (tables.h).  emit_ahead and one_pass
+// exist for some presets only: NULL otherwise.
+template <class T> struct GenSetup {
+    SceneBlob blob;
+    size_t lds_bytes;
+    ProbeKern<T> probe; GenKern<T> count, emit, emit_ahead; GenOneKern<T> one_pass;
+};
+template <class T> static int gen_setup(const ot_ctx* c, GenSetup<T>* g) {
+    const int fg = gen_preset(c->features);  // smallest generation preset that covers the scene
+    const bool lds = in_lds<T>(c);
+    *g = {make_blob<T>(c), lds ? image_of<T>(c).bytes : 0, probe_kernel<T>(fg, lds), gen_kernel<T>(fg, lds, false), gen_kernel<T>(fg, lds, true),
+          gen_ahead_kernel<T>(fg, lds), gen_one_kernel<T>(fg, lds)};
+    if (g->lds_bytes > 48 * 1024)
+        for (const void* k : {(const void*)g->probe, (const void*)g->count, (const void*)g->emit, (const void*)g->emit_ahead, (const void*)g->one_pass})
+            if (k) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g->lds_bytes));
+    return 0;
+}
+
+// Everything about the arguments of ot_trace_tree_* / ot_trace_generation_* that does not depend on the size of a generation,
+// refused before anything is enqueued.  `cursor`, `result`: state and result, or seg_cursor and n_next; `next`: the holders
+// children are written to, under the names the header gives them.
+struct NamedBuf { const GenBuf& buf; const char* name; };
+static int check_generation_args(const ot_ctx* c, const GenBuf& in, const int32_t* budget, const ot_segments* out, const int64_t* cursor,
+                                 const int64_t* result, const int32_t* counts, int32_t n_classes, std::initializer_list<NamedBuf> next) {
     if (!c) return fail(OT_ERR_INVALID, "ctx is NULL");
     if (!c->has_scene) return fail(OT_ERR_NOSCENE, "ot_scene_upload has not been called");
-    int rc = check_rays(rays, "rays");
+    int rc = check_rays(in.rays, "rays");
     if (rc) return rc;
-    rc = check_rays(next, "next");
-    if (rc) return rc;
+    for (const NamedBuf& b : next) {
+        rc = check_rays(b.buf.rays, b.name);
+        if (rc) return rc;
+        if (!b.buf.tree_out) return fail(OT_ERR_INVALID, "bad generation arguments");
+    }
     rc = check_segs(out);
     if (rc) return rc;
-    if (n < 1 || !tree || !budget || !seg_cursor || !next_tree || !n_next) return fail(OT_ERR_INVALID, "bad generation arguments");
-    if (n >= (int64_t)1 << 30) return fail(OT_ERR_INVALID, "generation too large");
-    const int fan = c->max_children < 1 ? 1 : c->max_children;
-    if (fan > 2) return fail(OT_ERR_UNSUPPORTED, "more than two children per hit");
-    if (next_capacity < n * fan) return fail(OT_ERR_CAPACITY, "next_capacity < n * max_children");
+    if (!in.tree || !budget || !cursor || !result) return fail(OT_ERR_INVALID, "bad generation arguments");
+    if (c->max_children > 2) return fail(OT_ERR_UNSUPPORTED, "more than two children per hit");
     if (c->n_slots > 0 && (!counts || n_classes < 1)) return fail(OT_ERR_INVALID, "scene has limited surfaces: counts table required");
-    HIP_TRY(hipSetDevice(c->device));
-    // scratch carve-up
+    return 0;
+}
+// ... and what does: per generation, whichever kernel takes it
+static int check_generation_size(const ot_ctx* c, int64_t n, int64_t next_capacity) {
+    if (n < 1) return fail(OT_ERR_INVALID, "bad generation arguments");
+    if (n >= (int64_t)1 << 30) return fail(OT_ERR_INVALID, "generation too large");
+    if (next_capacity < n * (c->max_children < 1 ? 1 : c->max_children)) return fail(OT_ERR_CAPACITY, "next_capacity < n * max_children");
+    return 0;
+}
+
+// One generation in two passes (kernels.h k_gen_pass): src's rays traced, the children into dst.
+// ahead_in: src.ahead holds what the emit pass of the generation before left for these rays (children per ray if processed):
+// no count pass over the rays, k_gen_recount instead.  dst.ahead, where there is one, receives the same for the children
+// (next_capacity bytes); both live outside c->gen, which may be reallocated between generations.
+// parent_index (OT_OPT_GEN_PARENT_INDEX, the single-generation entry points only): dst.tree_out[] receives the input index of
+// each child's parent instead of its tree id.
+template <class T>
+static int trace_generation(ot_ctx* c, const GenSetup<T>& g, const GenBuf& src, int64_t n, int32_t* budget, const ot_segments* out,
+                            int64_t out_capacity, int64_t* seg_cursor, const GenBuf& dst, int64_t next_capacity, int64_t* n_next,
+                            int32_t* counts, int32_t n_classes, bool ahead_in, bool parent_index = false) {
+    int rc = check_generation_size(c, n, next_capacity);
+    if (rc) return rc;
     const int ns = c->n_slots;
-    const size_t sz_slot = align_up(sizeof(int32_t) * n * (ns > 0 ? ns : 1));
-    const size_t sz_tot = align_up(sizeof(int64_t) * 4);
     const int64_t n_waves = (n + 63) / 64;
-    const size_t sz_code = align_up((size_t)n), sz_wave = align_up(sizeof(unsigned long long) * n_waves);
     const bool reuse = gen_reuse(c) && !ahead_in;
-    const size_t sz_hn = reuse ? align_up(sizeof(int32_t) * n) : 0, sz_ht = reuse ? align_up(sizeof(T) * n) : 0;
-    const size_t total = sz_tot + sz_code + 2 * sz_wave + (ns > 0 ? 3 * sz_slot : 0) + sz_hn + sz_ht;
-    if (c->gen.ensure(total)) return fail(OT_ERR_HIP, "hipMalloc of generation scratch failed");
-    uint8_t* p = (uint8_t*)c->gen.p;
-    int64_t* totals = (int64_t*)p;
-    unsigned long long* mismatch = nullptr;
-    p += sz_tot;
-    uint8_t* code = p; p += sz_code;
-    unsigned long long* wave_total = (unsigned long long*)p; p += sz_wave;
-    unsigned long long* wave_prefix = (unsigned long long*)p; p += sz_wave;
-    int32_t *probe = nullptr, *probe_ex = nullptr, *rank = nullptr;
-    if (ns > 0) {
-        probe = (int32_t*)p; p += sz_slot;
-        probe_ex = (int32_t*)p; p += sz_slot;
-        rank = (int32_t*)p; p += sz_slot;
-    }
-    int32_t* hit_node = reuse ? (int32_t*)p : nullptr;
-    p += sz_hn;
-    T* hit_t = reuse ? (T*)p : nullptr;
+    GenScratch<T> s;
+    if (c->gen.ensure(s.carve(nullptr, n, ns, reuse))) return fail(OT_ERR_HIP, "hipMalloc of generation scratch failed");
+    s.carve(c->gen.p, n, ns, reuse);
+    uint8_t* const code = ahead_in ? src.ahead : s.code;  // (the look-ahead bytes are rewritten in place by k_gen_recount)
     const size_t tmp = ns > 0 ? scan_tmp_bytes<int32_t>(n) : 0, tmp_w = scan_tmp_bytes<unsigned long long>(n_waves);
     if (c->scan_tmp.ensure((tmp > tmp_w ? tmp : tmp_w) + 256)) return fail(OT_ERR_HIP, "hipMalloc of scan scratch failed");
     const int block = 256;
@@ -1196,46 +1212,34 @@ static int trace_generation(ot_ctx* c, const ot_rays* rays, const int32_t* tree,
         HIP_TRY(hipMalloc((void**)&c->gen_mismatch, sizeof(unsigned long long)));
         HIP_TRY(hipMemsetAsync(c->gen_mismatch, 0, sizeof(unsigned long long), c->stream));
     }
-    mismatch = c->gen_mismatch;  // lives with the ctx: accumulated over all generations (ot_debug_generation_mismatches)
-    const SceneBlob blob = make_blob<T>(c);
-    const bool lds = in_lds<T>(c);
-    const size_t lds_bytes = lds ? image_of<T>(c).bytes : 0;
-    const int fg = gen_preset(c->features);  // smallest generation preset that covers the scene (tables.h)
-    const ProbeKern<T> k_probe = probe_kernel<T>(fg, lds);
-    const GenKern<T> k_count = gen_kernel<T>(fg, lds, false);
-    const GenKern<T> k_emit = ahead_out ? gen_ahead_kernel<T>(fg, lds) : gen_kernel<T>(fg, lds, true);
-    if (!k_emit) return fail(OT_ERR_UNSUPPORTED, "no look-ahead emit kernel for this scene");
-    if (ahead_in) code = ahead_in;  // rewritten in place by k_gen_recount
-    if (lds_bytes > 48 * 1024) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_count, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        HIP_TRY(hipFuncSetAttribute((const void*)k_emit, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    }
+    unsigned long long* const mismatch = c->gen_mismatch;  // lives with the ctx: accumulated over all generations (ot_debug_generation_mismatches)
+    const GenKern<T> k_emit = dst.ahead ? g.emit_ahead : g.emit;
+    const RaysT<T> rays = view<T>(src.rays);
     if (ns > 0) {  // FIFO-exact interact-count gating: probe -> per-slot scan -> rank within the tree
-        HIP_TRY(hipMemsetAsync(probe, 0, sizeof(int32_t) * n * ns, c->stream));
-        hipLaunchKernelGGL(k_probe, dim3(g1), dim3(block), lds_bytes, c->stream, blob, (T)c->unit, view<T>(rays), tree, n, budget,
-                           counts, n_classes, probe);
-        for (int s = 0; s < ns; ++s)
-            exclusive_scan<int32_t, int32_t>(c->scan_tmp.p, probe + (int64_t)s * n, probe_ex + (int64_t)s * n, n, c->stream);
-        hipLaunchKernelGGL(k_gen_rank, dim3(g1), dim3(block), 0, c->stream, tree, n, ns, probe_ex, rank);
+        HIP_TRY(hipMemsetAsync(s.probe, 0, sizeof(int32_t) * n * ns, c->stream));
+        hipLaunchKernelGGL(g.probe, dim3(g1), dim3(block), g.lds_bytes, c->stream, g.blob, (T)c->unit, rays, src.tree, n, budget, counts, n_classes,
+                           s.probe);
+        for (int k = 0; k < ns; ++k)
+            exclusive_scan<int32_t, int32_t>(c->scan_tmp.p, s.probe + (int64_t)k * n, s.probe_ex + (int64_t)k * n, n, c->stream);
+        hipLaunchKernelGGL(k_gen_rank, dim3(g1), dim3(block), 0, c->stream, src.tree, n, ns, s.probe_ex, s.rank);
     }
     // count -> scan of the wave totals -> emit (kernels.h: k_gen_pass)
     if (ahead_in)
-        hipLaunchKernelGGL(k_gen_recount, dim3(g1), dim3(block), 0, c->stream, tree, n, (const int32_t*)budget, code, wave_total, c->opt_gen_drop ? 1 : 0);
+        hipLaunchKernelGGL(k_gen_recount, dim3(g1), dim3(block), 0, c->stream, src.tree, n, (const int32_t*)budget, code, s.wave_total, c->opt_gen_drop ? 1 : 0);
     else
-        hipLaunchKernelGGL(k_count, dim3(g1), dim3(block), lds_bytes, c->stream, blob, (T)c->unit, view<T>(rays), tree, n, budget,
-                           (const int64_t*)seg_cursor, view<T>(out), out_capacity, view_out<T>(next), next_tree, next_capacity, code, wave_total,
-                           (const unsigned long long*)wave_prefix, counts, n_classes, (const int32_t*)rank, mismatch, hit_node, hit_t,
+        hipLaunchKernelGGL(g.count, dim3(g1), dim3(block), g.lds_bytes, c->stream, g.blob, (T)c->unit, rays, src.tree, n, budget,
+                           (const int64_t*)seg_cursor, view<T>(out), out_capacity, view_out<T>(dst.rays), dst.tree_out, next_capacity, code, s.wave_total,
+                           (const unsigned long long*)s.wave_prefix, counts, n_classes, (const int32_t*)s.rank, mismatch, s.hit_node, s.hit_t,
                            c->opt_gen_drop ? 1 : 0, (uint8_t*)nullptr);
-    exclusive_scan<unsigned long long, unsigned long long>(c->scan_tmp.p, wave_total, wave_prefix, n_waves, c->stream);
-    hipLaunchKernelGGL(k_gen_totals, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)wave_total,
-                       (const unsigned long long*)wave_prefix, n_waves, totals, seg_cursor, n_next);
-    hipLaunchKernelGGL(k_emit, dim3(g1), dim3(block), lds_bytes, c->stream, blob, (T)c->unit, view<T>(rays), tree, n, budget,
-                       (const int64_t*)(totals + 2), view<T>(out), out_capacity, view_out<T>(next), next_tree, next_capacity, code, wave_total,
-                       (const unsigned long long*)wave_prefix, counts, n_classes, (const int32_t*)rank, mismatch, hit_node, hit_t,
-                       (c->opt_gen_drop ? 1 : 0) | (parent_index ? 2 : 0), ahead_out);
+    exclusive_scan<unsigned long long, unsigned long long>(c->scan_tmp.p, s.wave_total, s.wave_prefix, n_waves, c->stream);
+    hipLaunchKernelGGL(k_gen_totals, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)s.wave_total,
+                       (const unsigned long long*)s.wave_prefix, n_waves, s.totals, seg_cursor, n_next);
+    hipLaunchKernelGGL(k_emit, dim3(g1), dim3(block), g.lds_bytes, c->stream, g.blob, (T)c->unit, rays, src.tree, n, budget,
+                       (const int64_t*)(s.totals + 2), view<T>(out), out_capacity, view_out<T>(dst.rays), dst.tree_out, next_capacity, code, s.wave_total,
+                       (const unsigned long long*)s.wave_prefix, counts, n_classes, (const int32_t*)s.rank, mismatch, s.hit_node, s.hit_t,
+                       (c->opt_gen_drop ? 1 : 0) | (parent_index ? 2 : 0), dst.ahead);
     if (ns > 0)
-        hipLaunchKernelGGL(k_gen_counts, dim3(g1), dim3(block), 0, c->stream, tree, rays->id, n, ns, rank, probe, c->slot_max, counts,
+        hipLaunchKernelGGL(k_gen_counts, dim3(g1), dim3(block), 0, c->stream, src.tree, src.rays->id, n, ns, s.rank, s.probe, c->slot_max, counts,
                            n_classes);
     HIP_TRY(hipGetLastError());
     return timing_end(c);
@@ -1357,150 +1361,143 @@ static int trace_trees_append(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t
     return launch_trees<T, SegPlanes<T>>(c, rays, n, cap, planes, ac, seg_count, counts, n_classes);
 }
 
-// One generation in one pass (kernels.h k_gen_one): zero the tile descriptors and the ticket, launch.  `rem`: what is left of
-// its tree's budget for every ray of the generation; `next_rem` receives the children's.
+// One generation in one pass (kernels.h k_gen_one): zero the tile descriptors and the ticket, launch.  src.rem: what is left of
+// its tree's budget for every ray of the generation; dst.rem receives the children's.  n_in / n_out: chained launches (trace_tree).
 template <class T>
-static int trace_generation_one(ot_ctx* c, const ot_rays* rays, const int32_t* tree, const int32_t* rem, int64_t n, int32_t* budget, const ot_segments* out,
-                                int64_t out_capacity, int64_t* state, const ot_rays* next, int32_t* next_tree, int32_t* next_rem, int64_t next_capacity,
-                                int32_t* counts, int32_t n_classes, const int64_t* n_in = nullptr, int64_t* n_out = nullptr) {
+static int trace_generation_one(ot_ctx* c, const GenSetup<T>& g, const GenBuf& src, int64_t n, int32_t* budget, const ot_segments* out,
+                                int64_t out_capacity, int64_t* state, const GenBuf& dst, int64_t next_capacity, int32_t* counts, int32_t n_classes,
+                                const int64_t* n_in, int64_t* n_out) {
+    int rc = check_generation_size(c, n, next_capacity);
+    if (rc) return rc;
     const int64_t n_tiles = (n + 63) / 64, n_groups = (n + 255) / 256;  // a tile = the 64 rays of one wave
     const size_t sz_desc = align_up(sizeof(unsigned long long) * n_tiles + 8);
     // (at least 64 KB: growing the scratch frees it, which waits for the device — not between the launches of a chain)
     if (c->gen.ensure(sz_desc < 65536 ? 65536 : sz_desc)) return fail(OT_ERR_HIP, "hipMalloc of generation scratch failed");
     unsigned long long* desc = (unsigned long long*)c->gen.p;
     uint32_t* ticket = (uint32_t*)(desc + n_tiles);
-    int rc = timing_begin(c);
+    rc = timing_begin(c);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(desc, 0, sizeof(unsigned long long) * n_tiles + 8, c->stream));
-    const SceneBlob blob = make_blob<T>(c);
-    const bool lds = in_lds<T>(c);
-    const size_t lds_bytes = lds ? image_of<T>(c).bytes : 0;
-    const int fg = gen_preset(c->features);
-    const GenOneKern<T> k = gen_one_kernel<T>(fg, lds);
-    if (lds_bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipLaunchKernelGGL(k, dim3((unsigned)n_groups), dim3(256), lds_bytes, c->stream, blob, (T)c->unit, view<T>(rays), tree, rem, n, budget, state, view<T>(out),
-                       out_capacity, view_out<T>(next), next_tree, next_rem, next_capacity, desc, ticket, counts, n_classes, c->opt_gen_drop ? 1 : 0, n_in, n_out);
+    hipLaunchKernelGGL(g.one_pass, dim3((unsigned)n_groups), dim3(256), g.lds_bytes, c->stream, g.blob, (T)c->unit, view<T>(src.rays), src.tree,
+                       (const int32_t*)src.rem, n, budget, state, view<T>(out), out_capacity, view_out<T>(dst.rays), dst.tree_out, dst.rem, next_capacity, desc,
+                       ticket, counts, n_classes, c->opt_gen_drop ? 1 : 0, n_in, n_out);
     HIP_TRY(hipGetLastError());
     return timing_end(c);
 }
 
-// The generation loop of a whole ray tree batch (optical_table.py:115-147) on the host side of the library: one
-// trace_generation per generation, the two counters read back (16 bytes, one stream synchronisation) and the two generation
-// buffers swapped — the loop the Python shell used to run with a dozen ctypes conversions per turn.  It stops when the
-// queue is empty, when the next generation does not fit the buffers or the segment arrays (the caller grows them and calls
-// again with the pending generation as input), or when the wall clock runs out.
+// The generation loop of a whole ray tree batch (optical_table.py:115-147): one launch sequence per generation, then the two
+// counters read back (16 bytes, one stream synchronisation).  gen[where] holds the pending generation, its children go to
+// gen[other(where)].  It stops when the queue is empty, when the next generation does not fit the buffers or the segment
+// arrays (the caller grows them and calls again with the pending generation as input), or when the wall clock runs out.
 template <class T>
 static int trace_tree(ot_ctx* c, const ot_rays* rays, const int32_t* tree, int64_t n, int32_t* budget, const ot_segments* out,
                       int64_t out_capacity, int64_t* state, const ot_rays* buf_a, int32_t* tree_a, const ot_rays* buf_b, int32_t* tree_b,
                       int64_t buf_capacity, int32_t* counts, int32_t n_classes, double max_seconds, int64_t* result) {
-    if (!c || !state || !result || !buf_a || !buf_b || !tree_a || !tree_b) return fail(OT_ERR_INVALID, "NULL argument");
-    if (!c->has_scene) return fail(OT_ERR_NOSCENE, "ot_scene_upload has not been called");
+    GenBuf gen[3] = {{rays, tree}, {buf_a, tree_a, tree_a}, {buf_b, tree_b, tree_b}};
+    int rc = check_generation_args(c, gen[0], budget, out, state, result, counts, n_classes, {{gen[1], "buf_a"}, {gen[2], "buf_b"}});
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
+    GenSetup<T> g;
+    rc = gen_setup<T>(c, &g);
+    if (rc) return rc;
     const int fan = c->max_children < 1 ? 1 : c->max_children;
     const auto t0 = std::chrono::steady_clock::now();
     if (!c->pinned_state) HIP_TRY(hipHostMalloc((void**)&c->pinned_state, 2 * sizeof(int64_t), hipHostMallocDefault));
     int64_t* const host_state = c->pinned_state;  // (page-locked: the copy is a DMA the stream waits for, not a staged memcpy)
     HIP_TRY(hipMemcpyAsync(host_state, state, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    int64_t written = host_state[0], cur_n = n, generations = 0;
-    const ot_rays* cur = rays;
-    const int32_t* cur_tree = tree;
-    int where = 0;  // which buffer holds the pending generation: 0 the caller's rays, 1 buf_a, 2 buf_b
-    int64_t reason = 0;
+    int64_t written = host_state[0], cur_n = n, generations = 0, reason = 0;
+    int where = 0;
+    // What the launch that produced the CURRENT generation left with it: its per-ray budgets in gen[where].rem (a one-pass
+    // generation; else they are seeded from budget[]), its look-ahead bytes in gen[where].ahead (a two-pass one with look-ahead)
+    bool rem_valid = false, ahead_valid = false;
     // One pass per generation (k_gen_one) where OT_OPT_GEN_ONEPASS allows it and the scene has no count-limited leaves (their
-    // gate needs the scans between a probe pass and the trace).  Its per-ray budgets live in the library: seeded from budget[]
-    // for the first generation of this call, two buffers of buf_capacity for the children.
-    const bool one_pass_kernel = gen_one_kernel<T>(gen_preset(c->features), in_lds<T>(c)) != nullptr;
-    // OT_OPT_GEN_ONEPASS: 1 every generation, 0 none, -1 (default) the SMALL ones: a generation of a few thousand rays is a
-    // handful of tiles that are all resident at once — nothing to wait for in the look-back — and one launch instead of six
-    // (count, three scan kernels, totals, emit) is what a tree of six rays costs: 1.08 -> ms per table.ray_tracing call.
+    // gate needs the scans between a probe pass and the trace).  OT_OPT_GEN_ONEPASS: 1 every generation, 0 none, -1 (default)
+    // the SMALL ones: a generation of a few thousand rays is a handful of tiles that are all resident at once — nothing to
+    // wait for in the look-back — and one launch instead of six (count, three scan kernels, totals, emit) is what a tree of
+    // six rays costs: 1.08 -> ms per table.ray_tracing call.
     constexpr int64_t ONE_PASS_SMALL = 1 << 16;
-    const bool one_pass_ok = c->n_slots == 0 && c->opt_gen_onepass != 0 && n > 0 && one_pass_kernel;
-    int32_t *rem_cur = nullptr, *rem_in = nullptr, *rem_a = nullptr, *rem_b = nullptr;
-    bool rem_valid = false;  // rem_cur holds the budgets of the CURRENT generation's rays (seeded, or written by a one-pass generation)
-    int chained_to = 0;      // buffer (1 / 2) the last generation of a chain of small generations left its children in, 0 = no chain ran
+    const bool one_pass_ok = c->n_slots == 0 && c->opt_gen_onepass != 0 && n > 0 && g.one_pass;
     int64_t* chain_n = nullptr;  // two device words: sizes handed from one chained generation to the next
     if (one_pass_ok) {
         if (c->gen_rem.ensure(sizeof(int32_t) * (size_t)(n + 2 * buf_capacity) + 256)) return fail(OT_ERR_HIP, "hipMalloc of the per-ray budgets failed");
-        rem_in = (int32_t*)c->gen_rem.p;
-        rem_a = rem_in + n;
-        rem_b = rem_a + buf_capacity;
+        gen[0].rem = (int32_t*)c->gen_rem.p;
+        gen[1].rem = gen[0].rem + n;
+        gen[2].rem = gen[1].rem + buf_capacity;
         if (!c->gen_chain) HIP_TRY(hipMalloc((void**)&c->gen_chain, 2 * sizeof(int64_t)));
         chain_n = c->gen_chain;
     }
     // Look-ahead (k_gen_pass MODE 2; OT_OPT_GEN_AHEAD): the emit pass of a two-pass generation leaves, per child, the number of
     // children that child will have; the next two-pass generation replaces its count pass over the rays by k_gen_recount over
     // those bytes.  Light scenes (no decision reuse: their search is a few planes) without count gates whose generation
-    // buffers carry no `len`; two byte arrays of buf_capacity used in turn.
-    const bool ahead_ok = c->opt_gen_ahead != 0 && c->n_slots == 0 && !gen_reuse(c) && !buf_a->length && !buf_b->length &&
-                          gen_ahead_kernel<T>(gen_preset(c->features), in_lds<T>(c)) != nullptr;
-    uint8_t *ahead_a = nullptr, *ahead_b = nullptr, *ahead_cur = nullptr;  // ahead_cur: the bytes of the CURRENT generation, if its producer left them
-    if (ahead_ok) {
+    // buffers carry no `len`; a byte array of buf_capacity with each buffer.
+    if (c->opt_gen_ahead != 0 && c->n_slots == 0 && !gen_reuse(c) && !gen[1].rays->length && !gen[2].rays->length && g.emit_ahead) {
         const size_t each = align_up((size_t)buf_capacity + 64);
         if (c->gen_ahead.ensure(2 * each)) return fail(OT_ERR_HIP, "hipMalloc of the look-ahead bytes failed");
-        ahead_a = (uint8_t*)c->gen_ahead.p;
-        ahead_b = ahead_a + each;
+        gen[1].ahead = (uint8_t*)c->gen_ahead.p;
+        gen[2].ahead = gen[1].ahead + each;
     }
     while (cur_n > 0) {
         if (written + cur_n > out_capacity) { reason = 1; break; }        // the segment arrays are too small for this generation
         if (cur_n * fan > buf_capacity) { reason = 2; break; }           // ... the generation buffers for the next one
-        const bool to_a = where != 1;
-        const bool one_pass = one_pass_ok && (c->opt_gen_onepass > 0 || cur_n <= ONE_PASS_SMALL);
-        int rc;
-        if (one_pass) {
-            if (!rem_valid) {  // first generation of the call, or the one before took the two passes: per-ray budgets from the tree table
-                rem_cur = where == 0 ? rem_in : (where == 1 ? rem_a : rem_b);
-                hipLaunchKernelGGL(k_gen_seed_rem, dim3((unsigned)((cur_n + 255) / 256)), dim3(256), 0, c->stream, cur_tree, (const int32_t*)budget, cur_n, rem_cur);
+        int src = where, dst = other(where);
+        if (one_pass_ok && (c->opt_gen_onepass > 0 || cur_n <= ONE_PASS_SMALL)) {
+            if (!rem_valid) {
+                hipLaunchKernelGGL(k_gen_seed_rem, dim3((unsigned)((cur_n + 255) / 256)), dim3(256), 0, c->stream, gen[src].tree, (const int32_t*)budget, cur_n, gen[src].rem);
                 HIP_TRY(hipGetLastError());
             }
-            ahead_cur = nullptr;
-            rc = trace_generation_one<T>(c, cur, cur_tree, rem_cur, cur_n, budget, out, out_capacity, state, to_a ? buf_a : buf_b, to_a ? tree_a : tree_b,
-                                         to_a ? rem_a : rem_b, buf_capacity, counts, n_classes, nullptr, chain_n);
-            rem_cur = to_a ? rem_a : rem_b;
+            rc = trace_generation_one<T>(c, g, gen[src], cur_n, budget, out, out_capacity, state, gen[dst], buf_capacity, counts, n_classes, nullptr, chain_n);
+            if (rc) return rc;
             rem_valid = true;
+            ahead_valid = false;
             // Small trees: further generations are enqueued WITHOUT reading anything back — each launch sized for the most rays
             // the one before can have emitted, its real size taken on the device from where that one left it (k_gen_one's n_in /
-            // n_out).  One read-back per chain instead of one per generation: a tree of a handful of rays is launch and
-            // synchronisation latency, nothing else.
-            if (rc == 0 && (max_seconds < 0 || max_seconds > 1.0)) {  // (a chain is at most fifteen launches of a few microseconds)
+            // n_out, the two words used in turn).  One read-back per chain instead of one per generation: a tree of a handful of
+            // rays is launch and synchronisation latency, nothing else.
+            if (max_seconds < 0 || max_seconds > 1.0) {  // (a chain is at most fifteen launches of a few microseconds)
                 int64_t bound = cur_n * fan, written_bound = written + cur_n;
-                int here = to_a ? 1 : 2, slot = 0;
                 for (int link = 0; link < 15 && bound <= 4096 && bound * fan <= buf_capacity && written_bound + bound <= out_capacity; ++link) {
-                    const bool from_a = here == 1;
-                    rc = trace_generation_one<T>(c, from_a ? buf_a : buf_b, from_a ? tree_a : tree_b, from_a ? rem_a : rem_b, bound, budget, out, out_capacity,
-                                                 state, from_a ? buf_b : buf_a, from_a ? tree_b : tree_a, from_a ? rem_b : rem_a, buf_capacity, counts, n_classes,
-                                                 chain_n + slot, chain_n + (slot ^ 1));
-                    if (rc) break;
+                    src = dst;
+                    dst = other(dst);
+                    rc = trace_generation_one<T>(c, g, gen[src], bound, budget, out, out_capacity, state, gen[dst], buf_capacity, counts, n_classes,
+                                                 chain_n + (link & 1), chain_n + (~link & 1));
+                    if (rc) return rc;
                     written_bound += bound;
                     bound *= fan;
-                    here = from_a ? 2 : 1;
-                    slot ^= 1;
                     ++generations;
-                    chained_to = here;
                 }
             }
         } else {
-            uint8_t* const ahead_next = ahead_ok ? (to_a ? ahead_a : ahead_b) : nullptr;
-            rc = trace_generation<T>(c, cur, cur_tree, cur_n, budget, out, out_capacity, state, to_a ? buf_a : buf_b, to_a ? tree_a : tree_b,
-                                     buf_capacity, state + 1, counts, n_classes, ahead_cur, ahead_next);
-            ahead_cur = ahead_next;
+            rc = trace_generation<T>(c, g, gen[src], cur_n, budget, out, out_capacity, state, gen[dst], buf_capacity, state + 1, counts, n_classes, ahead_valid);
+            if (rc) return rc;
             rem_valid = false;
+            ahead_valid = gen[dst].ahead != nullptr;
         }
-        if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(host_state, state, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));  // the one host synchronisation per generation (per chain of small generations)
         written = host_state[0];
         cur_n = host_state[1];
         ++generations;
-        where = chained_to ? chained_to : (to_a ? 1 : 2);
-        if (chained_to) rem_cur = where == 1 ? rem_a : rem_b;
-        chained_to = 0;
-        cur = where == 1 ? buf_a : buf_b;
-        cur_tree = where == 1 ? tree_a : tree_b;
+        where = dst;
         if (max_seconds >= 0 && cur_n > 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() >= max_seconds) { reason = 3; break; }
     }
     result[0] = written; result[1] = cur_n; result[2] = where; result[3] = generations; result[4] = reason;
     return 0;
+}
+
+// One generation for the caller (ot_trace_generation_*): the two passes, whatever OT_OPT_GEN_ONEPASS says
+template <class T>
+static int trace_one_generation(ot_ctx* c, const ot_rays* rays, const int32_t* tree, int64_t n, int32_t* budget, const ot_segments* out,
+                                int64_t out_capacity, int64_t* seg_cursor, const ot_rays* next, int32_t* next_tree, int64_t next_capacity,
+                                int64_t* n_next, int32_t* counts, int32_t n_classes) {
+    const GenBuf src = {rays, tree}, dst = {next, next_tree, next_tree};
+    int rc = check_generation_args(c, src, budget, out, seg_cursor, n_next, counts, n_classes, {{dst, "next"}});
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    GenSetup<T> g;
+    rc = gen_setup<T>(c, &g);
+    if (rc) return rc;
+    return trace_generation<T>(c, g, src, n, budget, out, out_capacity, seg_cursor, dst, next_capacity, n_next, counts, n_classes, false, c->opt_gen_parent);
 }
 
 extern "C" {
@@ -1548,15 +1545,13 @@ int ot_trace_generation_f64(ot_ctx* c, const ot_rays* rays, const int32_t* tree,
                             const ot_segments* out, int64_t out_capacity, int64_t* seg_cursor, const ot_rays* next,
                             int32_t* next_tree, int64_t next_capacity, int64_t* n_next, int32_t* counts,
                             int32_t n_classes) {
-    return trace_generation<double>(c, rays, tree, n, budget, out, out_capacity, seg_cursor, next, next_tree, next_capacity, n_next,
-                                    counts, n_classes, nullptr, nullptr, c && c->opt_gen_parent);
+    return trace_one_generation<double>(c, rays, tree, n, budget, out, out_capacity, seg_cursor, next, next_tree, next_capacity, n_next, counts, n_classes);
 }
 int ot_trace_generation_f32(ot_ctx* c, const ot_rays* rays, const int32_t* tree, int64_t n, int32_t* budget,
                             const ot_segments* out, int64_t out_capacity, int64_t* seg_cursor, const ot_rays* next,
                             int32_t* next_tree, int64_t next_capacity, int64_t* n_next, int32_t* counts,
                             int32_t n_classes) {
-    return trace_generation<float>(c, rays, tree, n, budget, out, out_capacity, seg_cursor, next, next_tree, next_capacity, n_next,
-                                   counts, n_classes, nullptr, nullptr, c && c->opt_gen_parent);
+    return trace_one_generation<float>(c, rays, tree, n, budget, out, out_capacity, seg_cursor, next, next_tree, next_capacity, n_next, counts, n_classes);
 }
 
 int ot_monitor_record_f64(ot_ctx* c, const ot_monitor* mon, const ot_segments* segs, int64_t n, const int32_t* seg_count,
@@ -1572,14 +1567,16 @@ int ot_monitor_record_f64(ot_ctx* c, const ot_monitor* mon, const ot_segments* s
         HIP_TRY(hipMemsetAsync(n_hits, 0, sizeof(int64_t), c->stream));
         return 0;
     }
-    const size_t sz_hit = align_up(sizeof(int32_t) * n), sz_off = align_up(sizeof(int64_t) * n), sz_P = align_up(sizeof(double) * 3 * n),
-                 sz_t = align_up(sizeof(double) * n);
-    if (c->mon.ensure(sz_hit + sz_off + sz_P + sz_t)) return fail(OT_ERR_HIP, "hipMalloc of monitor scratch failed");
-    uint8_t* p = (uint8_t*)c->mon.p;
-    int32_t* hit = (int32_t*)p; p += sz_hit;
-    int64_t* off = (int64_t*)p; p += sz_off;
-    double* P = (double*)p; p += sz_P;
-    double* tt = (double*)p;
+    int32_t* hit;
+    int64_t* off;
+    double *P, *tt;
+    const auto carve = [&](void* base) {
+        Carve cv{(uint8_t*)base};
+        hit = cv.take<int32_t>(n), off = cv.take<int64_t>(n), P = cv.take<double>(3 * n), tt = cv.take<double>(n);
+        return cv.used;
+    };
+    if (c->mon.ensure(carve(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of monitor scratch failed");
+    carve(c->mon.p);
     if (c->scan_tmp.ensure(scan_tmp_bytes<int64_t>(n) + 256)) return fail(OT_ERR_HIP, "hipMalloc of scan scratch failed");
     const int block = 256, grid = (int)((n + block - 1) / block);
     hipLaunchKernelGGL(k_mon_test, dim3(grid), dim3(block), 0, c->stream, *mon, view<double>(segs), n, seg_count, n_rays, hit, P, tt);

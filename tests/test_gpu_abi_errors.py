@@ -181,3 +181,60 @@ def test_trace_argument_checks(ctx):
     assert lib.ot_ctx_synchronize(c) == 0
     assert int(table.abs().sum()) == 0
     assert lib.ot_ctx_synchronize(None) == ERR_INVALID
+
+
+@pytest.mark.parametrize("onepass", [0, 1])
+def test_tree_and_generation_argument_checks(ctx, onepass):
+    """ot_trace_tree_* and ot_trace_generation_* refuse a malformed call at their entry, whichever kernel OT_OPT_GEN_ONEPASS
+    would give the generation, and the ctx traces a well-formed one afterwards."""
+    import torch
+    from optable_amd.batch import RayBatch, SegmentBatch
+
+    lib, c = ctx
+    assert lib.ot_set_option(c, abi.OPT_GEN_ONEPASS, onepass) == 0
+    n = 64
+    o, d = scenes.cfg2_rays(n, 0)
+    rays = RayBatch.from_arrays(o, d, wavelength=scenes.WL)
+    segs = SegmentBatch(1024)
+    bufs = [RayBatch(1024, initialise=False) for _ in range(2)]
+    trees = [torch.empty(1024, dtype=torch.int32, device="cuda") for _ in range(2)]
+    tree = torch.arange(n, dtype=torch.int32, device="cuda")
+    budget = torch.full((n,), 5, dtype=torch.int32, device="cuda")  # one entry per tree: 5 segments each, 320 of the 1024 slots
+    state = torch.zeros(2, dtype=torch.int64, device="cuda")
+    result = (C.c_int64 * 5)()
+    rs, ss, sa, sb = rays.c_struct(), segs.c_struct(), bufs[0].c_struct(), bufs[1].c_struct()
+
+    def tree_call(r=C.byref(rs), t=tree.data_ptr(), b=budget.data_ptr(), s=C.byref(ss), buf_b=C.byref(sb), counts=None, ncls=0):
+        return lib.ot_trace_tree_f64(c, r, t, n, b, s, segs.capacity, state.data_ptr(), C.byref(sa), trees[0].data_ptr(), buf_b,
+                                     trees[1].data_ptr(), bufs[0].n, counts, ncls, -1.0, result)
+
+    def generation_call(r=C.byref(rs), s=C.byref(ss), nxt=C.byref(sa)):
+        return lib.ot_trace_generation_f64(c, r, tree.data_ptr(), n, budget.data_ptr(), s, segs.capacity, state.data_ptr(), nxt,
+                                           trees[0].data_ptr(), bufs[0].n, state.data_ptr() + 8, None, 0)
+
+    broken, broken_buf = rays.c_struct(), bufs[1].c_struct()
+    broken.q_im = None
+    broken_buf.flags = None
+    _expect(lib, tree_call(), ERR_NOSCENE, "ot_scene_upload")
+    _expect(lib, generation_call(), ERR_NOSCENE, "ot_scene_upload")
+    sc = _compiled(lambda oa: dict(components=scenes.cfg2_components(oa)))
+    assert lib.ot_scene_upload(c, C.byref(sc.desc())) == 0
+    _expect(lib, tree_call(r=None), ERR_INVALID, "rays is NULL")
+    _expect(lib, tree_call(s=None), ERR_INVALID, "segments is NULL")
+    _expect(lib, tree_call(r=C.byref(broken)), ERR_INVALID, "rays has a NULL field")
+    _expect(lib, tree_call(buf_b=C.byref(broken_buf)), ERR_INVALID, "buf_b has a NULL field")
+    _expect(lib, tree_call(b=None), ERR_INVALID, "bad generation arguments")
+    _expect(lib, tree_call(t=None), ERR_INVALID, "bad generation arguments")
+    _expect(lib, generation_call(r=None), ERR_INVALID, "rays is NULL")
+    _expect(lib, generation_call(s=None), ERR_INVALID, "segments is NULL")
+    _expect(lib, generation_call(r=C.byref(broken)), ERR_INVALID, "rays has a NULL field")
+    _expect(lib, generation_call(nxt=C.byref(broken_buf)), ERR_INVALID, "next has a NULL field")
+    lim = _compiled(scenes.g13_count_shadow)  # a scene with a count-limited surface needs the table
+    assert lib.ot_scene_upload(c, C.byref(lim.desc())) == 0
+    _expect(lib, tree_call(), ERR_INVALID, "counts table")
+    # nothing was enqueued by any of them: the state is untouched, and the ctx traces
+    assert lib.ot_ctx_synchronize(c) == 0 and state.tolist() == [0, 0]
+    assert lib.ot_scene_upload(c, C.byref(sc.desc())) == 0
+    assert tree_call() == 0, lib.ot_last_error().decode()
+    assert result[4] == 0 and result[1] == 0 and 0 < result[0] <= 5 * n
+    assert lib.ot_ctx_synchronize(c) == 0

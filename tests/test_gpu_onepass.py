@@ -117,6 +117,36 @@ def test_one_pass_equals_two_pass_on_a_heavy_planar_scene():
     _both(table.compile(), batch, 20)
 
 
+@pytest.mark.parametrize("n", [1, 5, 64])
+def test_tiny_trees_take_every_route_of_the_generation_loop(n):
+    """Trees that double every generation, a handful of them: every generation stays under 4096 rays, so every one-pass
+    generation is a chain link; a segment array of 16 slots ends the chains on its bound and the call re-enters with the
+    pending generation wherever it was; at 64 trees the generations outgrow the buffers of 1024 rays.  Whatever the kernel
+    and however often the call comes back: the list of the two-pass run with room for everything, element by element."""
+    scene = _lattice()
+    rng = np.random.default_rng(7)
+    o = np.stack([np.zeros(n), rng.uniform(-0.3, 0.3, n), rng.uniform(-0.2, 0.2, n)], 1)
+    d = np.stack([np.ones(n), rng.uniform(-0.02, 0.02, n), rng.uniform(-0.01, 0.01, n)], 1)
+    batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=Q)
+    eng = get_engine()
+    eng.upload(scene)
+    try:
+        eng.set_option(abi.OPT_GEN_ONEPASS, 0)
+        ref = eng.trace_tree(batch, 40)
+        m = ref.n_valid
+        assert m > n
+        for onepass in (0, 1, -1):
+            eng.set_option(abi.OPT_GEN_ONEPASS, onepass)
+            for out_capacity in (None, 16):
+                got = eng.trace_tree(batch, 40, out_capacity=out_capacity)
+                assert got.n_valid == m, (onepass, out_capacity)
+                for f in abi.SEG_FIELDS + ("ray", "surface"):
+                    assert torch.equal(got.field(f)[:m], ref.field(f)[:m]), (onepass, out_capacity, f)
+                assert torch.equal(got.capped, ref.capped), (onepass, out_capacity)
+    finally:
+        eng.set_option(abi.OPT_GEN_ONEPASS, -1)
+
+
 def test_one_pass_resumes_after_its_buffers_grow():
     """Segment arrays and generation buffers that are too small at first: the library hands the pending generation back, the
     engine grows the buffers and calls again — the per-ray budgets of the one-pass kernels are re-seeded from the tree
