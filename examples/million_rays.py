@@ -33,3 +33,6 @@ hits = table.record_batch(screen, segs)                         # Monitor.record
 total = int(segs.count.sum())
 print(f"{n} rays, {total} segments in {dt * 1e3:.2f} ms ({total * 3 / dt:.3e} ray-surface intersections/s incl. launch)")
 print(f"monitor at x = 7.5: {len(hits)} crossings, rms radius {float(torch.sqrt((hits.yList() ** 2 + hits.zList() ** 2).mean())):.4f}")
+stack = [oa.Monitor([6.0 + 0.5 * k, 0, 0], 3, 3) for k in range(7)]  # a through-focus stack: all of it in one pass over the segments
+for mon, h in zip(stack, table.record_all(segs, monitors=stack)):
+    print(f"monitor at x = {mon.origin[0]:.1f}: {len(h)} crossings")

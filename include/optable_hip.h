@@ -419,6 +419,33 @@ int ot_monitor_record_f64(ot_ctx* ctx, const ot_monitor* mon, const ot_segments*
                           int64_t n_segments, const int32_t* seg_count, int64_t n_rays,
                           int64_t* hit_index, void* Px, void* Py, void* Pz, void* t, int64_t* n_hits);
 
+/* Monitor.record on EVERY monitor of a table (optical_table.py:145-146: `for monitor in self.monitors: monitor.record(rays)`;
+ * the test of monitor.py:183-193 as above) in one pass over the segments, read where they lie: no conversion, no per-slot
+ * scratch.  Two kernels over one partition of the slots — count the hits per monitor and workgroup, scan, write — for up to 32
+ * monitors at a time; longer lists are walked 32 at a time inside the call.
+ * The segments: field f of slot s (ox, oy, oz, dx, dy, dz, length) lies at base[f] + (s >> 6) * tile_stride + (s & 63) * width
+ * and its int32 `ray` at ray + (s >> 6) * ray_stride + (s & 63) * 4 — plain arrays (ot_segments, the planes of an
+ * ot_segment_block): base[f] = the array, tile_stride = 64 * width, ray_stride = 256; a block of 64-slot tiles (ot_trace_tiled_*):
+ * base[f] = block + 64 * f * width, ray = block + 64 * 12 * width, both strides the tile size 64 * (12 * width + 8).  width: bytes of
+ * a real, 4 or 8 (single precision is widened, exactly; the test is done in double precision either way); capacity: slots the
+ * source holds (n_segments may not exceed it).  seg_count / n_rays: as for ot_monitor_record_f64.
+ * Output, all on the device: the hits of monitor m are entries first[m] .. first[m + 1] - 1 of hit_index (slot indices,
+ * ascending), Px, Py, Pz, t (double), each of `capacity` entries; first has n_monitors + 1 entries, *n_total = first[n_monitors].
+ * Like the append layout's cursor, first and *n_total are exact even when they exceed `capacity`: entries beyond it are not
+ * written (nothing is written outside the buffers) and the caller repeats the call with room.  n_segments = 0: first all zero.
+ * OT_ERR_INVALID, nothing launched: a NULL argument or source field, n_monitors < 1, n_segments < 0 or >= 2^31, a width other
+ * than 4 or 8, a seg_count / n_rays combination ot_monitor_record_f64 refuses. */
+typedef struct ot_segment_source {
+    const void* base[7];
+    const void* ray;
+    int64_t tile_stride, ray_stride;
+    int64_t capacity;
+    int32_t width;
+} ot_segment_source;
+int ot_monitor_record_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitors, const ot_segment_source* src,
+                           int64_t n_segments, const int32_t* seg_count, int64_t n_rays, int64_t capacity, int64_t* first,
+                           int64_t* hit_index, void* Px, void* Py, void* Pz, void* t, int64_t* n_total);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled every trace launch is bracketed by hipEvents on the ctx stream. */
 int ot_timing_enable(ot_ctx* ctx, int enabled);

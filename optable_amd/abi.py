@@ -66,6 +66,15 @@ class OtMonitor(C.Structure):
                 ("half_width", C.c_double), ("half_height", C.c_double)]
 
 
+class OtSegmentSource(C.Structure):
+    """Where segments lie, whatever their layout (ot_monitor_record_many): field f of slot s at
+    base[f] + (s >> 6) * tile_stride + (s & 63) * width, `ray` likewise with ray_stride and 4-byte ints."""
+    _fields_ = [("base", C.c_void_p * 7), ("ray", C.c_void_p), ("tile_stride", C.c_int64), ("ray_stride", C.c_int64),
+                ("capacity", C.c_int64), ("width", C.c_int32)]
+
+
+MON_FIELDS = ("ox", "oy", "oz", "dx", "dy", "dz", "length")  # what a monitor pass reads of a segment, in the order of OtSegmentSource.base
+
 # flags / enums (== header)
 NODE_GROUP, NODE_LEAF = 0, 1
 NODE_CHECK_AABB, NODE_GRID, NODE_BOX_TRUSTED = 1, 2, 4
@@ -109,6 +118,8 @@ SYMBOLS = {
     "ot_trace_trees_plan": (C.c_int, [_vp, _i32, _i32, _i64, _vp]),
     "ot_monitor_record_f64": (C.c_int, [_vp, C.POINTER(OtMonitor), C.POINTER(OtSegments), _i64, _vp, _i64, _vp, _vp,
                                         _vp, _vp, _vp, _vp]),
+    "ot_monitor_record_many": (C.c_int, [_vp, C.POINTER(OtMonitor), _i32, C.POINTER(OtSegmentSource), _i64, _vp, _i64, _i64, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp]),
     "ot_timing_enable": (C.c_int, [_vp, C.c_int]),
     "ot_timing_read": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(_i64)]),
     "ot_timing_reset": (C.c_int, [_vp]),

@@ -172,6 +172,25 @@ __global__ void k_gen_counts(const int32_t* tree, const int32_t* ids, int64_t n,
 
 // ------------------------------------------------------------------------------------------
 // Monitor.record
+// The plane and aperture test of one segment (monitor.py:183-193): the segment in the monitor's frame, direction renormalised
+// (ray_to_local_coordinates), the crossing of the plane x = 0 within the segment's length and the rectangle.  One definition
+// for the one-monitor kernels (k_mon_test) and the many-monitor ones (k_mon_count / k_mon_emit): P = local hit point, t = distance.
+__device__ __forceinline__ bool mon_hit(const ot_monitor& mon, double sox, double soy, double soz, double sdx, double sdy, double sdz, double slen,
+                                        double& Px, double& Py, double& Pz, double& t) {
+    const double rx = sox - mon.origin[0], ry = soy - mon.origin[1], rz = soz - mon.origin[2];
+    const double* M = mon.M;
+    const double ox = M[0] * rx + M[3] * ry + M[6] * rz, oy = M[1] * rx + M[4] * ry + M[7] * rz,
+                 oz = M[2] * rx + M[5] * ry + M[8] * rz;
+    double dx = M[0] * sdx + M[3] * sdy + M[6] * sdz, dy = M[1] * sdx + M[4] * sdy + M[7] * sdz,
+           dz = M[2] * sdx + M[5] * sdy + M[8] * sdz;
+    const double inv = 1.0 / sqrt(dx * dx + dy * dy + dz * dz);  // ray_to_local_coordinates renormalises
+    dx *= inv; dy *= inv; dz *= inv;
+    if (dx == 0.0) return false;
+    t = -ox / dx;
+    if (fabs(t) < 1e-9 || t < 0.0 || t > slen) return false;
+    Px = ox + t * dx; Py = oy + t * dy; Pz = oz + t * dz;
+    return fabs(Py) <= mon.half_width && fabs(Pz) <= mon.half_height;
+}
 __global__ void k_mon_test(ot_monitor mon, SegsT<double> s, int64_t n, const int32_t* seg_count, int64_t n_rays, int32_t* hit,
                            double* P, double* tt) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -183,27 +202,13 @@ __global__ void k_mon_test(ot_monitor mon, SegsT<double> s, int64_t n, const int
         hit[i] = 0;
         return;
     }
-    const double rx = s.ox[i] - mon.origin[0], ry = s.oy[i] - mon.origin[1], rz = s.oz[i] - mon.origin[2];
-    const double* M = mon.M;
-    const double ox = M[0] * rx + M[3] * ry + M[6] * rz, oy = M[1] * rx + M[4] * ry + M[7] * rz,
-                 oz = M[2] * rx + M[5] * ry + M[8] * rz;
-    double dx = M[0] * s.dx[i] + M[3] * s.dy[i] + M[6] * s.dz[i], dy = M[1] * s.dx[i] + M[4] * s.dy[i] + M[7] * s.dz[i],
-           dz = M[2] * s.dx[i] + M[5] * s.dy[i] + M[8] * s.dz[i];
-    const double inv = 1.0 / sqrt(dx * dx + dy * dy + dz * dz);  // ray_to_local_coordinates renormalises
-    dx *= inv; dy *= inv; dz *= inv;
-    int32_t ok = 0;
-    if (dx != 0.0) {
-        const double t = -ox / dx;
-        if (!(fabs(t) < 1e-9 || t < 0.0 || t > s.len[i])) {
-            const double Px = ox + t * dx, Py = oy + t * dy, Pz = oz + t * dz;
-            if (fabs(Py) <= mon.half_width && fabs(Pz) <= mon.half_height) {
-                ok = 1;
-                P[3 * i] = Px; P[3 * i + 1] = Py; P[3 * i + 2] = Pz;
-                tt[i] = t;
-            }
-        }
+    double Px, Py, Pz, t;
+    const bool ok = mon_hit(mon, s.ox[i], s.oy[i], s.oz[i], s.dx[i], s.dy[i], s.dz[i], s.len[i], Px, Py, Pz, t);
+    if (ok) {
+        P[3 * i] = Px; P[3 * i + 1] = Py; P[3 * i + 2] = Pz;
+        tt[i] = t;
     }
-    hit[i] = ok;
+    hit[i] = ok ? 1 : 0;
 }
 __global__ void k_mon_compact(const int32_t* hit, const int64_t* off, const double* P, const double* tt, int64_t n,
                               int64_t* hit_index, double* Px, double* Py, double* Pz, double* t, int64_t* n_hits) {
@@ -216,3 +221,142 @@ __global__ void k_mon_compact(const int32_t* hit, const int64_t* off, const doub
     if (i == n - 1) *n_hits = off[i] + hit[i];
 }
 
+
+// ------------------------------------------------------------------------------------------
+// Monitor.record on up to MON_MAX monitors in one pass over the segments (ot_monitor_record_many), in two kernels that share
+// one partition of the slots: workgroup g owns the slots [g * span, (g + 1) * span), span = iters * MON_THREADS, and visits
+// them MON_THREADS at a time.  k_mon_count leaves count[m][g]; an exclusive_scan over them in monitor-major order gives every
+// workgroup its place in ONE concatenated output (monitor 0's hits, then monitor 1's, ...); k_mon_emit runs the same loads
+// and tests and writes each hit there, so the hits of a monitor come out in ascending slot order.  No per-slot scratch.
+// A segment is read where it lies, in either precision (fp32 widened in registers: exact): field f of slot s at
+//   base[f] + (s >> 6) * tile_stride + (s & 63) * width
+// — a block of 64-slot tiles with tile_stride = its tile size, plain arrays (slot arrays, planes of an append block) with
+// tile_stride = 64 * width.  Layout and precision are launch arguments: uniform branches in kernels bound by their loads.
+static constexpr int MON_THREADS = 256, MON_WAVES = MON_THREADS / 64, MON_MAX = 32;
+struct MonSource {
+    const uint8_t* base[7];  // ox oy oz dx dy dz length
+    const uint8_t* ray;      // int32 per slot, read only for lists with holes
+    int64_t tile_stride, ray_stride;
+    int32_t width;
+};
+struct MonSeg {
+    double ox, oy, oz, dx, dy, dz, len;
+    bool valid;
+};
+__device__ __forceinline__ double mon_real(const uint8_t* p, int32_t width) {
+    return width == 8 ? *reinterpret_cast<const double*>(p) : (double)*reinterpret_cast<const float*>(p);
+}
+// slot s with the validity rule of k_mon_test: k < |seg_count[ray]| in [k][ray] slots, ray >= 0 in lists with holes (n_rays < 0)
+__device__ __forceinline__ MonSeg mon_load(const MonSource& src, int64_t s, int64_t n, const int32_t* __restrict__ seg_count, int64_t n_rays) {
+    MonSeg g;
+    g.ox = g.oy = g.oz = g.dx = g.dy = g.dz = g.len = 0.0;
+    g.valid = s < n;
+    if (!g.valid) return g;
+    const int64_t tile = s >> 6, in_tile = s & 63;
+    if (seg_count) {
+        const uint32_t nr = (uint32_t)n_rays, su = (uint32_t)s;  // (n < 2^31)
+        const int32_t c = seg_count[su % nr];
+        g.valid = (int32_t)(su / nr) < (c < 0 ? -c : c);
+    } else if (n_rays < 0) {
+        g.valid = *reinterpret_cast<const int32_t*>(src.ray + tile * src.ray_stride + in_tile * 4) >= 0;
+    }
+    if (!g.valid) return g;
+    const int64_t at = tile * src.tile_stride + in_tile * src.width;
+    g.ox = mon_real(src.base[0] + at, src.width); g.oy = mon_real(src.base[1] + at, src.width); g.oz = mon_real(src.base[2] + at, src.width);
+    g.dx = mon_real(src.base[3] + at, src.width); g.dy = mon_real(src.base[4] + at, src.width); g.dz = mon_real(src.base[5] + at, src.width);
+    g.len = mon_real(src.base[6] + at, src.width);
+    return g;
+}
+// count[m * gridDim.x + g] = hits of monitor m among workgroup g's slots; count[n_mon * gridDim.x] = 0, so that the scan's last
+// element is the total
+__global__ __launch_bounds__(MON_THREADS) void k_mon_count(const ot_monitor* __restrict__ mons, int32_t n_mon, MonSource src, int64_t n, int32_t iters,
+                                                           const int32_t* __restrict__ seg_count, int64_t n_rays, int32_t* __restrict__ count) {
+    __shared__ int32_t total[MON_MAX];
+    const int lane = threadIdx.x & 63;
+    if (threadIdx.x < MON_MAX) total[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t first = (int64_t)blockIdx.x * iters * MON_THREADS;
+    for (int32_t it = 0; it < iters && first + (int64_t)it * MON_THREADS < n; ++it) {
+        const MonSeg g = mon_load(src, first + (int64_t)it * MON_THREADS + threadIdx.x, n, seg_count, n_rays);
+        if (!__ballot(g.valid)) continue;
+        for (int32_t m = 0; m < n_mon; ++m) {  // m is wave-uniform: the monitor comes through scalar loads
+            double Px, Py, Pz, t;
+            const bool hit = g.valid && mon_hit(mons[m], g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, g.len, Px, Py, Pz, t);
+            const unsigned long long b = __ballot(hit);
+            if (lane == 0 && b) atomicAdd(&total[m], (int32_t)__popcll(b));
+        }
+    }
+    __syncthreads();
+    if ((int32_t)threadIdx.x < n_mon) count[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = total[threadIdx.x];
+    if (blockIdx.x == 0 && threadIdx.x == 0) count[(int64_t)n_mon * gridDim.x] = 0;
+}
+// off = the exclusive scan of count (n_mon * gridDim.x + 1 elements).  Position of a hit in the concatenated output: first[0]
+// (the hits of the monitors of earlier launches: the host walks long lists MON_MAX monitors at a time) + off[m][g] + hits of
+// monitor m in the workgroup's earlier visits + in the earlier waves of this visit + in the lower lanes (v_mbcnt).  Writes stop
+// at `capacity`; first[1 .. n_mon] and *n_total are exact whatever the capacity.  A workgroup none of whose slots hit leaves
+// without reading a segment, and only the monitors it has hits on are tested again.
+__global__ __launch_bounds__(MON_THREADS) void k_mon_emit(const ot_monitor* __restrict__ mons, int32_t n_mon, MonSource src, int64_t n, int32_t iters,
+                                                          const int32_t* __restrict__ seg_count, int64_t n_rays, const int64_t* __restrict__ off,
+                                                          int64_t capacity, int64_t* first, int64_t* __restrict__ hit_index, double* __restrict__ Px,
+                                                          double* __restrict__ Py, double* __restrict__ Pz, double* __restrict__ tt, int64_t* n_total) {
+    __shared__ int32_t wave_hits[2][MON_MAX][MON_WAVES];  // [parity of the visit]: one barrier per visit
+    __shared__ int32_t seen[MON_WAVES][MON_MAX];          // every wave's own copy of the hits of the workgroup's earlier visits
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t G = gridDim.x, before_launch = first[0];
+    if (blockIdx.x == 0 && (int32_t)threadIdx.x < n_mon) first[threadIdx.x + 1] = before_launch + off[(int64_t)(threadIdx.x + 1) * G];
+    if (blockIdx.x == 0 && threadIdx.x == 0) *n_total = before_launch + off[(int64_t)n_mon * G];
+    bool mine = false;
+    if (lane < n_mon) {
+        const int64_t at = (int64_t)lane * G + blockIdx.x;
+        mine = off[at + 1] != off[at];
+    }
+    const uint32_t live = (uint32_t)__ballot(mine);  // monitors this workgroup has hits on
+    if (!live) return;
+    // seen[wave][] is this wave's own: written and read by lanes of one wave only, whose LDS operations retire in order; the
+    // wavefront fences keep the compiler from moving a read across the write before it
+    if (lane < MON_MAX) seen[wave][lane] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const int64_t start = (int64_t)blockIdx.x * iters * MON_THREADS;
+    for (int32_t it = 0; it < iters && start + (int64_t)it * MON_THREADS < n; ++it) {
+        const int64_t s = start + (int64_t)it * MON_THREADS + threadIdx.x;
+        const int p = it & 1;
+        const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
+        uint32_t hits = 0;
+        for (uint32_t rest = live; rest; rest &= rest - 1) {
+            const int m = __builtin_ctz(rest);
+            double x, y, z, t;
+            const bool hit = g.valid && mon_hit(mons[m], g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, g.len, x, y, z, t);
+            const unsigned long long b = __ballot(hit);
+            if (lane == 0) wave_hits[p][m][wave] = (int32_t)__popcll(b);
+            hits |= (hit ? 1u : 0u) << m;
+        }
+        __syncthreads();
+        for (uint32_t rest = live; rest; rest &= rest - 1) {
+            const int m = __builtin_ctz(rest);
+            int32_t below = 0, all = 0;
+#pragma unroll
+            for (int w = 0; w < MON_WAVES; ++w) {
+                const int32_t c = wave_hits[p][m][w];
+                below += w < wave ? c : 0;
+                all += c;
+            }
+            if (!all) continue;
+            const bool hit = (hits >> m) & 1u;
+            const unsigned long long b = __ballot(hit);
+            const int32_t earlier = seen[wave][m];
+            if (hit) {
+                const int64_t d = before_launch + off[(int64_t)m * G + blockIdx.x] + earlier + below + rank_below(b);
+                if (d < capacity) {
+                    double x, y, z, t;
+                    (void)mon_hit(mons[m], g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, g.len, x, y, z, t);
+                    hit_index[d] = s; Px[d] = x; Py[d] = y; Pz[d] = z; tt[d] = t;
+                }
+            }
+            if (lane == 0) seen[wave][m] = earlier + all;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+}

@@ -1587,6 +1587,61 @@ int ot_monitor_record_f64(ot_ctx* c, const ot_monitor* mon, const ot_segments* s
     return 0;
 }
 
+int ot_monitor_record_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const ot_segment_source* src, int64_t n,
+                           const int32_t* seg_count, int64_t n_rays, int64_t capacity, int64_t* first, int64_t* hit_index, void* Px, void* Py,
+                           void* Pz, void* t, int64_t* n_total) {
+    if (!c || !mons || !src || !first || !hit_index || !Px || !Py || !Pz || !t || !n_total) return fail(OT_ERR_INVALID, "NULL argument");
+    if (n_monitors < 1) return fail(OT_ERR_INVALID, "n_monitors must be at least 1");
+    if (n < 0 || n >= (int64_t)1 << 31) return fail(OT_ERR_INVALID, "bad segment count");
+    if (src->width != 4 && src->width != 8) return fail(OT_ERR_INVALID, "segment source: width must be 4 or 8");
+    for (const void* p : src->base)
+        if (!p) return fail(OT_ERR_INVALID, "segment source has a NULL field");
+    if (!src->ray) return fail(OT_ERR_INVALID, "segment source has a NULL field");
+    if (src->tile_stride < 64 * (int64_t)src->width || src->ray_stride < 256) return fail(OT_ERR_INVALID, "segment source: a tile stride shorter than 64 slots");
+    if (n > src->capacity) return fail(OT_ERR_INVALID, "n_segments exceeds the capacity of the segment source");
+    if (capacity < 0) return fail(OT_ERR_INVALID, "negative output capacity");
+    if (seg_count && (n_rays < 1 || n % n_rays != 0)) return fail(OT_ERR_INVALID, "n_segments must be a multiple of n_rays");
+    if (!seg_count && n_rays > 0) return fail(OT_ERR_INVALID, "n_rays without seg_count: pass 0 for a list, -1 for a list with holes");
+    HIP_TRY(hipSetDevice(c->device));
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(first, 0, sizeof(int64_t) * ((size_t)n_monitors + 1), c->stream));
+        HIP_TRY(hipMemsetAsync(n_total, 0, sizeof(int64_t), c->stream));
+        return 0;
+    }
+    // one partition of the slots for both passes: workgroups of `iters` visits of MON_THREADS slots (8 visits up to 2^25 slots: 2441
+    // workgroups for cfg 2's 5e6; more visits beyond, which keeps a launch at some 16 thousand workgroups however many slots)
+    const int32_t iters = (int32_t)std::max<int64_t>(8, n >> 22);
+    const int64_t span = (int64_t)iters * MON_THREADS, grid = (n + span - 1) / span;
+    const int32_t most = std::min<int32_t>(n_monitors, MON_MAX);
+    ot_monitor* table;
+    int32_t* count;
+    int64_t* off;
+    const auto carve = [&](void* base) {
+        Carve cv{(uint8_t*)base};
+        table = cv.take<ot_monitor>(n_monitors), count = cv.take<int32_t>(most * grid + 1), off = cv.take<int64_t>(most * grid + 1);
+        return cv.used;
+    };
+    if (c->mon.ensure(carve(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of monitor scratch failed");
+    carve(c->mon.p);
+    if (c->scan_tmp.ensure(scan_tmp_bytes<int64_t>(most * grid + 1) + 256)) return fail(OT_ERR_HIP, "hipMalloc of scan scratch failed");
+    HIP_TRY(hipMemcpyAsync(table, mons, sizeof(ot_monitor) * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(first, 0, sizeof(int64_t), c->stream));
+    MonSource ms;
+    for (int f = 0; f < 7; ++f) ms.base[f] = (const uint8_t*)src->base[f];
+    ms.ray = (const uint8_t*)src->ray;
+    ms.tile_stride = src->tile_stride, ms.ray_stride = src->ray_stride, ms.width = src->width;
+    // MON_MAX monitors per launch; a launch takes the hits before it from first[m0], where the launch before it left them
+    for (int32_t m0 = 0; m0 < n_monitors; m0 += MON_MAX) {
+        const int32_t nm = std::min<int32_t>(MON_MAX, n_monitors - m0);
+        hipLaunchKernelGGL(k_mon_count, dim3((unsigned)grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, iters, seg_count, n_rays, count);
+        exclusive_scan<int32_t, int64_t>(c->scan_tmp.p, count, off, nm * grid + 1, c->stream);
+        hipLaunchKernelGGL(k_mon_emit, dim3((unsigned)grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, iters, seg_count, n_rays, off,
+                           capacity, first + m0, hit_index, (double*)Px, (double*)Py, (double*)Pz, (double*)t, n_total);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int ot_debug_last_launch(ot_ctx* c, int32_t info[8]) {
     if (!c || !info) return fail(OT_ERR_INVALID, "NULL argument");
     for (int q = 0; q < 8; ++q) info[q] = c->last_launch[q];

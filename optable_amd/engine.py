@@ -80,6 +80,28 @@ def _counts_table(scene, counts, columns, device):
     return counts, counts.data_ptr(), counts.shape[1]
 
 
+def segment_source(segs):
+    """(ot_segment_source, n_segments, seg_count, n_rays) for a SegmentBatch AS IT LIES IN MEMORY, any layout, either precision
+    (include/optable_hip.h: ot_monitor_record_many).  The tiled fields are strided [tiles, 64] views of one block: their
+    address is the field's first tile and their row stride the tile size; every other field is a plain array (64-slot "tiles"
+    back to back).  n_segments / seg_count / n_rays as ot_monitor_record_f64 wants them: all whole [k][ray] planes with the
+    counts for slots and tiles, the first n_valid slots for lists (n_rays = -1: with holes).  Addresses only: no library call."""
+    src = abi.OtSegmentSource()
+    for k, f in enumerate(abi.MON_FIELDS):
+        src.base[k] = segs.field(f).data_ptr()
+    src.ray = segs.ray.data_ptr()
+    src.width = _width(segs.precision)
+
+    def tile_bytes(field):
+        return (field.stride(0) if field.dim() == 2 else 64) * field.element_size()
+
+    src.tile_stride, src.ray_stride, src.capacity = tile_bytes(segs.ox), tile_bytes(segs.ray), segs.capacity
+    if segs.layout in ("slots", "tiled"):
+        n_rays = int(segs.n_rays)
+        return src, (segs.capacity // n_rays * n_rays if n_rays else 0), segs.count, n_rays
+    return src, int(segs.n_valid), None, (-1 if segs.append else 0)
+
+
 # What a whole-trace launch writes, by library call: (the SegmentBatch made when the caller passes none, what makes a passed
 # one of the right precision unusable for `slots` = n x cap records, how the error says so)
 _APPEND_OUT = ({"block": True}, lambda out, slots: out.block is None or out.tiled,
@@ -623,6 +645,37 @@ class Engine:
                                                  t.data_ptr(), nh.data_ptr()), self.lib)
         k = int(nh.item())
         return idx[:k], torch.stack([p[:k] for p in P], dim=1), t[:k]
+
+    def monitor_record_many(self, monitor_structs, segs: SegmentBatch, capacity=None):
+        """Device pass of Monitor.record for a list of monitors over a SegmentBatch read as it lies (any layout, either
+        precision: no `to_slots`, no `astype`): ot_monitor_record_many, the segments read once per pass whatever the number of
+        monitors.  Returns one (slot index, P_local [h,3], t) per monitor, ascending slot order.  `capacity`: entries of the
+        concatenated output (default: the slots scanned); a pass that finds more is repeated once, whole, with exactly what it
+        found — the usual case for a stack of monitors that every ray crosses (M monitors x n rays hits against the slots of
+        the history): pass `capacity` >= the hits expected to spare the first pass."""
+        with self.lock:
+            return self._monitor_record_many(list(monitor_structs), segs, capacity)
+
+    def _monitor_record_many(self, mons, segs, capacity):
+        dev, M = segs.device, len(mons)
+        src, n_segments, count, n_rays = segment_source(segs)
+        if M == 0 or n_segments == 0:  # (zero-size tensors have no address to hand over)
+            none = torch.empty(0, dtype=torch.float64, device=dev)
+            return [(torch.empty(0, dtype=torch.int64, device=dev), none.reshape(0, 3), none) for _ in range(M)]
+        table = (abi.OtMonitor * M)(*mons)
+        capacity = max(n_segments if capacity is None else int(capacity), 1)
+        for _ in range(2):
+            idx = torch.empty(capacity, dtype=torch.int64, device=dev)
+            out = torch.empty((4, capacity), dtype=torch.float64, device=dev)  # Px, Py, Pz, t
+            first = torch.empty(M + 2, dtype=torch.int64, device=dev)          # first[0 .. M], then the total
+            abi.check(self.lib.ot_monitor_record_many(self._ctx, table, M, C.byref(src), n_segments, None if count is None else count.data_ptr(),
+                                                      n_rays, capacity, first.data_ptr(), idx.data_ptr(), *(out[k].data_ptr() for k in range(4)),
+                                                      first.data_ptr() + 8 * (M + 1)), self.lib)
+            first = first.tolist()  # (synchronises)
+            if first[M + 1] <= capacity:
+                break
+            capacity = first[M + 1]
+        return [(idx[a:b], out[:3, a:b].T, out[3, a:b]) for a, b in zip(first[:M], first[1:M + 1])]
 
     # -- measurement ---------------------------------------------------------------------------
     def timing(self, enabled=True):

@@ -185,7 +185,7 @@ class MonitorHits:
         import torch
 
         self.monitor, self.segs = monitor, segs
-        ray = segs.ray[slot].long()
+        ray = self._gather(segs.ray, slot).long()
         if segs.layout == "slots":  # [k][ray] slots: reference order is ray-major, then k
             order = torch.argsort(ray * (segs.capacity // max(segs.n_rays, 1)) + slot // max(segs.n_rays, 1))
         else:
@@ -194,6 +194,11 @@ class MonitorHits:
 
     def __len__(self):
         return int(self.slot.numel())
+
+    @staticmethod
+    def _gather(field, slot):
+        """`field` at the slots `slot`: the fields of a tiled batch are strided [tiles, 64] views (read in place), all others 1-D."""
+        return field[slot // 64, slot % 64] if field.dim() == 2 else field[slot]
 
     def _order(self, sort):
         import torch
@@ -226,7 +231,7 @@ class MonitorHits:
         return self.t[self._order(sort)]
 
     def IList(self, sort="YZ"):
-        return self.segs.intensity[self.slot[self._order(sort)]]
+        return self._gather(self.segs.intensity, self.slot[self._order(sort)])
 
     def ray_index(self, sort="YZ"):
         return self.ray[self._order(sort)]
@@ -235,13 +240,13 @@ class MonitorHits:
         import torch
 
         s = self.slot[self._order(sort)]
-        return torch.stack([self.segs.dx[s], self.segs.dy[s], self.segs.dz[s]], dim=1)
+        return torch.stack([self._gather(f, s) for f in (self.segs.dx, self.segs.dy, self.segs.dz)], dim=1)
 
     def tYList(self, sort="YZ"):
-        return self.directionList(sort) @ self._axis("Y")
+        return self.directionList(sort).double() @ self._axis("Y")  # (double like the axis: a single-precision history widens here)
 
     def tZList(self, sort="YZ"):
-        return self.directionList(sort) @ self._axis("Z")
+        return self.directionList(sort).double() @ self._axis("Z")
 
     def export_rays_npz(self, filename: str):
         """`Monitor.export_rays_npz` (monitor.py:255-269) from the device tensors: the same five arrays in the

@@ -228,6 +228,15 @@ class OpticalTable:
         slot, P, t = _engine().monitor_record(monitor_struct(monitor), segs)
         return MonitorHits(monitor, segs, slot, P, t)
 
+    def record_all(self, segs, monitors=None):
+        """`record_batch` for every monitor of the table (optical_table.py:145-146), or for those given: one `MonitorHits` per
+        monitor, in their order, from ONE pass over the segments read as they lie (any layout, either precision)."""
+        from .monitors import MonitorHits
+
+        monitors = list(self.monitors if monitors is None else monitors)
+        found = _engine().monitor_record_many([monitor_struct(m) for m in monitors], segs)
+        return [MonitorHits(m, segs, slot, P, t) for m, (slot, P, t) in zip(monitors, found)]
+
     # -- ABCD extraction (optical_table.py:211-297), a caller of the hot path ----------------------
     def calculate_abcd_matrix(self, mon0, mon1, rays, disp=1e-5, rot=1e-5, debugaxs=None):
         """Per-ray 2x2 ABCD matrix between two monitors by finite differences: three traces
