@@ -446,6 +446,32 @@ int ot_monitor_record_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monito
                            int64_t n_segments, const int32_t* seg_count, int64_t n_rays, int64_t capacity, int64_t* first,
                            int64_t* hit_index, void* Px, void* Py, void* Pz, void* t, int64_t* n_total);
 
+/* Detector images: the hits of ot_monitor_record_many binned per monitor on the device, with no hit list — a count image and
+ * an intensity image of nby x nbz bins for every monitor, from ONE launch of the count kernel per group of monitors (no scan,
+ * no second pass, no scratch sized by the hits).  The same segments, the same test; what np.histogram2d(y, z, bins = [y edges,
+ * z edges], weights = intensity) gives for the hits' coordinates.
+ * Coordinates of a hit at the local point P of monitor m: y = P . a_y, z = P . a_z with axes[m] = a_y, a_z (host, 6 doubles a
+ * monitor).  (0,1,0), (0,0,1) is the monitor's own frame; the Python layer passes the monitor's LAB tangents, on which the
+ * reference's yList / zList project the local point.
+ * Bins are defined by the edge table and nothing else: edges[m] = nby + 1 edges of y, then nbz + 1 edges of z (host), finite and
+ * strictly increasing.  Bin k of an axis takes v iff e[k] <= v < e[k + 1], the last bin also v == e[nb]; everything else, NaN
+ * included, is dropped (np.histogram's rule, exact for every double: the device steps against the table, it derives no edge).
+ * The weight of a hit is `intensity` (device) of its slot, addressed like src->base[f]: intensity + (s >> 6) * tile_stride +
+ * (s & 63) * width, in the source's precision.
+ * counts, weights: device, [n_monitors][nby][nbz] int64 / double.  accumulate = 0: the call zeroes both first; 1: it adds to
+ * what is there (a detector summed over the chunks of a streamed trace).  n_segments = 0 with accumulate = 0: zero images.
+ * Counts are integers, exact and the same every run.  The weights are fp64 atomic adds: their last bits depend on the order
+ * in which the hits arrive and may differ from run to run.
+ * Paths: while the images of a group of monitors fit 64 KB of LDS at 12 bytes a bin (5,450 bins: six monitors of 30 x 30),
+ * every workgroup keeps a private image and adds its non-zero bins to global memory at the end; the call walks the monitors in
+ * as few, as even groups as that allows (at most 32).  An image that does not fit alone goes to global atomics hit by hit.
+ * OT_ERR_INVALID, nothing launched or zeroed: a NULL argument, source field or intensity; n_monitors < 1; nby or nbz < 1 or
+ * nby * nbz > 2^24; accumulate other than 0 / 1; a width other than 4 / 8; every n_segments / seg_count / n_rays / capacity
+ * combination ot_monitor_record_many refuses; edges not finite and strictly increasing; axes not finite. */
+int ot_monitor_image_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges,
+                          int32_t nby, int32_t nbz, const ot_segment_source* src, const void* intensity, int64_t n_segments,
+                          const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* weights, int32_t accumulate);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled every trace launch is bracketed by hipEvents on the ctx stream. */
 int ot_timing_enable(ot_ctx* ctx, int enabled);

@@ -267,11 +267,92 @@ __device__ __forceinline__ MonSeg mon_load(const MonSource& src, int64_t s, int6
     g.len = mon_real(src.base[6] + at, src.width);
     return g;
 }
+// The image mode of k_mon_count (ot_monitor_image_many): the same partition, loads and tests, tallied by (monitor, bin) instead
+// of (monitor, workgroup).  All zero for ot_monitor_record_many.  A hit at the local point P of monitor m has the coordinates
+// y = P . a_y[m], z = P . a_z[m] (axes[m] = a_y, a_z) and the weight intensity[s], addressed like the fields of MonSource; it
+// lands in bin (ky, kz) of the monitor's edge tables (edges[m] = nby + 1 edges of y, then nbz + 1 of z) or is dropped.
+// lds_bins = n_mon * nby * nbz when the workgroup keeps a private image of the launch's monitors in dynamic LDS (lds_bins doubles,
+// then lds_bins int32: 12 bytes a bin) and adds its non-zero bins to global memory at the end, consecutive lanes consecutive
+// bins; 0 when every hit goes to global memory at once (an image no LDS holds).  MON_IMG_LDS_BINS: what fits 64 KB of LDS a
+// workgroup — the most a launch gets without a function attribute, two workgroups per CU — next to the 128 bytes of `total`.
+// Counts are integers, exact and the same every run; the weights are fp64 atomic adds, whose last bits depend on arrival order.
+static constexpr int MON_IMG_LDS_BINS = (65536 - MON_MAX * 4) / 12;  // 5450: six monitors of 30 x 30
+static constexpr int MON_IMG_MAX_BINS = 1 << 24;                     // nby * nbz of one monitor
+struct MonImage {
+    unsigned long long* counts;  // [n_mon][nby][nbz], of the launch's first monitor on; NULL: no image mode
+    double* weights;             // same shape
+    const double* edges;         // [n_mon][nby + 1 + nbz + 1]
+    const double* axes;          // [n_mon][6]
+    const uint8_t* intensity;
+    int32_t nby, nbz, lds_bins;
+};
+// The bin of v among the edges e[0 .. nb]: k with e[k] <= v < e[k + 1], the last bin closed at e[nb] (np.histogram's rule);
+// -1 for everything else, NaN included.  The guess comes from the range, the answer from the table: exact for every double.
+__device__ __forceinline__ int32_t mon_bin(const double* __restrict__ e, int32_t nb, double v) {
+    const double lo = e[0], hi = e[nb];
+    if (!(v >= lo && v <= hi)) return -1;
+    int32_t k = (int32_t)((v - lo) * (double)nb / (hi - lo));
+    k = k < 0 ? 0 : (k > nb - 1 ? nb - 1 : k);
+    while (k > 0 && v < e[k]) --k;
+    while (k < nb - 1 && v >= e[k + 1]) ++k;
+    return k;
+}
+// One workgroup's part of an image pass: k_mon_count's partition, loads and tests, every hit binned where the record mode counts it.
+__device__ __forceinline__ void mon_image_pass(const ot_monitor* __restrict__ mons, int32_t n_mon, const MonSource& src, int64_t n, int32_t iters,
+                                               const int32_t* __restrict__ seg_count, int64_t n_rays, const MonImage& img, double* weight,
+                                               int32_t* tally) {
+    for (int32_t b = threadIdx.x; b < img.lds_bins; b += MON_THREADS) weight[b] = 0.0, tally[b] = 0;
+    __syncthreads();
+    const int32_t per_mon = img.nby * img.nbz;
+    const int64_t first = (int64_t)blockIdx.x * iters * MON_THREADS;
+    for (int32_t it = 0; it < iters && first + (int64_t)it * MON_THREADS < n; ++it) {
+        const int64_t s = first + (int64_t)it * MON_THREADS + threadIdx.x;
+        const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
+        if (!__ballot(g.valid)) continue;
+        double w = 0.0;
+        bool have_w = false;  // the intensity of a slot is read once, at its first hit inside an image
+        for (int32_t m = 0; m < n_mon; ++m) {
+            double Px, Py, Pz, t;
+            if (!(g.valid && mon_hit(mons[m], g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, g.len, Px, Py, Pz, t))) continue;
+            const double* a = img.axes + 6 * m;
+            const double* e = img.edges + (int64_t)m * (img.nby + img.nbz + 2);
+            const int32_t ky = mon_bin(e, img.nby, Px * a[0] + Py * a[1] + Pz * a[2]);
+            const int32_t kz = mon_bin(e + img.nby + 1, img.nbz, Px * a[3] + Py * a[4] + Pz * a[5]);
+            if (ky < 0 || kz < 0) continue;
+            if (!have_w) {
+                w = mon_real(img.intensity + (s >> 6) * src.tile_stride + (s & 63) * src.width, src.width);
+                have_w = true;
+            }
+            const int32_t bin = m * per_mon + ky * img.nbz + kz;
+            if (img.lds_bins) {
+                atomicAdd(&tally[bin], 1);
+                unsafeAtomicAdd(&weight[bin], w);
+            } else {
+                atomicAdd(&img.counts[bin], 1ull);
+                unsafeAtomicAdd(&img.weights[bin], w);
+            }
+        }
+    }
+    __syncthreads();
+    for (int32_t b = threadIdx.x; b < img.lds_bins; b += MON_THREADS) {  // consecutive lanes, consecutive bins
+        const int32_t c = tally[b];
+        if (c) {
+            atomicAdd(&img.counts[b], (unsigned long long)c);
+            unsafeAtomicAdd(&img.weights[b], weight[b]);
+        }
+    }
+}
 // count[m * gridDim.x + g] = hits of monitor m among workgroup g's slots; count[n_mon * gridDim.x] = 0, so that the scan's last
-// element is the total
+// element is the total.  In image mode (img.counts set: one uniform branch at entry) `count` is not touched.
 __global__ __launch_bounds__(MON_THREADS) void k_mon_count(const ot_monitor* __restrict__ mons, int32_t n_mon, MonSource src, int64_t n, int32_t iters,
-                                                           const int32_t* __restrict__ seg_count, int64_t n_rays, int32_t* __restrict__ count) {
+                                                           const int32_t* __restrict__ seg_count, int64_t n_rays, int32_t* __restrict__ count,
+                                                           MonImage img) {
     __shared__ int32_t total[MON_MAX];
+    extern __shared__ double mon_image[];  // image mode through LDS: weights[lds_bins], then counts[lds_bins]
+    if (img.counts) {
+        mon_image_pass(mons, n_mon, src, n, iters, seg_count, n_rays, img, mon_image, reinterpret_cast<int32_t*>(mon_image + img.lds_bins));
+        return;
+    }
     const int lane = threadIdx.x & 63;
     if (threadIdx.x < MON_MAX) total[threadIdx.x] = 0;
     __syncthreads();

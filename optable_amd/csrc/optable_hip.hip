@@ -1633,10 +1633,97 @@ int ot_monitor_record_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors
     // MON_MAX monitors per launch; a launch takes the hits before it from first[m0], where the launch before it left them
     for (int32_t m0 = 0; m0 < n_monitors; m0 += MON_MAX) {
         const int32_t nm = std::min<int32_t>(MON_MAX, n_monitors - m0);
-        hipLaunchKernelGGL(k_mon_count, dim3((unsigned)grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, iters, seg_count, n_rays, count);
+        hipLaunchKernelGGL(k_mon_count, dim3((unsigned)grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, iters, seg_count, n_rays, count,
+                           MonImage{});
         exclusive_scan<int32_t, int64_t>(c->scan_tmp.p, count, off, nm * grid + 1, c->stream);
         hipLaunchKernelGGL(k_mon_emit, dim3((unsigned)grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, iters, seg_count, n_rays, off,
                            capacity, first + m0, hit_index, (double*)Px, (double*)Py, (double*)Pz, (double*)t, n_total);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// How ot_monitor_image_many walks n_monitors monitors of nby x nbz bins: `passes` launches of at most `per_pass` monitors each,
+// as even as they come (8 monitors of 30 x 30: 4 + 4, not 6 + 2), through LDS when a pass's bins fit MON_IMG_LDS_BINS, else
+// (one monitor alone does not fit) MON_MAX at a time straight to global memory.  optable_amd/engine.py image_plan says the same.
+struct ImagePlan {
+    int32_t per_pass, passes;
+    bool lds;
+};
+static ImagePlan image_plan(int32_t n_monitors, int32_t nby, int32_t nbz) {
+    const int64_t bins = (int64_t)nby * nbz;
+    ImagePlan p;
+    p.lds = bins <= MON_IMG_LDS_BINS;
+    const int32_t most = p.lds ? (int32_t)std::min<int64_t>(MON_MAX, MON_IMG_LDS_BINS / bins) : MON_MAX;
+    p.passes = (n_monitors + most - 1) / most;
+    p.per_pass = (n_monitors + p.passes - 1) / p.passes;
+    return p;
+}
+
+int ot_monitor_image_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, int32_t nby,
+                          int32_t nbz, const ot_segment_source* src, const void* intensity, int64_t n, const int32_t* seg_count,
+                          int64_t n_rays, int64_t* counts, double* weights, int32_t accumulate) {
+    if (!c || !mons || !axes || !edges || !src || !counts || !weights) return fail(OT_ERR_INVALID, "NULL argument");
+    if (n_monitors < 1) return fail(OT_ERR_INVALID, "n_monitors must be at least 1");
+    if (nby < 1 || nbz < 1) return fail(OT_ERR_INVALID, "nby and nbz must be at least 1");
+    if ((int64_t)nby * nbz > MON_IMG_MAX_BINS) return fail(OT_ERR_INVALID, "nby * nbz exceeds 2^24 bins per monitor");
+    if (accumulate != 0 && accumulate != 1) return fail(OT_ERR_INVALID, "accumulate must be 0 or 1");
+    if (n < 0 || n >= (int64_t)1 << 31) return fail(OT_ERR_INVALID, "bad segment count");
+    if (src->width != 4 && src->width != 8) return fail(OT_ERR_INVALID, "segment source: width must be 4 or 8");
+    for (const void* p : src->base)
+        if (!p) return fail(OT_ERR_INVALID, "segment source has a NULL field");
+    if (!src->ray) return fail(OT_ERR_INVALID, "segment source has a NULL field");
+    if (!intensity) return fail(OT_ERR_INVALID, "NULL intensity");
+    if (src->tile_stride < 64 * (int64_t)src->width || src->ray_stride < 256) return fail(OT_ERR_INVALID, "segment source: a tile stride shorter than 64 slots");
+    if (n > src->capacity) return fail(OT_ERR_INVALID, "n_segments exceeds the capacity of the segment source");
+    if (seg_count && (n_rays < 1 || n % n_rays != 0)) return fail(OT_ERR_INVALID, "n_segments must be a multiple of n_rays");
+    if (!seg_count && n_rays > 0) return fail(OT_ERR_INVALID, "n_rays without seg_count: pass 0 for a list, -1 for a list with holes");
+    const int32_t n_edges = nby + nbz + 2;
+    for (int32_t m = 0; m < n_monitors; ++m) {
+        const double* e = edges + (int64_t)m * n_edges;
+        for (int32_t k = 0; k < n_edges; ++k)  // (k = nby + 1 starts the z table: nothing before it to exceed)
+            if (!std::isfinite(e[k]) || (k && k != nby + 1 && !(e[k] > e[k - 1])))
+                return fail(OT_ERR_INVALID, "edges must be finite and strictly increasing");
+        for (int k = 0; k < 6; ++k)
+            if (!std::isfinite(axes[6 * (int64_t)m + k])) return fail(OT_ERR_INVALID, "axes must be finite");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bins = (size_t)nby * nbz;
+    if (!accumulate) {
+        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * bins * n_monitors, c->stream));
+        HIP_TRY(hipMemsetAsync(weights, 0, sizeof(double) * bins * n_monitors, c->stream));
+    }
+    if (n == 0) return 0;
+    const ImagePlan plan = image_plan(n_monitors, nby, nbz);
+    // the partition of k_mon_count, with workgroups long enough to be worth an image of their own: a thousand of them at most
+    // (two rounds of the chip at two a CU), each of which zeroes and flushes its LDS image once
+    const int32_t iters = (int32_t)std::max<int64_t>(8, (n + 1024 * MON_THREADS - 1) / (1024 * MON_THREADS));
+    const int64_t span = (int64_t)iters * MON_THREADS, grid = (n + span - 1) / span;
+    ot_monitor* table;
+    double *d_edges, *d_axes;
+    const auto carve = [&](void* base) {
+        Carve cv{(uint8_t*)base};
+        table = cv.take<ot_monitor>(n_monitors), d_edges = cv.take<double>((int64_t)n_monitors * n_edges), d_axes = cv.take<double>((int64_t)n_monitors * 6);
+        return cv.used;
+    };
+    if (c->mon.ensure(carve(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of monitor scratch failed");
+    carve(c->mon.p);
+    HIP_TRY(hipMemcpyAsync(table, mons, sizeof(ot_monitor) * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_edges, edges, sizeof(double) * (size_t)n_monitors * n_edges, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_axes, axes, sizeof(double) * (size_t)n_monitors * 6, hipMemcpyHostToDevice, c->stream));
+    MonSource ms;
+    for (int f = 0; f < 7; ++f) ms.base[f] = (const uint8_t*)src->base[f];
+    ms.ray = (const uint8_t*)src->ray;
+    ms.tile_stride = src->tile_stride, ms.ray_stride = src->ray_stride, ms.width = src->width;
+    for (int32_t m0 = 0; m0 < n_monitors; m0 += plan.per_pass) {
+        const int32_t nm = std::min<int32_t>(plan.per_pass, n_monitors - m0);
+        MonImage img;
+        img.counts = (unsigned long long*)counts + m0 * bins, img.weights = weights + m0 * bins;
+        img.edges = d_edges + (int64_t)m0 * n_edges, img.axes = d_axes + (int64_t)m0 * 6;
+        img.intensity = (const uint8_t*)intensity;
+        img.nby = nby, img.nbz = nbz, img.lds_bins = plan.lds ? (int32_t)(nm * bins) : 0;
+        hipLaunchKernelGGL(k_mon_count, dim3((unsigned)grid), dim3(MON_THREADS), (size_t)img.lds_bins * 12, c->stream, table + m0, nm, ms, n, iters,
+                           seg_count, n_rays, (int32_t*)nullptr, img);
     }
     HIP_TRY(hipGetLastError());
     return 0;

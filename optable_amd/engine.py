@@ -8,6 +8,7 @@ import ctypes as C
 import threading
 import time
 
+import numpy as np
 import torch
 
 from . import abi
@@ -100,6 +101,25 @@ def segment_source(segs):
         n_rays = int(segs.n_rays)
         return src, (segs.capacity // n_rays * n_rays if n_rays else 0), segs.count, n_rays
     return src, int(segs.n_valid), None, (-1 if segs.append else 0)
+
+
+# -- detector images (ot_monitor_image_many): how the library walks the monitors, in plain integers ---------------------------
+IMAGE_LDS_BINS = (65536 - 32 * 4) // 12  # misc_kernels.h MON_IMG_LDS_BINS: 64 KB of LDS a workgroup, less the hit tally, at 12 bytes a bin
+IMAGE_MAX_BINS = 1 << 24                 # MON_IMG_MAX_BINS: nby * nbz of one monitor
+IMAGE_MAX_MONITORS = 32                  # MON_MAX: monitors of one launch
+
+
+def image_plan(n_monitors, nby, nbz):
+    """How ot_monitor_image_many bins `n_monitors` monitors of nby x nbz bins (optable_hip.hip image_plan, the same rule):
+    {"path": "lds" when the images of a launch fit a workgroup's LDS, "global" when one monitor's alone does not and every hit
+    is a global atomic; "per_pass": monitors of a launch, as even as the most that fit allows; "passes": launches}."""
+    n_monitors, bins = int(n_monitors), int(nby) * int(nbz)
+    if n_monitors < 1 or nby < 1 or nbz < 1 or bins > IMAGE_MAX_BINS:
+        raise ValueError(f"no image of {n_monitors} monitors x {nby} x {nbz} bins")
+    lds = bins <= IMAGE_LDS_BINS
+    most = min(IMAGE_MAX_MONITORS, IMAGE_LDS_BINS // bins) if lds else IMAGE_MAX_MONITORS
+    passes = -(-n_monitors // most)
+    return {"path": "lds" if lds else "global", "per_pass": -(-n_monitors // passes), "passes": passes}
 
 
 # What a whole-trace launch writes, by library call: (the SegmentBatch made when the caller passes none, what makes a passed
@@ -676,6 +696,38 @@ class Engine:
                 break
             capacity = first[M + 1]
         return [(idx[a:b], out[:3, a:b].T, out[3, a:b]) for a, b in zip(first[:M], first[1:M + 1])]
+
+    def monitor_image_many(self, monitor_structs, axes, edges, bins, segs: SegmentBatch, into=None):
+        """Detector images of a list of monitors over a SegmentBatch read as it lies (ot_monitor_image_many: the hits of
+        `monitor_record_many`, binned on the device with no hit list).  axes: [M, 6] doubles (a_y, a_z per monitor); edges:
+        [M, nby + 1 + nbz + 1] doubles; bins = (nby, nbz).  Returns (counts, intensity): int64 / float64 [M, nby, nbz] device
+        tensors, zeroed by the call — or `into`, such a pair from an earlier call, with this call's hits added to it."""
+        with self.lock:
+            return self._monitor_image_many(list(monitor_structs), axes, edges, bins, segs, into)
+
+    def _monitor_image_many(self, mons, axes, edges, bins, segs, into):
+        dev, M, (nby, nbz) = segs.device, len(mons), bins
+        axes, edges = np.ascontiguousarray(axes, dtype=np.float64), np.ascontiguousarray(edges, dtype=np.float64)
+        if axes.shape != (M, 6) or edges.shape != (M, nby + nbz + 2):
+            raise ValueError(f"axes must be [{M}, 6] and edges [{M}, {nby + nbz + 2}]")
+        if into is None:
+            counts = torch.empty((M, nby, nbz), dtype=torch.int64, device=dev)  # (the call zeroes them)
+            weights = torch.empty((M, nby, nbz), dtype=torch.float64, device=dev)
+        else:
+            counts, weights = into
+            for t, dt in ((counts, torch.int64), (weights, torch.float64)):
+                if tuple(t.shape) != (M, nby, nbz) or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type:
+                    raise ValueError(f"into: contiguous int64 counts and float64 intensity of shape [{M}, {nby}, {nbz}] on {dev}")
+        src, n_segments, count, n_rays = segment_source(segs)
+        if M == 0 or n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
+            return (counts.zero_(), weights.zero_()) if into is None else (counts, weights)
+        table = (abi.OtMonitor * M)(*mons)
+        as_doubles = C.POINTER(C.c_double)
+        abi.check(self.lib.ot_monitor_image_many(self._ctx, table, M, axes.ctypes.data_as(as_doubles), edges.ctypes.data_as(as_doubles), nby, nbz,
+                                                 C.byref(src), segs.field("intensity").data_ptr(), n_segments,
+                                                 None if count is None else count.data_ptr(), n_rays, counts.data_ptr(), weights.data_ptr(),
+                                                 0 if into is None else 1), self.lib)
+        return counts, weights
 
     # -- measurement ---------------------------------------------------------------------------
     def timing(self, enabled=True):

@@ -255,3 +255,44 @@ class MonitorHits:
         print(f"Exporting {len(self)} rays to {filename} ...")
         arrays = {"xList": self.yList(), "yList": self.zList(), "tXList": self.tYList(), "tYList": self.tZList(), "IList": self.IList()}
         np.savez(filename, **{k: v.double().cpu().numpy() for k, v in arrays.items()})
+
+
+def image_bins(bins):
+    """`bins` of an image as (nby, nbz): an int (both axes) or a pair of ints, each at least 1; anything else is a ValueError."""
+    import operator
+
+    pair = bins if isinstance(bins, (tuple, list)) else (bins, bins)
+    try:
+        if len(pair) != 2 or any(isinstance(b, bool) for b in pair):
+            raise TypeError
+        nby, nbz = (operator.index(b) for b in pair)
+    except TypeError:
+        raise ValueError(f"bins must be an int or (nby, nbz), not {bins!r}") from None
+    if nby < 1 or nbz < 1:
+        raise ValueError(f"bins must be at least 1, not {bins!r}")
+    return nby, nbz
+
+
+def image_edges(monitor, nby, nbz):
+    """The bin edges of a monitor's image, as `Monitor.render_hist` / `_get_hist_y` bin it (monitor.py:195-200, 271-289):
+    nby equal bins over +-width / 2 along y, nbz over +-height / 2 along z — what np.histogram_bin_edges gives for that range."""
+    return (np.linspace(-monitor.width / 2, monitor.width / 2, nby + 1), np.linspace(-monitor.height / 2, monitor.height / 2, nbz + 1))
+
+
+class MonitorImage:
+    """A monitor's hits as an image, binned on the device (`OpticalTable.image_all`): `counts` (int64) and `intensity` (float64,
+    the sum of the hits' intensities), [nby, nbz] device tensors over `y_edges` x `z_edges` (numpy) of the coordinates
+    `MonitorHits.yList` / `zList` give — np.histogram2d(yList, zList, bins=[y_edges, z_edges], weights=IList).  Counts are exact
+    and the same every run; the intensity sums are atomic fp64 adds whose last bits depend on the order of arrival."""
+
+    def __init__(self, monitor, counts, intensity, y_edges, z_edges, stack=None):
+        self.monitor, self.counts, self.intensity, self.y_edges, self.z_edges = monitor, counts, intensity, y_edges, z_edges
+        self._stack = stack  # (counts, intensity, position) of the call's [M, nby, nbz] tensors, which `into=` adds to
+
+    @property
+    def bins(self):
+        return tuple(self.counts.shape)
+
+    def to_host(self):
+        """(counts, intensity, y_edges, z_edges) as numpy arrays."""
+        return self.counts.cpu().numpy(), self.intensity.cpu().numpy(), self.y_edges, self.z_edges

@@ -237,6 +237,39 @@ class OpticalTable:
         found = _engine().monitor_record_many([monitor_struct(m) for m in monitors], segs)
         return [MonitorHits(m, segs, slot, P, t) for m, (slot, P, t) in zip(monitors, found)]
 
+    def image_all(self, segs, bins=30, monitors=None, into=None):
+        """Every monitor of the table (or those given) as an image: one `MonitorImage` per monitor, in their order — the hits
+        of `record_all` binned on the device in the same pass that finds them, with no hit list (ot_monitor_image_many).  The
+        image of a monitor is np.histogram2d of its `yList` / `zList` with `bins` (an int or (nby, nbz)) equal bins over
+        +-width / 2, +-height / 2, weighted by `IList` (Monitor.render_hist: bins=30).  `into`: the list an earlier call with the
+        same monitors and bins returned; this call's hits are added to those images (a detector summed over the chunks of a
+        streamed trace)."""
+        from .monitors import MonitorImage, image_bins, image_edges
+
+        nby, nbz = image_bins(bins)
+        monitors = list(self.monitors if monitors is None else monitors)
+        edges = [image_edges(m, nby, nbz) for m in monitors]
+        stack = None
+        if into is not None:
+            into = list(into)
+            if len(into) != len(monitors) or any(im.monitor is not m or im.bins != (nby, nbz) for im, m in zip(into, monitors)):
+                raise ValueError("into: the list an earlier image_all returned for the same monitors and bins")
+            if any(im._stack is None or im._stack[0] is not into[0]._stack[0] or im._stack[2] != k or len(im._stack[0]) != len(into) for k, im in enumerate(into)):
+                raise ValueError("into: the whole list of one earlier call, in its order")
+            if not monitors:
+                return into
+            stack = into[0]._stack[:2]
+        axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in monitors], dtype=float).reshape(len(monitors), 6)
+        table = np.array([np.concatenate(e) for e in edges], dtype=float).reshape(len(monitors), nby + nbz + 2)
+        counts, weights = _engine().monitor_image_many([monitor_struct(m) for m in monitors], axes, table, (nby, nbz), segs, into=stack)
+        if into is not None:
+            return into
+        return [MonitorImage(m, counts[k], weights[k], ey, ez, stack=(counts, weights, k)) for k, (m, (ey, ez)) in enumerate(zip(monitors, edges))]
+
+    def image_batch(self, monitor, segs, bins=30):
+        """One monitor as an image (`image_all` for it alone): a `MonitorImage`."""
+        return self.image_all(segs, bins=bins, monitors=[monitor])[0]
+
     # -- ABCD extraction (optical_table.py:211-297), a caller of the hot path ----------------------
     def calculate_abcd_matrix(self, mon0, mon1, rays, disp=1e-5, rot=1e-5, debugaxs=None):
         """Per-ray 2x2 ABCD matrix between two monitors by finite differences: three traces
