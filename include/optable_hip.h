@@ -275,6 +275,38 @@ int ot_trace_tiled_f64(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t
 int ot_trace_tiled_f32(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments, void* tiles,
                        int64_t capacity, int32_t* seg_count, int32_t* counts, int32_t n_count_classes);
 
+/* Uniform fields.  A batch often holds ONE value in every element of a field: one wavelength and one q per beam, the
+ * reference's defaults for intensity, n and pathlength, one origin for a point source, one direction for a collimated beam
+ * (cfg 2: 72 of the 104 input bytes per ray).  The ot_rays arrays stay full arrays; `uniform_mask` is the caller's word that
+ * every element of a field has the bit pattern of element 0, and the lane-per-ray kernel then reads that one element per wave
+ * instead of one per ray.  Bit k (OT_UNIFORM_OX .. OT_UNIFORM_PATHLENGTH) stands for the k-th real field in the order of
+ * ot_rays; OT_UNIFORM_ID says id[i] == i for every ray; OT_UNIFORM_FLAGS says every flags word equals flags[0].  `length` has
+ * no bit.  A bit set for a field that is NOT uniform is the caller's error: every ray is then traced with element 0 of it.
+ * uniform_mask = 0 is ot_trace_* / ot_trace_tiled_* exactly (those call these with 0); bits outside OT_UNIFORM_ALL are
+ * OT_ERR_INVALID.  Same records either way.  The mask is honoured by the lane-per-ray kernel only: a call that lands on another
+ * kernel (heavy scenes) ignores it, as does every call after ot_set_option(OT_OPT_UNIFORM, 0). */
+enum ot_uniform_bits {
+    OT_UNIFORM_OX = 1 << 0, OT_UNIFORM_OY = 1 << 1, OT_UNIFORM_OZ = 1 << 2,
+    OT_UNIFORM_DX = 1 << 3, OT_UNIFORM_DY = 1 << 4, OT_UNIFORM_DZ = 1 << 5,
+    OT_UNIFORM_WAVELENGTH = 1 << 6, OT_UNIFORM_Q_RE = 1 << 7, OT_UNIFORM_Q_IM = 1 << 8,
+    OT_UNIFORM_INTENSITY = 1 << 9, OT_UNIFORM_N = 1 << 10, OT_UNIFORM_PATHLENGTH = 1 << 11,
+    OT_UNIFORM_ID = 1 << 12,     /* id[i] == i                       */
+    OT_UNIFORM_FLAGS = 1 << 13,  /* flags[i] == flags[0]             */
+    OT_UNIFORM_ALL = (1 << 14) - 1
+};
+int ot_trace_uniform_f64(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments,
+                         const ot_segments* out, int32_t* seg_count, int32_t* counts,
+                         int32_t n_count_classes, uint32_t uniform_mask);
+int ot_trace_uniform_f32(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments,
+                         const ot_segments* out, int32_t* seg_count, int32_t* counts,
+                         int32_t n_count_classes, uint32_t uniform_mask);
+int ot_trace_tiled_uniform_f64(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments, void* tiles,
+                               int64_t capacity, int32_t* seg_count, int32_t* counts, int32_t n_count_classes,
+                               uint32_t uniform_mask);
+int ot_trace_tiled_uniform_f32(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments, void* tiles,
+                               int64_t capacity, int32_t* seg_count, int32_t* counts, int32_t n_count_classes,
+                               uint32_t uniform_mask);
+
 /* The same trace with the APPEND layout: a dense list of segment records instead of max_segments * n_rays slots.
  * The reference returns a list with one entry per processed segment (optical_table.py:125-134); the [k][ray] slots of
  * ot_trace_* hold that list with a hole for every segment a ray did not live to (cfg 3: 11 GB of slots for 2.8 GB of
@@ -526,9 +558,11 @@ enum ot_option {
                                   more entries, fewer waves per CU.  0 (default): two under caps of up to 16, three above */
     OT_OPT_POOL_JITTER = 18,   /* test knob of the block pool's cross-wave protocol: one in `value` publications of a state or control word is
                                   held back ~8000 cycles after the records it announces were written (0 = off).  Results must not change. */
-    OT_OPT_GEN_DROP_DOOMED = 15 /* ot_trace_generation_*: a tree whose budget ends with this generation gets no children in `next` (they
+    OT_OPT_GEN_DROP_DOOMED = 15,/* ot_trace_generation_*: a tree whose budget ends with this generation gets no children in `next` (they
                                   could never be processed: optical_table.py:138-144) — 1 (default) / 0: emit them, for a caller who
                                   wants to go on with a larger budget */
+    OT_OPT_UNIFORM = 26        /* ot_trace_uniform_*, ot_trace_tiled_uniform_*, ot_bench_stream_*uniform_*: 1 (default) the uniform_mask is
+                                  honoured; 0 it is dropped and every field is read per ray (A/B runs with one library).  Identical records. */
 };
 int ot_set_option(ot_ctx* ctx, int32_t option, int32_t value);
 
@@ -543,6 +577,16 @@ int ot_bench_stream_tiled_f64(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, 
                               int64_t capacity, int32_t* seg_count);
 int ot_bench_stream_tiled_f32(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments, void* tiles,
                               int64_t capacity, int32_t* seg_count);
+/* ... and of the uniform-field entry points: "the same bytes as the trace" holds with a mask too, so the ceiling reads the
+ * flagged fields the way the trace does (element 0, once per wave).  A mask of 0 is the four calls above. */
+int ot_bench_stream_uniform_f64(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments,
+                                const ot_segments* out, int32_t* seg_count, uint32_t uniform_mask);
+int ot_bench_stream_uniform_f32(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments,
+                                const ot_segments* out, int32_t* seg_count, uint32_t uniform_mask);
+int ot_bench_stream_tiled_uniform_f64(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments, void* tiles,
+                                      int64_t capacity, int32_t* seg_count, uint32_t uniform_mask);
+int ot_bench_stream_tiled_uniform_f32(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments, void* tiles,
+                                      int64_t capacity, int32_t* seg_count, uint32_t uniform_mask);
 
 #ifdef __cplusplus
 }

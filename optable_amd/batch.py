@@ -17,8 +17,24 @@ def real_dtype(precision):
     return _REAL[precision]
 
 
+_BITS = {"f64": torch.int64, "f32": torch.int32}  # a real field as bit patterns
+
+
 class RayBatch:
-    """N rays (reference: N `Ray` objects, ray.py:63-104)."""
+    """N rays (reference: N `Ray` objects, ray.py:63-104).
+
+    Uniform-field hint.  The fields are always full tensors; beside them a batch remembers which of them hold ONE bit pattern in
+    every element (`flags` likewise; `id`: equal to arange(n)).  `from_arrays` finds that out on the host, `slice`, `clone` and
+    `multiplexed_in_wavelength` pass it on, every other constructor carries none.  `uniform_mask` is what the lane-per-ray
+    kernel is told (abi.UNIFORM_*): it reads a flagged field once per wave instead of once per ray.  An entry holds only while
+    the tensor it was taken from is still the batch's field AND that tensor's `_version` is what it was: any in-place torch
+    write to the field — or to the staging block it is a row of, or to the batch it is a slice of: views share one counter —
+    drops the entry, silently and for good.  The hole: a write that bypasses the counter is not seen — through `tensor.data`,
+    by a kernel handed `data_ptr()`, or (host batches) through the array `tensor.numpy()` shares the memory with; whoever writes
+    that way calls `forget_uniform()`.  Tensors made under `torch.inference_mode()` have no version counter: a batch built there
+    carries no hint.  The engine itself never writes into a caller's batch."""
+
+    _uniform = {}  # field name (abi.RAY_FIELDS, "id", "flags") -> (tensor, its _version when the field was found uniform); never mutated in place
 
     def __init__(self, n, precision="f64", device="cuda", initialise=True):
         self.n, self.precision, self.device = int(n), precision, torch.device(device)
@@ -43,6 +59,36 @@ class RayBatch:
     # lives in `n_index` on the Python side.
     def field(self, name):
         return self.n_index if name == "n" else getattr(self, name)
+
+    @property
+    def uniform_mask(self):
+        """abi.UNIFORM_* bits of the fields whose hint still holds (entries that no longer do are dropped here)."""
+        if not self._uniform:
+            return 0
+        mask, stale = 0, False
+        for name, (t, version) in self._uniform.items():
+            if self.field(name) is t and t._version == version:
+                mask |= abi.UNIFORM_BIT[name]
+            else:
+                stale = True
+        if stale:
+            self._uniform = {name: tv for name, tv in self._uniform.items() if mask & abi.UNIFORM_BIT[name]}
+        return mask
+
+    def forget_uniform(self):
+        """Drop the hint: every field is read per ray again.  For callers that wrote a field behind torch's back."""
+        self._uniform = {}
+        return self
+
+    def _vouch(self, names):
+        """Hint entries for the fields `names`, taken on this batch's tensors as they are now (none for a tensor without a version
+        counter: inference mode)."""
+        self._uniform = {f: (self.field(f), self.field(f)._version) for f in names if not self.field(f).is_inference()}
+
+    def _inherit_uniform(self, src, names):
+        """The entries of `src` that still hold, for the fields `names`, re-taken on this batch's own tensors."""
+        mask = src.uniform_mask
+        self._vouch([f for f in names if mask & abi.UNIFORM_BIT[f]] if self.n > 0 else [])
 
     @classmethod
     def from_arrays(cls, origin, direction, wavelength=0.0, intensity=1.0, q=None, n_index=1.0,
@@ -71,7 +117,8 @@ class RayBatch:
         else:
             host[row["q_re"]] = host[row["q_im"]] = 0.0
         dev = torch.device(device)
-        block = torch.from_numpy(host.base if host.base is not None else host).to(dt).to(dev)[:, :nrays]
+        staged = torch.from_numpy(host.base if host.base is not None else host).to(dt)
+        block = staged.to(dev)[:, :nrays]
         b = object.__new__(cls)
         b.n, b.precision, b.device = int(nrays), precision, dev
         for f, k in row.items():
@@ -82,6 +129,13 @@ class RayBatch:
         else:
             b.id = torch.arange(nrays, dtype=torch.int32, device=dev)
         b.length = None
+        # uniform fields: one BIT PATTERN in every element, in the batch's precision (== would merge -0.0 with 0.0); never NaN
+        b._uniform = {}
+        if nrays > 0:
+            bits = staged.view(_BITS[precision])[:, :nrays]
+            same = ((bits == bits[:, :1]).all(dim=1) & ~torch.isnan(staged[:, 0])).tolist()
+            arange_ids = ids is None or np.array_equal(np.asarray(ids).reshape(-1), np.arange(nrays))
+            b._vouch([f for f, k in row.items() if same[k]] + ["flags"] + (["id"] if arange_ids else []))  # (flags: torch.full)
         return b
 
     def slice(self, lo, hi):
@@ -93,6 +147,7 @@ class RayBatch:
             setattr(out, name, self.field(f)[lo:hi])
         out.id, out.flags = self.id[lo:hi], self.flags[lo:hi]
         out.length = None if self.length is None else self.length[lo:hi]
+        out._inherit_uniform(self, abi.RAY_FIELDS + ("flags",) + (("id",) if lo == 0 else ()))  # (views: they share the source's version counters)
         return out
 
     def take(self, index):
@@ -122,6 +177,7 @@ class RayBatch:
         """Same rays (storage shared) under other ids (int32 device tensor)."""
         out = self.slice(0, self.n)
         out.id = ids.to(torch.int32).contiguous()
+        out._uniform = {}
         return out
 
     def sorted_spatially(self, cells=32):
@@ -168,6 +224,7 @@ class RayBatch:
                 setattr(out, name, self.field(f).repeat(W))
         out.id, out.flags = self.id.repeat(W), self.flags.repeat(W)
         out.length = None if self.length is None else self.length.repeat(W)
+        out._inherit_uniform(self, tuple(f for f in abi.RAY_FIELDS if f != "wavelength") + ("flags",) + (("id",) if W == 1 else ()))
         return out
 
     def clone(self):
@@ -178,6 +235,7 @@ class RayBatch:
             setattr(out, "n_index" if f == "n" else f, self.field(f).clone())
         out.id, out.flags = self.id.clone(), self.flags.clone()
         out.length = None if self.length is None else self.length.clone()
+        out._inherit_uniform(self, abi.RAY_FIELDS + ("id", "flags"))
         return out
 
     def translate_(self, vec):

@@ -219,6 +219,46 @@ template <class T> __device__ __forceinline__ RayState<T> load_ray(const RaysT<T
     r.last = (int32_t)((uint32_t)flags >> 8) - 1;  // bits 8..31: node the ray was emitted on, plus one (generation buffers; 0 for a caller's ray)
     return r;
 }
+// Uniform fields (include/optable_hip.h: OT_UNIFORM_*): a field the caller vouches holds ONE bit pattern in every ray of the
+// batch is not streamed per lane — the wave reads element 0, once, through the scalar cache (a load from the constant address
+// space at a wave-uniform address: s_load, not part of the non-temporal stream).  The mask is a kernel argument, so each test is a
+// scalar branch and a launch with mask 0 issues the loads of load_ray.  k_trace_fused and k_stream_ceiling only: every other
+// kernel reads the full arrays, which are always valid.
+template <class V> __device__ __forceinline__ V ld_shared(const V* p) {
+    typedef const __attribute__((address_space(4))) V* ConstPtr;
+    ConstPtr q = (ConstPtr)(uintptr_t)p;
+    asm volatile("" : "+s"(q));  // read HERE, where the ray is loaded: not hoisted and kept live across the grid-stride loop
+    return *q;
+}
+// the mask as the ray load sees it: opaque HERE, so that the fourteen bit tests are made where the ray is loaded (a scalar compare
+// and branch each) instead of once before the grid-stride loop and kept in fourteen scalar register pairs across it
+__device__ __forceinline__ uint32_t uniform_here(uint32_t mask) {
+    asm volatile("" : "+s"(mask));
+    return mask;
+}
+template <class V> __device__ __forceinline__ V ld_field(const V* p, int64_t i, uint32_t mask, uint32_t bit) {
+    if (mask & bit) return ld_shared(p);
+    return ld_once(p + i);
+}
+__device__ __forceinline__ int32_t ld_flags(const int32_t* flags, int64_t i, uint32_t mask) {
+    if (mask & OT_UNIFORM_FLAGS) return ld_shared(flags);
+    return flags[i];
+}
+__device__ __forceinline__ int32_t ld_id(const int32_t* id, int64_t i, uint32_t mask) {
+    if (mask & OT_UNIFORM_ID) return (int32_t)i;  // the hint for `id` says id[i] == i
+    return id[i];
+}
+template <class T> __device__ __forceinline__ RayState<T> load_ray(const RaysT<T>& in, int64_t i, int32_t flags, uint32_t mask) {
+    RayState<T> r;
+    r.ox = ld_field(in.ox, i, mask, OT_UNIFORM_OX); r.oy = ld_field(in.oy, i, mask, OT_UNIFORM_OY); r.oz = ld_field(in.oz, i, mask, OT_UNIFORM_OZ);
+    r.dx = ld_field(in.dx, i, mask, OT_UNIFORM_DX); r.dy = ld_field(in.dy, i, mask, OT_UNIFORM_DY); r.dz = ld_field(in.dz, i, mask, OT_UNIFORM_DZ);
+    r.wl = ld_field(in.wl, i, mask, OT_UNIFORM_WAVELENGTH); r.qr = ld_field(in.qr, i, mask, OT_UNIFORM_Q_RE); r.qi = ld_field(in.qi, i, mask, OT_UNIFORM_Q_IM);
+    r.I = ld_field(in.I, i, mask, OT_UNIFORM_INTENSITY); r.n = ld_field(in.n, i, mask, OT_UNIFORM_N); r.pl = ld_field(in.pl, i, mask, OT_UNIFORM_PATHLENGTH);
+    r.len = in.len ? in.len[i] : Num<T>::inf();
+    r.has_q = (flags & OT_RAY_HAS_Q) != 0;
+    r.last = (int32_t)((uint32_t)flags >> 8) - 1;
+    return r;
+}
 
 // ------------------------------------------------------------------------------------------
 // Building blocks of the persistent lane-per-ray kernels (k_trace_trees, k_trace_rolling, k_trace_refill, k_trace_pool).
@@ -306,9 +346,26 @@ template <class T, uint32_t F> __device__ __forceinline__ int32_t seg_surface(co
 // ------------------------------------------------------------------------------------------
 // k_trace_fused: the hot kernel
 // OUT: SegsT<T> (the [k][ray] slots of ot_trace_*: 14 arrays) or SegTiles<T> (the same slots in 64-slot tiles, ot_trace_tiled_*)
+// The parameter list of k_trace_fused, in order = the layout of its kernel-argument segment (as LeadArgs for the persistent kernels)
+template <class T, class OUT> struct FusedArgs {
+    SceneBlob blob; T unit; RaysT<T> in; int64_t n; int32_t K; OUT out; int32_t* seg_count; int32_t* counts; int32_t n_classes; int32_t pair;
+    uint32_t uniform;
+};
+using FusedArgsF64 = FusedArgs<double, SegsT<double>>;
+using FusedArgsF32 = FusedArgs<float, SegTiles<float>>;
+static_assert(offsetof(FusedArgsF64, in) == 56 && offsetof(FusedArgsF32, in) == 56,
+              "the ray pointers follow SceneBlob (48 bytes) and unit (padded to 8): tests/test_fused_args_cpu.py checks the code objects");
 template <class T, uint32_t F, bool SCENE_IN_LDS, int MINW, bool NT, class OUT>
-__global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T unit, RaysT<T> in, int64_t n, int32_t K, OUT out,
-                                                     int32_t* __restrict__ seg_count, int32_t* counts, int32_t n_classes, int32_t pair) {
+__global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T unit, RaysT<T> in_arg, int64_t n, int32_t K, OUT out,
+                                                     int32_t* __restrict__ seg_count, int32_t* counts, int32_t n_classes, int32_t pair,
+                                                     uint32_t uniform) {
+    // `in_arg` only reserves the ray pointers' place in the argument segment: they are read from there (FusedArgs::in), ahead of the
+    // staging for the first rays of a workgroup — the load's latency hides behind the staging, as when they were preloaded — and at
+    // the end of a grid-stride iteration for the next, so never held across the segment loop.  (With the branches of the uniform
+    // fields around the loads, pointers held across the loop are spilled to lanes as one sixteen-register tuple and read back whole
+    // for every field.)
+    using Args = FusedArgs<T, OUT>;
+    RaysT<T> in = karg_struct<RaysT<T>>(karg_words(offsetof(Args, in)));
     extern __shared__ __align__(16) uint32_t lds[];
     const uint32_t* base = blob.words;
     if (SCENE_IN_LDS) {
@@ -325,11 +382,18 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
         int32_t cls = 0, used = 0;
         MatCache<T> mc = {T(1)};
         if (active) {
-            const int32_t fl = in.flags[i];
-            r = load_ray(in, i, fl);
+            const uint32_t um = uniform_here(uniform);
+            int32_t fl;
+            if (um == 0) {  // no hint: the loads of before behind ONE scalar branch, not fourteen (cfg 4 with the hint off: 0.6 % of the launch)
+                fl = in.flags[i];
+                r = load_ray(in, i, fl);
+            } else {
+                fl = ld_flags(in.flags, i, um);
+                r = load_ray(in, i, fl, um);
+            }
             if ((uint32_t)r.last >= (uint32_t)sc.n_nodes) r.last = -1;  // bits 8.. of a caller's flags that name no node of this scene
             if constexpr (F & F_REFRACT) mc = make_matcache<T, F>(sc, r.wl);
-            cls = in.id[i];
+            cls = ld_id(in.id, i, um);
             if (fl & OT_RAY_DEAD) {  // optical_component.py:349: a dead ray hits nothing and is returned as is
                 store_segment<T, NT>(out, i, r, r.len, (int32_t)i, -2);
                 used = 1;
@@ -367,6 +431,7 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
             }
         }
         if (i < n) seg_count[i] = used;
+        if (i0 + stride < n) in = karg_struct<RaysT<T>>(karg_words(offsetof(Args, in)));
     }
 }
 
@@ -1560,11 +1625,12 @@ __global__ __launch_bounds__(1024, 1) void k_trace_pool(
 // writes K segment records per ray through the same SoA streams.  What this access pattern can
 // reach on the device; reported next to the trace kernel (bench.py).
 template <class T, bool NT, class OUT>
-__global__ __launch_bounds__(256) void k_stream_ceiling(RaysT<T> in, int64_t n, int32_t K, OUT out, int32_t* seg_count, int32_t pair) {
+__global__ __launch_bounds__(256) void k_stream_ceiling(RaysT<T> in, int64_t n, int32_t K, OUT out, int32_t* seg_count, int32_t pair, uint32_t uniform) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        RayState<T> r = load_ray(in, i, in.flags[i]);
-        const int32_t cls = in.id[i];
+        const uint32_t um = uniform_here(uniform);
+        RayState<T> r = load_ray(in, i, ld_flags(in.flags, i, um), um);  // uniform fields: as the trace reads them (load_ray)
+        const int32_t cls = ld_id(in.id, i, um);
         const bool both = pair && (i | 1) < n;  // n is even when `pair` is set: both lanes of a pair are in range
         for (int32_t k = 0; k < K; ++k) {
             if (both) store_segment_paired<T, NT>(out, (int64_t)k * n + i, r, r.len, (int32_t)i, cls, (threadIdx.x & 1) != 0);

@@ -142,6 +142,7 @@ struct ot_ctx {
     int32_t opt_nt = 1, opt_minw = 4, opt_blocks_per_cu = 0;  // defaults from tools/tune.py on MI355X
     Scratch gen, scan_tmp, mon, gen_rem, gen_ahead, trees;
     int32_t opt_trees_global = 0;      // k_trace_trees: 1 = every scene through the all-features kernel that reads its image from global memory (test knob)
+    int32_t opt_uniform = 1;  // the lane-per-ray kernel reads fields flagged in a call's uniform_mask once per wave (0: the mask is dropped)
     int32_t opt_trees_flat = 1;        // k_trace_trees: planar scenes under a top-level grid of leaves search through the wave-wide pair queue
     int32_t opt_trees_refill_at = 16;  // k_trace_trees: idle lanes of a wave at which they take their next trees (64: a wave takes 64 trees at a time)
     int32_t opt_trees_lds = 0;  // k_trace_trees: queue entries per lane kept in LDS (the rest of a tree's queue lives in a global scratch); 0: by the cap
@@ -1007,10 +1008,16 @@ template <class T> static bool wants_rolling(const ot_ctx* c, int32_t K) {
     return c->opt_kernel == 2 || (c->opt_kernel == 0 && c->n_nodes >= 24 && K > 2) || (f64 && (fused_preset(c->features) == 4 || !in_lds<T>(c)));
 }
 
+// the uniform_mask of a call (include/optable_hip.h: OT_UNIFORM_*)
+static int check_uniform(uint32_t uniform) {
+    if (uniform & ~(uint32_t)OT_UNIFORM_ALL) return fail(OT_ERR_INVALID, "uniform_mask has bits outside OT_UNIFORM_ALL");
+    return 0;
+}
+
 // one lane per ray (k_trace_fused); OUT = SegsT<T> or SegTiles<T>
 template <class T, class OUT>
 static int launch_fused(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const OUT& out, int32_t pair, int32_t* seg_count, int32_t* counts,
-                        int32_t n_classes) {
+                        int32_t n_classes, uint32_t uniform) {
     const bool f64 = sizeof(T) == 8;
     const int fi = fused_preset(c->features);
     const size_t bytes = image_of<T>(c).bytes;
@@ -1035,20 +1042,24 @@ static int launch_fused(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, co
     FusedKern<T, OUT> kern = fused_kernel<T, OUT>(fi, lds, mw, c->opt_nt != 0);
     if (!kern) return fail(OT_ERR_UNSUPPORTED, "no kernel instantiation for this scene / option combination");
     const LaunchShape shape = {1, block, 0, grid, (int32_t)(lds ? bytes : 0), 0, 0, std::is_same<OUT, SegTiles<T>>::value ? LL_TILES : 0};
-    return launch_kernel(c, kern, shape, nullptr, nullptr, make_blob<T>(c), (T)c->unit, view<T>(rays), n, K, out, seg_count, counts, n_classes, pair);
+    return launch_kernel(c, kern, shape, nullptr, nullptr, make_blob<T>(c), (T)c->unit, view<T>(rays), n, K, out, seg_count, counts, n_classes, pair,
+                         c->opt_uniform ? uniform : 0u);
 }
 
 template <class T>
 static int trace_fused(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
-                       int32_t* counts, int32_t n_classes) {
+                       int32_t* counts, int32_t n_classes, uint32_t uniform) {
     int rc = check_trace_args(c, rays, n, K, seg_count, counts, n_classes);
     if (rc) return rc;
     rc = check_segs(out);
     if (rc) return rc;
+    rc = check_uniform(uniform);
+    if (rc) return rc;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
+    // (the rolling lists read the full arrays: the mask ends here)
     if (wants_rolling<T>(c, K)) return launch_rolling<T, SegsT<T>>(c, rays, n, K, view<T>(out), AppendCtl{nullptr, 0, 0}, seg_count, counts, n_classes);
-    return launch_fused<T, SegsT<T>>(c, rays, n, K, view<T>(out), pair_ok<T>(c, out, n), seg_count, counts, n_classes);
+    return launch_fused<T, SegsT<T>>(c, rays, n, K, view<T>(out), pair_ok<T>(c, out, n), seg_count, counts, n_classes, uniform);
 }
 
 // Tiled layout: the lane-per-ray kernel only (light scenes; heavy ones have the append layout)
@@ -1059,17 +1070,19 @@ template <class T> static int check_tiles(const void* tiles, int64_t capacity, i
 }
 template <class T>
 static int trace_tiled(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count, int32_t* counts,
-                       int32_t n_classes) {
+                       int32_t n_classes, uint32_t uniform) {
     int rc = check_trace_args(c, rays, n, K, seg_count, counts, n_classes);
     if (rc) return rc;
     rc = check_tiles<T>(tiles, capacity, n, K);
+    if (rc) return rc;
+    rc = check_uniform(uniform);
     if (rc) return rc;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
     if (wants_rolling<T>(c, K))
         return fail(OT_ERR_UNSUPPORTED, "the tiled layout belongs to the lane-per-ray kernel (light scenes); heavy scenes write [k][ray] slots (ot_trace_*) or the append layout (ot_trace_append_*)");
     const int32_t pair = (c->opt_pair && !(n & 1) && sizeof(T) == 8) ? 1 : 0;  // lane pairs write 16 bytes: even slot on the even lane
-    return launch_fused<T, SegTiles<T>>(c, rays, n, K, SegTiles<T>{(uint8_t*)tiles}, pair, seg_count, counts, n_classes);
+    return launch_fused<T, SegTiles<T>>(c, rays, n, K, SegTiles<T>{(uint8_t*)tiles}, pair, seg_count, counts, n_classes, uniform);
 }
 
 // the segment block of the append layout (ot_trace_append_*, ot_trace_trees_append_*)
@@ -1102,21 +1115,38 @@ static int trace_append(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, co
 
 extern "C" {
 
+int ot_trace_uniform_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
+                         int32_t* counts, int32_t n_classes, uint32_t uniform) {
+    return trace_fused<double>(c, rays, n, K, out, seg_count, counts, n_classes, uniform);
+}
+int ot_trace_uniform_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
+                         int32_t* counts, int32_t n_classes, uint32_t uniform) {
+    return trace_fused<float>(c, rays, n, K, out, seg_count, counts, n_classes, uniform);
+}
+int ot_trace_tiled_uniform_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count,
+                               int32_t* counts, int32_t n_classes, uint32_t uniform) {
+    return trace_tiled<double>(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, uniform);
+}
+int ot_trace_tiled_uniform_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count,
+                               int32_t* counts, int32_t n_classes, uint32_t uniform) {
+    return trace_tiled<float>(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, uniform);
+}
+// (no uniform fields: the same path with an empty mask)
 int ot_trace_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
                  int32_t* counts, int32_t n_classes) {
-    return trace_fused<double>(c, rays, n, K, out, seg_count, counts, n_classes);
+    return ot_trace_uniform_f64(c, rays, n, K, out, seg_count, counts, n_classes, 0u);
 }
 int ot_trace_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
                  int32_t* counts, int32_t n_classes) {
-    return trace_fused<float>(c, rays, n, K, out, seg_count, counts, n_classes);
+    return ot_trace_uniform_f32(c, rays, n, K, out, seg_count, counts, n_classes, 0u);
 }
 int ot_trace_tiled_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count, int32_t* counts,
                        int32_t n_classes) {
-    return trace_tiled<double>(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes);
+    return ot_trace_tiled_uniform_f64(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, 0u);
 }
 int ot_trace_tiled_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count, int32_t* counts,
                        int32_t n_classes) {
-    return trace_tiled<float>(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes);
+    return ot_trace_tiled_uniform_f32(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, 0u);
 }
 int ot_trace_append_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segment_block* out, int64_t* n_slots,
                         int32_t* seg_count, int32_t* counts, int32_t n_classes) {
@@ -1788,8 +1818,8 @@ template <class T> static int probe_layouts(ot_ctx* c) {
     HIP_TRY(hipEventCreate(&e1));
     double best[2] = {1e30, 1e30};
     auto launch = [&](int layout) {
-        if (layout == 0) hipLaunchKernelGGL((k_stream_ceiling<T, true, SegsT<T>>), dim3(grid), dim3(block), 0, c->stream, view<T>(&in), n, K, view<T>(&sg), seg_count, pair);
-        else hipLaunchKernelGGL((k_stream_ceiling<T, true, SegTiles<T>>), dim3(grid), dim3(block), 0, c->stream, view<T>(&in), n, K, SegTiles<T>{tiles}, seg_count, pair);
+        if (layout == 0) hipLaunchKernelGGL((k_stream_ceiling<T, true, SegsT<T>>), dim3(grid), dim3(block), 0, c->stream, view<T>(&in), n, K, view<T>(&sg), seg_count, pair, 0u);
+        else hipLaunchKernelGGL((k_stream_ceiling<T, true, SegTiles<T>>), dim3(grid), dim3(block), 0, c->stream, view<T>(&in), n, K, SegTiles<T>{tiles}, seg_count, pair, 0u);
     };
     int rc = 0;
     for (int round = 0; round < 3 && !rc; ++round)
@@ -1914,6 +1944,9 @@ int ot_set_option(ot_ctx* c, int32_t option, int32_t value) {
         case OT_OPT_REFILL_TICKET:
             if (value < 0 || value > 4096 || value % 64) return fail(OT_ERR_INVALID, "OT_OPT_REFILL_TICKET takes 0 (by batch size) or a multiple of 64 up to 4096");
             c->opt_refill_ticket = value; return 0;
+        case OT_OPT_UNIFORM:
+            if (value < 0 || value > 1) return fail(OT_ERR_INVALID, "OT_OPT_UNIFORM takes 0 or 1");
+            c->opt_uniform = value; return 0;
         case OT_OPT_BLOCKS_PER_CU:
             if (value < 0 || value > 65536) return fail(OT_ERR_INVALID, "OT_OPT_BLOCKS_PER_CU out of range");
             c->opt_blocks_per_cu = value; return 0;
@@ -1924,10 +1957,13 @@ int ot_set_option(ot_ctx* c, int32_t option, int32_t value) {
 }  // extern "C"
 
 template <class T, class OUT>
-static int bench_stream(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const OUT& out, int32_t pair, int32_t* seg_count) {
+static int bench_stream(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const OUT& out, int32_t pair, int32_t* seg_count, uint32_t uniform) {
     if (!c) return fail(OT_ERR_INVALID, "ctx is NULL");
     int rc = check_rays(rays, "rays");
     if (rc) return rc;
+    rc = check_uniform(uniform);
+    if (rc) return rc;
+    if (!c->opt_uniform) uniform = 0;
     if (n < 1 || K < 1 || !seg_count || n >= (int64_t)1 << 31) return fail(OT_ERR_INVALID, "bad n / K / seg_count");
     HIP_TRY(hipSetDevice(c->device));
     const int block = 256;
@@ -1936,30 +1972,42 @@ static int bench_stream(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, co
     rc = timing_begin(c);
     if (rc) return rc;
     if (c->opt_nt)
-        hipLaunchKernelGGL((k_stream_ceiling<T, true, OUT>), dim3(grid), dim3(block), 0, c->stream, view<T>(rays), n, K, out, seg_count, pair);
+        hipLaunchKernelGGL((k_stream_ceiling<T, true, OUT>), dim3(grid), dim3(block), 0, c->stream, view<T>(rays), n, K, out, seg_count, pair, uniform);
     else
-        hipLaunchKernelGGL((k_stream_ceiling<T, false, OUT>), dim3(grid), dim3(block), 0, c->stream, view<T>(rays), n, K, out, seg_count, pair);
+        hipLaunchKernelGGL((k_stream_ceiling<T, false, OUT>), dim3(grid), dim3(block), 0, c->stream, view<T>(rays), n, K, out, seg_count, pair, uniform);
     HIP_TRY(hipGetLastError());
     return timing_end(c);
 }
 
 extern "C" {
 
-int ot_bench_stream_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count) {
+int ot_bench_stream_uniform_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count, uint32_t uniform) {
     const int rc = check_segs(out);
-    return rc ? rc : bench_stream<double, SegsT<double>>(c, rays, n, K, view<double>(out), pair_ok<double>(c, out, n), seg_count);
+    return rc ? rc : bench_stream<double, SegsT<double>>(c, rays, n, K, view<double>(out), pair_ok<double>(c, out, n), seg_count, uniform);
+}
+int ot_bench_stream_uniform_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count, uint32_t uniform) {
+    const int rc = check_segs(out);
+    return rc ? rc : bench_stream<float, SegsT<float>>(c, rays, n, K, view<float>(out), pair_ok<float>(c, out, n), seg_count, uniform);
+}
+int ot_bench_stream_tiled_uniform_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count, uint32_t uniform) {
+    const int rc = check_tiles<double>(tiles, capacity, n, K);
+    return rc ? rc : bench_stream<double, SegTiles<double>>(c, rays, n, K, SegTiles<double>{(uint8_t*)tiles}, (c && c->opt_pair && !(n & 1)) ? 1 : 0, seg_count, uniform);
+}
+int ot_bench_stream_tiled_uniform_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count, uint32_t uniform) {
+    const int rc = check_tiles<float>(tiles, capacity, n, K);
+    return rc ? rc : bench_stream<float, SegTiles<float>>(c, rays, n, K, SegTiles<float>{(uint8_t*)tiles}, 0, seg_count, uniform);
+}
+int ot_bench_stream_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count) {
+    return ot_bench_stream_uniform_f64(c, rays, n, K, out, seg_count, 0u);
 }
 int ot_bench_stream_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count) {
-    const int rc = check_segs(out);
-    return rc ? rc : bench_stream<float, SegsT<float>>(c, rays, n, K, view<float>(out), pair_ok<float>(c, out, n), seg_count);
+    return ot_bench_stream_uniform_f32(c, rays, n, K, out, seg_count, 0u);
 }
 int ot_bench_stream_tiled_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count) {
-    const int rc = check_tiles<double>(tiles, capacity, n, K);
-    return rc ? rc : bench_stream<double, SegTiles<double>>(c, rays, n, K, SegTiles<double>{(uint8_t*)tiles}, (c && c->opt_pair && !(n & 1)) ? 1 : 0, seg_count);
+    return ot_bench_stream_tiled_uniform_f64(c, rays, n, K, tiles, capacity, seg_count, 0u);
 }
 int ot_bench_stream_tiled_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count) {
-    const int rc = check_tiles<float>(tiles, capacity, n, K);
-    return rc ? rc : bench_stream<float, SegTiles<float>>(c, rays, n, K, SegTiles<float>{(uint8_t*)tiles}, 0, seg_count);
+    return ot_bench_stream_tiled_uniform_f32(c, rays, n, K, tiles, capacity, seg_count, 0u);
 }
 
 #ifdef OT_STAMP

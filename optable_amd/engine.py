@@ -294,7 +294,10 @@ class Engine:
             ss = out.c_struct()
             where = (C.byref(ss),)
         if not skip:
-            abi.check(self._fn(name, rays.precision)(self._ctx, C.byref(rs), rays.n, K, *where, out.count.data_ptr(), counts_ptr, n_classes),
+            hint = ()
+            if name in ("ot_trace", "ot_trace_tiled"):  # the calls that can land on the lane-per-ray kernel take the batch's uniform-field hint
+                name, hint = name + "_uniform", (rays.uniform_mask,)
+            abi.check(self._fn(name, rays.precision)(self._ctx, C.byref(rs), rays.n, K, *where, out.count.data_ptr(), counts_ptr, n_classes, *hint),
                       self.lib)
         if "block" in kind:
             out.cursor, out.n_valid = cursor, None  # device scalar: read lazily (n_valid) so that back-to-back launches do not synchronise
@@ -750,16 +753,17 @@ class Engine:
             self.trees_refill_at = int(value)  # (what the caller asked for: trace_branching's own choice for a batch, `_refill_at`, does not come through here)
 
     def stream_ceiling(self, rays: RayBatch, max_segments, out: SegmentBatch):
-        """Same bytes as `trace` with no tracing (roofline companion), in the layout of `out` (slots or tiled)."""
+        """Same bytes as `trace` with no tracing (roofline companion), in the layout of `out` (slots or tiled): fields the batch
+        knows to be uniform are read once per wave here too."""
         if out.count is None or out.count.numel() != rays.n:
             out.count = torch.empty(rays.n, dtype=torch.int32, device=rays.device)
         if out.tiled:
             rs = rays.c_struct()
-            abi.check(self._fn("ot_bench_stream_tiled", rays.precision)(self._ctx, C.byref(rs), rays.n, int(max_segments), out.block.data_ptr(), out.capacity, out.count.data_ptr()), self.lib)
+            abi.check(self._fn("ot_bench_stream_tiled_uniform", rays.precision)(self._ctx, C.byref(rs), rays.n, int(max_segments), out.block.data_ptr(), out.capacity, out.count.data_ptr(), rays.uniform_mask), self.lib)
             return
         rs, ss = rays.c_struct(), out.c_struct()
-        abi.check(self._fn("ot_bench_stream", rays.precision)(self._ctx, C.byref(rs), rays.n, int(max_segments), C.byref(ss),
-                                                              out.count.data_ptr()), self.lib)
+        abi.check(self._fn("ot_bench_stream_uniform", rays.precision)(self._ctx, C.byref(rs), rays.n, int(max_segments), C.byref(ss),
+                                                                      out.count.data_ptr(), rays.uniform_mask), self.lib)
 
     def last_launch(self):
         """Shape of the last trace launch (include/optable_hip.h: ot_debug_last_launch) as a dict."""
