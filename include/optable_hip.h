@@ -307,6 +307,46 @@ int ot_trace_tiled_uniform_f32(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays,
                                int64_t capacity, int32_t* seg_count, int32_t* counts, int32_t n_count_classes,
                                uint32_t uniform_mask);
 
+/* Resident planes.  A caller that traces into the SAME output again and again (a sustained loop, a stream slot) finds part of
+ * every record there already: `ray` is the ray's index whatever the rays do, and in a scene without Snell interfaces every
+ * segment of a ray carries the ray's own `n` — and its `intensity`, where every mirror and lens passes all of it or nothing.
+ * `resident_mask` is the caller's word that the output holds, for every ray i and every k < |seg_count[i]| AS seg_count STANDS
+ * WHEN THE CALL IS MADE (the array being passed in: the counts of the launch that wrote those records), the value this launch
+ * would write into that plane of slot k * n_rays + i.  The lane-per-ray kernel then reads the old count with the ray and leaves
+ * a flagged plane unwritten for a segment — unless any ray of the wave is past its old count there (a ray that lives longer
+ * than last time): then the whole wave writes the full record.  A ray that arrives dead always gets its full record.
+ * Same records either way, 4 + 8 + 8 of 104 bytes per record fewer written (fp64) for 4 bytes per ray more read.
+ * The library masks the caller's word with what the uploaded scene and the call's uniform_mask keep invariant
+ * (ot_trace_resident_plan), so a mask that is wrong for the SCENE skips nothing that changes; a mask that is wrong about the
+ * OUTPUT (other n_rays, another layout, other values of n / intensity, records written by something else since, a seg_count
+ * that is not the one of the launch that wrote them) is the caller's error: the skipped planes keep what they held.
+ * resident_mask = 0 is ot_trace_uniform_* / ot_trace_tiled_uniform_* exactly (those call these with 0); bits outside
+ * OT_RESIDENT_ALL are OT_ERR_INVALID.  A call that lands on another kernel (heavy scenes) ignores the mask, as does every call
+ * after ot_set_option(OT_OPT_RESIDENT, 0). */
+enum ot_resident_bits {
+    OT_RESIDENT_RAY = 1 << 0,        /* ray[k * n_rays + i] == i: every scene                                                  */
+    OT_RESIDENT_N = 1 << 1,          /* n: needs OT_UNIFORM_N and a scene without Snell interfaces                             */
+    OT_RESIDENT_INTENSITY = 1 << 2,  /* intensity: needs OT_UNIFORM_INTENSITY, such a scene, reflectivity / transmission 0 or 1 */
+    OT_RESIDENT_ALL = (1 << 3) - 1
+};
+int ot_trace_resident_f64(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments,
+                          const ot_segments* out, int32_t* seg_count, int32_t* counts,
+                          int32_t n_count_classes, uint32_t uniform_mask, uint32_t resident_mask);
+int ot_trace_resident_f32(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments,
+                          const ot_segments* out, int32_t* seg_count, int32_t* counts,
+                          int32_t n_count_classes, uint32_t uniform_mask, uint32_t resident_mask);
+int ot_trace_tiled_resident_f64(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments, void* tiles,
+                                int64_t capacity, int32_t* seg_count, int32_t* counts, int32_t n_count_classes,
+                                uint32_t uniform_mask, uint32_t resident_mask);
+int ot_trace_tiled_resident_f32(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments, void* tiles,
+                                int64_t capacity, int32_t* seg_count, int32_t* counts, int32_t n_count_classes,
+                                uint32_t uniform_mask, uint32_t resident_mask);
+/* *planes = the OT_RESIDENT_* planes that EVERY record of such a call on the uploaded scene holds one known value in (what a
+ * later call into the same output may flag); 0 when the call would not land on the lane-per-ray kernel (or n_rays is 0, or
+ * after ot_set_option(OT_OPT_RESIDENT, 0)).  real_bytes: 4 or 8. */
+int ot_trace_resident_plan(ot_ctx* ctx, int32_t real_bytes, uint32_t uniform_mask, int64_t n_rays, int32_t max_segments,
+                           int32_t* planes);
+
 /* The same trace with the APPEND layout: a dense list of segment records instead of max_segments * n_rays slots.
  * The reference returns a list with one entry per processed segment (optical_table.py:125-134); the [k][ray] slots of
  * ot_trace_* hold that list with a hole for every segment a ray did not live to (cfg 3: 11 GB of slots for 2.8 GB of
@@ -561,8 +601,10 @@ enum ot_option {
     OT_OPT_GEN_DROP_DOOMED = 15,/* ot_trace_generation_*: a tree whose budget ends with this generation gets no children in `next` (they
                                   could never be processed: optical_table.py:138-144) — 1 (default) / 0: emit them, for a caller who
                                   wants to go on with a larger budget */
-    OT_OPT_UNIFORM = 26        /* ot_trace_uniform_*, ot_trace_tiled_uniform_*, ot_bench_stream_*uniform_*: 1 (default) the uniform_mask is
+    OT_OPT_UNIFORM = 26,       /* ot_trace_uniform_*, ot_trace_tiled_uniform_*, ot_bench_stream_*uniform_*: 1 (default) the uniform_mask is
                                   honoured; 0 it is dropped and every field is read per ray (A/B runs with one library).  Identical records. */
+    OT_OPT_RESIDENT = 27       /* ot_trace_resident_*, ot_trace_tiled_resident_*: 1 (default) the resident_mask is honoured; 0 it is dropped
+                                  and every record is written whole (A/B runs with one library).  Identical records. */
 };
 int ot_set_option(ot_ctx* ctx, int32_t option, int32_t value);
 

@@ -83,11 +83,15 @@ RAY_HAS_Q, RAY_DEAD = 1, 2
 OPT_NT_STORES, OPT_MIN_WAVES, OPT_BLOCKS_PER_CU, OPT_KERNEL, OPT_LDS_LIMIT_KB, OPT_LIST_CAP, OPT_PAIR_STORES, OPT_MIX_GENERATIONS, OPT_FLAT_QUEUE, OPT_LDS_RECORDS = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 OPT_APPEND_CHUNK, OPT_INSTANCING, OPT_GEN_REUSE, OPT_BLOCK_POOL, OPT_GEN_DROP_DOOMED, OPT_REFILL, OPT_REFILL_TICKET, OPT_POOL_JITTER, OPT_GEN_ONEPASS, OPT_GEN_AHEAD, OPT_TREES_LDS_ENTRIES, OPT_TREES_REFILL_AT, OPT_TREES_FLAT, OPT_GEN_PARENT_INDEX, OPT_TREES_GLOBAL_IMAGE = 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25
 OPT_UNIFORM = 26
+OPT_RESIDENT = 27
 # uniform_mask of ot_trace_uniform_* / ot_trace_tiled_uniform_* / ot_bench_stream_*uniform_* (== header: OT_UNIFORM_*): bit k = the
 # k-th real field of RAY_FIELDS holds one bit pattern in every ray; id: id[i] == i; flags: every word equals flags[0]
 UNIFORM_BIT = {f: 1 << k for k, f in enumerate(RAY_FIELDS)}
 UNIFORM_BIT.update(id=1 << 12, flags=1 << 13)
 UNIFORM_ID, UNIFORM_FLAGS, UNIFORM_ALL = 1 << 12, 1 << 13, (1 << 14) - 1
+# resident_mask of ot_trace_resident_* / ot_trace_tiled_resident_* (== header: OT_RESIDENT_*): planes a reused output already holds
+RESIDENT_RAY, RESIDENT_N, RESIDENT_INTENSITY, RESIDENT_ALL = 1, 2, 4, 7
+RESIDENT_FIELD = {RESIDENT_RAY: "ray", RESIDENT_N: "n", RESIDENT_INTENSITY: "intensity"}  # bit -> SegmentBatch.field name
 
 # every symbol the header declares, with its ctypes signature
 _vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
@@ -110,6 +114,11 @@ SYMBOLS = {
     "ot_trace_uniform_f32": (C.c_int, _TRACE_ARGS + [_u32]),
     "ot_trace_tiled_uniform_f64": (C.c_int, [_vp, C.POINTER(OtRays), _i64, _i32, _vp, _i64, _vp, _vp, _i32, _u32]),
     "ot_trace_tiled_uniform_f32": (C.c_int, [_vp, C.POINTER(OtRays), _i64, _i32, _vp, _i64, _vp, _vp, _i32, _u32]),
+    "ot_trace_resident_f64": (C.c_int, _TRACE_ARGS + [_u32, _u32]),
+    "ot_trace_resident_f32": (C.c_int, _TRACE_ARGS + [_u32, _u32]),
+    "ot_trace_tiled_resident_f64": (C.c_int, [_vp, C.POINTER(OtRays), _i64, _i32, _vp, _i64, _vp, _vp, _i32, _u32, _u32]),
+    "ot_trace_tiled_resident_f32": (C.c_int, [_vp, C.POINTER(OtRays), _i64, _i32, _vp, _i64, _vp, _vp, _i32, _u32, _u32]),
+    "ot_trace_resident_plan": (C.c_int, [_vp, _i32, _u32, _i64, _i32, C.POINTER(_i32)]),
     "ot_bench_stream_uniform_f64": (C.c_int, [_vp, C.POINTER(OtRays), _i64, _i32, C.POINTER(OtSegments), _vp, _u32]),
     "ot_bench_stream_uniform_f32": (C.c_int, [_vp, C.POINTER(OtRays), _i64, _i32, C.POINTER(OtSegments), _vp, _u32]),
     "ot_bench_stream_tiled_uniform_f64": (C.c_int, [_vp, C.POINTER(OtRays), _i64, _i32, _vp, _i64, _vp, _u32]),

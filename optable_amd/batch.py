@@ -32,9 +32,13 @@ class RayBatch:
     drops the entry, silently and for good.  The hole: a write that bypasses the counter is not seen — through `tensor.data`,
     by a kernel handed `data_ptr()`, or (host batches) through the array `tensor.numpy()` shares the memory with; whoever writes
     that way calls `forget_uniform()`.  Tensors made under `torch.inference_mode()` have no version counter: a batch built there
-    carries no hint.  The engine itself never writes into a caller's batch."""
+    carries no hint.  The engine itself never writes into a caller's batch.
+    Where the hint was found on the host (`from_arrays`, and what passes it on) the batch also knows the one VALUE of such a field
+    as a bit pattern (`uniform_bits`), without a device read: what tells the engine that two batches carry the same `n` and
+    `intensity` (resident planes of a reused output, SegmentBatch)."""
 
     _uniform = {}  # field name (abi.RAY_FIELDS, "id", "flags") -> (tensor, its _version when the field was found uniform); never mutated in place
+    _uniform_value = {}  # real field name -> the bit pattern (int) every element of it holds, where that is known; never mutated in place
 
     def __init__(self, n, precision="f64", device="cuda", initialise=True):
         self.n, self.precision, self.device = int(n), precision, torch.device(device)
@@ -75,20 +79,30 @@ class RayBatch:
             self._uniform = {name: tv for name, tv in self._uniform.items() if mask & abi.UNIFORM_BIT[name]}
         return mask
 
+    def uniform_bits(self, name):
+        """The bit pattern (int, in the batch's precision) every element of the real field `name` holds, or None: the hint for the
+        field no longer holds, or the batch never knew the value."""
+        if not self.uniform_mask & abi.UNIFORM_BIT[name]:
+            return None
+        return self._uniform_value.get(name)
+
     def forget_uniform(self):
         """Drop the hint: every field is read per ray again.  For callers that wrote a field behind torch's back."""
         self._uniform = {}
+        self._uniform_value = {}
         return self
 
-    def _vouch(self, names):
+    def _vouch(self, names, values=None):
         """Hint entries for the fields `names`, taken on this batch's tensors as they are now (none for a tensor without a version
-        counter: inference mode)."""
+        counter: inference mode).  values: {field: bit pattern} for the fields whose one value is known."""
         self._uniform = {f: (self.field(f), self.field(f)._version) for f in names if not self.field(f).is_inference()}
+        self._uniform_value = {f: int(v) for f, v in (values or {}).items() if f in self._uniform}
 
     def _inherit_uniform(self, src, names):
         """The entries of `src` that still hold, for the fields `names`, re-taken on this batch's own tensors."""
         mask = src.uniform_mask
-        self._vouch([f for f in names if mask & abi.UNIFORM_BIT[f]] if self.n > 0 else [])
+        self._vouch([f for f in names if mask & abi.UNIFORM_BIT[f]] if self.n > 0 else [],
+                    src._uniform_value)
 
     @classmethod
     def from_arrays(cls, origin, direction, wavelength=0.0, intensity=1.0, q=None, n_index=1.0,
@@ -135,7 +149,9 @@ class RayBatch:
             bits = staged.view(_BITS[precision])[:, :nrays]
             same = ((bits == bits[:, :1]).all(dim=1) & ~torch.isnan(staged[:, 0])).tolist()
             arange_ids = ids is None or np.array_equal(np.asarray(ids).reshape(-1), np.arange(nrays))
-            b._vouch([f for f, k in row.items() if same[k]] + ["flags"] + (["id"] if arange_ids else []))  # (flags: torch.full)
+            first = bits[:, 0].tolist()
+            b._vouch([f for f, k in row.items() if same[k]] + ["flags"] + (["id"] if arange_ids else []),  # (flags: torch.full)
+                     {f: first[k] for f, k in row.items() if same[k]})
         return b
 
     def slice(self, lo, hi):
@@ -177,7 +193,7 @@ class RayBatch:
         """Same rays (storage shared) under other ids (int32 device tensor)."""
         out = self.slice(0, self.n)
         out.id = ids.to(torch.int32).contiguous()
-        out._uniform = {}
+        out.forget_uniform()
         return out
 
     def sorted_spatially(self, cells=32):
@@ -283,8 +299,19 @@ class SegmentBatch:
     append  non-branching trace, dense (ot_trace_append_*): the first `n_valid` slots are records in append order or
             holes (`ray == -1`, the unused tail of a wave's last chunk); `count[i]` as for slots.
     For `list` and `append` a STABLE sort by `ray` gives the reference's order (input ray major, then segment order).
+
+    Resident planes.  A batch the engine's lane-per-ray kernel has written keeps a token of what every record of that launch
+    holds in the planes `ray`, `n` and `intensity` (abi.RESIDENT_*: the ray's index; the input batch's one `n` / `intensity` where
+    the scene hands them on unchanged — the library says which), and the next such launch into the SAME batch leaves those planes
+    unwritten where the old records reach (`Engine.trace`).  The rule: the token holds while `n_rays`, the layout, the engine and
+    its stream are the same, the input's `n` / `intensity` have the same bit pattern, and the plane tensors and `count` (tiles: the
+    block) are still the batch's and at the `_version` they had — any in-place torch write to one of them ends it, silently;
+    the engine clears it before every launch that writes into the batch.  The hole, as for the input hint: a write torch does
+    not see (`tensor.data`, a foreign kernel handed `data_ptr()`, numpy sharing the memory) — whoever writes that way calls
+    `forget_resident()`.  Tensors without a version counter (inference mode) carry no token.
     """
 
+    _resident = None                # the token (a dict, never mutated in place), or None
     tiled = append = False          # defaults for batches assembled field by field (astype, to_slots, table.py)
     trees = False                   # True: `count[i]` rays of a ray TREE per input ray (Engine.trace_trees), not the segments of one path
     block = cursor = _n_valid = count = n_rays = None
@@ -346,6 +373,50 @@ class SegmentBatch:
     @property
     def layout(self):
         return "append" if self.append else ("tiled" if self.tiled else ("slots" if self.count is not None else "list"))
+
+    def forget_resident(self):
+        """Drop the resident-plane token: the next trace into this batch writes every record whole.  For callers that wrote into
+        the batch behind torch's back."""
+        self._resident = None
+        return self
+
+    def _resident_tensors(self, planes, layout):
+        """[(attribute, tensor)] whose contents the token for `planes` stands on"""
+        if layout == "tiled":
+            names = ["block"]
+        else:
+            names = [("n_index" if f == "n" else f) for bit, f in abi.RESIDENT_FIELD.items() if planes & bit]
+        return [(name, getattr(self, name, None)) for name in names + ["count"]]
+
+    def _set_resident(self, planes, n_rays, layout, values, engine, stream):
+        """After a launch of `engine` on `stream` that wrote this batch through the resident entry points: every record holds
+        its ray's index in `ray` and, for the bits of `planes`, the bit pattern values[bit] in `n` / `intensity` (a plane whose
+        value is not known is not kept)."""
+        planes &= abi.RESIDENT_RAY | sum(bit for bit in (abi.RESIDENT_N, abi.RESIDENT_INTENSITY) if values.get(bit) is not None)
+        tensors = self._resident_tensors(planes, layout) if planes else []
+        if not planes or any(t is None or t.is_inference() for _, t in tensors):
+            self._resident = None
+            return
+        self._resident = {"planes": planes, "n_rays": int(n_rays), "layout": layout, "values": {b: values[b] for b in values if planes & b},
+                          "engine": engine, "stream": stream, "tensors": [(name, t, t._version) for name, t in tensors]}
+
+    def resident_mask(self, n_rays, layout, values, engine, stream):
+        """abi.RESIDENT_* planes a launch of `engine` on `stream` for `n_rays` rays in `layout`, whose input carries the bit
+        patterns `values` ({abi.RESIDENT_N: ..., abi.RESIDENT_INTENSITY: ...}, None where not known), may leave unwritten: those
+        of the token, if every entry of it still matches; else 0."""
+        tok = self._resident
+        if tok is None:
+            return 0
+        if tok["n_rays"] != int(n_rays) or tok["layout"] != layout or tok["engine"] is not engine or tok["stream"] != stream:
+            return 0
+        for name, t, version in tok["tensors"]:
+            if getattr(self, name, None) is not t or t._version != version:
+                return 0
+        mask = tok["planes"] & abi.RESIDENT_RAY
+        for bit, old in tok["values"].items():
+            if values.get(bit) is not None and values[bit] == old:
+                mask |= bit
+        return mask
 
     def block_struct(self):
         s = abi.OtSegmentBlock()

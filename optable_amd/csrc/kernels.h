@@ -201,6 +201,79 @@ __device__ __forceinline__ void store_segment_paired(const SegsT<T>& out, int64_
     store_pair<NT>(out.ray, out.surface, slot, tree, surface, odd);
 }
 
+// Resident planes (include/optable_hip.h: OT_RESIDENT_*): a plane the caller vouches the output already holds, in every slot this
+// launch would write it to, is not written again — `ray`, and `n` / `intensity` where the scene hands the batch's one value through.
+// The mask is a kernel argument: every plane test is a scalar branch.  k_trace_fused only, and only for a segment no storing lane of
+// the wave is past its old count on (the kernel decides that per wave, never per lane); everything else writes full records.
+template <class T, bool NT>
+__device__ __forceinline__ void store_segment_reduced(const SegsT<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
+                                                      int32_t surface, uint32_t resident) {
+    st<NT>(out.ox + slot, r.ox); st<NT>(out.oy + slot, r.oy); st<NT>(out.oz + slot, r.oz);
+    st<NT>(out.dx + slot, r.dx); st<NT>(out.dy + slot, r.dy); st<NT>(out.dz + slot, r.dz);
+    st<NT>(out.len + slot, len);
+    if (!(resident & OT_RESIDENT_INTENSITY)) st<NT>(out.I + slot, r.I);
+    st<NT>(out.qr + slot, r.qr); st<NT>(out.qi + slot, r.qi);
+    if (!(resident & OT_RESIDENT_N)) st<NT>(out.n + slot, r.n);
+    st<NT>(out.pl + slot, r.pl);
+    if (!(resident & OT_RESIDENT_RAY)) st<NT>(out.ray + slot, tree);
+    st<NT>(out.surface + slot, surface);
+}
+template <class T, bool NT>
+__device__ __forceinline__ void store_segment_reduced(const SegTiles<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
+                                                      int32_t surface, uint32_t resident) {
+    uint8_t* tb = out.base + (slot >> 6) * SegTiles<T>::TILE_BYTES;
+    T* p = reinterpret_cast<T*>(tb) + (slot & 63);
+    st<NT>(p, r.ox); st<NT>(p + 64, r.oy); st<NT>(p + 128, r.oz);
+    st<NT>(p + 192, r.dx); st<NT>(p + 256, r.dy); st<NT>(p + 320, r.dz);
+    st<NT>(p + 384, len);
+    if (!(resident & OT_RESIDENT_INTENSITY)) st<NT>(p + 448, r.I);
+    st<NT>(p + 512, r.qr); st<NT>(p + 576, r.qi);
+    if (!(resident & OT_RESIDENT_N)) st<NT>(p + 640, r.n);
+    st<NT>(p + 704, r.pl);
+    int32_t* q = reinterpret_cast<int32_t*>(tb + 768 * sizeof(T)) + (slot & 63);
+    if (!(resident & OT_RESIDENT_RAY)) st<NT>(q, tree);
+    st<NT>(q + 64, surface);
+}
+// ... in lane pairs: the partners that lose their mate are paired anew where the types allow (`length` with `pathlength` when
+// `intensity` and `n` are both resident); one that finds none goes alone, one element per lane (`surface`: 4 bytes).
+// LEN .. SURFACE: the planes concerned, element 0 of each; l: this lane's element in them.
+template <class T, bool NT>
+__device__ __forceinline__ void store_mates_reduced(T* LEN, T* I, T* N, T* PL, int32_t* RAY, int32_t* SURFACE, int64_t l, const RayState<T>& r,
+                                                    T len, int32_t tree, int32_t surface, bool odd, uint32_t resident) {
+    const bool keep_I = !(resident & OT_RESIDENT_INTENSITY), keep_n = !(resident & OT_RESIDENT_N);
+    if (keep_I) store_pair<NT>(LEN, I, l, len, r.I, odd);
+    if (keep_n) store_pair<NT>(N, PL, l, r.n, r.pl, odd);
+    if (!keep_I && !keep_n) store_pair<NT>(LEN, PL, l, len, r.pl, odd);
+    else {
+        if (!keep_I) st<NT>(LEN + l, len);
+        if (!keep_n) st<NT>(PL + l, r.pl);
+    }
+    if (resident & OT_RESIDENT_RAY) st<NT>(SURFACE + l, surface);
+    else store_pair<NT>(RAY, SURFACE, l, tree, surface, odd);
+}
+template <class T, bool NT>
+__device__ __forceinline__ void store_segment_paired_reduced(const SegTiles<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
+                                                             int32_t surface, bool odd, uint32_t resident) {
+    uint8_t* tb = out.base + (slot >> 6) * SegTiles<T>::TILE_BYTES;
+    T* p = reinterpret_cast<T*>(tb);
+    const int64_t l = slot & 63;
+    store_pair<NT>(p, p + 64, l, r.ox, r.oy, odd);
+    store_pair<NT>(p + 128, p + 192, l, r.oz, r.dx, odd);
+    store_pair<NT>(p + 256, p + 320, l, r.dy, r.dz, odd);
+    store_pair<NT>(p + 512, p + 576, l, r.qr, r.qi, odd);
+    int32_t* q = reinterpret_cast<int32_t*>(tb + 768 * sizeof(T));
+    store_mates_reduced<T, NT>(p + 384, p + 448, p + 640, p + 704, q, q + 64, l, r, len, tree, surface, odd, resident);
+}
+template <class T, bool NT>
+__device__ __forceinline__ void store_segment_paired_reduced(const SegsT<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
+                                                             int32_t surface, bool odd, uint32_t resident) {
+    store_pair<NT>(out.ox, out.oy, slot, r.ox, r.oy, odd);
+    store_pair<NT>(out.oz, out.dx, slot, r.oz, r.dx, odd);
+    store_pair<NT>(out.dy, out.dz, slot, r.dy, r.dz, odd);
+    store_pair<NT>(out.qr, out.qi, slot, r.qr, r.qi, odd);
+    store_mates_reduced<T, NT>(out.len, out.I, out.n, out.pl, out.ray, out.surface, slot, r, len, tree, surface, odd, resident);
+}
+
 // set bits of a wave-uniform mask below this lane (v_mbcnt: the mask comes from scalar registers, no per-lane lane-mask constant to keep)
 __device__ __forceinline__ int rank_below(unsigned long long m) {
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -343,13 +416,37 @@ template <class T, uint32_t F> __device__ __forceinline__ int32_t seg_surface(co
     return hit ? leaf_id_of<T, F>(sc, node) : (active ? -1 : -2);
 }
 
+// k_trace_fused keeps a ray's segment count in ONE register across the segment loop.  Without resident planes it is the plain count
+// (negative: the tree branched) and max_segments is free.  With them (`packed`) the register also carries the ray's OLD count, which
+// decides what may be left unwritten: bits 0..14 segments written, bit 15 the tree branched, bits 16..30 the old count capped at
+// SEGS_MAX — a cap that loses nothing, since the host drops the mask when max_segments exceeds SEGS_MAX, so k never reaches it.
+struct SegCount {
+    static constexpr uint32_t SEGS_MAX = 0x7fffu, BRANCHED = 0x8000u;
+    static __device__ __forceinline__ uint32_t start(int32_t before) {  // packed: nothing written yet, `before` = seg_count as it stood
+        const uint32_t old = (uint32_t)(before < 0 ? -before : before);
+        return (old > SEGS_MAX ? SEGS_MAX : old) << 16;
+    }
+    static __device__ __forceinline__ uint32_t old_count(uint32_t c) { return c >> 16; }  // (0 where nothing was packed)
+    static __device__ __forceinline__ uint32_t written(uint32_t c, int32_t segments, bool packed) {
+        return packed ? ((c & 0xffff0000u) | (uint32_t)segments) : (uint32_t)segments;
+    }
+    static __device__ __forceinline__ uint32_t branched(uint32_t c, int32_t segments, bool packed) {
+        return packed ? (c | BRANCHED) : (uint32_t)(-segments);
+    }
+    static __device__ __forceinline__ int32_t result(uint32_t c, bool packed) {  // what seg_count receives
+        if (!packed) return (int32_t)c;
+        const int32_t segments = (int32_t)(c & SEGS_MAX);
+        return (c & BRANCHED) ? -segments : segments;
+    }
+};
+
 // ------------------------------------------------------------------------------------------
 // k_trace_fused: the hot kernel
 // OUT: SegsT<T> (the [k][ray] slots of ot_trace_*: 14 arrays) or SegTiles<T> (the same slots in 64-slot tiles, ot_trace_tiled_*)
 // The parameter list of k_trace_fused, in order = the layout of its kernel-argument segment (as LeadArgs for the persistent kernels)
 template <class T, class OUT> struct FusedArgs {
     SceneBlob blob; T unit; RaysT<T> in; int64_t n; int32_t K; OUT out; int32_t* seg_count; int32_t* counts; int32_t n_classes; int32_t pair;
-    uint32_t uniform;
+    uint32_t uniform; uint32_t resident;
 };
 using FusedArgsF64 = FusedArgs<double, SegsT<double>>;
 using FusedArgsF32 = FusedArgs<float, SegTiles<float>>;
@@ -358,7 +455,7 @@ static_assert(offsetof(FusedArgsF64, in) == 56 && offsetof(FusedArgsF32, in) == 
 template <class T, uint32_t F, bool SCENE_IN_LDS, int MINW, bool NT, class OUT>
 __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T unit, RaysT<T> in_arg, int64_t n, int32_t K, OUT out,
                                                      int32_t* __restrict__ seg_count, int32_t* counts, int32_t n_classes, int32_t pair,
-                                                     uint32_t uniform) {
+                                                     uint32_t uniform, uint32_t resident) {
     // `in_arg` only reserves the ray pointers' place in the argument segment: they are read from there (FusedArgs::in), ahead of the
     // staging for the first rays of a workgroup — the load's latency hides behind the staging, as when they were preloaded — and at
     // the end of a grid-stride iteration for the next, so never held across the segment loop.  (With the branches of the uniform
@@ -379,9 +476,13 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
         const int64_t i = i0 + threadIdx.x;
         bool active = i < n;
         RayState<T> r = {};
-        int32_t cls = 0, used = 0;
+        int32_t cls = 0;
+        uint32_t used = 0;  // segments written, and with resident planes the ray's old count beside it (SegCount)
         MatCache<T> mc = {T(1)};
         if (active) {
+            if (resident) {  // (this lane writes the element at the end, and no other lane touches it)
+                used = SegCount::start(seg_count[i]);
+            }
             const uint32_t um = uniform_here(uniform);
             int32_t fl;
             if (um == 0) {  // no hint: the loads of before behind ONE scalar branch, not fourteen (cfg 4 with the hint off: 0.6 % of the launch)
@@ -396,7 +497,7 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
             cls = ld_id(in.id, i, um);
             if (fl & OT_RAY_DEAD) {  // optical_component.py:349: a dead ray hits nothing and is returned as is
                 store_segment<T, NT>(out, i, r, r.len, (int32_t)i, -2);
-                used = 1;
+                used = 1;  // (its old count is not needed: it writes nothing more)
                 active = false;
             }
         }
@@ -407,30 +508,44 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
             // segment record: pairs of lanes that both store write two fields per 16-byte store (store_segment_paired)
             const unsigned long long storing = __ballot(active);
             const bool both = pair && ((storing >> (threadIdx.x & 62)) & 3ull) == 3ull;
+            // resident planes are skipped for the WHOLE wave or not at all: one storing lane past its old count (a ray that lives
+            // longer than last time) and every lane of the wave writes this segment's full record
+            const uint32_t rm = uniform_here(resident);  // (the plane tests are made at the stores, not kept in scalar registers across the search)
+            const bool whole = rm == 0 || __any(active && (uint32_t)k >= SegCount::old_count(used));
             if (both) {
                 const bool hit = h.node >= 0;
-                store_segment_paired<T, NT>(out, (int64_t)k * n + i, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : -1,
-                                            (threadIdx.x & 1) != 0);
+                if (whole)
+                    store_segment_paired<T, NT>(out, (int64_t)k * n + i, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : -1,
+                                                (threadIdx.x & 1) != 0);
+                else
+                    store_segment_paired_reduced<T, NT>(out, (int64_t)k * n + i, r, hit ? h.t : r.len, (int32_t)i,
+                                                        hit ? leaf_id_of<T, F>(sc, h.node) : -1, (threadIdx.x & 1) != 0, rm);
             }
             if (active) {
                 const int64_t slot = (int64_t)k * n + i;
-                used = k + 1;
+                used = SegCount::written(used, k + 1, resident != 0);
                 if (h.node < 0) {  // escaped: archived unchanged (optical_table.py:132-134)
-                    if (!both) store_segment<T, NT>(out, slot, r, r.len, (int32_t)i, -1);
+                    if (!both) {
+                        if (whole) store_segment<T, NT>(out, slot, r, r.len, (int32_t)i, -1);
+                        else store_segment_reduced<T, NT>(out, slot, r, r.len, (int32_t)i, -1, rm);
+                    }
                     active = false;
                 } else {
-                    if (!both) store_segment<T, NT>(out, slot, r, h.t, (int32_t)i, leaf_id_of<T, F>(sc, h.node));
+                    if (!both) {
+                        if (whole) store_segment<T, NT>(out, slot, r, h.t, (int32_t)i, leaf_id_of<T, F>(sc, h.node));
+                        else store_segment_reduced<T, NT>(out, slot, r, h.t, (int32_t)i, leaf_id_of<T, F>(sc, h.node), rm);
+                    }
                     RayState<T> child;
                     const int nk = interact<T, F, 1>(sc, r, h, &child, mc);
                     if (nk == 1) r = child;
                     else {
                         active = false;
-                        if (nk > 1) used = -(k + 1);  // the tree branches here: not representable in [k][ray] slots
+                        if (nk > 1) used = SegCount::branched(used, k + 1, resident != 0);  // the tree branches here: not representable in [k][ray] slots
                     }
                 }
             }
         }
-        if (i < n) seg_count[i] = used;
+        if (i < n) seg_count[i] = SegCount::result(used, resident != 0);
         if (i0 + stride < n) in = karg_struct<RaysT<T>>(karg_words(offsetof(Args, in)));
     }
 }

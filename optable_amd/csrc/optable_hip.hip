@@ -143,6 +143,8 @@ struct ot_ctx {
     Scratch gen, scan_tmp, mon, gen_rem, gen_ahead, trees;
     int32_t opt_trees_global = 0;      // k_trace_trees: 1 = every scene through the all-features kernel that reads its image from global memory (test knob)
     int32_t opt_uniform = 1;  // the lane-per-ray kernel reads fields flagged in a call's uniform_mask once per wave (0: the mask is dropped)
+    int32_t opt_resident = 1; // ... and leaves the planes of a call's resident_mask unwritten where the output holds them (0: the mask is dropped)
+    bool whole_intensity = false;  // every leaf hands a ray's intensity on unchanged or not at all (found at upload: resident_planes)
     int32_t opt_trees_flat = 1;        // k_trace_trees: planar scenes under a top-level grid of leaves search through the wave-wide pair queue
     int32_t opt_trees_refill_at = 16;  // k_trace_trees: idle lanes of a wave at which they take their next trees (64: a wave takes 64 trees at a time)
     int32_t opt_trees_lds = 0;  // k_trace_trees: queue entries per lane kept in LDS (the rest of a tree's queue lives in a global scratch); 0: by the cap
@@ -657,6 +659,15 @@ int ot_scene_upload(ot_ctx* c, const ot_scene_desc* s) {
     c->n_nodes = s->n_nodes; c->n_mats = s->n_materials; c->n_aux = s->n_aux;
     c->n_slots = s->n_count_slots; c->max_children = s->max_children; c->unit = s->unit;
     c->features = scene_features(s);
+    // Does `intensity` survive every interaction bit for bit?  x * 1 keeps the bits of x, so: reflectivity and transmission of every
+    // leaf exactly 0 or 1 (a zero emits nothing), and a thin lens — which emits its ray whatever `transmission` is — exactly 1.
+    c->whole_intensity = true;
+    for (int i = 0; i < s->n_nodes; ++i) {
+        const ot_node& h = s->nodes[i];
+        if (h.kind != OT_NODE_LEAF) continue;
+        const bool unit_rt = (h.reflectivity == 0.0 || h.reflectivity == 1.0) && (h.transmission == 0.0 || h.transmission == 1.0);
+        if (!unit_rt || (h.interaction == OT_INT_LENS && h.transmission != 1.0)) c->whole_intensity = false;
+    }
     c->has_implicit = false;
     for (int i = 0; i < s->n_nodes; ++i)
         if (s->nodes[i].kind == OT_NODE_LEAF && s->nodes[i].shape == OT_SHAPE_IMPLICIT_CHEB) c->has_implicit = true;
@@ -1014,10 +1025,29 @@ static int check_uniform(uint32_t uniform) {
     return 0;
 }
 
+// the resident_mask of a call (include/optable_hip.h: OT_RESIDENT_*)
+static int check_resident(uint32_t resident) {
+    if (resident & ~(uint32_t)OT_RESIDENT_ALL) return fail(OT_ERR_INVALID, "resident_mask has bits outside OT_RESIDENT_ALL");
+    return 0;
+}
+// The planes every record of a lane-per-ray launch with this uniform_mask holds ONE known value in, whatever the rays do: `ray` is
+// the ray's index.  `n`: a preset without Snell interfaces hands r.n to every child (trace_core.h interact: lens and mirror
+// branches), so a uniform input field is a uniform plane; `intensity` likewise where every leaf multiplies it by exactly 1.
+// This rule, not the caller, decides what a launch may leave unwritten: launch_fused masks the caller's word with it.
+template <class T> static uint32_t resident_planes(const ot_ctx* c, uint32_t uniform, int32_t K) {
+    if (!c->opt_resident || K > (int32_t)SegCount::SEGS_MAX) return 0;  // (the kernel keeps a ray's old and new count in one register: kernels.h SegCount)
+    if (!c->opt_uniform) uniform = 0;
+    uint32_t planes = OT_RESIDENT_RAY;
+    const bool hands_on = fused_preset(c->features) == 0 && in_lds<T>(c);  // the preset FA: no F_REFRACT (tables.h; inst_fused.hip lookup)
+    if (hands_on && (uniform & OT_UNIFORM_N)) planes |= OT_RESIDENT_N;
+    if (hands_on && (uniform & OT_UNIFORM_INTENSITY) && c->whole_intensity) planes |= OT_RESIDENT_INTENSITY;
+    return planes;
+}
+
 // one lane per ray (k_trace_fused); OUT = SegsT<T> or SegTiles<T>
 template <class T, class OUT>
 static int launch_fused(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const OUT& out, int32_t pair, int32_t* seg_count, int32_t* counts,
-                        int32_t n_classes, uint32_t uniform) {
+                        int32_t n_classes, uint32_t uniform, uint32_t resident) {
     const bool f64 = sizeof(T) == 8;
     const int fi = fused_preset(c->features);
     const size_t bytes = image_of<T>(c).bytes;
@@ -1043,23 +1073,25 @@ static int launch_fused(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, co
     if (!kern) return fail(OT_ERR_UNSUPPORTED, "no kernel instantiation for this scene / option combination");
     const LaunchShape shape = {1, block, 0, grid, (int32_t)(lds ? bytes : 0), 0, 0, std::is_same<OUT, SegTiles<T>>::value ? LL_TILES : 0};
     return launch_kernel(c, kern, shape, nullptr, nullptr, make_blob<T>(c), (T)c->unit, view<T>(rays), n, K, out, seg_count, counts, n_classes, pair,
-                         c->opt_uniform ? uniform : 0u);
+                         c->opt_uniform ? uniform : 0u, resident & resident_planes<T>(c, uniform, K));
 }
 
 template <class T>
 static int trace_fused(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
-                       int32_t* counts, int32_t n_classes, uint32_t uniform) {
+                       int32_t* counts, int32_t n_classes, uint32_t uniform, uint32_t resident) {
     int rc = check_trace_args(c, rays, n, K, seg_count, counts, n_classes);
     if (rc) return rc;
     rc = check_segs(out);
     if (rc) return rc;
     rc = check_uniform(uniform);
     if (rc) return rc;
+    rc = check_resident(resident);
+    if (rc) return rc;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
-    // (the rolling lists read the full arrays: the mask ends here)
+    // (the rolling lists read the full arrays and write whole records: the masks end here)
     if (wants_rolling<T>(c, K)) return launch_rolling<T, SegsT<T>>(c, rays, n, K, view<T>(out), AppendCtl{nullptr, 0, 0}, seg_count, counts, n_classes);
-    return launch_fused<T, SegsT<T>>(c, rays, n, K, view<T>(out), pair_ok<T>(c, out, n), seg_count, counts, n_classes, uniform);
+    return launch_fused<T, SegsT<T>>(c, rays, n, K, view<T>(out), pair_ok<T>(c, out, n), seg_count, counts, n_classes, uniform, resident);
 }
 
 // Tiled layout: the lane-per-ray kernel only (light scenes; heavy ones have the append layout)
@@ -1070,19 +1102,21 @@ template <class T> static int check_tiles(const void* tiles, int64_t capacity, i
 }
 template <class T>
 static int trace_tiled(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count, int32_t* counts,
-                       int32_t n_classes, uint32_t uniform) {
+                       int32_t n_classes, uint32_t uniform, uint32_t resident) {
     int rc = check_trace_args(c, rays, n, K, seg_count, counts, n_classes);
     if (rc) return rc;
     rc = check_tiles<T>(tiles, capacity, n, K);
     if (rc) return rc;
     rc = check_uniform(uniform);
     if (rc) return rc;
+    rc = check_resident(resident);
+    if (rc) return rc;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
     if (wants_rolling<T>(c, K))
         return fail(OT_ERR_UNSUPPORTED, "the tiled layout belongs to the lane-per-ray kernel (light scenes); heavy scenes write [k][ray] slots (ot_trace_*) or the append layout (ot_trace_append_*)");
     const int32_t pair = (c->opt_pair && !(n & 1) && sizeof(T) == 8) ? 1 : 0;  // lane pairs write 16 bytes: even slot on the even lane
-    return launch_fused<T, SegTiles<T>>(c, rays, n, K, SegTiles<T>{(uint8_t*)tiles}, pair, seg_count, counts, n_classes, uniform);
+    return launch_fused<T, SegTiles<T>>(c, rays, n, K, SegTiles<T>{(uint8_t*)tiles}, pair, seg_count, counts, n_classes, uniform, resident);
 }
 
 // the segment block of the append layout (ot_trace_append_*, ot_trace_trees_append_*)
@@ -1115,21 +1149,49 @@ static int trace_append(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, co
 
 extern "C" {
 
+int ot_trace_resident_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
+                          int32_t* counts, int32_t n_classes, uint32_t uniform, uint32_t resident) {
+    return trace_fused<double>(c, rays, n, K, out, seg_count, counts, n_classes, uniform, resident);
+}
+int ot_trace_resident_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
+                          int32_t* counts, int32_t n_classes, uint32_t uniform, uint32_t resident) {
+    return trace_fused<float>(c, rays, n, K, out, seg_count, counts, n_classes, uniform, resident);
+}
+int ot_trace_tiled_resident_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count,
+                                int32_t* counts, int32_t n_classes, uint32_t uniform, uint32_t resident) {
+    return trace_tiled<double>(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, uniform, resident);
+}
+int ot_trace_tiled_resident_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count,
+                                int32_t* counts, int32_t n_classes, uint32_t uniform, uint32_t resident) {
+    return trace_tiled<float>(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, uniform, resident);
+}
+// Which planes would such a call keep invariant on the uploaded scene (0: it would not land on the lane-per-ray kernel)?
+int ot_trace_resident_plan(ot_ctx* c, int32_t real_bytes, uint32_t uniform, int64_t n, int32_t K, int32_t* planes) {
+    if (!c || !planes || (real_bytes != 4 && real_bytes != 8) || n < 0 || K < 1) return fail(OT_ERR_INVALID, "ot_trace_resident_plan: bad argument");
+    if (!c->has_scene) return fail(OT_ERR_NOSCENE, "ot_scene_upload has not been called");
+    const int rc = check_uniform(uniform);
+    if (rc) return rc;
+    const bool f64 = real_bytes == 8;
+    const bool fused = n > 0 && c->max_children <= 2 && !(f64 ? wants_rolling<double>(c, K) : wants_rolling<float>(c, K));
+    *planes = !fused ? 0 : (int32_t)(f64 ? resident_planes<double>(c, uniform, K) : resident_planes<float>(c, uniform, K));
+    return 0;
+}
+// (nothing resident: the same path with an empty mask)
 int ot_trace_uniform_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
                          int32_t* counts, int32_t n_classes, uint32_t uniform) {
-    return trace_fused<double>(c, rays, n, K, out, seg_count, counts, n_classes, uniform);
+    return ot_trace_resident_f64(c, rays, n, K, out, seg_count, counts, n_classes, uniform, 0u);
 }
 int ot_trace_uniform_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
                          int32_t* counts, int32_t n_classes, uint32_t uniform) {
-    return trace_fused<float>(c, rays, n, K, out, seg_count, counts, n_classes, uniform);
+    return ot_trace_resident_f32(c, rays, n, K, out, seg_count, counts, n_classes, uniform, 0u);
 }
 int ot_trace_tiled_uniform_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count,
                                int32_t* counts, int32_t n_classes, uint32_t uniform) {
-    return trace_tiled<double>(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, uniform);
+    return ot_trace_tiled_resident_f64(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, uniform, 0u);
 }
 int ot_trace_tiled_uniform_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count,
                                int32_t* counts, int32_t n_classes, uint32_t uniform) {
-    return trace_tiled<float>(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, uniform);
+    return ot_trace_tiled_resident_f32(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, uniform, 0u);
 }
 // (no uniform fields: the same path with an empty mask)
 int ot_trace_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
@@ -1947,6 +2009,9 @@ int ot_set_option(ot_ctx* c, int32_t option, int32_t value) {
         case OT_OPT_UNIFORM:
             if (value < 0 || value > 1) return fail(OT_ERR_INVALID, "OT_OPT_UNIFORM takes 0 or 1");
             c->opt_uniform = value; return 0;
+        case OT_OPT_RESIDENT:
+            if (value < 0 || value > 1) return fail(OT_ERR_INVALID, "OT_OPT_RESIDENT takes 0 or 1");
+            c->opt_resident = value; return 0;
         case OT_OPT_BLOCKS_PER_CU:
             if (value < 0 || value > 65536) return fail(OT_ERR_INVALID, "OT_OPT_BLOCKS_PER_CU out of range");
             c->opt_blocks_per_cu = value; return 0;

@@ -23,7 +23,7 @@ constexpr uint32_t FM = FE | F_MISC;                           // + cylinders, p
 }  // namespace preset
 
 template <class T, class OUT>
-using FusedKern = void (*)(SceneBlob, T, RaysT<T>, int64_t, int32_t, OUT, int32_t*, int32_t*, int32_t, int32_t, uint32_t);
+using FusedKern = void (*)(SceneBlob, T, RaysT<T>, int64_t, int32_t, OUT, int32_t*, int32_t*, int32_t, int32_t, uint32_t, uint32_t);
 template <class T, class OUT>
 using RollingKern = void (*)(SceneBlob, T, RaysT<T>, int64_t, int32_t, OUT, AppendCtl, int32_t*, int32_t*, int32_t, WaveScratch<T>, int32_t,
                              int32_t, unsigned long long*, int32_t, int32_t);

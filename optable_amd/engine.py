@@ -71,6 +71,16 @@ def _width(precision):
     return 8 if precision == "f64" else 4
 
 
+def _keeps_bits(bits, precision):
+    """`bits` (the pattern of a uniform intensity, or None) if x * 1 gives back exactly that pattern on the device: not a
+    subnormal, which a kernel built to flush them would turn into zero (NaN never carries a hint)."""
+    if bits is None:
+        return None
+    exponent = (bits >> 52) & 0x7ff if precision == "f64" else (bits >> 23) & 0xff
+    mantissa = bits & ((1 << 52) - 1) if precision == "f64" else bits & ((1 << 23) - 1)
+    return None if (exponent == 0 and mantissa != 0) else bits
+
+
 def _counts_table(scene, counts, columns, device):
     """The interact-count table of a launch as (table, its address, its columns): the caller's, else a zeroed one of `columns`
     columns when the scene has count-limited surfaces, else none."""
@@ -147,6 +157,8 @@ class Engine:
         self._ctx = C.c_void_p()
         stream = torch.cuda.current_stream(self.device).cuda_stream
         abi.check(self.lib.ot_ctx_create(device, C.c_void_p(stream), C.byref(self._ctx)), self.lib)
+        self._stream = stream       # the stream the launches go to (part of an output's resident-plane token)
+        self._resident_plans = {}   # (precision, uniform mask, n, K) -> planes ot_trace_resident_plan reported for the uploaded scene
         self.scene = None
         self.append_chunk = 512  # OT_OPT_APPEND_CHUNK as last set through set_option (the library's default)
         self.trees_refill_at = 16  # OT_OPT_TREES_REFILL_AT likewise
@@ -161,6 +173,7 @@ class Engine:
         """Launch on `stream` (a torch.cuda.Stream; default: torch's current stream) from now on."""
         handle = (stream or torch.cuda.current_stream(self.device)).cuda_stream
         abi.check(self.lib.ot_ctx_set_stream(self._ctx, C.c_void_p(handle)), self.lib)
+        self._stream = handle
 
     def close(self):
         if self._ctx:
@@ -176,6 +189,7 @@ class Engine:
         self.scene = scene
         self._records_per_ray = {}
         self._layout_choice = {}
+        self._resident_plans = {}
 
     def _refuse_hooks(self):
         """Whole-trace launches cannot call back into Python: a scene with user-defined `interact_local` leaves
@@ -279,9 +293,24 @@ class Engine:
             out.tiled = False  # (forced, though the check above has just refused a tiled `out` and a new block is not tiled)
         return out
 
+    def resident_plan(self, precision, uniform_mask, n_rays, max_segments):
+        """abi.RESIDENT_* planes every record of a lane-per-ray launch of such a batch holds one known value in on the uploaded
+        scene (ot_trace_resident_plan: the library's rule, asked once per scene and call shape); 0: not that kernel."""
+        key = (precision, int(uniform_mask), int(n_rays), int(max_segments))
+        planes = self._resident_plans.get(key)
+        if planes is None:
+            got = C.c_int32()
+            abi.check(self.lib.ot_trace_resident_plan(self._ctx, _width(precision), key[1], key[2], key[3], C.byref(got)), self.lib)
+            if len(self._resident_plans) > 64:
+                self._resident_plans = {}
+            planes = self._resident_plans[key] = int(got.value)
+        return planes
+
     def _launch(self, name, rays, K, out, counts_ptr, n_classes, skip=False):
         """The library call `name`_f64 / _f32 on the whole batch, `out` handed over the way its layout wants.  skip: everything
-        but the call itself (the append cursor is still made, zeroed and attached)."""
+        but the call itself (the append cursor is still made, zeroed and attached).
+        Resident planes (SegmentBatch): whatever token `out` carries is read and cleared before the call; the calls that can land on
+        the lane-per-ray kernel pass what it allows and leave a new one."""
         kind = _OUT[name][0]
         rs = rays.c_struct()
         if "block" in kind:
@@ -293,12 +322,22 @@ class Engine:
         else:
             ss = out.c_struct()
             where = (C.byref(ss),)
-        if not skip:
-            hint = ()
+        if skip:
+            out.forget_resident()
+        else:
+            hint, planes = (), 0
             if name in ("ot_trace", "ot_trace_tiled"):  # the calls that can land on the lane-per-ray kernel take the batch's uniform-field hint
-                name, hint = name + "_uniform", (rays.uniform_mask,)
+                layout = "tiled" if "tiled" in kind else "slots"
+                um = rays.uniform_mask
+                planes = self.resident_plan(rays.precision, um, rays.n, K)
+                values = {abi.RESIDENT_N: rays.uniform_bits("n"), abi.RESIDENT_INTENSITY: _keeps_bits(rays.uniform_bits("intensity"), rays.precision)}
+                resident = out.resident_mask(rays.n, layout, values, self, self._stream) & planes
+                name, hint = name + "_resident", (um, resident)
+            out.forget_resident()
             abi.check(self._fn(name, rays.precision)(self._ctx, C.byref(rs), rays.n, K, *where, out.count.data_ptr(), counts_ptr, n_classes, *hint),
                       self.lib)
+            if planes:
+                out._set_resident(planes, rays.n, layout, values, self, self._stream)
         if "block" in kind:
             out.cursor, out.n_valid = cursor, None  # device scalar: read lazily (n_valid) so that back-to-back launches do not synchronise
 
@@ -746,6 +785,7 @@ class Engine:
         return ms.value, cnt.value
 
     def set_option(self, option, value):
+        self._resident_plans = {}
         abi.check(self.lib.ot_set_option(self._ctx, option, value), self.lib)
         if option == abi.OPT_APPEND_CHUNK:
             self.append_chunk = int(value)  # (the capacity estimates of the append layout count holes in chunks)
@@ -755,6 +795,7 @@ class Engine:
     def stream_ceiling(self, rays: RayBatch, max_segments, out: SegmentBatch):
         """Same bytes as `trace` with no tracing (roofline companion), in the layout of `out` (slots or tiled): fields the batch
         knows to be uniform are read once per wave here too."""
+        out.forget_resident()  # (the ceiling writes whole records of its own into `out`)
         if out.count is None or out.count.numel() != rays.n:
             out.count = torch.empty(rays.n, dtype=torch.int32, device=rays.device)
         if out.tiled:

@@ -49,6 +49,10 @@ def trace_host(table, origin, direction, wavelength=0.0, q=None, max_segments=8,
     stage_w = [torch.empty(chunk, dtype=torch.float64).pin_memory() for _ in streams] if wl_arr is not None else None
     stage_q = [torch.empty((chunk, 2), dtype=torch.float64).pin_memory() for _ in streams] if q_arr is not None else None
     ready = [None, None]                      # event: the staging blocks' uploads have finished
+    # one output per stream slot for the full-size chunks: a chunk's records are copied out on the slot's own stream before the
+    # next trace there overwrites them, and a reused output keeps its resident planes (SegmentBatch: every chunk has n = I = 1)
+    slot_out = [None, None]
+    one = int(np.ones(1, dtype=np_dt).view(np.int64 if precision == "f64" else np.int32)[0])
     out_count = torch.empty(n, dtype=torch.int32).pin_memory()
     out_final = {f: torch.empty(n, dtype=dt).pin_memory() for f in FINAL_FIELDS}   # contiguous per field: direct DMA
     out_hist = out_surf = None
@@ -92,7 +96,14 @@ def trace_host(table, origin, direction, wavelength=0.0, q=None, max_segments=8,
             batch.id = torch.arange(m, dtype=torch.int32, device=dev)
             batch.flags = torch.full((m,), abi.RAY_HAS_Q if q is not None else 0, dtype=torch.int32, device=dev)
             batch.length = None
-            segs = engines[slot].trace(batch, K, out=SegmentBatch(m * K, precision, dev))
+            batch._vouch(["intensity", "n"], {"intensity": one, "n": one})  # (filled with 1.0 above, by this function alone)
+            if m == chunk:
+                if slot_out[slot] is None:
+                    slot_out[slot] = SegmentBatch(m * K, precision, dev)
+                seg_out = slot_out[slot]
+            else:  # a shorter last chunk
+                seg_out = SegmentBatch(m * K, precision, dev)
+            segs = engines[slot].trace(batch, K, out=seg_out)
             out_count[lo:hi].copy_(segs.count, non_blocking=True)
             last = (segs.count.long() - 1).clamp_(min=0) * m + torch.arange(m, device=dev)
             for f in FINAL_FIELDS:
