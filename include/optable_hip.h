@@ -544,6 +544,33 @@ int ot_monitor_image_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitor
                           int32_t nby, int32_t nbz, const ot_segment_source* src, const void* intensity, int64_t n_segments,
                           const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* weights, int32_t accumulate);
 
+/* Coherent detector images: ot_monitor_image_many with a phasor in place of the weight — per monitor a count image and the two
+ * parts of a complex field image, re = sum a cos(phi), im = sum a sin(phi) over the hits of a bin, from the same launches of the
+ * count kernel (a third mode of it), the same test and the same bin rule; mons, axes, edges, nby, nbz, src, n_segments, seg_count,
+ * n_rays and accumulate as there.
+ * A hit of slot s at the distance t: L = t * n[s] + pathlength[s] (Ray.pathlength(t)), x = L / wavelength cycles,
+ * phi = 2 pi (x - floor x) (Ray.phase(t)), a = sqrt(intensity[s]) for amplitude_mode 0 (intensity is a power) or intensity[s] for 1
+ * (scenes whose splitting ratios are amplitudes).  All in double precision; the model's phase and nothing more: no pi on
+ * reflection, no Gaussian envelope.
+ * intensity, n_index, pathlength: device planes of the segments, addressed like src->base[f].  The wavelength of a hit is
+ * wavelength[ray[s]] (device, n_wavelengths doubles: one per input ray, ray[s] through src->ray) or, with wavelength = NULL,
+ * wavelength_uniform for every hit.  A hit inside the image whose ray lies outside [0, n_wavelengths), or whose wavelength is not
+ * finite and > 0, adds nothing to the images and one to *skipped (device); nothing is read out of range.
+ * counts, re, im: device, [n_monitors][nby][nbz] int64 / double / double; skipped: device, one int64.  accumulate = 0 zeroes all
+ * four first, 1 adds to what is there.  Counts are integers, exact and the same every run.  re and im are fp64 atomic sums:
+ * their last bits depend on the order in which the hits arrive and may differ from run to run.
+ * Paths: as for ot_monitor_image_many at 20 bytes of LDS a bin (3,270 bins: three monitors of 30 x 30 a group); an image that
+ * does not fit alone goes to global atomics hit by hit.
+ * OT_ERR_INVALID, nothing launched or zeroed: everything ot_monitor_image_many refuses; src->width other than 8 (single-precision
+ * path lengths carry some 0.02 cycle of phase noise at table scale: refused, not approximated); a NULL n_index, pathlength, counts,
+ * re, im or skipped; wavelength = NULL with wavelength_uniform not finite or not > 0; a wavelength array with n_wavelengths < 1;
+ * an amplitude_mode other than 0 / 1. */
+int ot_monitor_field_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges,
+                          int32_t nby, int32_t nbz, const ot_segment_source* src, const void* intensity, const void* n_index,
+                          const void* pathlength, const double* wavelength, int64_t n_wavelengths, double wavelength_uniform,
+                          int32_t amplitude_mode, int64_t n_segments, const int32_t* seg_count, int64_t n_rays, int64_t* counts,
+                          double* re, double* im, int64_t* skipped, int32_t accumulate);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled every trace launch is bracketed by hipEvents on the ctx stream. */
 int ot_timing_enable(ot_ctx* ctx, int enabled);

@@ -342,15 +342,107 @@ __device__ __forceinline__ void mon_image_pass(const ot_monitor* __restrict__ mo
         }
     }
 }
+// The field mode of k_mon_count (ot_monitor_field_many): the image mode's partition, loads, tests and bin rule, with a phasor in
+// place of the weight.  All zero for the two other modes.  A hit of slot s at the distance t has the optical path
+// L = t * n[s] + pathlength[s] (Ray.pathlength(t)), x = L / wavelength cycles, the phase 2 pi (x - floor x) (Ray.phase(t)) and the
+// amplitude sqrt(intensity[s]) (amplitude_mode 0) or intensity[s] (1); its bin gets a cos, a sin and one count.  n and pathlength are
+// addressed like the fields of MonSource and read as doubles (the host refuses single precision); the wavelength is
+// wavelength[ray[s]] or, with no array, wavelength_uniform.  A hit inside the image whose ray is outside [0, n_wavelengths) or
+// whose wavelength is not finite and > 0 adds nothing and is counted in *skipped: nothing is read out of range.
+// Through LDS: re[lds_bins], im[lds_bins] (double), tally[lds_bins] (int32) — 20 bytes a bin.
+static constexpr int MON_FIELD_LDS_BINS = (65536 - MON_MAX * 4) / 20;  // 3270: three monitors of 30 x 30
+struct MonField {
+    double *re, *im;  // [n_mon][nby][nbz], of the launch's first monitor on; re NULL: no field mode
+    const uint8_t *n_index, *pathlength;
+    const double* wavelength;  // [n_wavelengths], or NULL: wavelength_uniform for every ray
+    unsigned long long* skipped;
+    double wavelength_uniform;
+    int32_t n_wavelengths, amplitude_mode;
+};
+__device__ __forceinline__ void mon_field_pass(const ot_monitor* __restrict__ mons, int32_t n_mon, const MonSource& src, int64_t n, int32_t iters,
+                                               const int32_t* __restrict__ seg_count, int64_t n_rays, const MonImage& img, const MonField& fld,
+                                               double* re, double* im, int32_t* tally) {
+    for (int32_t b = threadIdx.x; b < img.lds_bins; b += MON_THREADS) re[b] = 0.0, im[b] = 0.0, tally[b] = 0;
+    __syncthreads();
+    const int32_t per_mon = img.nby * img.nbz;
+    const int64_t first = (int64_t)blockIdx.x * iters * MON_THREADS;
+    int32_t skipped = 0;
+    for (int32_t it = 0; it < iters && first + (int64_t)it * MON_THREADS < n; ++it) {
+        const int64_t s = first + (int64_t)it * MON_THREADS + threadIdx.x;
+        const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
+        if (!__ballot(g.valid)) continue;
+        double a = 0.0, n_index = 0.0, pl = 0.0, wl = 0.0;
+        int32_t have = 0;  // amplitude, index, path and wavelength of a slot are read once, at its first hit inside an image; -1: refused
+        for (int32_t m = 0; m < n_mon; ++m) {
+            double Px, Py, Pz, t;
+            if (!(g.valid && mon_hit(mons[m], g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, g.len, Px, Py, Pz, t))) continue;
+            const double* ax = img.axes + 6 * m;
+            const double* e = img.edges + (int64_t)m * (img.nby + img.nbz + 2);
+            const int32_t ky = mon_bin(e, img.nby, Px * ax[0] + Py * ax[1] + Pz * ax[2]);
+            const int32_t kz = mon_bin(e + img.nby + 1, img.nbz, Px * ax[3] + Py * ax[4] + Pz * ax[5]);
+            if (ky < 0 || kz < 0) continue;
+            if (!have) {
+                have = 1;
+                wl = fld.wavelength_uniform;
+                if (fld.wavelength) {
+                    const int32_t ray = *reinterpret_cast<const int32_t*>(src.ray + (s >> 6) * src.ray_stride + (s & 63) * 4);
+                    if (ray >= 0 && ray < fld.n_wavelengths) wl = fld.wavelength[ray];
+                    else have = -1;
+                }
+                if (!(wl > 0.0 && wl < HUGE_VAL)) have = -1;
+                if (have > 0) {
+                    const int64_t at = (s >> 6) * src.tile_stride + (s & 63) * 8;
+                    a = *reinterpret_cast<const double*>(img.intensity + at);
+                    if (fld.amplitude_mode == 0) a = sqrt(a);
+                    n_index = *reinterpret_cast<const double*>(fld.n_index + at);
+                    pl = *reinterpret_cast<const double*>(fld.pathlength + at);
+                }
+            }
+            if (have < 0) {
+                ++skipped;
+                continue;
+            }
+            const double L = t * n_index + pl;
+            const double x = L / wl;
+            const double f = x - floor(x);
+            double sn, cs;
+            sincospi(2.0 * f, &sn, &cs);
+            const int32_t bin = m * per_mon + ky * img.nbz + kz;
+            if (img.lds_bins) {
+                atomicAdd(&tally[bin], 1);
+                unsafeAtomicAdd(&re[bin], a * cs);
+                unsafeAtomicAdd(&im[bin], a * sn);
+            } else {
+                atomicAdd(&img.counts[bin], 1ull);
+                unsafeAtomicAdd(&fld.re[bin], a * cs);
+                unsafeAtomicAdd(&fld.im[bin], a * sn);
+            }
+        }
+    }
+    if (skipped) atomicAdd(fld.skipped, (unsigned long long)skipped);
+    __syncthreads();
+    for (int32_t b = threadIdx.x; b < img.lds_bins; b += MON_THREADS) {  // consecutive lanes, consecutive bins
+        const int32_t c = tally[b];
+        if (c) {
+            atomicAdd(&img.counts[b], (unsigned long long)c);
+            unsafeAtomicAdd(&fld.re[b], re[b]);
+            unsafeAtomicAdd(&fld.im[b], im[b]);
+        }
+    }
+}
 // count[m * gridDim.x + g] = hits of monitor m among workgroup g's slots; count[n_mon * gridDim.x] = 0, so that the scan's last
-// element is the total.  In image mode (img.counts set: one uniform branch at entry) `count` is not touched.
+// element is the total.  In image and field mode (img.counts set: one uniform branch at entry) `count` is not touched.
 __global__ __launch_bounds__(MON_THREADS) void k_mon_count(const ot_monitor* __restrict__ mons, int32_t n_mon, MonSource src, int64_t n, int32_t iters,
                                                            const int32_t* __restrict__ seg_count, int64_t n_rays, int32_t* __restrict__ count,
-                                                           MonImage img) {
+                                                           MonImage img, MonField fld) {
     __shared__ int32_t total[MON_MAX];
-    extern __shared__ double mon_image[];  // image mode through LDS: weights[lds_bins], then counts[lds_bins]
+    extern __shared__ double mon_image[];  // through LDS: weights[lds_bins], then counts[lds_bins]; field mode: re, im, then counts
     if (img.counts) {
-        mon_image_pass(mons, n_mon, src, n, iters, seg_count, n_rays, img, mon_image, reinterpret_cast<int32_t*>(mon_image + img.lds_bins));
+        if (fld.re)
+            mon_field_pass(mons, n_mon, src, n, iters, seg_count, n_rays, img, fld, mon_image, mon_image + img.lds_bins,
+                           reinterpret_cast<int32_t*>(mon_image + 2 * img.lds_bins));
+        else
+            mon_image_pass(mons, n_mon, src, n, iters, seg_count, n_rays, img, mon_image, reinterpret_cast<int32_t*>(mon_image + img.lds_bins));
         return;
     }
     const int lane = threadIdx.x & 63;

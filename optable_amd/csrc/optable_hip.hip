@@ -1726,7 +1726,7 @@ int ot_monitor_record_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors
     for (int32_t m0 = 0; m0 < n_monitors; m0 += MON_MAX) {
         const int32_t nm = std::min<int32_t>(MON_MAX, n_monitors - m0);
         hipLaunchKernelGGL(k_mon_count, dim3((unsigned)grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, iters, seg_count, n_rays, count,
-                           MonImage{});
+                           MonImage{}, MonField{});
         exclusive_scan<int32_t, int64_t>(c->scan_tmp.p, count, off, nm * grid + 1, c->stream);
         hipLaunchKernelGGL(k_mon_emit, dim3((unsigned)grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, iters, seg_count, n_rays, off,
                            capacity, first + m0, hit_index, (double*)Px, (double*)Py, (double*)Pz, (double*)t, n_total);
@@ -1735,27 +1735,29 @@ int ot_monitor_record_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors
     return 0;
 }
 
-// How ot_monitor_image_many walks n_monitors monitors of nby x nbz bins: `passes` launches of at most `per_pass` monitors each,
-// as even as they come (8 monitors of 30 x 30: 4 + 4, not 6 + 2), through LDS when a pass's bins fit MON_IMG_LDS_BINS, else
-// (one monitor alone does not fit) MON_MAX at a time straight to global memory.  optable_amd/engine.py image_plan says the same.
+// How ot_monitor_image_many / ot_monitor_field_many walk n_monitors monitors of nby x nbz bins: `passes` launches of at most
+// `per_pass` monitors each, as even as they come (8 monitors of 30 x 30: 4 + 4, not 6 + 2), through LDS when a pass's bins fit
+// `budget` (MON_IMG_LDS_BINS; MON_FIELD_LDS_BINS for a field: 8 monitors go 3 + 3 + 2), else (one monitor alone does not fit)
+// MON_MAX at a time straight to global memory.  optable_amd/engine.py image_plan / field_plan say the same.
 struct ImagePlan {
     int32_t per_pass, passes;
     bool lds;
 };
-static ImagePlan image_plan(int32_t n_monitors, int32_t nby, int32_t nbz) {
+static ImagePlan image_plan(int32_t n_monitors, int32_t nby, int32_t nbz, int32_t budget) {
     const int64_t bins = (int64_t)nby * nbz;
     ImagePlan p;
-    p.lds = bins <= MON_IMG_LDS_BINS;
-    const int32_t most = p.lds ? (int32_t)std::min<int64_t>(MON_MAX, MON_IMG_LDS_BINS / bins) : MON_MAX;
+    p.lds = bins <= budget;
+    const int32_t most = p.lds ? (int32_t)std::min<int64_t>(MON_MAX, budget / bins) : MON_MAX;
     p.passes = (n_monitors + most - 1) / most;
     p.per_pass = (n_monitors + p.passes - 1) / p.passes;
     return p;
 }
 
-int ot_monitor_image_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, int32_t nby,
-                          int32_t nbz, const ot_segment_source* src, const void* intensity, int64_t n, const int32_t* seg_count,
-                          int64_t n_rays, int64_t* counts, double* weights, int32_t accumulate) {
-    if (!c || !mons || !axes || !edges || !src || !counts || !weights) return fail(OT_ERR_INVALID, "NULL argument");
+// What the two calls refuse alike (their own outputs apart), before anything is launched or zeroed.
+static int check_image_call(const ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, int32_t nby,
+                            int32_t nbz, const ot_segment_source* src, const void* intensity, int64_t n, const int32_t* seg_count,
+                            int64_t n_rays, int32_t accumulate) {
+    if (!c || !mons || !axes || !edges || !src) return fail(OT_ERR_INVALID, "NULL argument");
     if (n_monitors < 1) return fail(OT_ERR_INVALID, "n_monitors must be at least 1");
     if (nby < 1 || nbz < 1) return fail(OT_ERR_INVALID, "nby and nbz must be at least 1");
     if ((int64_t)nby * nbz > MON_IMG_MAX_BINS) return fail(OT_ERR_INVALID, "nby * nbz exceeds 2^24 bins per monitor");
@@ -1779,14 +1781,16 @@ int ot_monitor_image_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors,
         for (int k = 0; k < 6; ++k)
             if (!std::isfinite(axes[6 * (int64_t)m + k])) return fail(OT_ERR_INVALID, "axes must be finite");
     }
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t bins = (size_t)nby * nbz;
-    if (!accumulate) {
-        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * bins * n_monitors, c->stream));
-        HIP_TRY(hipMemsetAsync(weights, 0, sizeof(double) * bins * n_monitors, c->stream));
-    }
-    if (n == 0) return 0;
-    const ImagePlan plan = image_plan(n_monitors, nby, nbz);
+    return 0;
+}
+
+// The launches of a checked call whose outputs are zeroed or kept: the monitors, edges and axes to the device, then k_mon_count in
+// image mode (fld.re NULL, 12 bytes of LDS a bin) or field mode (20) once per pass of the plan.  img.counts / img.weights and
+// fld.re / fld.im come in as the images of monitor 0 and go to the kernel as those of the pass's first monitor.
+static int image_passes(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, const ot_segment_source* src,
+                        int64_t n, const int32_t* seg_count, int64_t n_rays, const ImagePlan& plan, MonImage img, MonField fld) {
+    const int32_t n_edges = img.nby + img.nbz + 2;
+    const size_t bins = (size_t)img.nby * img.nbz, bytes_a_bin = fld.re ? 20 : 12;
     // the partition of k_mon_count, with workgroups long enough to be worth an image of their own: a thousand of them at most
     // (two rounds of the chip at two a CU), each of which zeroes and flushes its LDS image once
     const int32_t iters = (int32_t)std::max<int64_t>(8, (n + 1024 * MON_THREADS - 1) / (1024 * MON_THREADS));
@@ -1809,16 +1813,73 @@ int ot_monitor_image_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors,
     ms.tile_stride = src->tile_stride, ms.ray_stride = src->ray_stride, ms.width = src->width;
     for (int32_t m0 = 0; m0 < n_monitors; m0 += plan.per_pass) {
         const int32_t nm = std::min<int32_t>(plan.per_pass, n_monitors - m0);
-        MonImage img;
-        img.counts = (unsigned long long*)counts + m0 * bins, img.weights = weights + m0 * bins;
-        img.edges = d_edges + (int64_t)m0 * n_edges, img.axes = d_axes + (int64_t)m0 * 6;
-        img.intensity = (const uint8_t*)intensity;
-        img.nby = nby, img.nbz = nbz, img.lds_bins = plan.lds ? (int32_t)(nm * bins) : 0;
-        hipLaunchKernelGGL(k_mon_count, dim3((unsigned)grid), dim3(MON_THREADS), (size_t)img.lds_bins * 12, c->stream, table + m0, nm, ms, n, iters,
-                           seg_count, n_rays, (int32_t*)nullptr, img);
+        MonImage pass = img;
+        MonField pass_field = fld;
+        pass.counts += m0 * bins;
+        if (fld.re) pass_field.re += m0 * bins, pass_field.im += m0 * bins;
+        else pass.weights += m0 * bins;
+        pass.edges = d_edges + (int64_t)m0 * n_edges, pass.axes = d_axes + (int64_t)m0 * 6;
+        pass.lds_bins = plan.lds ? (int32_t)(nm * bins) : 0;
+        hipLaunchKernelGGL(k_mon_count, dim3((unsigned)grid), dim3(MON_THREADS), (size_t)pass.lds_bins * bytes_a_bin, c->stream, table + m0, nm, ms, n,
+                           iters, seg_count, n_rays, (int32_t*)nullptr, pass, pass_field);
     }
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int ot_monitor_image_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, int32_t nby,
+                          int32_t nbz, const ot_segment_source* src, const void* intensity, int64_t n, const int32_t* seg_count,
+                          int64_t n_rays, int64_t* counts, double* weights, int32_t accumulate) {
+    if (!counts || !weights) return fail(OT_ERR_INVALID, "NULL argument");
+    const int rc = check_image_call(c, mons, n_monitors, axes, edges, nby, nbz, src, intensity, n, seg_count, n_rays, accumulate);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bins = (size_t)nby * nbz;
+    if (!accumulate) {
+        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * bins * n_monitors, c->stream));
+        HIP_TRY(hipMemsetAsync(weights, 0, sizeof(double) * bins * n_monitors, c->stream));
+    }
+    if (n == 0) return 0;
+    MonImage img{};
+    img.counts = (unsigned long long*)counts, img.weights = weights;
+    img.intensity = (const uint8_t*)intensity;
+    img.nby = nby, img.nbz = nbz;
+    return image_passes(c, mons, n_monitors, axes, edges, src, n, seg_count, n_rays, image_plan(n_monitors, nby, nbz, MON_IMG_LDS_BINS), img, MonField{});
+}
+
+int ot_monitor_field_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, int32_t nby,
+                          int32_t nbz, const ot_segment_source* src, const void* intensity, const void* n_index, const void* pathlength,
+                          const double* wavelength, int64_t n_wavelengths, double wavelength_uniform, int32_t amplitude_mode, int64_t n,
+                          const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* re, double* im, int64_t* skipped,
+                          int32_t accumulate) {
+    if (!counts || !re || !im || !skipped) return fail(OT_ERR_INVALID, "NULL argument");
+    const int rc = check_image_call(c, mons, n_monitors, axes, edges, nby, nbz, src, intensity, n, seg_count, n_rays, accumulate);
+    if (rc) return rc;
+    if (src->width != 8) return fail(OT_ERR_INVALID, "a field needs double-precision segments: width must be 8");
+    if (!n_index || !pathlength) return fail(OT_ERR_INVALID, "NULL n_index or pathlength");
+    if (wavelength && (n_wavelengths < 1 || n_wavelengths >= (int64_t)1 << 31)) return fail(OT_ERR_INVALID, "n_wavelengths must be at least 1 (and below 2^31)");
+    if (!wavelength && !(std::isfinite(wavelength_uniform) && wavelength_uniform > 0.0))
+        return fail(OT_ERR_INVALID, "wavelength_uniform must be finite and > 0 when there is no wavelength array");
+    if (amplitude_mode != 0 && amplitude_mode != 1) return fail(OT_ERR_INVALID, "amplitude_mode must be 0 (sqrt) or 1 (linear)");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bins = (size_t)nby * nbz;
+    if (!accumulate) {
+        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * bins * n_monitors, c->stream));
+        HIP_TRY(hipMemsetAsync(re, 0, sizeof(double) * bins * n_monitors, c->stream));
+        HIP_TRY(hipMemsetAsync(im, 0, sizeof(double) * bins * n_monitors, c->stream));
+        HIP_TRY(hipMemsetAsync(skipped, 0, sizeof(int64_t), c->stream));
+    }
+    if (n == 0) return 0;
+    MonImage img{};
+    img.counts = (unsigned long long*)counts;
+    img.intensity = (const uint8_t*)intensity;
+    img.nby = nby, img.nbz = nbz;
+    MonField fld{};
+    fld.re = re, fld.im = im;
+    fld.n_index = (const uint8_t*)n_index, fld.pathlength = (const uint8_t*)pathlength;
+    fld.wavelength = wavelength, fld.n_wavelengths = (int32_t)n_wavelengths, fld.wavelength_uniform = wavelength_uniform;
+    fld.skipped = (unsigned long long*)skipped, fld.amplitude_mode = amplitude_mode;
+    return image_passes(c, mons, n_monitors, axes, edges, src, n, seg_count, n_rays, image_plan(n_monitors, nby, nbz, MON_FIELD_LDS_BINS), img, fld);
 }
 
 int ot_debug_last_launch(ot_ctx* c, int32_t info[8]) {

@@ -119,17 +119,25 @@ IMAGE_MAX_BINS = 1 << 24                 # MON_IMG_MAX_BINS: nby * nbz of one mo
 IMAGE_MAX_MONITORS = 32                  # MON_MAX: monitors of one launch
 
 
-def image_plan(n_monitors, nby, nbz):
+FIELD_LDS_BINS = (65536 - 32 * 4) // 20  # MON_FIELD_LDS_BINS: the same LDS at 20 bytes a bin (re, im, count) — ot_monitor_field_many
+
+
+def image_plan(n_monitors, nby, nbz, budget=IMAGE_LDS_BINS):
     """How ot_monitor_image_many bins `n_monitors` monitors of nby x nbz bins (optable_hip.hip image_plan, the same rule):
-    {"path": "lds" when the images of a launch fit a workgroup's LDS, "global" when one monitor's alone does not and every hit
-    is a global atomic; "per_pass": monitors of a launch, as even as the most that fit allows; "passes": launches}."""
+    {"path": "lds" when the images of a launch fit a workgroup's LDS (`budget` bins), "global" when one monitor's alone does not
+    and every hit is a global atomic; "per_pass": monitors of a launch, as even as the most that fit allows; "passes": launches}."""
     n_monitors, bins = int(n_monitors), int(nby) * int(nbz)
     if n_monitors < 1 or nby < 1 or nbz < 1 or bins > IMAGE_MAX_BINS:
         raise ValueError(f"no image of {n_monitors} monitors x {nby} x {nbz} bins")
-    lds = bins <= IMAGE_LDS_BINS
-    most = min(IMAGE_MAX_MONITORS, IMAGE_LDS_BINS // bins) if lds else IMAGE_MAX_MONITORS
+    lds = bins <= budget
+    most = min(IMAGE_MAX_MONITORS, budget // bins) if lds else IMAGE_MAX_MONITORS
     passes = -(-n_monitors // most)
     return {"path": "lds" if lds else "global", "per_pass": -(-n_monitors // passes), "passes": passes}
+
+
+def field_plan(n_monitors, nby, nbz):
+    """`image_plan` for ot_monitor_field_many: the same rule with FIELD_LDS_BINS (three monitors of 30 x 30 a launch)."""
+    return image_plan(n_monitors, nby, nbz, FIELD_LDS_BINS)
 
 
 # What a whole-trace launch writes, by library call: (the SegmentBatch made when the caller passes none, what makes a passed
@@ -770,6 +778,52 @@ class Engine:
                                                  None if count is None else count.data_ptr(), n_rays, counts.data_ptr(), weights.data_ptr(),
                                                  0 if into is None else 1), self.lib)
         return counts, weights
+
+    def monitor_field_many(self, monitor_structs, axes, edges, bins, segs: SegmentBatch, wavelength, amplitude_mode=0, into=None):
+        """Coherent detector images of a list of monitors over a double-precision SegmentBatch read as it lies
+        (ot_monitor_field_many: `monitor_image_many` with the phasor a exp(i phi) of every hit in place of its intensity).  axes,
+        edges, bins as there.  wavelength: a float for all rays, or a float64 device tensor indexed by the segments' `ray`;
+        amplitude_mode: 0 = sqrt(intensity), 1 = intensity.  Returns (counts, re, im, skipped): int64 / float64 / float64
+        [M, nby, nbz] device tensors and an int64 device tensor of one element (hits left out because their ray or wavelength
+        was unusable), zeroed by the call — or `into`, such a tuple from an earlier call, with this call's hits added to it."""
+        with self.lock:
+            return self._monitor_field_many(list(monitor_structs), axes, edges, bins, segs, wavelength, amplitude_mode, into)
+
+    def _monitor_field_many(self, mons, axes, edges, bins, segs, wavelength, amplitude_mode, into):
+        dev, M, (nby, nbz) = segs.device, len(mons), bins
+        axes, edges = np.ascontiguousarray(axes, dtype=np.float64), np.ascontiguousarray(edges, dtype=np.float64)
+        if axes.shape != (M, 6) or edges.shape != (M, nby + nbz + 2):
+            raise ValueError(f"axes must be [{M}, 6] and edges [{M}, {nby + nbz + 2}]")
+        if segs.precision != "f64":
+            raise ValueError("a field needs double-precision segments")
+        if torch.is_tensor(wavelength):
+            if wavelength.dtype != torch.float64 or wavelength.dim() != 1 or not wavelength.is_contiguous() or wavelength.device.type != dev.type:
+                raise ValueError(f"wavelength: a float or a contiguous float64 vector on {dev}")
+            table_ptr, n_table, uniform = (wavelength.data_ptr() if wavelength.numel() else None), int(wavelength.numel()), 0.0
+        else:
+            table_ptr, n_table, uniform = None, 0, float(wavelength)
+        if into is None:
+            counts = torch.empty((M, nby, nbz), dtype=torch.int64, device=dev)  # (the call zeroes them)
+            re, im = (torch.empty((M, nby, nbz), dtype=torch.float64, device=dev) for _ in range(2))
+            skipped = torch.empty(1, dtype=torch.int64, device=dev)
+        else:
+            counts, re, im, skipped = into
+            for t, dt in ((counts, torch.int64), (re, torch.float64), (im, torch.float64)):
+                if tuple(t.shape) != (M, nby, nbz) or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type:
+                    raise ValueError(f"into: contiguous int64 counts and float64 re, im of shape [{M}, {nby}, {nbz}] on {dev}")
+            if tuple(skipped.shape) != (1,) or skipped.dtype != torch.int64 or skipped.device.type != dev.type:
+                raise ValueError(f"into: skipped is one int64 on {dev}")
+        src, n_segments, count, n_rays = segment_source(segs)
+        if M == 0 or n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
+            return (counts.zero_(), re.zero_(), im.zero_(), skipped.zero_()) if into is None else (counts, re, im, skipped)
+        table = (abi.OtMonitor * M)(*mons)
+        as_doubles = C.POINTER(C.c_double)
+        abi.check(self.lib.ot_monitor_field_many(self._ctx, table, M, axes.ctypes.data_as(as_doubles), edges.ctypes.data_as(as_doubles), nby, nbz,
+                                                 C.byref(src), segs.field("intensity").data_ptr(), segs.field("n").data_ptr(),
+                                                 segs.field("pathlength").data_ptr(), table_ptr, n_table, uniform, int(amplitude_mode), n_segments,
+                                                 None if count is None else count.data_ptr(), n_rays, counts.data_ptr(), re.data_ptr(),
+                                                 im.data_ptr(), skipped.data_ptr(), 0 if into is None else 1), self.lib)
+        return counts, re, im, skipped
 
     # -- measurement ---------------------------------------------------------------------------
     def timing(self, enabled=True):

@@ -236,6 +236,23 @@ class MonitorHits:
     def ray_index(self, sort="YZ"):
         return self.ray[self._order(sort)]
 
+    def pathlengthList(self, sort="YZ"):
+        """The optical path length of every hit, `Ray.pathlength(t)` of its segment: pathlength[slot] + t * n[slot]."""
+        order = self._order(sort)
+        s = self.slot[order]
+        return self._gather(self.segs.pathlength, s) + self.t[order] * self._gather(self.segs.n_index, s)
+
+    def phaseList(self, wavelength, sort="YZ"):
+        """The phase of every hit in [0, 2 pi), `Ray.phase(t)` of its segment: 2 pi (x - floor x) with x = pathlengthList / wavelength
+        cycles.  `wavelength`: a float for all rays, or the `RayBatch` that was traced (its wavelengths, as double, by the hits'
+        `ray_index`).  What `OpticalTable.field_all` sums per bin, as a list."""
+        import torch
+
+        if hasattr(wavelength, "wavelength"):
+            wavelength = wavelength.wavelength.double()[self.ray_index(sort)]
+        x = self.pathlengthList(sort).double() / wavelength
+        return 2 * np.pi * (x - torch.floor(x))
+
     def directionList(self, sort="YZ"):
         import torch
 
@@ -296,3 +313,33 @@ class MonitorImage:
     def to_host(self):
         """(counts, intensity, y_edges, z_edges) as numpy arrays."""
         return self.counts.cpu().numpy(), self.intensity.cpu().numpy(), self.y_edges, self.z_edges
+
+
+class MonitorField:
+    """A monitor's hits as a coherent image, summed on the device (`OpticalTable.field_all`): `counts` (int64) and `re`, `im`
+    (float64), [nby, nbz] device tensors over `y_edges` x `z_edges` (numpy) — per bin the number of hits and the sum of their
+    phasors a exp(i phi), a = sqrt(IList) (or IList: amplitude="linear"), phi = `MonitorHits.phaseList`.  Counts are exact and the
+    same every run; re and im are atomic fp64 sums whose last bits depend on the order of arrival."""
+
+    def __init__(self, monitor, counts, re, im, y_edges, z_edges, stack=None):
+        self.monitor, self.counts, self.re, self.im, self.y_edges, self.z_edges = monitor, counts, re, im, y_edges, z_edges
+        self._stack = stack  # (counts, re, im, skipped, position) of the call's [M, nby, nbz] tensors, which `into=` adds to
+
+    @property
+    def bins(self):
+        return tuple(self.counts.shape)
+
+    @property
+    def field(self):
+        """re + i im, a complex128 tensor."""
+        import torch
+
+        return torch.complex(self.re, self.im)
+
+    def intensity(self):
+        """|field|^2 = re^2 + im^2: what a detector reads."""
+        return self.re**2 + self.im**2
+
+    def to_host(self):
+        """(counts, re, im, y_edges, z_edges) as numpy arrays."""
+        return self.counts.cpu().numpy(), self.re.cpu().numpy(), self.im.cpu().numpy(), self.y_edges, self.z_edges

@@ -270,6 +270,67 @@ class OpticalTable:
         """One monitor as an image (`image_all` for it alone): a `MonitorImage`."""
         return self.image_all(segs, bins=bins, monitors=[monitor])[0]
 
+    def field_all(self, segs, wavelength=0.0, bins=30, monitors=None, into=None, amplitude="sqrt"):
+        """Every monitor of the table (or those given) as a COHERENT image: one `MonitorField` per monitor, in their order — per
+        bin of `image_all`'s images the count of hits and the complex sum of a exp(i phi) over them, summed on the device in the
+        pass that finds the hits, with no hit list (ot_monitor_field_many).  phi is `Ray.phase(t)` at the monitor,
+        2 pi frac((pathlength + t n) / wavelength), and a = sqrt(intensity) (amplitude="sqrt": intensity is a power) or the
+        intensity as it stands (amplitude="linear": scenes built on amplitude-style splitting ratios).  It is the model's phase and
+        nothing more: no pi on reflection, no Gaussian envelope.  `MonitorField.intensity()` is what an optical table shows.
+        `wavelength`: one float for all rays, or the `RayBatch` that was traced (its wavelengths by the segments' `ray`; children
+        of a ray tree inherit theirs).  `segs` must be double precision: single-precision path lengths carry some 0.02 cycle of
+        phase noise at table scale.  `into`: as for `image_all`."""
+        import torch
+        from .batch import RayBatch
+        from .monitors import MonitorField, image_bins, image_edges
+
+        nby, nbz = image_bins(bins)
+        if amplitude not in ("sqrt", "linear"):
+            raise ValueError(f"amplitude must be 'sqrt' or 'linear', not {amplitude!r}")
+        if segs.precision != "f64":
+            raise ValueError("field_all needs a double-precision SegmentBatch: a field from single-precision path lengths is refused, not approximated")
+        if isinstance(wavelength, RayBatch):
+            if segs.n_rays is not None and wavelength.n != int(segs.n_rays):
+                raise ValueError(f"wavelength: a RayBatch of {wavelength.n} rays for segments of {int(segs.n_rays)}")
+            wavelength = wavelength.wavelength.double().contiguous()
+            if not bool(((wavelength > 0) & torch.isfinite(wavelength)).all()):
+                raise ValueError("wavelength: every ray of the batch needs a finite wavelength > 0")
+        else:
+            try:
+                value = float(wavelength)
+            except (TypeError, ValueError):
+                raise ValueError(f"wavelength must be a float or the RayBatch that was traced, not {wavelength!r}") from None
+            if not (np.isfinite(value) and value > 0):
+                raise ValueError(f"wavelength={wavelength!r}: a field needs a finite wavelength > 0 (pass it, or the RayBatch that was traced)")
+            wavelength = value
+        monitors = list(self.monitors if monitors is None else monitors)
+        edges = [image_edges(m, nby, nbz) for m in monitors]
+        stack = None
+        if into is not None:
+            into = list(into)
+            if len(into) != len(monitors) or any(f.monitor is not m or f.bins != (nby, nbz) for f, m in zip(into, monitors)):
+                raise ValueError("into: the list an earlier field_all returned for the same monitors and bins")
+            if any(f._stack is None or f._stack[0] is not into[0]._stack[0] or f._stack[4] != k or len(f._stack[0]) != len(into) for k, f in enumerate(into)):
+                raise ValueError("into: the whole list of one earlier call, in its order")
+            if not monitors:
+                return into
+            stack = into[0]._stack[:4]
+        axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in monitors], dtype=float).reshape(len(monitors), 6)
+        table = np.array([np.concatenate(e) for e in edges], dtype=float).reshape(len(monitors), nby + nbz + 2)
+        counts, re, im, skipped = _engine().monitor_field_many([monitor_struct(m) for m in monitors], axes, table, (nby, nbz), segs, wavelength,
+                                                               amplitude_mode=("sqrt", "linear").index(amplitude), into=stack)
+        left_out = int(skipped.item())
+        if left_out:
+            raise ValueError(f"field_all: {left_out} hits left out — their `ray` is no index into the wavelengths given, or its wavelength "
+                             "is not finite and > 0")
+        if into is not None:
+            return into
+        return [MonitorField(m, counts[k], re[k], im[k], ey, ez, stack=(counts, re, im, skipped, k)) for k, (m, (ey, ez)) in enumerate(zip(monitors, edges))]
+
+    def field_batch(self, monitor, segs, wavelength=0.0, bins=30, amplitude="sqrt"):
+        """One monitor as a coherent image (`field_all` for it alone): a `MonitorField`."""
+        return self.field_all(segs, wavelength, bins=bins, monitors=[monitor], amplitude=amplitude)[0]
+
     # -- ABCD extraction (optical_table.py:211-297), a caller of the hot path ----------------------
     def calculate_abcd_matrix(self, mon0, mon1, rays, disp=1e-5, rot=1e-5, debugaxs=None):
         """Per-ray 2x2 ABCD matrix between two monitors by finite differences: three traces
