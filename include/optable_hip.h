@@ -571,6 +571,34 @@ int ot_monitor_field_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitor
                           int32_t amplitude_mode, int64_t n_segments, const int32_t* seg_count, int64_t n_rays, int64_t* counts,
                           double* re, double* im, int64_t* skipped, int32_t accumulate);
 
+/* Gaussian-beam detector images: ot_monitor_image_many with every hit spread over its Gaussian spot — per monitor a count image
+ * and the power every bin receives, from the same launches of the count kernel (a fourth mode of it), the same test and, for the
+ * count, the same bin rule; mons, axes, edges, nby, nbz, src, n_segments, seg_count, n_rays and accumulate as there.
+ * A hit of slot s at the distance t, at y0 = P . a_y, z0 = P . a_z: q = q_re[s] + t + i q_im[s] (GaussianBeam.q_at_z),
+ * w^2 = wavelength (qr^2 + qi^2) / (n[s] pi qi) (Ray.spot_size(t)), and bin (ky, kz) gets intensity[s] Fy(ky) Fz(kz) with
+ * Fy(k) = (erf(sqrt2 (ey[k + 1] - y0) / w) - erf(sqrt2 (ey[k] - y0) / w)) / 2 and Fz likewise: the integral over the bin of
+ * I 2 / (pi w^2) exp(-2 r^2 / w^2).  The beam is taken at normal incidence in the monitor's (y, z): a tilted beam's spot is not
+ * stretched.  Bins whose nearer edge lies more than 5 w from the centre along an axis are left out (a share below 1.5e-23).  All
+ * in double precision, whatever the segments' (spot sizes are not phase-sensitive: width 4 is accepted and widened exactly).
+ * The centre is counted in counts where ot_monitor_image_many counts the hit; a centre outside the edges is counted nowhere and
+ * its tails are still deposited.
+ * intensity, q_re, q_im, n_index: device planes of the segments, addressed like src->base[f], in the source's precision.  The
+ * wavelength of a hit as for ot_monitor_field_many.  A hit whose ray lies outside [0, n_wavelengths), or whose wavelength, n, qi
+ * or w is not finite and > 0 (a ray without q has q = 0), adds nothing anywhere and one to *skipped (device); nothing is read
+ * out of range.
+ * counts, power: device, [n_monitors][nby][nbz] int64 / double; skipped: device, one int64.  accumulate = 0 zeroes all three first,
+ * 1 adds to what is there.  Counts are exact and the same every run; power is fp64 atomic sums, whose last bits depend on the
+ * order of arrival.
+ * Paths: as for ot_monitor_image_many at 12 bytes of LDS a bin next to 4 KB of per-wave erf tables (5,109 bins: five monitors of
+ * 30 x 30 a group); an image that does not fit alone goes to global atomics bin by bin.
+ * OT_ERR_INVALID, nothing launched or zeroed: everything ot_monitor_image_many refuses; a NULL q_re, q_im, n_index, counts, power
+ * or skipped; wavelength = NULL with wavelength_uniform not finite or not > 0; a wavelength array with n_wavelengths < 1. */
+int ot_monitor_beam_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges,
+                         int32_t nby, int32_t nbz, const ot_segment_source* src, const void* intensity, const void* q_re,
+                         const void* q_im, const void* n_index, const double* wavelength, int64_t n_wavelengths,
+                         double wavelength_uniform, int64_t n_segments, const int32_t* seg_count, int64_t n_rays, int64_t* counts,
+                         double* power, int64_t* skipped, int32_t accumulate);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled every trace launch is bracketed by hipEvents on the ctx stream. */
 int ot_timing_enable(ot_ctx* ctx, int enabled);

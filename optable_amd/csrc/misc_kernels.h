@@ -430,15 +430,181 @@ __device__ __forceinline__ void mon_field_pass(const ot_monitor* __restrict__ mo
         }
     }
 }
+// The beam mode of k_mon_count (ot_monitor_beam_many): the image mode's partition, loads, tests and bin rule for the count, with
+// the hit's power spread over its Gaussian spot.  All zero for the three other modes.  A hit of slot s at the distance t and the
+// image coordinates (y0, z0) carries q = q_re[s] + t + i q_im[s] (GaussianBeam.q_at_z) and the spot size
+//   w^2 = wavelength (qr^2 + qi^2) / (n[s] pi qi)            (Ray.spot_size(t), written without the reciprocal)
+// and bin (ky, kz) gets intensity[s] Fy(ky) Fz(kz), Fy(k) = (erf(sqrt2 (ey[k + 1] - y0) / w) - erf(sqrt2 (ey[k] - y0) / w)) / 2: the
+// integral over the bin of I 2 / (pi w^2) exp(-2 r^2 / w^2), the beam taken at normal incidence.  Bins whose nearer edge lies
+// more than 5 w from the centre along an axis are left out (a share below erfc(5 sqrt2) = 1.5e-23).  All in double precision;
+// intensity, q_re, q_im and n are addressed like the fields of MonSource, in its precision; the wavelength as in the field mode.
+// A hit whose wavelength, n or qi is not finite and > 0, whose ray is no index into the wavelengths or whose w is not finite
+// and > 0 adds nothing and is counted in *skipped.
+// One hit has a footprint of 1 to nby * nbz bins, so the deposit is the wave's work, not the lane's: every lane finds its own
+// slot's hit, counts its centre and steps out its footprint (64 searches side by side), then the wave takes the hits with a
+// footprint one at a time (the lowest set bit of their ballot; y0, z0, w, I and the footprint come through v_readlane, as
+// scalars), its lanes evaluate erf at the footprint's edges — 63 x 63 bins at a time: 64 + 64 edges, one erf a lane or two — into
+// the wave's strip of LDS, and then stride over the footprint's bins with one atomic add each.  fy + fz + 2 erfs a hit instead of
+// fy * fz and no private array.  Registers: the pass reads q, n, the wavelength and the intensity at every hit instead of keeping
+// them from one monitor of a slot to the next, and erf is a call (mon_beam_erf) — k_mon_count stays within 128 registers.
+// Wave-synchronous throughout: the strip is the wave's own, its LDS operations retire in order, and the wavefront fences keep
+// the compiler from moving a read across a write.  No barrier inside the visit loop.
+// Through LDS: MON_WAVES strips of MON_BEAM_STRIP doubles, then power[lds_bins] (double), then tally[lds_bins] (int32): 12 bytes
+// a bin next to 4 KB of strips (the strips are there on the global path too).
+static constexpr int MON_BEAM_STRIP = 128, MON_BEAM_CHUNK = 63;  // erf at the 64 + 64 edges of 63 x 63 bins
+static constexpr int MON_BEAM_LDS_BINS = (65536 - MON_MAX * 4 - MON_WAVES * MON_BEAM_STRIP * 8) / 12;  // 5109: five monitors of 30 x 30
+struct MonBeam {
+    double* power;  // [n_mon][nby][nbz], of the launch's first monitor on; NULL: no beam mode
+    const uint8_t *q_re, *q_im, *n_index;
+    const double* wavelength;  // [n_wavelengths], or NULL: wavelength_uniform for every ray
+    unsigned long long* skipped;
+    double wavelength_uniform;
+    int32_t n_wavelengths;
+};
+// lane `from`'s v in every lane (from is wave-uniform): a scalar
+__device__ __forceinline__ double mon_lane_value(double v, int from) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), from), __builtin_amdgcn_readlane(__double2loint(v), from));
+}
+// The footprint of [lo, hi] among the bins of e[0 .. nb]: the first bin whose upper edge is >= lo (nb: none) and the last whose
+// lower edge is <= hi (-1: none).  As in mon_bin the guess comes from the range and the answer from the table.
+__device__ __forceinline__ int32_t mon_beam_guess(const double* __restrict__ e, int32_t nb, double v) {
+    const float g = (float)(v - e[0]) * (float)nb / (float)(e[nb] - e[0]);  // (single precision will do: the table decides)
+    return (int32_t)fminf(fmaxf(g, 0.0f), (float)(nb - 1));                 // (a NaN guess starts at 0)
+}
+__device__ __forceinline__ int32_t mon_beam_first(const double* __restrict__ e, int32_t nb, double lo) {
+    int32_t k = mon_beam_guess(e, nb, lo);
+    while (k > 0 && e[k] >= lo) --k;
+    while (k < nb && e[k + 1] < lo) ++k;
+    return k;
+}
+__device__ __forceinline__ int32_t mon_beam_last(const double* __restrict__ e, int32_t nb, double hi) {
+    int32_t k = mon_beam_guess(e, nb, hi);
+    while (k >= 0 && e[k] > hi) --k;
+    while (k < nb - 1 && e[k + 1] <= hi) ++k;
+    return k;
+}
+// erf as a call, not inlined: inlined, the coefficients of its polynomials are hoisted out of every loop of the pass and sit in 42
+// vector registers from its first instruction to its last (157 registers, or 128 and scratch)
+__device__ __noinline__ double mon_beam_erf(double x) { return erf(x); }
+// One hit, by its whole wave: centre (y0, z0), spot size w, power I and the footprint ky0 .. ky1 x kz0 .. kz1 are wave-uniform; the
+// monitor's nby x nbz bins of power are `in_lds` or, when that is NULL, `in_global`.
+__device__ __forceinline__ void mon_beam_deposit(const double* __restrict__ ey, const double* __restrict__ ez, int32_t nbz, double y0, double z0, double w,
+                                                 double I, int32_t ky0, int32_t ky1, int32_t kz0, int32_t kz1, double* strip, int lane, double* in_lds,
+                                                 double* in_global) {
+    for (int32_t by = ky0; by <= ky1; by += MON_BEAM_CHUNK) {
+        const int32_t ny = min(MON_BEAM_CHUNK, ky1 - by + 1);
+        for (int32_t bz = kz0; bz <= kz1; bz += MON_BEAM_CHUNK) {
+            const int32_t nz = min(MON_BEAM_CHUNK, kz1 - bz + 1);
+            // strip[0 .. ny] = erf at the y edges by .. by + ny, strip[ny + 1 .. ny + nz + 1] = at the z edges bz .. bz + nz
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            for (int32_t j = lane; j < ny + nz + 2; j += 64) {
+                const double d = j <= ny ? ey[by + j] - y0 : ez[bz + j - ny - 1] - z0;
+                strip[j] = mon_beam_erf(M_SQRT2 * d / w);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            for (int32_t b = lane; b < ny * nz; b += 64) {
+                const int32_t iy = b / nz, iz = b - iy * nz;
+                const double fy = 0.5 * (strip[iy + 1] - strip[iy]), fz = 0.5 * (strip[ny + iz + 2] - strip[ny + iz + 1]);
+                const double share = I * fy * fz;
+                if (share == 0.0) continue;
+                if (in_lds) unsafeAtomicAdd(&in_lds[(by + iy) * nbz + bz + iz], share);
+                else unsafeAtomicAdd(&in_global[(by + iy) * nbz + bz + iz], share);
+            }
+        }
+    }
+}
+__device__ __forceinline__ void mon_beam_pass(const ot_monitor* __restrict__ mons, int32_t n_mon, const MonSource& src, int64_t n, int32_t iters,
+                                              const int32_t* __restrict__ seg_count, int64_t n_rays, const MonImage& img, const MonBeam& beam,
+                                              double* strips, double* power, int32_t* tally) {
+    for (int32_t b = threadIdx.x; b < img.lds_bins; b += MON_THREADS) power[b] = 0.0, tally[b] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    double* strip = strips + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * MON_BEAM_STRIP;
+    const int32_t per_mon = img.nby * img.nbz;
+    const int64_t first = (int64_t)blockIdx.x * iters * MON_THREADS;
+    int32_t skipped = 0;
+    for (int32_t it = 0; it < iters && first + (int64_t)it * MON_THREADS < n; ++it) {
+        const int64_t s = first + (int64_t)it * MON_THREADS + threadIdx.x;
+        const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
+        if (!__ballot(g.valid)) continue;
+        // the 64 slots of a wave are one tile: its place is a scalar, and the lane's within it one 32-bit offset for every plane
+        const int64_t tile = __builtin_amdgcn_readfirstlane((int32_t)(s >> 6));
+        const int64_t at_tile = tile * src.tile_stride;
+        const uint32_t at_lane = (uint32_t)(lane * src.width);
+        for (int32_t m = 0; m < n_mon; ++m) {
+            double Px, Py, Pz, t;
+            const bool hit = g.valid && mon_hit(mons[m], g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, g.len, Px, Py, Pz, t);
+            if (!__ballot(hit)) continue;
+            const double* ax = img.axes + 6 * m;
+            const double* ey = img.edges + (int64_t)m * (img.nby + img.nbz + 2);
+            const double* ez = ey + img.nby + 1;
+            // the lane's own hit: its spot (nothing of a slot is kept from one monitor to the next: the registers are erf's), the
+            // count of its centre, its footprint
+            double y0 = 0.0, z0 = 0.0, w = 0.0, I = 0.0;
+            int32_t ky0 = 0, ky1 = -1, kz0 = 0, kz1 = -1;
+            if (hit) {
+                double wl = beam.wavelength_uniform;
+                bool usable = true;
+                if (beam.wavelength) {
+                    const int32_t ray = *reinterpret_cast<const int32_t*>(src.ray + tile * src.ray_stride + (uint32_t)(lane * 4));
+                    usable = ray >= 0 && ray < beam.n_wavelengths;
+                    if (usable) wl = beam.wavelength[ray];
+                }
+                const double qr = mon_real(beam.q_re + at_tile + at_lane, src.width) + t, qi = mon_real(beam.q_im + at_tile + at_lane, src.width);
+                const double n_index = mon_real(beam.n_index + at_tile + at_lane, src.width);
+                w = sqrt(wl * (qr * qr + qi * qi) / (n_index * M_PI * qi));
+                usable = usable && wl > 0.0 && wl < HUGE_VAL && n_index > 0.0 && n_index < HUGE_VAL && qi > 0.0 && qi < HUGE_VAL && w > 0.0 && w < HUGE_VAL;
+                if (usable) {
+                    I = mon_real(img.intensity + at_tile + at_lane, src.width);
+                    y0 = Px * ax[0] + Py * ax[1] + Pz * ax[2];
+                    z0 = Px * ax[3] + Py * ax[4] + Pz * ax[5];
+                    const int32_t ky = mon_bin(ey, img.nby, y0), kz = mon_bin(ez, img.nbz, z0);
+                    if (ky >= 0 && kz >= 0) {  // the centre is counted where the image mode counts the hit
+                        const int32_t bin = m * per_mon + ky * img.nbz + kz;
+                        if (img.lds_bins) atomicAdd(&tally[bin], 1);
+                        else atomicAdd(&img.counts[bin], 1ull);
+                    }
+                    const double reach = 5.0 * w;
+                    ky0 = mon_beam_first(ey, img.nby, y0 - reach), ky1 = mon_beam_last(ey, img.nby, y0 + reach);
+                    kz0 = mon_beam_first(ez, img.nbz, z0 - reach), kz1 = mon_beam_last(ez, img.nbz, z0 + reach);
+                } else {
+                    ++skipped;
+                }
+            }
+            // the wave takes its hits one at a time
+            for (unsigned long long rest = __ballot(ky0 <= ky1 && kz0 <= kz1); rest; rest &= rest - 1) {
+                const int from = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(rest));
+                mon_beam_deposit(ey, ez, img.nbz, mon_lane_value(y0, from), mon_lane_value(z0, from), mon_lane_value(w, from), mon_lane_value(I, from),
+                                 __builtin_amdgcn_readlane(ky0, from), __builtin_amdgcn_readlane(ky1, from), __builtin_amdgcn_readlane(kz0, from),
+                                 __builtin_amdgcn_readlane(kz1, from), strip, lane, img.lds_bins ? power + m * per_mon : nullptr,
+                                 beam.power + (int64_t)m * per_mon);
+            }
+        }
+    }
+    if (skipped) atomicAdd(beam.skipped, (unsigned long long)skipped);
+    __syncthreads();
+    for (int32_t b = threadIdx.x; b < img.lds_bins; b += MON_THREADS) {  // consecutive lanes, consecutive bins
+        const int32_t c = tally[b];
+        const double p = power[b];
+        if (c) atomicAdd(&img.counts[b], (unsigned long long)c);
+        if (p != 0.0) unsafeAtomicAdd(&beam.power[b], p);
+    }
+}
 // count[m * gridDim.x + g] = hits of monitor m among workgroup g's slots; count[n_mon * gridDim.x] = 0, so that the scan's last
-// element is the total.  In image and field mode (img.counts set: one uniform branch at entry) `count` is not touched.
+// element is the total.  In image, field and beam mode (img.counts set: one uniform branch at entry) `count` is not touched.
 __global__ __launch_bounds__(MON_THREADS) void k_mon_count(const ot_monitor* __restrict__ mons, int32_t n_mon, MonSource src, int64_t n, int32_t iters,
                                                            const int32_t* __restrict__ seg_count, int64_t n_rays, int32_t* __restrict__ count,
-                                                           MonImage img, MonField fld) {
+                                                           MonImage img, MonField fld, MonBeam beam) {
     __shared__ int32_t total[MON_MAX];
-    extern __shared__ double mon_image[];  // through LDS: weights[lds_bins], then counts[lds_bins]; field mode: re, im, then counts
+    // through LDS: weights[lds_bins], then counts[lds_bins]; field mode: re, im, then counts; beam mode: the waves' strips, power, then counts
+    extern __shared__ double mon_image[];
     if (img.counts) {
-        if (fld.re)
+        if (beam.power)
+            mon_beam_pass(mons, n_mon, src, n, iters, seg_count, n_rays, img, beam, mon_image, mon_image + MON_WAVES * MON_BEAM_STRIP,
+                          reinterpret_cast<int32_t*>(mon_image + MON_WAVES * MON_BEAM_STRIP + img.lds_bins));
+        else if (fld.re)
             mon_field_pass(mons, n_mon, src, n, iters, seg_count, n_rays, img, fld, mon_image, mon_image + img.lds_bins,
                            reinterpret_cast<int32_t*>(mon_image + 2 * img.lds_bins));
         else

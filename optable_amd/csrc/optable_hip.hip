@@ -1726,7 +1726,7 @@ int ot_monitor_record_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors
     for (int32_t m0 = 0; m0 < n_monitors; m0 += MON_MAX) {
         const int32_t nm = std::min<int32_t>(MON_MAX, n_monitors - m0);
         hipLaunchKernelGGL(k_mon_count, dim3((unsigned)grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, iters, seg_count, n_rays, count,
-                           MonImage{}, MonField{});
+                           MonImage{}, MonField{}, MonBeam{});
         exclusive_scan<int32_t, int64_t>(c->scan_tmp.p, count, off, nm * grid + 1, c->stream);
         hipLaunchKernelGGL(k_mon_emit, dim3((unsigned)grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, iters, seg_count, n_rays, off,
                            capacity, first + m0, hit_index, (double*)Px, (double*)Py, (double*)Pz, (double*)t, n_total);
@@ -1735,10 +1735,11 @@ int ot_monitor_record_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors
     return 0;
 }
 
-// How ot_monitor_image_many / ot_monitor_field_many walk n_monitors monitors of nby x nbz bins: `passes` launches of at most
-// `per_pass` monitors each, as even as they come (8 monitors of 30 x 30: 4 + 4, not 6 + 2), through LDS when a pass's bins fit
-// `budget` (MON_IMG_LDS_BINS; MON_FIELD_LDS_BINS for a field: 8 monitors go 3 + 3 + 2), else (one monitor alone does not fit)
-// MON_MAX at a time straight to global memory.  optable_amd/engine.py image_plan / field_plan say the same.
+// How ot_monitor_image_many / ot_monitor_field_many / ot_monitor_beam_many walk n_monitors monitors of nby x nbz bins: `passes`
+// launches of at most `per_pass` monitors each, as even as they come (8 monitors of 30 x 30: 4 + 4, not 6 + 2), through LDS when a
+// pass's bins fit `budget` (MON_IMG_LDS_BINS; MON_FIELD_LDS_BINS for a field: 8 monitors go 3 + 3 + 2; MON_BEAM_LDS_BINS for beams:
+// 6 go 3 + 3), else (one monitor alone does not fit) MON_MAX at a time straight to global memory.  optable_amd/engine.py image_plan /
+// field_plan / beam_plan say the same.
 struct ImagePlan {
     int32_t per_pass, passes;
     bool lds;
@@ -1753,7 +1754,7 @@ static ImagePlan image_plan(int32_t n_monitors, int32_t nby, int32_t nbz, int32_
     return p;
 }
 
-// What the two calls refuse alike (their own outputs apart), before anything is launched or zeroed.
+// What the three calls refuse alike (their own outputs apart), before anything is launched or zeroed.
 static int check_image_call(const ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, int32_t nby,
                             int32_t nbz, const ot_segment_source* src, const void* intensity, int64_t n, const int32_t* seg_count,
                             int64_t n_rays, int32_t accumulate) {
@@ -1785,12 +1786,14 @@ static int check_image_call(const ot_ctx* c, const ot_monitor* mons, int32_t n_m
 }
 
 // The launches of a checked call whose outputs are zeroed or kept: the monitors, edges and axes to the device, then k_mon_count in
-// image mode (fld.re NULL, 12 bytes of LDS a bin) or field mode (20) once per pass of the plan.  img.counts / img.weights and
-// fld.re / fld.im come in as the images of monitor 0 and go to the kernel as those of the pass's first monitor.
+// image mode (fld.re and beam.power NULL, 12 bytes of LDS a bin), field mode (20) or beam mode (12, behind the waves' edge strips)
+// once per pass of the plan.  img.counts / img.weights, fld.re / fld.im and beam.power come in as the images of monitor 0 and go
+// to the kernel as those of the pass's first monitor.
 static int image_passes(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, const ot_segment_source* src,
-                        int64_t n, const int32_t* seg_count, int64_t n_rays, const ImagePlan& plan, MonImage img, MonField fld) {
+                        int64_t n, const int32_t* seg_count, int64_t n_rays, const ImagePlan& plan, MonImage img, MonField fld, MonBeam beam) {
     const int32_t n_edges = img.nby + img.nbz + 2;
     const size_t bins = (size_t)img.nby * img.nbz, bytes_a_bin = fld.re ? 20 : 12;
+    const size_t strips = beam.power ? sizeof(double) * MON_WAVES * MON_BEAM_STRIP : 0;
     // the partition of k_mon_count, with workgroups long enough to be worth an image of their own: a thousand of them at most
     // (two rounds of the chip at two a CU), each of which zeroes and flushes its LDS image once
     const int32_t iters = (int32_t)std::max<int64_t>(8, (n + 1024 * MON_THREADS - 1) / (1024 * MON_THREADS));
@@ -1815,13 +1818,15 @@ static int image_passes(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, c
         const int32_t nm = std::min<int32_t>(plan.per_pass, n_monitors - m0);
         MonImage pass = img;
         MonField pass_field = fld;
+        MonBeam pass_beam = beam;
         pass.counts += m0 * bins;
-        if (fld.re) pass_field.re += m0 * bins, pass_field.im += m0 * bins;
+        if (beam.power) pass_beam.power += m0 * bins;
+        else if (fld.re) pass_field.re += m0 * bins, pass_field.im += m0 * bins;
         else pass.weights += m0 * bins;
         pass.edges = d_edges + (int64_t)m0 * n_edges, pass.axes = d_axes + (int64_t)m0 * 6;
         pass.lds_bins = plan.lds ? (int32_t)(nm * bins) : 0;
-        hipLaunchKernelGGL(k_mon_count, dim3((unsigned)grid), dim3(MON_THREADS), (size_t)pass.lds_bins * bytes_a_bin, c->stream, table + m0, nm, ms, n,
-                           iters, seg_count, n_rays, (int32_t*)nullptr, pass, pass_field);
+        hipLaunchKernelGGL(k_mon_count, dim3((unsigned)grid), dim3(MON_THREADS), strips + (size_t)pass.lds_bins * bytes_a_bin, c->stream, table + m0, nm,
+                           ms, n, iters, seg_count, n_rays, (int32_t*)nullptr, pass, pass_field, pass_beam);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1844,7 +1849,8 @@ int ot_monitor_image_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors,
     img.counts = (unsigned long long*)counts, img.weights = weights;
     img.intensity = (const uint8_t*)intensity;
     img.nby = nby, img.nbz = nbz;
-    return image_passes(c, mons, n_monitors, axes, edges, src, n, seg_count, n_rays, image_plan(n_monitors, nby, nbz, MON_IMG_LDS_BINS), img, MonField{});
+    return image_passes(c, mons, n_monitors, axes, edges, src, n, seg_count, n_rays, image_plan(n_monitors, nby, nbz, MON_IMG_LDS_BINS), img, MonField{},
+                        MonBeam{});
 }
 
 int ot_monitor_field_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, int32_t nby,
@@ -1879,7 +1885,40 @@ int ot_monitor_field_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors,
     fld.n_index = (const uint8_t*)n_index, fld.pathlength = (const uint8_t*)pathlength;
     fld.wavelength = wavelength, fld.n_wavelengths = (int32_t)n_wavelengths, fld.wavelength_uniform = wavelength_uniform;
     fld.skipped = (unsigned long long*)skipped, fld.amplitude_mode = amplitude_mode;
-    return image_passes(c, mons, n_monitors, axes, edges, src, n, seg_count, n_rays, image_plan(n_monitors, nby, nbz, MON_FIELD_LDS_BINS), img, fld);
+    return image_passes(c, mons, n_monitors, axes, edges, src, n, seg_count, n_rays, image_plan(n_monitors, nby, nbz, MON_FIELD_LDS_BINS), img, fld,
+                        MonBeam{});
+}
+
+int ot_monitor_beam_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, int32_t nby,
+                         int32_t nbz, const ot_segment_source* src, const void* intensity, const void* q_re, const void* q_im,
+                         const void* n_index, const double* wavelength, int64_t n_wavelengths, double wavelength_uniform, int64_t n,
+                         const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* power, int64_t* skipped, int32_t accumulate) {
+    if (!counts || !power || !skipped) return fail(OT_ERR_INVALID, "NULL argument");
+    const int rc = check_image_call(c, mons, n_monitors, axes, edges, nby, nbz, src, intensity, n, seg_count, n_rays, accumulate);
+    if (rc) return rc;
+    if (!q_re || !q_im || !n_index) return fail(OT_ERR_INVALID, "NULL q_re, q_im or n_index");
+    if (wavelength && (n_wavelengths < 1 || n_wavelengths >= (int64_t)1 << 31)) return fail(OT_ERR_INVALID, "n_wavelengths must be at least 1 (and below 2^31)");
+    if (!wavelength && !(std::isfinite(wavelength_uniform) && wavelength_uniform > 0.0))
+        return fail(OT_ERR_INVALID, "wavelength_uniform must be finite and > 0 when there is no wavelength array");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bins = (size_t)nby * nbz;
+    if (!accumulate) {
+        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * bins * n_monitors, c->stream));
+        HIP_TRY(hipMemsetAsync(power, 0, sizeof(double) * bins * n_monitors, c->stream));
+        HIP_TRY(hipMemsetAsync(skipped, 0, sizeof(int64_t), c->stream));
+    }
+    if (n == 0) return 0;
+    MonImage img{};
+    img.counts = (unsigned long long*)counts;
+    img.intensity = (const uint8_t*)intensity;
+    img.nby = nby, img.nbz = nbz;
+    MonBeam beam{};
+    beam.power = power;
+    beam.q_re = (const uint8_t*)q_re, beam.q_im = (const uint8_t*)q_im, beam.n_index = (const uint8_t*)n_index;
+    beam.wavelength = wavelength, beam.n_wavelengths = (int32_t)n_wavelengths, beam.wavelength_uniform = wavelength_uniform;
+    beam.skipped = (unsigned long long*)skipped;
+    return image_passes(c, mons, n_monitors, axes, edges, src, n, seg_count, n_rays, image_plan(n_monitors, nby, nbz, MON_BEAM_LDS_BINS), img, MonField{},
+                        beam);
 }
 
 int ot_debug_last_launch(ot_ctx* c, int32_t info[8]) {

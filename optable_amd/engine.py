@@ -120,6 +120,7 @@ IMAGE_MAX_MONITORS = 32                  # MON_MAX: monitors of one launch
 
 
 FIELD_LDS_BINS = (65536 - 32 * 4) // 20  # MON_FIELD_LDS_BINS: the same LDS at 20 bytes a bin (re, im, count) — ot_monitor_field_many
+BEAM_LDS_BINS = (65536 - 32 * 4 - 4 * 128 * 8) // 12  # MON_BEAM_LDS_BINS: 12 bytes a bin (power, count) next to four waves' erf tables — ot_monitor_beam_many
 
 
 def image_plan(n_monitors, nby, nbz, budget=IMAGE_LDS_BINS):
@@ -138,6 +139,11 @@ def image_plan(n_monitors, nby, nbz, budget=IMAGE_LDS_BINS):
 def field_plan(n_monitors, nby, nbz):
     """`image_plan` for ot_monitor_field_many: the same rule with FIELD_LDS_BINS (three monitors of 30 x 30 a launch)."""
     return image_plan(n_monitors, nby, nbz, FIELD_LDS_BINS)
+
+
+def beam_plan(n_monitors, nby, nbz):
+    """`image_plan` for ot_monitor_beam_many: the same rule with BEAM_LDS_BINS (five monitors of 30 x 30 a launch; six go 3 + 3)."""
+    return image_plan(n_monitors, nby, nbz, BEAM_LDS_BINS)
 
 
 # What a whole-trace launch writes, by library call: (the SegmentBatch made when the caller passes none, what makes a passed
@@ -824,6 +830,50 @@ class Engine:
                                                  None if count is None else count.data_ptr(), n_rays, counts.data_ptr(), re.data_ptr(),
                                                  im.data_ptr(), skipped.data_ptr(), 0 if into is None else 1), self.lib)
         return counts, re, im, skipped
+
+    def monitor_beam_many(self, monitor_structs, axes, edges, bins, segs: SegmentBatch, wavelength, into=None):
+        """Gaussian-beam detector images of a list of monitors over a SegmentBatch read as it lies, either precision
+        (ot_monitor_beam_many: `monitor_image_many` with every hit's intensity spread over its Gaussian spot, from the segments'
+        q, n and the wavelength).  axes, edges, bins as there.  wavelength: a float for all rays, or a float64 device tensor indexed
+        by the segments' `ray`.  Returns (counts, power, skipped): int64 / float64 [M, nby, nbz] device tensors and an int64 device
+        tensor of one element (hits left out: no q, or an unusable ray, wavelength or index), zeroed by the call — or `into`, such
+        a tuple from an earlier call, with this call's hits added to it."""
+        with self.lock:
+            return self._monitor_beam_many(list(monitor_structs), axes, edges, bins, segs, wavelength, into)
+
+    def _monitor_beam_many(self, mons, axes, edges, bins, segs, wavelength, into):
+        dev, M, (nby, nbz) = segs.device, len(mons), bins
+        axes, edges = np.ascontiguousarray(axes, dtype=np.float64), np.ascontiguousarray(edges, dtype=np.float64)
+        if axes.shape != (M, 6) or edges.shape != (M, nby + nbz + 2):
+            raise ValueError(f"axes must be [{M}, 6] and edges [{M}, {nby + nbz + 2}]")
+        if torch.is_tensor(wavelength):
+            if wavelength.dtype != torch.float64 or wavelength.dim() != 1 or not wavelength.is_contiguous() or wavelength.device.type != dev.type:
+                raise ValueError(f"wavelength: a float or a contiguous float64 vector on {dev}")
+            table_ptr, n_table, uniform = (wavelength.data_ptr() if wavelength.numel() else None), int(wavelength.numel()), 0.0
+        else:
+            table_ptr, n_table, uniform = None, 0, float(wavelength)
+        if into is None:
+            counts = torch.empty((M, nby, nbz), dtype=torch.int64, device=dev)  # (the call zeroes them)
+            power = torch.empty((M, nby, nbz), dtype=torch.float64, device=dev)
+            skipped = torch.empty(1, dtype=torch.int64, device=dev)
+        else:
+            counts, power, skipped = into
+            for t, dt in ((counts, torch.int64), (power, torch.float64)):
+                if tuple(t.shape) != (M, nby, nbz) or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type:
+                    raise ValueError(f"into: contiguous int64 counts and float64 power of shape [{M}, {nby}, {nbz}] on {dev}")
+            if tuple(skipped.shape) != (1,) or skipped.dtype != torch.int64 or skipped.device.type != dev.type:
+                raise ValueError(f"into: skipped is one int64 on {dev}")
+        src, n_segments, count, n_rays = segment_source(segs)
+        if M == 0 or n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
+            return (counts.zero_(), power.zero_(), skipped.zero_()) if into is None else (counts, power, skipped)
+        table = (abi.OtMonitor * M)(*mons)
+        as_doubles = C.POINTER(C.c_double)
+        abi.check(self.lib.ot_monitor_beam_many(self._ctx, table, M, axes.ctypes.data_as(as_doubles), edges.ctypes.data_as(as_doubles), nby, nbz,
+                                                C.byref(src), segs.field("intensity").data_ptr(), segs.field("q_re").data_ptr(),
+                                                segs.field("q_im").data_ptr(), segs.field("n").data_ptr(), table_ptr, n_table, uniform, n_segments,
+                                                None if count is None else count.data_ptr(), n_rays, counts.data_ptr(), power.data_ptr(),
+                                                skipped.data_ptr(), 0 if into is None else 1), self.lib)
+        return counts, power, skipped
 
     # -- measurement ---------------------------------------------------------------------------
     def timing(self, enabled=True):

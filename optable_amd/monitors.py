@@ -253,6 +253,44 @@ class MonitorHits:
         x = self.pathlengthList(sort).double() / wavelength
         return 2 * np.pi * (x - torch.floor(x))
 
+    def _wavelengths(self, wavelength, sort):
+        """`wavelength` per hit: a float for all rays as it is, the `RayBatch` that was traced by the hits' `ray_index`, as double."""
+        return wavelength.wavelength.double()[self.ray_index(sort)] if hasattr(wavelength, "wavelength") else wavelength
+
+    def qList(self, sort="YZ"):
+        """The complex beam parameter of every hit at the monitor, `Ray.q_at_z(t)` of its segment: q[slot] + t (complex128)."""
+        import torch
+
+        order = self._order(sort)
+        s = self.slot[order]
+        return torch.complex(self._gather(self.segs.q_re, s).double() + self.t[order], self._gather(self.segs.q_im, s).double())
+
+    def spotsizeList(self, wavelength, sort="YZ"):
+        """The 1 / e^2 radius of every hit's beam at the monitor, `Ray.spot_size(t)` of its segment: sqrt(-wavelength / (n pi
+        Im(1 / q))) with q = `qList`, written without the reciprocal — the w over which `OpticalTable.beam_all` spreads the hit.
+        `wavelength` as for `phaseList`.  NaN or inf where the segment carries no q."""
+        import torch
+
+        q = self.qList(sort)
+        n = self._gather(self.segs.n_index, self.slot[self._order(sort)]).double()
+        return torch.sqrt(self._wavelengths(wavelength, sort) * (q.real**2 + q.imag**2) / (n * np.pi * q.imag))
+
+    def waistList(self, wavelength, sort="YZ"):
+        """The waist radius of every hit's beam, `Monitor.get_beam_waist`: `Ray.waist(q)` = sqrt(wavelength Im(q) / (n pi))."""
+        import torch
+
+        n = self._gather(self.segs.n_index, self.slot[self._order(sort)]).double()
+        return torch.sqrt(self._wavelengths(wavelength, sort) * self.qList(sort).imag / (n * np.pi))
+
+    def waistdistanceList(self, sort="YZ"):
+        """The distance of every hit from its beam's waist, `Monitor.get_waist_distance`: Re(q) at the monitor, with the sign
+        turned for rays that travel along the monitor's normal (direction . normal > 0)."""
+        import torch
+
+        along = self.directionList(sort).double() @ torch.as_tensor(np.asarray(self.monitor.normal, dtype=float), device=self.slot.device)
+        z = self.qList(sort).real
+        return torch.where(along > 0, -z, z)
+
     def directionList(self, sort="YZ"):
         import torch
 
@@ -343,3 +381,30 @@ class MonitorField:
     def to_host(self):
         """(counts, re, im, y_edges, z_edges) as numpy arrays."""
         return self.counts.cpu().numpy(), self.re.cpu().numpy(), self.im.cpu().numpy(), self.y_edges, self.z_edges
+
+
+class MonitorBeam:
+    """A monitor's hits as the image their Gaussian beams make, summed on the device (`OpticalTable.beam_all`): `counts` (int64,
+    the hit centres, as `MonitorImage.counts`) and `power` (float64), [nby, nbz] device tensors over `y_edges` x `z_edges` (numpy)
+    — per bin the sum over the hits of IList times the share of a Gaussian spot of radius `MonitorHits.spotsizeList` around
+    (yList, zList) that falls into the bin, the beam taken at normal incidence.  Counts are exact and the same every run; power
+    is atomic fp64 sums whose last bits depend on the order of arrival."""
+
+    def __init__(self, monitor, counts, power, y_edges, z_edges, stack=None):
+        self.monitor, self.counts, self.power, self.y_edges, self.z_edges = monitor, counts, power, y_edges, z_edges
+        self._stack = stack  # (counts, power, skipped, position) of the call's [M, nby, nbz] tensors, which `into=` adds to
+
+    @property
+    def bins(self):
+        return tuple(self.counts.shape)
+
+    def irradiance(self):
+        """`power` per unit area: every bin's power over its area (y width x z width), a float64 [nby, nbz] device tensor."""
+        import torch
+
+        area = np.outer(np.diff(self.y_edges), np.diff(self.z_edges))
+        return self.power / torch.as_tensor(area, device=self.power.device)
+
+    def to_host(self):
+        """(counts, power, y_edges, z_edges) as numpy arrays."""
+        return self.counts.cpu().numpy(), self.power.cpu().numpy(), self.y_edges, self.z_edges

@@ -280,8 +280,6 @@ class OpticalTable:
         `wavelength`: one float for all rays, or the `RayBatch` that was traced (its wavelengths by the segments' `ray`; children
         of a ray tree inherit theirs).  `segs` must be double precision: single-precision path lengths carry some 0.02 cycle of
         phase noise at table scale.  `into`: as for `image_all`."""
-        import torch
-        from .batch import RayBatch
         from .monitors import MonitorField, image_bins, image_edges
 
         nby, nbz = image_bins(bins)
@@ -289,20 +287,7 @@ class OpticalTable:
             raise ValueError(f"amplitude must be 'sqrt' or 'linear', not {amplitude!r}")
         if segs.precision != "f64":
             raise ValueError("field_all needs a double-precision SegmentBatch: a field from single-precision path lengths is refused, not approximated")
-        if isinstance(wavelength, RayBatch):
-            if segs.n_rays is not None and wavelength.n != int(segs.n_rays):
-                raise ValueError(f"wavelength: a RayBatch of {wavelength.n} rays for segments of {int(segs.n_rays)}")
-            wavelength = wavelength.wavelength.double().contiguous()
-            if not bool(((wavelength > 0) & torch.isfinite(wavelength)).all()):
-                raise ValueError("wavelength: every ray of the batch needs a finite wavelength > 0")
-        else:
-            try:
-                value = float(wavelength)
-            except (TypeError, ValueError):
-                raise ValueError(f"wavelength must be a float or the RayBatch that was traced, not {wavelength!r}") from None
-            if not (np.isfinite(value) and value > 0):
-                raise ValueError(f"wavelength={wavelength!r}: a field needs a finite wavelength > 0 (pass it, or the RayBatch that was traced)")
-            wavelength = value
+        wavelength = _wavelengths_of(wavelength, segs, "a field")
         monitors = list(self.monitors if monitors is None else monitors)
         edges = [image_edges(m, nby, nbz) for m in monitors]
         stack = None
@@ -330,6 +315,48 @@ class OpticalTable:
     def field_batch(self, monitor, segs, wavelength=0.0, bins=30, amplitude="sqrt"):
         """One monitor as a coherent image (`field_all` for it alone): a `MonitorField`."""
         return self.field_all(segs, wavelength, bins=bins, monitors=[monitor], amplitude=amplitude)[0]
+
+    def beam_all(self, segs, wavelength=0.0, bins=30, monitors=None, into=None):
+        """Every monitor of the table (or those given) as the image its GAUSSIAN BEAMS make: one `MonitorBeam` per monitor, in
+        their order — per bin of `image_all`'s images the count of hit centres and the power the bin receives when every hit is
+        spread over its spot, I 2 / (pi w^2) exp(-2 r^2 / w^2) integrated over the bin, w = `Ray.spot_size(t)` at the monitor from
+        the segment's q, n and the wavelength; summed on the device in the pass that finds the hits, with no hit list
+        (ot_monitor_beam_many).  It is `Monitor.render_scatter(gaussian_beam=True)`'s circle made quantitative: the beam is taken
+        at normal incidence in the monitor's (y, z), so a tilted beam's spot is not stretched, and a spot that reaches over the
+        monitor's rim loses that part (the sum of `power` is at most the hits' intensity).  A hit whose centre lies outside the
+        edges is counted nowhere and still deposits its tails.  `wavelength`: one float for all rays, or the `RayBatch` that was
+        traced, as for `field_all`.  `segs` in either precision (all arithmetic is double).  A hit without q (a batch traced
+        without a Gaussian beam) or with an unusable index raises ValueError.  `into`: as for `image_all`."""
+        from .monitors import MonitorBeam, image_bins, image_edges
+
+        nby, nbz = image_bins(bins)
+        wavelength = _wavelengths_of(wavelength, segs, "a beam image")
+        monitors = list(self.monitors if monitors is None else monitors)
+        edges = [image_edges(m, nby, nbz) for m in monitors]
+        stack = None
+        if into is not None:
+            into = list(into)
+            if len(into) != len(monitors) or any(b.monitor is not m or b.bins != (nby, nbz) for b, m in zip(into, monitors)):
+                raise ValueError("into: the list an earlier beam_all returned for the same monitors and bins")
+            if any(b._stack is None or b._stack[0] is not into[0]._stack[0] or b._stack[3] != k or len(b._stack[0]) != len(into) for k, b in enumerate(into)):
+                raise ValueError("into: the whole list of one earlier call, in its order")
+            if not monitors:
+                return into
+            stack = into[0]._stack[:3]
+        axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in monitors], dtype=float).reshape(len(monitors), 6)
+        table = np.array([np.concatenate(e) for e in edges], dtype=float).reshape(len(monitors), nby + nbz + 2)
+        counts, power, skipped = _engine().monitor_beam_many([monitor_struct(m) for m in monitors], axes, table, (nby, nbz), segs, wavelength, into=stack)
+        left_out = int(skipped.item())
+        if left_out:
+            raise ValueError(f"beam_all: {left_out} hits left out — they carry no q (a batch traced without a Gaussian beam), or their wavelength "
+                             "or refractive index is not finite and > 0, or their `ray` is no index into the wavelengths given")
+        if into is not None:
+            return into
+        return [MonitorBeam(m, counts[k], power[k], ey, ez, stack=(counts, power, skipped, k)) for k, (m, (ey, ez)) in enumerate(zip(monitors, edges))]
+
+    def beam_batch(self, monitor, segs, wavelength=0.0, bins=30):
+        """One monitor as a Gaussian-beam image (`beam_all` for it alone): a `MonitorBeam`."""
+        return self.beam_all(segs, wavelength, bins=bins, monitors=[monitor])[0]
 
     # -- ABCD extraction (optical_table.py:211-297), a caller of the hot path ----------------------
     def calculate_abcd_matrix(self, mon0, mon1, rays, disp=1e-5, rot=1e-5, debugaxs=None):
@@ -605,6 +632,28 @@ class OpticalTable:
 # scene of fixture g25).  Only for the very ray object handed to the hook, and only while it still has the origin and direction
 # it was handed over with; any other question goes to the device.
 _HOOK_MEMO = {}
+
+
+def _wavelengths_of(wavelength, segs, what):
+    """The `wavelength` argument of `field_all` / `beam_all` as the engine takes it: a float > 0, or the double wavelengths of the
+    `RayBatch` that was traced (one per input ray of `segs`); anything else is a ValueError that names `what` needs it."""
+    import torch
+    from .batch import RayBatch
+
+    if isinstance(wavelength, RayBatch):
+        if segs.n_rays is not None and wavelength.n != int(segs.n_rays):
+            raise ValueError(f"wavelength: a RayBatch of {wavelength.n} rays for segments of {int(segs.n_rays)}")
+        wavelength = wavelength.wavelength.double().contiguous()
+        if not bool(((wavelength > 0) & torch.isfinite(wavelength)).all()):
+            raise ValueError("wavelength: every ray of the batch needs a finite wavelength > 0")
+        return wavelength
+    try:
+        value = float(wavelength)
+    except (TypeError, ValueError):
+        raise ValueError(f"wavelength must be a float or the RayBatch that was traced, not {wavelength!r}") from None
+    if not (np.isfinite(value) and value > 0):
+        raise ValueError(f"wavelength={wavelength!r}: {what} needs a finite wavelength > 0 (pass it, or the RayBatch that was traced)")
+    return value
 
 
 def _memo_for(comp, ray_local):
