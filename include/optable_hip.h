@@ -599,6 +599,41 @@ int ot_monitor_beam_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitors
                          double wavelength_uniform, int64_t n_segments, const int32_t* seg_count, int64_t n_rays, int64_t* counts,
                          double* power, int64_t* skipped, int32_t accumulate);
 
+/* Coherent Gaussian-beam detector images: the complex field the hits' Gaussian beams make on every monitor, sampled at the bin
+ * centres — ot_monitor_field_many with every hit a beam (envelope, wavefront curvature, tilt) instead of a point phasor, from a
+ * kernel of its own (k_mon_wave) on the same partition, test and, for the count, bin rule; mons, axes, edges, nby, nbz, src,
+ * n_segments, seg_count, n_rays and accumulate as for ot_monitor_image_many.
+ * A hit of slot s at the distance t, at y0 = P . a_y, z0 = P . a_z, of the segment direction d (ty = d . a_y, tz = d . a_z):
+ *   q = q_re[s] + t + i q_im[s],  |q|^2 = qr^2 + qi^2,  w^2 = wavelength |q|^2 / (n[s] pi qi)        (Ray.spot_size(t))
+ *   cycles = (pathlength[s] + t n[s]) / wavelength + n (ty Dy + tz Dz) / wavelength + n qr (Dy^2 + Dz^2) / (2 wavelength |q|^2)
+ *   u(yc, zc) = a sqrt(2 / (pi w^2)) exp(-(Dy^2 + Dz^2) / w^2) exp(i (2 pi frac(cycles) - g))
+ * at the centre (yc, zc) of a bin, Dy = yc - y0, Dz = zc - z0; a = sqrt(intensity[s]) (amplitude_mode 0) or intensity[s] (1);
+ * g = atan2(qr, qi) (gouy = 1) or 0 (gouy = 0) — the tracer's q accumulates no Gouy phase across lenses, so g is exact only for a
+ * beam that has met no focusing element since its waist.  The sum of |u|^2 times the bin area over a finely sampled image is a^2.
+ * re, im get the sum of u over the hits; counts the hit centres where ot_monitor_image_many counts them.  The envelope is taken at
+ * normal incidence (a tilted beam's spot is not stretched), q is not advanced across the tilt, and bin centres more than 6 w from
+ * the hit's along an axis are left out (below exp(-36) of the peak).  All in double precision: width 8 only.
+ * Sampling: the cycle rate along y is n ty / wavelength + n qr Dy / (wavelength |q|^2), likewise z.  A hit whose largest rate over
+ * its footprint (at one of its two end centres) times the mean bin width (last edge - first edge) / bins exceeds 0.5 on either
+ * axis is still deposited and adds one to *aliased (device): the image is undersampled there.
+ * intensity, n_index, pathlength, q_re, q_im: device planes of the segments, addressed like src->base[f].  The wavelength of a hit
+ * as for ot_monitor_field_many.  A hit whose ray lies outside [0, n_wavelengths), or whose wavelength, n, qi or w is not finite and
+ * > 0 (a ray without q has q = 0), adds nothing anywhere and one to *skipped (device); nothing is read out of range.
+ * counts, re, im: device, [n_monitors][nby][nbz] int64 / double / double; skipped, aliased: device, one int64 each.  accumulate = 0
+ * zeroes all five first, 1 adds to what is there (a field is linear: the chunks of a streamed trace add).  Counts are exact and the
+ * same every run; re and im are fp64 atomic sums, whose last bits depend on the order of arrival.
+ * Paths: as for ot_monitor_image_many at 20 bytes of LDS a bin next to 8 KB of per-wave strips (2,860 bins: three monitors of
+ * 30 x 30 a group); an image that does not fit alone goes to global atomics bin by bin.
+ * OT_ERR_INVALID, nothing launched or zeroed: everything ot_monitor_image_many refuses; width 4; a NULL n_index, pathlength, q_re,
+ * q_im, counts, re, im, skipped or aliased; wavelength = NULL with wavelength_uniform not finite or not > 0; a wavelength array
+ * with n_wavelengths < 1; amplitude_mode or gouy outside {0, 1}. */
+int ot_monitor_wave_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges,
+                         int32_t nby, int32_t nbz, const ot_segment_source* src, const void* intensity, const void* n_index,
+                         const void* pathlength, const void* q_re, const void* q_im, const double* wavelength, int64_t n_wavelengths,
+                         double wavelength_uniform, int32_t amplitude_mode, int32_t gouy, int64_t n_segments, const int32_t* seg_count,
+                         int64_t n_rays, int64_t* counts, double* re, double* im, int64_t* skipped, int64_t* aliased,
+                         int32_t accumulate);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled every trace launch is bracketed by hipEvents on the ctx stream. */
 int ot_timing_enable(ot_ctx* ctx, int enabled);

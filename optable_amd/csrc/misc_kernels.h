@@ -88,8 +88,10 @@ template <class In, class Out> static void exclusive_scan(void* tmp, const In* i
     if (n <= 0) return;
     const int64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
     Out* tile_sum = (Out*)tmp;
+    // the spine only adds: every 64-bit Out shares the unsigned instantiation (the same bits in two's complement), one kernel less
+    using Spine = std::conditional_t<sizeof(Out) == 8, unsigned long long, Out>;
     hipLaunchKernelGGL((k_scan_tiles<In, Out>), dim3((unsigned)tiles), dim3(SCAN_THREADS), 0, stream, in, n, tile_sum);
-    hipLaunchKernelGGL((k_scan_spine<Out>), dim3(1), dim3(SCAN_THREADS), 0, stream, tile_sum, tiles);
+    hipLaunchKernelGGL((k_scan_spine<Spine>), dim3(1), dim3(SCAN_THREADS), 0, stream, (Spine*)tile_sum, tiles);
     hipLaunchKernelGGL((k_scan_apply<In, Out>), dim3((unsigned)tiles), dim3(SCAN_THREADS), 0, stream, in, n, (const Out*)tile_sum, out);
 }
 
@@ -628,6 +630,216 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_count(const ot_monitor* __r
     __syncthreads();
     if ((int32_t)threadIdx.x < n_mon) count[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = total[threadIdx.x];
     if (blockIdx.x == 0 && threadIdx.x == 0) count[(int64_t)n_mon * gridDim.x] = 0;
+}
+// Coherent Gaussian-beam images (ot_monitor_wave_many), a kernel of its own — k_mon_count's partition, loads, tests and bin rule
+// for the count, the beam pass's walk over a hit's footprint, with a complex, phase-carrying deposit SAMPLED AT THE BIN CENTRE.
+// A hit of slot s at the distance t, at (y0, z0) = (P . a_y, P . a_z), of the segment direction d:
+//   q = q_re[s] + t + i q_im[s],  |q|^2 = qr^2 + qi^2,  w^2 = wavelength |q|^2 / (n[s] pi qi)       (the beam pass's w)
+//   ty = d . a_y, tz = d . a_z (MonitorHits.tYList / tZList),  a = sqrt(intensity[s]) (amplitude_mode 0) or intensity[s] (1)
+//   cycles = (pathlength[s] + t n) / wavelength                         Ray.phase(t), as the field mode
+//          + n (ty Dy + tz Dz) / wavelength                             tilt: the beam's plane-wave phase across the monitor
+//          + n qr (Dy^2 + Dz^2) / (2 wavelength |q|^2)                  wavefront curvature, k r^2 / (2 R)
+//   u(yc, zc) = a sqrt(2 / (pi w^2)) exp(-(Dy^2 + Dz^2) / w^2) exp(i (2 pi frac(cycles) - g)),   Dy = yc - y0, Dz = zc - z0
+// with g = atan2(qr, qi) (gouy = 1: exp(-i g) = (qi - i qr) / |q|, no arc tangent is taken) or 0.  It is separable,
+// u = A gy(Dy) gz(Dz): A = a sqrt(2 / (pi w^2)) exp(-i g),
+// gy(D) = exp(-D^2 / w^2) exp(2 pi i frac(f + D (ry + kc D))) with f = frac(L / wavelength), ry = n ty / wavelength and
+// kc = n qr / (2 wavelength |q|^2), gz likewise with f = 0 — one exp and one sincospi of a reduced cycle count per bin centre
+// and axis.  All in double; the host refuses single-precision segments.
+// The footprint of a hit is the bins whose CENTRE lies within 6 w of the hit's along either axis (beyond, the amplitude is below
+// exp(-36) of the peak): a spot narrower than a bin that falls between the centres deposits nothing.  The envelope is taken at
+// normal incidence and q is not advanced across the tilt.
+// Sampling: the cycle rate along y is ry + 2 kc D, linear in D; where its largest magnitude over the footprint (at one of the two
+// end centres) times the mean bin width (e[nb] - e[0]) / nb exceeds 0.5 on either axis, the hit is counted in *aliased — and is
+// deposited all the same.  A hit whose ray lies outside [0, n_wavelengths) or whose wavelength, n, qi or w is not finite and > 0
+// adds nothing and is counted in *skipped.
+// As in the beam pass every lane finds its own slot's hit, counts its centre and steps out its footprint; the wave then takes the
+// hits with a footprint one at a time (ballot, v_readlane), its lanes put A gy at the footprint's y centres and gz at its z
+// centres into the wave's strip of LDS — 63 x 63 bins at a time, 63 + 63 complex values — and stride over the bins with one
+// complex product and two atomic adds each: fy + fz exp / sincospi pairs a hit, not fy * fz.  Wave-synchronous, no barrier inside
+// the visit loop, the beam pass's wavefront fences.
+// Through LDS: MON_WAVES strips of MON_WAVE_STRIP doubles, re[lds_bins], im[lds_bins] (double), tally[lds_bins] (int32): 20 bytes a
+// bin next to 8 KB of strips (and the 128 bytes the count kernel's tally takes, left free here: one rule for every budget).
+static constexpr int MON_WAVE_STRIP = 256, MON_WAVE_CHUNK = 63;
+static constexpr int MON_WAVE_LDS_BINS = (65536 - MON_MAX * 4 - MON_WAVES * MON_WAVE_STRIP * 8) / 20;  // 2860: three monitors of 30 x 30
+struct MonWave {
+    double *re, *im;  // [n_mon][nby][nbz], of the launch's first monitor on
+    const uint8_t *q_re, *q_im, *n_index, *pathlength;
+    const double* wavelength;  // [n_wavelengths], or NULL: wavelength_uniform for every ray
+    unsigned long long *skipped, *aliased;
+    double wavelength_uniform;
+    int32_t n_wavelengths, amplitude_mode, gouy;
+};
+// exp and the phasor of a cycle count as calls, not inlined, as the beam pass's erf: inlined, their polynomials' coefficients are
+// hoisted out of every loop of the kernel and held in vector registers from its first instruction to its last (223 registers)
+__device__ __noinline__ double mon_wave_exp(double x) { return exp(x); }
+__device__ __noinline__ double2 mon_wave_cis(double cycles) {  // (cos, sin) of 2 pi frac(cycles)
+    double sn, cs;
+    sincospi(2.0 * (cycles - floor(cycles)), &sn, &cs);
+    return make_double2(cs, sn);
+}
+// exp(-D^2 / w2) exp(2 pi i frac(f + D (rate + kc D))): the factor of one axis at the distance D from the hit's centre
+__device__ __forceinline__ void mon_wave_axis(double D, double w2, double f, double rate, double kc, double& re, double& im) {
+    const double2 p = mon_wave_cis(f + D * (rate + kc * D));
+    const double env = mon_wave_exp(-(D * D) / w2);
+    re = env * p.x, im = env * p.y;
+}
+// One hit, by its whole wave: everything but `lane` is wave-uniform; the monitor's nby x nbz bins are re_lds / im_lds or, when
+// re_lds is NULL, re_global / im_global.
+__device__ __forceinline__ void mon_wave_deposit(const double* __restrict__ ey, const double* __restrict__ ez, int32_t nbz, double y0, double z0, double w2,
+                                                 double Are, double Aim, double f, double ry, double rz, double kc, int32_t ky0, int32_t ky1, int32_t kz0,
+                                                 int32_t kz1, double* strip, int lane, double* re_lds, double* im_lds, double* re_global,
+                                                 double* im_global) {
+    for (int32_t by = ky0; by <= ky1; by += MON_WAVE_CHUNK) {
+        const int32_t ny = min(MON_WAVE_CHUNK, ky1 - by + 1);
+        for (int32_t bz = kz0; bz <= kz1; bz += MON_WAVE_CHUNK) {
+            const int32_t nz = min(MON_WAVE_CHUNK, kz1 - bz + 1);
+            // strip[2 j], strip[2 j + 1] = A gy at the y centres by .. by + ny - 1 (j < ny), gz at the z centres bz .. (j - ny)
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            for (int32_t j = lane; j < ny + nz; j += 64) {
+                const bool along_y = j < ny;
+                const double* e = along_y ? ey + by + j : ez + bz + j - ny;
+                const double D = 0.5 * (e[0] + e[1]) - (along_y ? y0 : z0);
+                double gr, gi;
+                mon_wave_axis(D, w2, along_y ? f : 0.0, along_y ? ry : rz, kc, gr, gi);
+                strip[2 * j] = along_y ? Are * gr - Aim * gi : gr;
+                strip[2 * j + 1] = along_y ? Are * gi + Aim * gr : gi;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            for (int32_t b = lane; b < ny * nz; b += 64) {
+                const int32_t iy = b / nz, iz = b - iy * nz;
+                const double yr = strip[2 * iy], yi = strip[2 * iy + 1], zr = strip[2 * (ny + iz)], zi = strip[2 * (ny + iz) + 1];
+                const double ur = yr * zr - yi * zi, ui = yr * zi + yi * zr;
+                if (ur == 0.0 && ui == 0.0) continue;
+                const int32_t bin = (by + iy) * nbz + bz + iz;
+                if (re_lds) {
+                    unsafeAtomicAdd(&re_lds[bin], ur);
+                    unsafeAtomicAdd(&im_lds[bin], ui);
+                } else {
+                    unsafeAtomicAdd(&re_global[bin], ur);
+                    unsafeAtomicAdd(&im_global[bin], ui);
+                }
+            }
+        }
+    }
+}
+// The bins of e[0 .. nb] whose centre lies in [lo, hi]: the footprint helpers of the beam pass give the bins that reach into
+// the range, and the bin at either end is dropped when its centre is outside.
+__device__ __forceinline__ void mon_wave_footprint(const double* __restrict__ e, int32_t nb, double lo, double hi, int32_t& k0, int32_t& k1) {
+    k0 = mon_beam_first(e, nb, lo), k1 = mon_beam_last(e, nb, hi);
+    if (k0 <= k1 && 0.5 * (e[k0] + e[k0 + 1]) < lo) ++k0;
+    if (k0 <= k1 && 0.5 * (e[k1] + e[k1 + 1]) > hi) --k1;
+}
+__global__ __launch_bounds__(MON_THREADS, 4) void k_mon_wave(const ot_monitor* __restrict__ mons, int32_t n_mon, MonSource src, int64_t n, int32_t iters,
+                                                          const int32_t* __restrict__ seg_count, int64_t n_rays, MonImage img, MonWave wav) {
+    extern __shared__ double mon_wave_lds[];  // the waves' strips, then re, im, tally
+    double* re = mon_wave_lds + MON_WAVES * MON_WAVE_STRIP;
+    double* im = re + img.lds_bins;
+    int32_t* tally = reinterpret_cast<int32_t*>(im + img.lds_bins);
+    for (int32_t b = threadIdx.x; b < img.lds_bins; b += MON_THREADS) re[b] = 0.0, im[b] = 0.0, tally[b] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    double* strip = mon_wave_lds + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * MON_WAVE_STRIP;
+    const int32_t per_mon = img.nby * img.nbz;
+    const int64_t first = (int64_t)blockIdx.x * iters * MON_THREADS;
+    int32_t skipped = 0, aliased = 0;
+    for (int32_t it = 0; it < iters && first + (int64_t)it * MON_THREADS < n; ++it) {
+        int32_t tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));  // (opaque: the seven per-lane plane addresses are formed here, not held across the loop)
+        const int64_t s = first + (int64_t)it * MON_THREADS + tid;
+        if (!__ballot(mon_load(src, s, n, seg_count, n_rays).valid)) continue;
+        // the 64 slots of a wave are one tile: its place is a scalar, and the lane's within it one 32-bit offset for every plane
+        const int64_t tile = __builtin_amdgcn_readfirstlane((int32_t)(s >> 6));
+        const int64_t at_tile = tile * src.tile_stride;
+        const uint32_t at_lane = (uint32_t)(lane * 8);
+        for (int32_t m = 0; m < n_mon; ++m) {
+            // the segment again for every monitor (from the cache): held across the deposits it would cost 14 registers
+            asm volatile("" : "+v"(tid));
+            const MonSeg g = mon_load(src, first + (int64_t)it * MON_THREADS + tid, n, seg_count, n_rays);
+            double Px, Py, Pz, t;
+            const bool hit = g.valid && mon_hit(mons[m], g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, g.len, Px, Py, Pz, t);
+            if (!__ballot(hit)) continue;
+            const double* ax = img.axes + 6 * m;
+            const double* ey = img.edges + (int64_t)m * (img.nby + img.nbz + 2);
+            const double* ez = ey + img.nby + 1;
+            // the lane's own hit: A, w^2, the rates, the count of its centre, its footprint and the sampling test
+            double y0 = 0.0, z0 = 0.0, w2 = 0.0, Are = 0.0, Aim = 0.0, f = 0.0, ry = 0.0, rz = 0.0, kc = 0.0;
+            int32_t ky0 = 0, ky1 = -1, kz0 = 0, kz1 = -1;
+            bool usable = true, alias = false;
+            if (hit) {
+                double wl = wav.wavelength_uniform;
+                if (wav.wavelength) {
+                    const int32_t ray = *reinterpret_cast<const int32_t*>(src.ray + tile * src.ray_stride + (uint32_t)(lane * 4));
+                    usable = ray >= 0 && ray < wav.n_wavelengths;
+                    if (usable) wl = wav.wavelength[ray];
+                }
+                const double qr = *reinterpret_cast<const double*>(wav.q_re + at_tile + at_lane) + t;
+                const double qi = *reinterpret_cast<const double*>(wav.q_im + at_tile + at_lane);
+                const double n_index = *reinterpret_cast<const double*>(wav.n_index + at_tile + at_lane);
+                const double q2 = qr * qr + qi * qi;
+                w2 = wl * q2 / (n_index * M_PI * qi);
+                const double w = sqrt(w2);
+                usable = usable && wl > 0.0 && wl < HUGE_VAL && n_index > 0.0 && n_index < HUGE_VAL && qi > 0.0 && qi < HUGE_VAL && w > 0.0 && w < HUGE_VAL;
+                if (usable) {
+                    y0 = Px * ax[0] + Py * ax[1] + Pz * ax[2];
+                    z0 = Px * ax[3] + Py * ax[4] + Pz * ax[5];
+                    const int32_t ky = mon_bin(ey, img.nby, y0), kz = mon_bin(ez, img.nbz, z0);
+                    if (ky >= 0 && kz >= 0) {  // the centre is counted where the image mode counts the hit
+                        const int32_t bin = m * per_mon + ky * img.nbz + kz;
+                        if (img.lds_bins) atomicAdd(&tally[bin], 1);
+                        else atomicAdd(&img.counts[bin], 1ull);
+                    }
+                    const double reach = 6.0 * w;
+                    mon_wave_footprint(ey, img.nby, y0 - reach, y0 + reach, ky0, ky1);
+                    mon_wave_footprint(ez, img.nbz, z0 - reach, z0 + reach, kz0, kz1);
+                    if (ky0 <= ky1 && kz0 <= kz1) {
+                        double a = *reinterpret_cast<const double*>(img.intensity + at_tile + at_lane);
+                        if (wav.amplitude_mode == 0) a = sqrt(a);
+                        const double L = t * n_index + *reinterpret_cast<const double*>(wav.pathlength + at_tile + at_lane);
+                        f = L / wl;
+                        f -= floor(f);  // the cycles of the path ride along y: one phasor less a hit
+                        Are = a * sqrt(2.0 / (M_PI * w2)), Aim = 0.0;
+                        if (wav.gouy) {  // exp(-i g), g = atan2(qr, qi), is (qi - i qr) / |q|
+                            const double inv = Are / sqrt(q2);
+                            Are = qi * inv, Aim = -qr * inv;
+                        }
+                        ry = n_index * (g.dx * ax[0] + g.dy * ax[1] + g.dz * ax[2]) / wl;
+                        rz = n_index * (g.dx * ax[3] + g.dy * ax[4] + g.dz * ax[5]) / wl;
+                        kc = n_index * qr / (2.0 * wl * q2);
+                        // the largest cycle rate over the footprint, at one of its end centres, in cycles a bin
+                        const double by0 = 0.5 * (ey[ky0] + ey[ky0 + 1]) - y0, by1 = 0.5 * (ey[ky1] + ey[ky1 + 1]) - y0;
+                        const double bz0 = 0.5 * (ez[kz0] + ez[kz0 + 1]) - z0, bz1 = 0.5 * (ez[kz1] + ez[kz1 + 1]) - z0;
+                        const double turn_y = fmax(fabs(ry + 2.0 * kc * by0), fabs(ry + 2.0 * kc * by1)) * ((ey[img.nby] - ey[0]) / (double)img.nby);
+                        const double turn_z = fmax(fabs(rz + 2.0 * kc * bz0), fabs(rz + 2.0 * kc * bz1)) * ((ez[img.nbz] - ez[0]) / (double)img.nbz);
+                        alias = turn_y > 0.5 || turn_z > 0.5;
+                    }
+                }
+            }
+            // (wave-wide tallies: scalars)
+            skipped += (int32_t)__popcll(__ballot(hit && !usable));
+            aliased += (int32_t)__popcll(__ballot(alias));
+            // the wave takes its hits one at a time
+            for (unsigned long long rest = __ballot(ky0 <= ky1 && kz0 <= kz1); rest; rest &= rest - 1) {
+                const int from = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(rest));
+                mon_wave_deposit(ey, ez, img.nbz, mon_lane_value(y0, from), mon_lane_value(z0, from), mon_lane_value(w2, from), mon_lane_value(Are, from),
+                                 mon_lane_value(Aim, from), mon_lane_value(f, from), mon_lane_value(ry, from), mon_lane_value(rz, from), mon_lane_value(kc, from),
+                                 __builtin_amdgcn_readlane(ky0, from), __builtin_amdgcn_readlane(ky1, from), __builtin_amdgcn_readlane(kz0, from),
+                                 __builtin_amdgcn_readlane(kz1, from), strip, lane, img.lds_bins ? re + m * per_mon : nullptr, im + m * per_mon,
+                                 wav.re + (int64_t)m * per_mon, wav.im + (int64_t)m * per_mon);
+            }
+        }
+    }
+    if (lane == 0 && skipped) atomicAdd(wav.skipped, (unsigned long long)skipped);
+    if (lane == 0 && aliased) atomicAdd(wav.aliased, (unsigned long long)aliased);
+    __syncthreads();
+    for (int32_t b = threadIdx.x; b < img.lds_bins; b += MON_THREADS) {  // consecutive lanes, consecutive bins
+        const int32_t c = tally[b];
+        const double r = re[b], i = im[b];
+        if (c) atomicAdd(&img.counts[b], (unsigned long long)c);
+        if (r != 0.0) unsafeAtomicAdd(&wav.re[b], r);
+        if (i != 0.0) unsafeAtomicAdd(&wav.im[b], i);
+    }
 }
 // off = the exclusive scan of count (n_mon * gridDim.x + 1 elements).  Position of a hit in the concatenated output: first[0]
 // (the hits of the monitors of earlier launches: the host walks long lists MON_MAX monitors at a time) + off[m][g] + hits of

@@ -1787,13 +1787,14 @@ static int check_image_call(const ot_ctx* c, const ot_monitor* mons, int32_t n_m
 
 // The launches of a checked call whose outputs are zeroed or kept: the monitors, edges and axes to the device, then k_mon_count in
 // image mode (fld.re and beam.power NULL, 12 bytes of LDS a bin), field mode (20) or beam mode (12, behind the waves' edge strips)
-// once per pass of the plan.  img.counts / img.weights, fld.re / fld.im and beam.power come in as the images of monitor 0 and go
+// — or, with `wav`, k_mon_wave (20, behind its strips) — once per pass of the plan.  img.counts / img.weights, fld.re / fld.im and beam.power come in as the images of monitor 0 and go
 // to the kernel as those of the pass's first monitor.
 static int image_passes(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, const ot_segment_source* src,
-                        int64_t n, const int32_t* seg_count, int64_t n_rays, const ImagePlan& plan, MonImage img, MonField fld, MonBeam beam) {
+                        int64_t n, const int32_t* seg_count, int64_t n_rays, const ImagePlan& plan, MonImage img, MonField fld, MonBeam beam,
+                        const MonWave* wav = nullptr) {
     const int32_t n_edges = img.nby + img.nbz + 2;
-    const size_t bins = (size_t)img.nby * img.nbz, bytes_a_bin = fld.re ? 20 : 12;
-    const size_t strips = beam.power ? sizeof(double) * MON_WAVES * MON_BEAM_STRIP : 0;
+    const size_t bins = (size_t)img.nby * img.nbz, bytes_a_bin = fld.re || wav ? 20 : 12;
+    const size_t strips = sizeof(double) * MON_WAVES * (wav ? MON_WAVE_STRIP : beam.power ? MON_BEAM_STRIP : 0);
     // the partition of k_mon_count, with workgroups long enough to be worth an image of their own: a thousand of them at most
     // (two rounds of the chip at two a CU), each of which zeroes and flushes its LDS image once
     const int32_t iters = (int32_t)std::max<int64_t>(8, (n + 1024 * MON_THREADS - 1) / (1024 * MON_THREADS));
@@ -1822,9 +1823,16 @@ static int image_passes(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, c
         pass.counts += m0 * bins;
         if (beam.power) pass_beam.power += m0 * bins;
         else if (fld.re) pass_field.re += m0 * bins, pass_field.im += m0 * bins;
-        else pass.weights += m0 * bins;
+        else if (!wav) pass.weights += m0 * bins;
         pass.edges = d_edges + (int64_t)m0 * n_edges, pass.axes = d_axes + (int64_t)m0 * 6;
         pass.lds_bins = plan.lds ? (int32_t)(nm * bins) : 0;
+        if (wav) {  // a kernel of its own, on the same partition
+            MonWave pass_wave = *wav;
+            pass_wave.re += m0 * bins, pass_wave.im += m0 * bins;
+            hipLaunchKernelGGL(k_mon_wave, dim3((unsigned)grid), dim3(MON_THREADS), strips + (size_t)pass.lds_bins * bytes_a_bin, c->stream, table + m0, nm,
+                               ms, n, iters, seg_count, n_rays, pass, pass_wave);
+            continue;
+        }
         hipLaunchKernelGGL(k_mon_count, dim3((unsigned)grid), dim3(MON_THREADS), strips + (size_t)pass.lds_bins * bytes_a_bin, c->stream, table + m0, nm,
                            ms, n, iters, seg_count, n_rays, (int32_t*)nullptr, pass, pass_field, pass_beam);
     }
@@ -1919,6 +1927,46 @@ int ot_monitor_beam_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, 
     beam.skipped = (unsigned long long*)skipped;
     return image_passes(c, mons, n_monitors, axes, edges, src, n, seg_count, n_rays, image_plan(n_monitors, nby, nbz, MON_BEAM_LDS_BINS), img, MonField{},
                         beam);
+}
+
+int ot_monitor_wave_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, int32_t nby,
+                         int32_t nbz, const ot_segment_source* src, const void* intensity, const void* n_index, const void* pathlength,
+                         const void* q_re, const void* q_im, const double* wavelength, int64_t n_wavelengths, double wavelength_uniform,
+                         int32_t amplitude_mode, int32_t gouy, int64_t n, const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* re,
+                         double* im, int64_t* skipped, int64_t* aliased, int32_t accumulate) {
+    if (!counts || !re || !im || !skipped || !aliased) return fail(OT_ERR_INVALID, "NULL argument");
+    const int rc = check_image_call(c, mons, n_monitors, axes, edges, nby, nbz, src, intensity, n, seg_count, n_rays, accumulate);
+    if (rc) return rc;
+    if (src->width != 8) return fail(OT_ERR_INVALID, "a beam field needs double-precision segments: width must be 8");
+    if (!n_index || !pathlength || !q_re || !q_im) return fail(OT_ERR_INVALID, "NULL n_index, pathlength, q_re or q_im");
+    if (wavelength && (n_wavelengths < 1 || n_wavelengths >= (int64_t)1 << 31)) return fail(OT_ERR_INVALID, "n_wavelengths must be at least 1 (and below 2^31)");
+    if (!wavelength && !(std::isfinite(wavelength_uniform) && wavelength_uniform > 0.0))
+        return fail(OT_ERR_INVALID, "wavelength_uniform must be finite and > 0 when there is no wavelength array");
+    if (amplitude_mode != 0 && amplitude_mode != 1) return fail(OT_ERR_INVALID, "amplitude_mode must be 0 (sqrt) or 1 (linear)");
+    if (gouy != 0 && gouy != 1) return fail(OT_ERR_INVALID, "gouy must be 0 or 1");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bins = (size_t)nby * nbz;
+    if (!accumulate) {
+        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * bins * n_monitors, c->stream));
+        HIP_TRY(hipMemsetAsync(re, 0, sizeof(double) * bins * n_monitors, c->stream));
+        HIP_TRY(hipMemsetAsync(im, 0, sizeof(double) * bins * n_monitors, c->stream));
+        HIP_TRY(hipMemsetAsync(skipped, 0, sizeof(int64_t), c->stream));
+        HIP_TRY(hipMemsetAsync(aliased, 0, sizeof(int64_t), c->stream));
+    }
+    if (n == 0) return 0;
+    MonImage img{};
+    img.counts = (unsigned long long*)counts;
+    img.intensity = (const uint8_t*)intensity;
+    img.nby = nby, img.nbz = nbz;
+    MonWave wav{};
+    wav.re = re, wav.im = im;
+    wav.q_re = (const uint8_t*)q_re, wav.q_im = (const uint8_t*)q_im;
+    wav.n_index = (const uint8_t*)n_index, wav.pathlength = (const uint8_t*)pathlength;
+    wav.wavelength = wavelength, wav.n_wavelengths = (int32_t)n_wavelengths, wav.wavelength_uniform = wavelength_uniform;
+    wav.skipped = (unsigned long long*)skipped, wav.aliased = (unsigned long long*)aliased;
+    wav.amplitude_mode = amplitude_mode, wav.gouy = gouy;
+    return image_passes(c, mons, n_monitors, axes, edges, src, n, seg_count, n_rays, image_plan(n_monitors, nby, nbz, MON_WAVE_LDS_BINS), img, MonField{},
+                        MonBeam{}, &wav);
 }
 
 int ot_debug_last_launch(ot_ctx* c, int32_t info[8]) {

@@ -121,6 +121,7 @@ IMAGE_MAX_MONITORS = 32                  # MON_MAX: monitors of one launch
 
 FIELD_LDS_BINS = (65536 - 32 * 4) // 20  # MON_FIELD_LDS_BINS: the same LDS at 20 bytes a bin (re, im, count) — ot_monitor_field_many
 BEAM_LDS_BINS = (65536 - 32 * 4 - 4 * 128 * 8) // 12  # MON_BEAM_LDS_BINS: 12 bytes a bin (power, count) next to four waves' erf tables — ot_monitor_beam_many
+WAVE_LDS_BINS = (65536 - 32 * 4 - 4 * 256 * 8) // 20  # MON_WAVE_LDS_BINS: 20 bytes a bin (re, im, count) next to four waves' strips of 256 doubles — ot_monitor_wave_many
 
 
 def image_plan(n_monitors, nby, nbz, budget=IMAGE_LDS_BINS):
@@ -144,6 +145,11 @@ def field_plan(n_monitors, nby, nbz):
 def beam_plan(n_monitors, nby, nbz):
     """`image_plan` for ot_monitor_beam_many: the same rule with BEAM_LDS_BINS (five monitors of 30 x 30 a launch; six go 3 + 3)."""
     return image_plan(n_monitors, nby, nbz, BEAM_LDS_BINS)
+
+
+def wave_plan(n_monitors, nby, nbz):
+    """`image_plan` for ot_monitor_wave_many: the same rule with WAVE_LDS_BINS (three monitors of 30 x 30 a launch; four go 2 + 2)."""
+    return image_plan(n_monitors, nby, nbz, WAVE_LDS_BINS)
 
 
 # What a whole-trace launch writes, by library call: (the SegmentBatch made when the caller passes none, what makes a passed
@@ -874,6 +880,55 @@ class Engine:
                                                 None if count is None else count.data_ptr(), n_rays, counts.data_ptr(), power.data_ptr(),
                                                 skipped.data_ptr(), 0 if into is None else 1), self.lib)
         return counts, power, skipped
+
+    def monitor_wave_many(self, monitor_structs, axes, edges, bins, segs: SegmentBatch, wavelength, amplitude_mode=0, gouy=0, into=None):
+        """Coherent Gaussian-beam detector images of a list of monitors over a double-precision SegmentBatch read as it lies
+        (ot_monitor_wave_many: `monitor_field_many` with every hit a Gaussian beam — envelope, wavefront curvature and tilt from the
+        segments' q, n and direction — sampled at the bin centres).  axes, edges, bins, wavelength, amplitude_mode as there; gouy: 1
+        subtracts atan2(Re q, Im q) from every hit's phase.  Returns (counts, re, im, skipped, aliased): int64 / float64 / float64
+        [M, nby, nbz] device tensors and two int64 device tensors of one element (hits left out: no q, or an unusable ray, wavelength
+        or index; hits whose phase turns more than half a cycle a bin somewhere on their footprint, deposited all the same), zeroed
+        by the call — or `into`, such a tuple from an earlier call, with this call's hits added to it."""
+        with self.lock:
+            return self._monitor_wave_many(list(monitor_structs), axes, edges, bins, segs, wavelength, amplitude_mode, gouy, into)
+
+    def _monitor_wave_many(self, mons, axes, edges, bins, segs, wavelength, amplitude_mode, gouy, into):
+        dev, M, (nby, nbz) = segs.device, len(mons), bins
+        axes, edges = np.ascontiguousarray(axes, dtype=np.float64), np.ascontiguousarray(edges, dtype=np.float64)
+        if axes.shape != (M, 6) or edges.shape != (M, nby + nbz + 2):
+            raise ValueError(f"axes must be [{M}, 6] and edges [{M}, {nby + nbz + 2}]")
+        if segs.precision != "f64":
+            raise ValueError("a beam field needs double-precision segments")
+        if torch.is_tensor(wavelength):
+            if wavelength.dtype != torch.float64 or wavelength.dim() != 1 or not wavelength.is_contiguous() or wavelength.device.type != dev.type:
+                raise ValueError(f"wavelength: a float or a contiguous float64 vector on {dev}")
+            table_ptr, n_table, uniform = (wavelength.data_ptr() if wavelength.numel() else None), int(wavelength.numel()), 0.0
+        else:
+            table_ptr, n_table, uniform = None, 0, float(wavelength)
+        if into is None:
+            counts = torch.empty((M, nby, nbz), dtype=torch.int64, device=dev)  # (the call zeroes them)
+            re, im = (torch.empty((M, nby, nbz), dtype=torch.float64, device=dev) for _ in range(2))
+            skipped, aliased = (torch.empty(1, dtype=torch.int64, device=dev) for _ in range(2))
+        else:
+            counts, re, im, skipped, aliased = into
+            for t, dt in ((counts, torch.int64), (re, torch.float64), (im, torch.float64)):
+                if tuple(t.shape) != (M, nby, nbz) or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type:
+                    raise ValueError(f"into: contiguous int64 counts and float64 re, im of shape [{M}, {nby}, {nbz}] on {dev}")
+            for t in (skipped, aliased):
+                if tuple(t.shape) != (1,) or t.dtype != torch.int64 or t.device.type != dev.type:
+                    raise ValueError(f"into: skipped and aliased are one int64 each on {dev}")
+        src, n_segments, count, n_rays = segment_source(segs)
+        if M == 0 or n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
+            return (counts.zero_(), re.zero_(), im.zero_(), skipped.zero_(), aliased.zero_()) if into is None else (counts, re, im, skipped, aliased)
+        table = (abi.OtMonitor * M)(*mons)
+        as_doubles = C.POINTER(C.c_double)
+        abi.check(self.lib.ot_monitor_wave_many(self._ctx, table, M, axes.ctypes.data_as(as_doubles), edges.ctypes.data_as(as_doubles), nby, nbz,
+                                                C.byref(src), segs.field("intensity").data_ptr(), segs.field("n").data_ptr(),
+                                                segs.field("pathlength").data_ptr(), segs.field("q_re").data_ptr(), segs.field("q_im").data_ptr(),
+                                                table_ptr, n_table, uniform, int(amplitude_mode), int(gouy), n_segments,
+                                                None if count is None else count.data_ptr(), n_rays, counts.data_ptr(), re.data_ptr(),
+                                                im.data_ptr(), skipped.data_ptr(), aliased.data_ptr(), 0 if into is None else 1), self.lib)
+        return counts, re, im, skipped, aliased
 
     # -- measurement ---------------------------------------------------------------------------
     def timing(self, enabled=True):

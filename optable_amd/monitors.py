@@ -291,6 +291,34 @@ class MonitorHits:
         z = self.qList(sort).real
         return torch.where(along > 0, -z, z)
 
+    def radiusList(self, sort="YZ"):
+        """The radius of curvature of every hit's wavefront at the monitor, `Ray.radius_of_curvature(q)` = |q|^2 / Re(q) with q =
+        `qList` (inf at a waist, negative before it): the R of the curvature phase k r^2 / (2 R) in `OpticalTable.wave_all`."""
+        q = self.qList(sort)
+        return (q.real**2 + q.imag**2) / q.real
+
+    def gouyList(self, sort="YZ"):
+        """The Gouy phase of every hit's beam at the monitor, atan2(Re(q), Im(q)) with q = `qList`: what `wave_all(gouy=True)`
+        subtracts from the phase.  The tracer's q does not accumulate it across lenses: exact only for a beam that has met no
+        focusing element since its waist."""
+        import torch
+
+        q = self.qList(sort)
+        return torch.atan2(q.real, q.imag)
+
+    def amplitudeList(self, wavelength, sort="YZ", amplitude="sqrt"):
+        """The on-axis field amplitude of every hit's beam at the monitor, a sqrt(2 / pi) / w with w = `spotsizeList` and a =
+        sqrt(IList) (amplitude="sqrt") or IList ("linear"): the peak of |u| in `OpticalTable.wave_all`, whose square integrates
+        to a^2 over the plane."""
+        import torch
+
+        if amplitude not in ("sqrt", "linear"):
+            raise ValueError(f"amplitude must be 'sqrt' or 'linear', not {amplitude!r}")
+        a = self.IList(sort).double()
+        if amplitude == "sqrt":
+            a = torch.sqrt(a)
+        return a * np.sqrt(2 / np.pi) / self.spotsizeList(wavelength, sort)
+
     def directionList(self, sort="YZ"):
         import torch
 
@@ -408,3 +436,45 @@ class MonitorBeam:
     def to_host(self):
         """(counts, power, y_edges, z_edges) as numpy arrays."""
         return self.counts.cpu().numpy(), self.power.cpu().numpy(), self.y_edges, self.z_edges
+
+
+class MonitorWave:
+    """A monitor's hits as the coherent image their Gaussian beams make, summed on the device (`OpticalTable.wave_all`): `counts`
+    (int64, the hit centres, as `MonitorImage.counts`) and `re`, `im` (float64), [nby, nbz] device tensors over `y_edges` x
+    `z_edges` (numpy) — per bin the sum over the hits of the beam's complex field at the bin's CENTRE: amplitude
+    `MonitorHits.amplitudeList` under a Gaussian envelope of radius `spotsizeList` around (yList, zList), with the phase
+    `phaseList` plus the beam's tilt (`tYList`, `tZList`) and wavefront curvature (`radiusList`) across the monitor.  `aliased`:
+    how many hits of the call (all its monitors together, every call that added `into` it) turn their phase more than half a cycle
+    from one bin centre to the next somewhere on their footprint — where it is not 0 the image is undersampled.  Counts are exact
+    and the same every run; re and im are atomic fp64 sums whose last bits depend on the order of arrival."""
+
+    def __init__(self, monitor, counts, re, im, y_edges, z_edges, aliased=0, stack=None):
+        self.monitor, self.counts, self.re, self.im, self.y_edges, self.z_edges = monitor, counts, re, im, y_edges, z_edges
+        self.aliased = aliased
+        self._stack = stack  # (counts, re, im, skipped, aliased, position) of the call's [M, nby, nbz] tensors, which `into=` adds to
+
+    @property
+    def bins(self):
+        return tuple(self.counts.shape)
+
+    @property
+    def field(self):
+        """re + i im, a complex128 tensor."""
+        import torch
+
+        return torch.complex(self.re, self.im)
+
+    def irradiance(self):
+        """|field|^2 = re^2 + im^2: power per unit area at every bin's centre, a float64 [nby, nbz] device tensor."""
+        return self.re**2 + self.im**2
+
+    def power(self):
+        """`irradiance()` times the bin's area (y width x z width): the power a bin receives, midpoint rule."""
+        import torch
+
+        area = np.outer(np.diff(self.y_edges), np.diff(self.z_edges))
+        return self.irradiance() * torch.as_tensor(area, device=self.re.device)
+
+    def to_host(self):
+        """(counts, re, im, y_edges, z_edges) as numpy arrays."""
+        return self.counts.cpu().numpy(), self.re.cpu().numpy(), self.im.cpu().numpy(), self.y_edges, self.z_edges

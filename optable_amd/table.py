@@ -358,6 +358,71 @@ class OpticalTable:
         """One monitor as a Gaussian-beam image (`beam_all` for it alone): a `MonitorBeam`."""
         return self.beam_all(segs, wavelength, bins=bins, monitors=[monitor])[0]
 
+    def wave_all(self, segs, wavelength=0.0, bins=30, monitors=None, into=None, amplitude="sqrt", gouy=False):
+        """Every monitor of the table (or those given) as the COHERENT image its GAUSSIAN BEAMS make: one `MonitorWave` per monitor,
+        in their order — per bin of `image_all`'s images the count of hit centres and the complex sum over the hits of the beam's
+        field SAMPLED AT THE BIN CENTRE (yc, zc),
+            u = a sqrt(2 / (pi w^2)) exp(-(Dy^2 + Dz^2) / w^2) exp(i (2 pi frac(cycles) - g)),     Dy = yc - y0, Dz = zc - z0,
+            cycles = (pathlength + t n) / wavelength + n (ty Dy + tz Dz) / wavelength + n Re(q) (Dy^2 + Dz^2) / (2 wavelength |q|^2):
+        `Ray.phase(t)` as in `field_all`, the beam's tilt (`MonitorHits.tYList` / `tZList`) and its wavefront curvature
+        (`radiusList`), under the envelope of `beam_all`'s spot w (`spotsizeList`); summed on the device in the pass that finds the
+        hits, with no hit list (ot_monitor_wave_many).  a = sqrt(intensity) (amplitude="sqrt") or the intensity as it stands
+        ("linear"), as in `field_all`.  Two traced rays give an interferometer's fringes; `MonitorWave.irradiance()` is what a
+        camera shows.  gouy=True subtracts g = atan2(Re q, Im q) from every hit's phase (`gouyList`); the tracer's q does not
+        accumulate the Gouy phase across lenses, so g is exact only for a beam that has met no focusing element since its waist
+        (default False: g = 0).  Limits: the envelope is taken at normal incidence (a tilted spot is not stretched), q is not advanced
+        across the tilt, bin centres more than 6 w from the hit's along an axis are left out (below exp(-36) of the peak), no pi
+        on reflection.  A field sampled at bin centres means nothing where the phase turns more than half a cycle from one bin to
+        the next: hits for which it does somewhere on their footprint are deposited all the same, counted in `MonitorWave.aliased`
+        and announced by one RuntimeWarning.  `wavelength`, `into` and the double-precision `segs` as for `field_all` (a field is
+        linear: chunks add).  A hit without q or with an unusable index raises ValueError, as in `beam_all`."""
+        import warnings
+        from .monitors import MonitorWave, image_bins, image_edges
+
+        nby, nbz = image_bins(bins)
+        if amplitude not in ("sqrt", "linear"):
+            raise ValueError(f"amplitude must be 'sqrt' or 'linear', not {amplitude!r}")
+        if not isinstance(gouy, (bool, np.bool_)):
+            raise ValueError(f"gouy must be True or False, not {gouy!r}")
+        if segs.precision != "f64":
+            raise ValueError("wave_all needs a double-precision SegmentBatch: a field from single-precision path lengths is refused, not approximated")
+        wavelength = _wavelengths_of(wavelength, segs, "a beam field")
+        monitors = list(self.monitors if monitors is None else monitors)
+        edges = [image_edges(m, nby, nbz) for m in monitors]
+        stack, before = None, 0
+        if into is not None:
+            into = list(into)
+            if len(into) != len(monitors) or any(not isinstance(f, MonitorWave) or f.monitor is not m or f.bins != (nby, nbz) for f, m in zip(into, monitors)):
+                raise ValueError("into: the list an earlier wave_all returned for the same monitors and bins")
+            if any(f._stack is None or f._stack[0] is not into[0]._stack[0] or f._stack[5] != k or len(f._stack[0]) != len(into) for k, f in enumerate(into)):
+                raise ValueError("into: the whole list of one earlier call, in its order")
+            if not monitors:
+                return into
+            stack, before = into[0]._stack[:5], into[0].aliased
+        axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in monitors], dtype=float).reshape(len(monitors), 6)
+        table = np.array([np.concatenate(e) for e in edges], dtype=float).reshape(len(monitors), nby + nbz + 2)
+        counts, re, im, skipped, aliased = _engine().monitor_wave_many([monitor_struct(m) for m in monitors], axes, table, (nby, nbz), segs, wavelength,
+                                                                       amplitude_mode=("sqrt", "linear").index(amplitude), gouy=int(gouy), into=stack)
+        left_out = int(skipped.item())
+        if left_out:
+            raise ValueError(f"wave_all: {left_out} hits left out — they carry no q (a batch traced without a Gaussian beam), or their wavelength "
+                             "or refractive index is not finite and > 0, or their `ray` is no index into the wavelengths given")
+        total = int(aliased.item())
+        if total > before:
+            warnings.warn(f"wave_all: {total - before} hits are aliased — somewhere on their footprint the phase of their beam turns more than half "
+                          "a cycle from one bin centre to the next, and the sampled field means nothing there: use a smaller monitor or more bins",
+                          RuntimeWarning, stacklevel=2)
+        if into is not None:
+            for f in into:
+                f.aliased = total
+            return into
+        return [MonitorWave(m, counts[k], re[k], im[k], ey, ez, total, stack=(counts, re, im, skipped, aliased, k))
+                for k, (m, (ey, ez)) in enumerate(zip(monitors, edges))]
+
+    def wave_batch(self, monitor, segs, wavelength=0.0, bins=30, amplitude="sqrt", gouy=False):
+        """One monitor as a coherent Gaussian-beam image (`wave_all` for it alone): a `MonitorWave`."""
+        return self.wave_all(segs, wavelength, bins=bins, monitors=[monitor], amplitude=amplitude, gouy=gouy)[0]
+
     # -- ABCD extraction (optical_table.py:211-297), a caller of the hot path ----------------------
     def calculate_abcd_matrix(self, mon0, mon1, rays, disp=1e-5, rot=1e-5, debugaxs=None):
         """Per-ray 2x2 ABCD matrix between two monitors by finite differences: three traces
@@ -635,7 +700,7 @@ _HOOK_MEMO = {}
 
 
 def _wavelengths_of(wavelength, segs, what):
-    """The `wavelength` argument of `field_all` / `beam_all` as the engine takes it: a float > 0, or the double wavelengths of the
+    """The `wavelength` argument of `field_all` / `beam_all` / `wave_all` as the engine takes it: a float > 0, or the double wavelengths of the
     `RayBatch` that was traced (one per input ray of `segs`); anything else is a ValueError that names `what` needs it."""
     import torch
     from .batch import RayBatch
