@@ -347,6 +347,43 @@ int ot_trace_tiled_resident_f32(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays
 int ot_trace_resident_plan(ot_ctx* ctx, int32_t real_bytes, uint32_t uniform_mask, int64_t n_rays, int32_t max_segments,
                            int32_t* planes);
 
+/* First-segment fields.  Segment 0 of a ray's record is the input ray handed through, whatever the scene does: the lane-per-ray
+ * kernel stores there what it loaded.  So where the batch holds ONE bit pattern in a field (uniform_mask), slot 0 * n_rays + i of
+ * that plane receives the same pattern on every launch, and a caller that traces batch after batch from the same source into the
+ * same output rewrites it for nothing.  `first_mask` uses the OT_UNIFORM_* bit positions of the eleven real fields a record
+ * shares with a ray (OT_FIRST_FIELDS: ox .. dz, q_re, q_im, intensity, n, pathlength).  A set bit is the caller's word that, for
+ * every ray i with |seg_count[i]| >= 1 AS seg_count STANDS WHEN THE CALL IS MADE, slot 0 * n_rays + i of that plane already holds
+ * the bit pattern this launch would write there.  The kernel then leaves the plane unwritten at segment 0 under the rule of the
+ * resident planes: for a whole wave or not at all (a wave with a ray whose old count is 0 writes whole records), and a ray that
+ * arrives dead always gets its full record.  Segments k >= 1 are not concerned.  Same records either way; cfg 2 (a point source:
+ * ox, oy, oz, q_re, q_im, pathlength beside the resident n and intensity) writes 48 bytes per ray fewer.
+ * The library masks the caller's word with the call's uniform_mask, so a bit for a field that is not flagged uniform skips nothing;
+ * a mask that is wrong about the OUTPUT is the caller's error, as for resident_mask.  Both masks are independent: resident_mask
+ * is checked and honoured exactly as by ot_trace_resident_* (which call these with first_mask = 0).  Bits outside OT_FIRST_FIELDS
+ * are OT_ERR_INVALID.  The mask is dropped when the call lands on another kernel, when max_segments exceeds 32767, after
+ * ot_set_option(OT_OPT_UNIFORM, 0), and unless OT_OPT_RESIDENT is 1. */
+enum ot_first_bits {
+    OT_FIRST_FIELDS = OT_UNIFORM_OX | OT_UNIFORM_OY | OT_UNIFORM_OZ | OT_UNIFORM_DX | OT_UNIFORM_DY | OT_UNIFORM_DZ | OT_UNIFORM_Q_RE |
+                      OT_UNIFORM_Q_IM | OT_UNIFORM_INTENSITY | OT_UNIFORM_N | OT_UNIFORM_PATHLENGTH
+};
+int ot_trace_reuse_f64(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments,
+                       const ot_segments* out, int32_t* seg_count, int32_t* counts,
+                       int32_t n_count_classes, uint32_t uniform_mask, uint32_t resident_mask, uint32_t first_mask);
+int ot_trace_reuse_f32(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments,
+                       const ot_segments* out, int32_t* seg_count, int32_t* counts,
+                       int32_t n_count_classes, uint32_t uniform_mask, uint32_t resident_mask, uint32_t first_mask);
+int ot_trace_tiled_reuse_f64(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments, void* tiles,
+                             int64_t capacity, int32_t* seg_count, int32_t* counts, int32_t n_count_classes,
+                             uint32_t uniform_mask, uint32_t resident_mask, uint32_t first_mask);
+int ot_trace_tiled_reuse_f32(ot_ctx* ctx, const ot_rays* rays, int64_t n_rays, int32_t max_segments, void* tiles,
+                             int64_t capacity, int32_t* seg_count, int32_t* counts, int32_t n_count_classes,
+                             uint32_t uniform_mask, uint32_t resident_mask, uint32_t first_mask);
+/* ot_trace_resident_plan, and beside it *first_fields = the OT_FIRST_FIELDS bits such a call would honour: the fields of
+ * uniform_mask among the eleven; 0 when the call would not land on the lane-per-ray kernel, n_rays is 0, max_segments exceeds
+ * 32767, OT_OPT_UNIFORM is 0 or OT_OPT_RESIDENT is not 1. */
+int ot_trace_reuse_plan(ot_ctx* ctx, int32_t real_bytes, uint32_t uniform_mask, int64_t n_rays, int32_t max_segments,
+                        int32_t* planes, uint32_t* first_fields);
+
 /* The same trace with the APPEND layout: a dense list of segment records instead of max_segments * n_rays slots.
  * The reference returns a list with one entry per processed segment (optical_table.py:125-134); the [k][ray] slots of
  * ot_trace_* hold that list with a hole for every segment a ray did not live to (cfg 3: 11 GB of slots for 2.8 GB of
@@ -693,8 +730,9 @@ enum ot_option {
                                   wants to go on with a larger budget */
     OT_OPT_UNIFORM = 26,       /* ot_trace_uniform_*, ot_trace_tiled_uniform_*, ot_bench_stream_*uniform_*: 1 (default) the uniform_mask is
                                   honoured; 0 it is dropped and every field is read per ray (A/B runs with one library).  Identical records. */
-    OT_OPT_RESIDENT = 27       /* ot_trace_resident_*, ot_trace_tiled_resident_*: 1 (default) the resident_mask is honoured; 0 it is dropped
-                                  and every record is written whole (A/B runs with one library).  Identical records. */
+    OT_OPT_RESIDENT = 27       /* ot_trace_resident_*, ot_trace_reuse_* and their tiled forms: 1 (default) the resident_mask and the first_mask
+                                  are honoured; 2 the resident_mask only; 0 both are dropped and every record is written whole (A/B runs
+                                  with one library).  Identical records. */
 };
 int ot_set_option(ot_ctx* ctx, int32_t option, int32_t value);
 

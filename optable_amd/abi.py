@@ -92,6 +92,10 @@ UNIFORM_ID, UNIFORM_FLAGS, UNIFORM_ALL = 1 << 12, 1 << 13, (1 << 14) - 1
 # resident_mask of ot_trace_resident_* / ot_trace_tiled_resident_* (== header: OT_RESIDENT_*): planes a reused output already holds
 RESIDENT_RAY, RESIDENT_N, RESIDENT_INTENSITY, RESIDENT_ALL = 1, 2, 4, 7
 RESIDENT_FIELD = {RESIDENT_RAY: "ray", RESIDENT_N: "n", RESIDENT_INTENSITY: "intensity"}  # bit -> SegmentBatch.field name
+# first_mask of ot_trace_reuse_* / ot_trace_tiled_reuse_* (== header: OT_FIRST_FIELDS): the UNIFORM_BIT positions of the eleven real
+# fields a segment record shares with a ray; segment 0 of a reused output already holds the batch's one bit pattern there
+FIRST_FIELD = {UNIFORM_BIT[f]: f for f in RAY_FIELDS if f != "wavelength"}  # bit -> field name (RayBatch and SegmentBatch alike)
+FIRST_FIELDS = sum(FIRST_FIELD)
 
 # every symbol the header declares, with its ctypes signature
 _vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
@@ -119,6 +123,11 @@ SYMBOLS = {
     "ot_trace_tiled_resident_f64": (C.c_int, [_vp, C.POINTER(OtRays), _i64, _i32, _vp, _i64, _vp, _vp, _i32, _u32, _u32]),
     "ot_trace_tiled_resident_f32": (C.c_int, [_vp, C.POINTER(OtRays), _i64, _i32, _vp, _i64, _vp, _vp, _i32, _u32, _u32]),
     "ot_trace_resident_plan": (C.c_int, [_vp, _i32, _u32, _i64, _i32, C.POINTER(_i32)]),
+    "ot_trace_reuse_f64": (C.c_int, _TRACE_ARGS + [_u32, _u32, _u32]),
+    "ot_trace_reuse_f32": (C.c_int, _TRACE_ARGS + [_u32, _u32, _u32]),
+    "ot_trace_tiled_reuse_f64": (C.c_int, [_vp, C.POINTER(OtRays), _i64, _i32, _vp, _i64, _vp, _vp, _i32, _u32, _u32, _u32]),
+    "ot_trace_tiled_reuse_f32": (C.c_int, [_vp, C.POINTER(OtRays), _i64, _i32, _vp, _i64, _vp, _vp, _i32, _u32, _u32, _u32]),
+    "ot_trace_reuse_plan": (C.c_int, [_vp, _i32, _u32, _i64, _i32, C.POINTER(_i32), C.POINTER(_u32)]),
     "ot_bench_stream_uniform_f64": (C.c_int, [_vp, C.POINTER(OtRays), _i64, _i32, C.POINTER(OtSegments), _vp, _u32]),
     "ot_bench_stream_uniform_f32": (C.c_int, [_vp, C.POINTER(OtRays), _i64, _i32, C.POINTER(OtSegments), _vp, _u32]),
     "ot_bench_stream_tiled_uniform_f64": (C.c_int, [_vp, C.POINTER(OtRays), _i64, _i32, _vp, _i64, _vp, _u32]),

@@ -86,6 +86,12 @@ class RayBatch:
             return None
         return self._uniform_value.get(name)
 
+    def uniform_values(self):
+        """{real field: bit pattern} for every field whose hint still holds and whose one value is known (`uniform_bits` of each,
+        with the hint checked once)."""
+        mask = self.uniform_mask
+        return {f: v for f, v in self._uniform_value.items() if mask & abi.UNIFORM_BIT[f]}
+
     def forget_uniform(self):
         """Drop the hint: every field is read per ray again.  For callers that wrote a field behind torch's back."""
         self._uniform = {}
@@ -309,9 +315,17 @@ class SegmentBatch:
     the engine clears it before every launch that writes into the batch.  The hole, as for the input hint: a write torch does
     not see (`tensor.data`, a foreign kernel handed `data_ptr()`, numpy sharing the memory) — whoever writes that way calls
     `forget_resident()`.  Tensors without a version counter (inference mode) carry no token.
+
+    First-segment fields.  Segment 0 of a ray is the input ray handed through, so such a launch also leaves a second token, apart
+    from the first: {record field: bit pattern} for the fields its input batch held ONE known pattern in (`RayBatch.uniform_bits`:
+    a point source's origin, a beam's q, the default pathlength ...), whatever the scene.  The next such launch into the same
+    batch leaves those planes unwritten at k = 0 where its input carries the same pattern (abi.FIRST_FIELD; the library says which
+    it honours).  It stands on the same rule and has the same hole: `n_rays`, layout, engine and stream, and those fields' plane
+    tensors and `count` (tiles: the block) at their `_version`; `forget_resident()` ends both tokens.
     """
 
     _resident = None                # the token (a dict, never mutated in place), or None
+    _first = None                   # the first-segment token (likewise), or None
     tiled = append = False          # defaults for batches assembled field by field (astype, to_slots, table.py)
     trees = False                   # True: `count[i]` rays of a ray TREE per input ray (Engine.trace_trees), not the segments of one path
     block = cursor = _n_valid = count = n_rays = None
@@ -378,7 +392,35 @@ class SegmentBatch:
         """Drop the resident-plane token: the next trace into this batch writes every record whole.  For callers that wrote into
         the batch behind torch's back."""
         self._resident = None
+        self._first = None
         return self
+
+    def _set_first(self, values, n_rays, layout, engine, stream):
+        """After a launch of `engine` on `stream` that wrote this batch through the lane-per-ray entry points: segment 0 of every
+        ray holds, in the record fields of `values` ({field name: bit pattern}, None where the input's was not uniform or not
+        known), that pattern — whether or not the launch skipped anything."""
+        values = {f: int(v) for f, v in values.items() if v is not None and f in abi.FIRST_FIELD.values()}
+        names = ["block"] if layout == "tiled" else [("n_index" if f == "n" else f) for f in values]
+        tensors = [(name, getattr(self, name, None)) for name in names + ["count"]]
+        if not values or any(t is None or t.is_inference() for _, t in tensors):
+            self._first = None
+            return
+        self._first = {"values": values, "n_rays": int(n_rays), "layout": layout, "engine": engine, "stream": stream,
+                       "tensors": [(name, t, t._version) for name, t in tensors]}
+
+    def first_mask(self, n_rays, layout, values, engine, stream):
+        """abi.FIRST_FIELD bits of the record fields a launch of `engine` on `stream` for `n_rays` rays in `layout`, whose input
+        carries the bit patterns `values` ({field name: pattern or None}), may leave unwritten at segment 0: the fields of the
+        token with that very pattern, if every other entry of it still matches; else 0."""
+        tok = self._first
+        if tok is None:
+            return 0
+        if tok["n_rays"] != int(n_rays) or tok["layout"] != layout or tok["engine"] is not engine or tok["stream"] != stream:
+            return 0
+        for name, t, version in tok["tensors"]:
+            if getattr(self, name, None) is not t or t._version != version:
+                return 0
+        return sum(abi.UNIFORM_BIT[f] for f, old in tok["values"].items() if values.get(f) == old)  # (a token entry is never None)
 
     def _resident_tensors(self, planes, layout):
         """[(attribute, tensor)] whose contents the token for `planes` stands on"""

@@ -234,6 +234,51 @@ __device__ __forceinline__ void store_segment_reduced(const SegTiles<T>& out, in
     if (!(resident & OT_RESIDENT_RAY)) st<NT>(q, tree);
     st<NT>(q + 64, surface);
 }
+// First-segment fields (include/optable_hip.h: ot_trace_reuse_*): segment 0 of a ray is the input ray handed through, so where the
+// batch holds one bit pattern in a field and the output's slot 0 already holds it, that plane is left unwritten as well — at k == 0
+// only.  The kernel receives those fields as OT_UNIFORM_* bits above the planes (resident >> FIRST_SHIFT) and hands the stores
+// `first`: that at k == 0, nothing at k >= 1 (scalar: k is the wave's loop counter).  A record with `first` bits goes unpaired, from
+// ONE place in the segment loop (before the ray is handed to interact, as the paired stores are).
+constexpr uint32_t FIRST_SHIFT = 8;
+template <class T, bool NT>
+__device__ __forceinline__ void store_segment_first(const SegsT<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
+                                                    int32_t surface, uint32_t resident, uint32_t first) {
+    if (!(first & OT_UNIFORM_OX)) st<NT>(out.ox + slot, r.ox);
+    if (!(first & OT_UNIFORM_OY)) st<NT>(out.oy + slot, r.oy);
+    if (!(first & OT_UNIFORM_OZ)) st<NT>(out.oz + slot, r.oz);
+    if (!(first & OT_UNIFORM_DX)) st<NT>(out.dx + slot, r.dx);
+    if (!(first & OT_UNIFORM_DY)) st<NT>(out.dy + slot, r.dy);
+    if (!(first & OT_UNIFORM_DZ)) st<NT>(out.dz + slot, r.dz);
+    st<NT>(out.len + slot, len);
+    if (!(resident & OT_RESIDENT_INTENSITY) && !(first & OT_UNIFORM_INTENSITY)) st<NT>(out.I + slot, r.I);
+    if (!(first & OT_UNIFORM_Q_RE)) st<NT>(out.qr + slot, r.qr);
+    if (!(first & OT_UNIFORM_Q_IM)) st<NT>(out.qi + slot, r.qi);
+    if (!(resident & OT_RESIDENT_N) && !(first & OT_UNIFORM_N)) st<NT>(out.n + slot, r.n);
+    if (!(first & OT_UNIFORM_PATHLENGTH)) st<NT>(out.pl + slot, r.pl);
+    if (!(resident & OT_RESIDENT_RAY)) st<NT>(out.ray + slot, tree);
+    st<NT>(out.surface + slot, surface);
+}
+template <class T, bool NT>
+__device__ __forceinline__ void store_segment_first(const SegTiles<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
+                                                    int32_t surface, uint32_t resident, uint32_t first) {
+    uint8_t* tb = out.base + (slot >> 6) * SegTiles<T>::TILE_BYTES;
+    T* p = reinterpret_cast<T*>(tb) + (slot & 63);
+    if (!(first & OT_UNIFORM_OX)) st<NT>(p, r.ox);
+    if (!(first & OT_UNIFORM_OY)) st<NT>(p + 64, r.oy);
+    if (!(first & OT_UNIFORM_OZ)) st<NT>(p + 128, r.oz);
+    if (!(first & OT_UNIFORM_DX)) st<NT>(p + 192, r.dx);
+    if (!(first & OT_UNIFORM_DY)) st<NT>(p + 256, r.dy);
+    if (!(first & OT_UNIFORM_DZ)) st<NT>(p + 320, r.dz);
+    st<NT>(p + 384, len);
+    if (!(resident & OT_RESIDENT_INTENSITY) && !(first & OT_UNIFORM_INTENSITY)) st<NT>(p + 448, r.I);
+    if (!(first & OT_UNIFORM_Q_RE)) st<NT>(p + 512, r.qr);
+    if (!(first & OT_UNIFORM_Q_IM)) st<NT>(p + 576, r.qi);
+    if (!(resident & OT_RESIDENT_N) && !(first & OT_UNIFORM_N)) st<NT>(p + 640, r.n);
+    if (!(first & OT_UNIFORM_PATHLENGTH)) st<NT>(p + 704, r.pl);
+    int32_t* q = reinterpret_cast<int32_t*>(tb + 768 * sizeof(T)) + (slot & 63);
+    if (!(resident & OT_RESIDENT_RAY)) st<NT>(q, tree);
+    st<NT>(q + 64, surface);
+}
 // ... in lane pairs: the partners that lose their mate are paired anew where the types allow (`length` with `pathlength` when
 // `intensity` and `n` are both resident); one that finds none goes alone, one element per lane (`surface`: 4 bytes).
 // LEN .. SURFACE: the planes concerned, element 0 of each; l: this lane's element in them.
@@ -507,19 +552,23 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
             const Hit<T> h = nearest_hit<T, F, GATE_PLAIN>(sc, r, active, gate);
             // segment record: pairs of lanes that both store write two fields per 16-byte store (store_segment_paired)
             const unsigned long long storing = __ballot(active);
-            const bool both = pair && ((storing >> (threadIdx.x & 62)) & 3ull) == 3ull;
             // resident planes are skipped for the WHOLE wave or not at all: one storing lane past its old count (a ray that lives
             // longer than last time) and every lane of the wave writes this segment's full record
             const uint32_t rm = uniform_here(resident);  // (the plane tests are made at the stores, not kept in scalar registers across the search)
             const bool whole = rm == 0 || __any(active && (uint32_t)k >= SegCount::old_count(used));
+            const uint32_t fm = (k == 0 && !whole) ? rm >> FIRST_SHIFT : 0u;  // first-segment fields: a reduced record 0 that leaves any of them out goes unpaired
+            const bool both = fm != 0 || (pair && ((storing >> (threadIdx.x & 62)) & 3ull) == 3ull);  // (stored here, not below)
             if (both) {
                 const bool hit = h.node >= 0;
                 if (whole)
                     store_segment_paired<T, NT>(out, (int64_t)k * n + i, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : -1,
                                                 (threadIdx.x & 1) != 0);
-                else
+                else if (fm == 0)
                     store_segment_paired_reduced<T, NT>(out, (int64_t)k * n + i, r, hit ? h.t : r.len, (int32_t)i,
                                                         hit ? leaf_id_of<T, F>(sc, h.node) : -1, (threadIdx.x & 1) != 0, rm);
+                else if (active)  // (last: the two paired forms, every other segment's, keep the places they had; and the slot is
+                                  // written k * n + i here too — `i` alone, equal at k == 0, costs the FA MINW = 4 kernels 8-38 vector spills)
+                    store_segment_first<T, NT>(out, (int64_t)k * n + i, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : -1, rm, fm);
             }
             if (active) {
                 const int64_t slot = (int64_t)k * n + i;

@@ -143,7 +143,7 @@ struct ot_ctx {
     Scratch gen, scan_tmp, mon, gen_rem, gen_ahead, trees;
     int32_t opt_trees_global = 0;      // k_trace_trees: 1 = every scene through the all-features kernel that reads its image from global memory (test knob)
     int32_t opt_uniform = 1;  // the lane-per-ray kernel reads fields flagged in a call's uniform_mask once per wave (0: the mask is dropped)
-    int32_t opt_resident = 1; // ... and leaves the planes of a call's resident_mask unwritten where the output holds them (0: the mask is dropped)
+    int32_t opt_resident = 1; // ... and leaves the planes of a call's resident_mask and the fields of its first_mask unwritten where the output holds them (2: planes only; 0: both masks are dropped)
     bool whole_intensity = false;  // every leaf hands a ray's intensity on unchanged or not at all (found at upload: resident_planes)
     int32_t opt_trees_flat = 1;        // k_trace_trees: planar scenes under a top-level grid of leaves search through the wave-wide pair queue
     int32_t opt_trees_refill_at = 16;  // k_trace_trees: idle lanes of a wave at which they take their next trees (64: a wave takes 64 trees at a time)
@@ -1044,10 +1044,23 @@ template <class T> static uint32_t resident_planes(const ot_ctx* c, uint32_t uni
     return planes;
 }
 
+// the first_mask of a call (include/optable_hip.h: OT_FIRST_FIELDS)
+static int check_first(uint32_t first) {
+    if (first & ~(uint32_t)OT_FIRST_FIELDS) return fail(OT_ERR_INVALID, "first_mask has bits outside OT_FIRST_FIELDS");
+    return 0;
+}
+// The record fields segment 0 of every ray holds ONE known bit pattern in: segment 0 is the input ray handed through (k_trace_fused
+// stores what it loaded), so every uniform input field among the eleven a record shares with a ray, whatever the scene does.
+// OT_OPT_RESIDENT = 2 keeps the planes and drops these.
+static uint32_t first_fields(const ot_ctx* c, uint32_t uniform, int32_t K) {
+    if (c->opt_resident != 1 || !c->opt_uniform || K > (int32_t)SegCount::SEGS_MAX) return 0;
+    return uniform & (uint32_t)OT_FIRST_FIELDS;
+}
+
 // one lane per ray (k_trace_fused); OUT = SegsT<T> or SegTiles<T>
 template <class T, class OUT>
 static int launch_fused(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const OUT& out, int32_t pair, int32_t* seg_count, int32_t* counts,
-                        int32_t n_classes, uint32_t uniform, uint32_t resident) {
+                        int32_t n_classes, uint32_t uniform, uint32_t resident, uint32_t first) {
     const bool f64 = sizeof(T) == 8;
     const int fi = fused_preset(c->features);
     const size_t bytes = image_of<T>(c).bytes;
@@ -1073,12 +1086,13 @@ static int launch_fused(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, co
     if (!kern) return fail(OT_ERR_UNSUPPORTED, "no kernel instantiation for this scene / option combination");
     const LaunchShape shape = {1, block, 0, grid, (int32_t)(lds ? bytes : 0), 0, 0, std::is_same<OUT, SegTiles<T>>::value ? LL_TILES : 0};
     return launch_kernel(c, kern, shape, nullptr, nullptr, make_blob<T>(c), (T)c->unit, view<T>(rays), n, K, out, seg_count, counts, n_classes, pair,
-                         c->opt_uniform ? uniform : 0u, resident & resident_planes<T>(c, uniform, K));
+                         c->opt_uniform ? uniform : 0u,
+                         (resident & resident_planes<T>(c, uniform, K)) | ((first & first_fields(c, uniform, K)) << FIRST_SHIFT));
 }
 
 template <class T>
 static int trace_fused(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
-                       int32_t* counts, int32_t n_classes, uint32_t uniform, uint32_t resident) {
+                       int32_t* counts, int32_t n_classes, uint32_t uniform, uint32_t resident, uint32_t first) {
     int rc = check_trace_args(c, rays, n, K, seg_count, counts, n_classes);
     if (rc) return rc;
     rc = check_segs(out);
@@ -1087,11 +1101,13 @@ static int trace_fused(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, con
     if (rc) return rc;
     rc = check_resident(resident);
     if (rc) return rc;
+    rc = check_first(first);
+    if (rc) return rc;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
     // (the rolling lists read the full arrays and write whole records: the masks end here)
     if (wants_rolling<T>(c, K)) return launch_rolling<T, SegsT<T>>(c, rays, n, K, view<T>(out), AppendCtl{nullptr, 0, 0}, seg_count, counts, n_classes);
-    return launch_fused<T, SegsT<T>>(c, rays, n, K, view<T>(out), pair_ok<T>(c, out, n), seg_count, counts, n_classes, uniform, resident);
+    return launch_fused<T, SegsT<T>>(c, rays, n, K, view<T>(out), pair_ok<T>(c, out, n), seg_count, counts, n_classes, uniform, resident, first);
 }
 
 // Tiled layout: the lane-per-ray kernel only (light scenes; heavy ones have the append layout)
@@ -1102,7 +1118,7 @@ template <class T> static int check_tiles(const void* tiles, int64_t capacity, i
 }
 template <class T>
 static int trace_tiled(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count, int32_t* counts,
-                       int32_t n_classes, uint32_t uniform, uint32_t resident) {
+                       int32_t n_classes, uint32_t uniform, uint32_t resident, uint32_t first) {
     int rc = check_trace_args(c, rays, n, K, seg_count, counts, n_classes);
     if (rc) return rc;
     rc = check_tiles<T>(tiles, capacity, n, K);
@@ -1111,12 +1127,14 @@ static int trace_tiled(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, voi
     if (rc) return rc;
     rc = check_resident(resident);
     if (rc) return rc;
+    rc = check_first(first);
+    if (rc) return rc;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
     if (wants_rolling<T>(c, K))
         return fail(OT_ERR_UNSUPPORTED, "the tiled layout belongs to the lane-per-ray kernel (light scenes); heavy scenes write [k][ray] slots (ot_trace_*) or the append layout (ot_trace_append_*)");
     const int32_t pair = (c->opt_pair && !(n & 1) && sizeof(T) == 8) ? 1 : 0;  // lane pairs write 16 bytes: even slot on the even lane
-    return launch_fused<T, SegTiles<T>>(c, rays, n, K, SegTiles<T>{(uint8_t*)tiles}, pair, seg_count, counts, n_classes, uniform, resident);
+    return launch_fused<T, SegTiles<T>>(c, rays, n, K, SegTiles<T>{(uint8_t*)tiles}, pair, seg_count, counts, n_classes, uniform, resident, first);
 }
 
 // the segment block of the append layout (ot_trace_append_*, ot_trace_trees_append_*)
@@ -1149,21 +1167,38 @@ static int trace_append(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, co
 
 extern "C" {
 
+int ot_trace_reuse_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
+                       int32_t* counts, int32_t n_classes, uint32_t uniform, uint32_t resident, uint32_t first) {
+    return trace_fused<double>(c, rays, n, K, out, seg_count, counts, n_classes, uniform, resident, first);
+}
+int ot_trace_reuse_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
+                       int32_t* counts, int32_t n_classes, uint32_t uniform, uint32_t resident, uint32_t first) {
+    return trace_fused<float>(c, rays, n, K, out, seg_count, counts, n_classes, uniform, resident, first);
+}
+int ot_trace_tiled_reuse_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count,
+                             int32_t* counts, int32_t n_classes, uint32_t uniform, uint32_t resident, uint32_t first) {
+    return trace_tiled<double>(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, uniform, resident, first);
+}
+int ot_trace_tiled_reuse_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count,
+                             int32_t* counts, int32_t n_classes, uint32_t uniform, uint32_t resident, uint32_t first) {
+    return trace_tiled<float>(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, uniform, resident, first);
+}
+// (no first-segment fields: the same path with an empty mask)
 int ot_trace_resident_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
                           int32_t* counts, int32_t n_classes, uint32_t uniform, uint32_t resident) {
-    return trace_fused<double>(c, rays, n, K, out, seg_count, counts, n_classes, uniform, resident);
+    return ot_trace_reuse_f64(c, rays, n, K, out, seg_count, counts, n_classes, uniform, resident, 0u);
 }
 int ot_trace_resident_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, const ot_segments* out, int32_t* seg_count,
                           int32_t* counts, int32_t n_classes, uint32_t uniform, uint32_t resident) {
-    return trace_fused<float>(c, rays, n, K, out, seg_count, counts, n_classes, uniform, resident);
+    return ot_trace_reuse_f32(c, rays, n, K, out, seg_count, counts, n_classes, uniform, resident, 0u);
 }
 int ot_trace_tiled_resident_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count,
                                 int32_t* counts, int32_t n_classes, uint32_t uniform, uint32_t resident) {
-    return trace_tiled<double>(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, uniform, resident);
+    return ot_trace_tiled_reuse_f64(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, uniform, resident, 0u);
 }
 int ot_trace_tiled_resident_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count,
                                 int32_t* counts, int32_t n_classes, uint32_t uniform, uint32_t resident) {
-    return trace_tiled<float>(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, uniform, resident);
+    return ot_trace_tiled_reuse_f32(c, rays, n, K, tiles, capacity, seg_count, counts, n_classes, uniform, resident, 0u);
 }
 // Which planes would such a call keep invariant on the uploaded scene (0: it would not land on the lane-per-ray kernel)?
 int ot_trace_resident_plan(ot_ctx* c, int32_t real_bytes, uint32_t uniform, int64_t n, int32_t K, int32_t* planes) {
@@ -1174,6 +1209,15 @@ int ot_trace_resident_plan(ot_ctx* c, int32_t real_bytes, uint32_t uniform, int6
     const bool f64 = real_bytes == 8;
     const bool fused = n > 0 && c->max_children <= 2 && !(f64 ? wants_rolling<double>(c, K) : wants_rolling<float>(c, K));
     *planes = !fused ? 0 : (int32_t)(f64 ? resident_planes<double>(c, uniform, K) : resident_planes<float>(c, uniform, K));
+    return 0;
+}
+// ... and which record fields would its segment 0 hold the batch's one bit pattern in (0 likewise, and for planes only: OT_OPT_RESIDENT = 2)?
+int ot_trace_reuse_plan(ot_ctx* c, int32_t real_bytes, uint32_t uniform, int64_t n, int32_t K, int32_t* planes, uint32_t* first_fields_out) {
+    if (!first_fields_out) return fail(OT_ERR_INVALID, "ot_trace_reuse_plan: bad argument");
+    const int rc = ot_trace_resident_plan(c, real_bytes, uniform, n, K, planes);
+    if (rc) return rc;
+    const bool fused = n > 0 && c->max_children <= 2 && !(real_bytes == 8 ? wants_rolling<double>(c, K) : wants_rolling<float>(c, K));
+    *first_fields_out = fused ? first_fields(c, uniform, K) : 0u;
     return 0;
 }
 // (nothing resident: the same path with an empty mask)
@@ -2158,7 +2202,7 @@ int ot_set_option(ot_ctx* c, int32_t option, int32_t value) {
             if (value < 0 || value > 1) return fail(OT_ERR_INVALID, "OT_OPT_UNIFORM takes 0 or 1");
             c->opt_uniform = value; return 0;
         case OT_OPT_RESIDENT:
-            if (value < 0 || value > 1) return fail(OT_ERR_INVALID, "OT_OPT_RESIDENT takes 0 or 1");
+            if (value < 0 || value > 2) return fail(OT_ERR_INVALID, "OT_OPT_RESIDENT takes 0, 1 or 2");
             c->opt_resident = value; return 0;
         case OT_OPT_BLOCKS_PER_CU:
             if (value < 0 || value > 65536) return fail(OT_ERR_INVALID, "OT_OPT_BLOCKS_PER_CU out of range");

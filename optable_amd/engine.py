@@ -71,6 +71,10 @@ def _width(precision):
     return 8 if precision == "f64" else 4
 
 
+# the first-segment fields Engine.trace flags of its own accord (Engine._launch says why `n` and `intensity` are left out)
+_ENGINE_FIRST = abi.FIRST_FIELDS & ~(abi.UNIFORM_BIT["n"] | abi.UNIFORM_BIT["intensity"])
+
+
 def _keeps_bits(bits, precision):
     """`bits` (the pattern of a uniform intensity, or None) if x * 1 gives back exactly that pattern on the device: not a
     subnormal, which a kernel built to flush them would turn into zero (NaN never carries a hint)."""
@@ -179,6 +183,7 @@ class Engine:
         abi.check(self.lib.ot_ctx_create(device, C.c_void_p(stream), C.byref(self._ctx)), self.lib)
         self._stream = stream       # the stream the launches go to (part of an output's resident-plane token)
         self._resident_plans = {}   # (precision, uniform mask, n, K) -> planes ot_trace_resident_plan reported for the uploaded scene
+        self._first_plans = {}      # the same key -> first-segment fields ot_trace_reuse_plan reported
         self.scene = None
         self.append_chunk = 512  # OT_OPT_APPEND_CHUNK as last set through set_option (the library's default)
         self.trees_refill_at = 16  # OT_OPT_TREES_REFILL_AT likewise
@@ -210,6 +215,7 @@ class Engine:
         self._records_per_ray = {}
         self._layout_choice = {}
         self._resident_plans = {}
+        self._first_plans = {}
 
     def _refuse_hooks(self):
         """Whole-trace launches cannot call back into Python: a scene with user-defined `interact_local` leaves
@@ -326,11 +332,28 @@ class Engine:
             planes = self._resident_plans[key] = int(got.value)
         return planes
 
+    def first_plan(self, precision, uniform_mask, n_rays, max_segments):
+        """abi.FIRST_FIELD bits of the record fields a lane-per-ray launch of such a batch would leave unwritten at segment 0 when
+        told to (ot_trace_reuse_plan: the library's rule, asked once per scene and call shape); 0: not that kernel, or switched off."""
+        key = (precision, int(uniform_mask), int(n_rays), int(max_segments))
+        fields = self._first_plans.get(key)
+        if fields is None:
+            planes, got = C.c_int32(), C.c_uint32()
+            abi.check(self.lib.ot_trace_reuse_plan(self._ctx, _width(precision), key[1], key[2], key[3], C.byref(planes), C.byref(got)), self.lib)
+            if len(self._first_plans) > 64:
+                self._first_plans = {}
+            fields = self._first_plans[key] = int(got.value)
+        return fields
+
     def _launch(self, name, rays, K, out, counts_ptr, n_classes, skip=False):
         """The library call `name`_f64 / _f32 on the whole batch, `out` handed over the way its layout wants.  skip: everything
         but the call itself (the append cursor is still made, zeroed and attached).
         Resident planes (SegmentBatch): whatever token `out` carries is read and cleared before the call; the calls that can land on
-        the lane-per-ray kernel pass what it allows and leave a new one."""
+        the lane-per-ray kernel pass what it allows and leave a new one.  The first-segment token likewise: the fields whose one bit
+        pattern in `rays` is the token's go out as first_mask.  `n` and `intensity` are never among them (_ENGINE_FIRST): where their
+        planes are resident the plane mask covers segment 0 already, and where the scene changes them a reused output gets those
+        planes rewritten whole, segment 0 included (tests/test_gpu_resident.py pins it); the library itself takes the two bits
+        from a caller of ot_trace_reuse_*."""
         kind = _OUT[name][0]
         rs = rays.c_struct()
         if "block" in kind:
@@ -350,14 +373,17 @@ class Engine:
                 layout = "tiled" if "tiled" in kind else "slots"
                 um = rays.uniform_mask
                 planes = self.resident_plan(rays.precision, um, rays.n, K)
-                values = {abi.RESIDENT_N: rays.uniform_bits("n"), abi.RESIDENT_INTENSITY: _keeps_bits(rays.uniform_bits("intensity"), rays.precision)}
+                firsts = rays.uniform_values()  # {field: the batch's one bit pattern in it}, the hint checked once
+                values = {abi.RESIDENT_N: firsts.get("n"), abi.RESIDENT_INTENSITY: _keeps_bits(firsts.get("intensity"), rays.precision)}
                 resident = out.resident_mask(rays.n, layout, values, self, self._stream) & planes
-                name, hint = name + "_resident", (um, resident)
+                first = out.first_mask(rays.n, layout, firsts, self, self._stream) & self.first_plan(rays.precision, um, rays.n, K) & _ENGINE_FIRST
+                name, hint = name + "_reuse", (um, resident, first)
             out.forget_resident()
             abi.check(self._fn(name, rays.precision)(self._ctx, C.byref(rs), rays.n, K, *where, out.count.data_ptr(), counts_ptr, n_classes, *hint),
                       self.lib)
             if planes:
                 out._set_resident(planes, rays.n, layout, values, self, self._stream)
+                out._set_first(firsts, rays.n, layout, self, self._stream)
         if "block" in kind:
             out.cursor, out.n_valid = cursor, None  # device scalar: read lazily (n_valid) so that back-to-back launches do not synchronise
 
@@ -945,6 +971,7 @@ class Engine:
 
     def set_option(self, option, value):
         self._resident_plans = {}
+        self._first_plans = {}
         abi.check(self.lib.ot_set_option(self._ctx, option, value), self.lib)
         if option == abi.OPT_APPEND_CHUNK:
             self.append_chunk = int(value)  # (the capacity estimates of the append layout count holes in chunks)
