@@ -671,6 +671,34 @@ int ot_monitor_wave_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitors
                          int64_t n_rays, int64_t* counts, double* re, double* im, int64_t* skipped, int64_t* aliased,
                          int32_t accumulate);
 
+/* Fluence maps: every segment rasterised into a projected view of the table (what OpticalTable.render(type=..., roi=...) draws
+ * line by line, as numbers) — per pixel the number of segment pieces inside it and their intensity-weighted path length.
+ * The view: axes = a_u, a_v, a_w (host, 9 doubles); a point x has the image coordinates u = x . a_u, v = x . a_v and the depth
+ * w = x . a_w.  The pixels: u_edges (nu + 1) and v_edges (nv + 1), host, finite and strictly increasing; the box of the view is
+ * [u_edges[0], u_edges[nu]] x [v_edges[0], v_edges[nv]] x [w_lo, w_hi], where a depth bound may be infinite.
+ * A segment is the points o + t dh, t in [0, length], dh = d / |d|.  Its parameter interval is clipped to the box (a coordinate
+ * that does not move is inside iff lo <= x <= hi), and the grid lines it crosses cut the rest into pieces, each in one pixel.
+ * Every crossing parameter is (edge - o) / dh with the edge read from the table.  A piece lies in the pixel that holds its
+ * midpoint: a segment along a grid line in the upper pixel (half-open bins, the last one closed), a piece that starts on a line
+ * on the side it moves to; the passage of a corner is a piece of no length.  Pixel (i, j) gets one count and
+ * intensity * (t_b - t_a) for every piece of positive length; nothing is counted twice on a line.
+ * intensity: device plane of the segments, addressed like src->base[f], in the source's precision; NULL: weight 1 (path length).
+ * src, n_segments, seg_count, n_rays as for ot_monitor_record_many.
+ * A valid segment with a NaN in origin, direction or length, with |d| = 0, or whose clipped interval is not finite (an unbounded
+ * last segment inside an infinite depth range) deposits nothing and adds one to *skipped.
+ * counts, fluence: device, [nu][nv] uint64 / double; skipped: device, one uint64.  accumulate = 0 zeroes all three first (also
+ * for n_segments = 0), 1 adds to what is there.  Counts are integers, exact and the same every run; the fluence is fp64 atomic
+ * adds whose last bits depend on the order of arrival.
+ * Paths: an image of up to 5,450 pixels (12 bytes of LDS a pixel) is kept per workgroup and flushed at the end; a larger one
+ * takes every piece as a global atomic.  One lane walks one segment: nu + nv + 1 steps at most.
+ * OT_ERR_INVALID, nothing launched or zeroed: a NULL argument (intensity apart); nu or nv < 1; nu * nv > 2^24; accumulate other
+ * than 0 / 1; everything ot_monitor_record_many refuses of src, n_segments, seg_count and n_rays; edges not finite and strictly
+ * increasing; w_lo > w_hi (or a NaN); axes not finite. */
+int ot_fluence_map(ot_ctx* ctx, const double* axes, const double* u_edges, int32_t nu, const double* v_edges, int32_t nv,
+                   double w_lo, double w_hi, const ot_segment_source* src, const void* intensity, int64_t n_segments,
+                   const int32_t* seg_count, int64_t n_rays, unsigned long long* counts, double* fluence,
+                   unsigned long long* skipped, int32_t accumulate);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled every trace launch is bracketed by hipEvents on the ctx stream. */
 int ot_timing_enable(ot_ctx* ctx, int enabled);

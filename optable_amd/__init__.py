@@ -19,6 +19,7 @@ from .assemblies import (ComponentGroup, GlassSlab, CircleGlassSlab, MLA, MMA, M
                          PlanoConvexLens, BiConvexLens, Doublet, ASphericLens, ASphericExactSphericalLens,
                          ASphericParametricLens)
 from .monitors import Monitor
+from .fluence import FluenceMap
 from .table import OpticalTable
 from .scene import compile_scene, CompiledScene, SceneError
 from .adapter import install

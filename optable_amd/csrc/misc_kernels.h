@@ -176,7 +176,7 @@ __global__ void k_gen_counts(const int32_t* tree, const int32_t* ids, int64_t n,
 // Monitor.record
 // The plane and aperture test of one segment (monitor.py:183-193): the segment in the monitor's frame, direction renormalised
 // (ray_to_local_coordinates), the crossing of the plane x = 0 within the segment's length and the rectangle.  One definition
-// for the one-monitor kernels (k_mon_test) and the many-monitor ones (k_mon_count / k_mon_emit): P = local hit point, t = distance.
+// for every monitor kernel (k_mon_count / k_mon_emit, k_mon_wave): P = local hit point, t = distance.
 __device__ __forceinline__ bool mon_hit(const ot_monitor& mon, double sox, double soy, double soz, double sdx, double sdy, double sdz, double slen,
                                         double& Px, double& Py, double& Pz, double& t) {
     const double rx = sox - mon.origin[0], ry = soy - mon.origin[1], rz = soz - mon.origin[2];
@@ -193,36 +193,6 @@ __device__ __forceinline__ bool mon_hit(const ot_monitor& mon, double sox, doubl
     Px = ox + t * dx; Py = oy + t * dy; Pz = oz + t * dz;
     return fabs(Py) <= mon.half_width && fabs(Pz) <= mon.half_height;
 }
-__global__ void k_mon_test(ot_monitor mon, SegsT<double> s, int64_t n, const int32_t* seg_count, int64_t n_rays, int32_t* hit,
-                           double* P, double* tt) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (seg_count) {  // [k][ray] layout of ot_trace_*: slot i is valid iff k < |seg_count[ray]|
-        const int32_t c = seg_count[i % n_rays];
-        if (i / n_rays >= (c < 0 ? -c : c)) { hit[i] = 0; return; }
-    } else if (n_rays < 0 && s.ray[i] < 0) {  // a list with holes: the append layout of ot_trace_append_*
-        hit[i] = 0;
-        return;
-    }
-    double Px, Py, Pz, t;
-    const bool ok = mon_hit(mon, s.ox[i], s.oy[i], s.oz[i], s.dx[i], s.dy[i], s.dz[i], s.len[i], Px, Py, Pz, t);
-    if (ok) {
-        P[3 * i] = Px; P[3 * i + 1] = Py; P[3 * i + 2] = Pz;
-        tt[i] = t;
-    }
-    hit[i] = ok ? 1 : 0;
-}
-__global__ void k_mon_compact(const int32_t* hit, const int64_t* off, const double* P, const double* tt, int64_t n,
-                              int64_t* hit_index, double* Px, double* Py, double* Pz, double* t, int64_t* n_hits) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (hit[i]) {
-        const int64_t d = off[i];
-        hit_index[d] = i; Px[d] = P[3 * i]; Py[d] = P[3 * i + 1]; Pz[d] = P[3 * i + 2]; t[d] = tt[i];
-    }
-    if (i == n - 1) *n_hits = off[i] + hit[i];
-}
-
 
 // ------------------------------------------------------------------------------------------
 // Monitor.record on up to MON_MAX monitors in one pass over the segments (ot_monitor_record_many), in two kernels that share
@@ -248,7 +218,7 @@ struct MonSeg {
 __device__ __forceinline__ double mon_real(const uint8_t* p, int32_t width) {
     return width == 8 ? *reinterpret_cast<const double*>(p) : (double)*reinterpret_cast<const float*>(p);
 }
-// slot s with the validity rule of k_mon_test: k < |seg_count[ray]| in [k][ray] slots, ray >= 0 in lists with holes (n_rays < 0)
+// slot s and whether it holds a segment: k < |seg_count[ray]| in [k][ray] slots, ray >= 0 in lists with holes (n_rays < 0)
 __device__ __forceinline__ MonSeg mon_load(const MonSource& src, int64_t s, int64_t n, const int32_t* __restrict__ seg_count, int64_t n_rays) {
     MonSeg g;
     g.ox = g.oy = g.oz = g.dx = g.dy = g.dz = g.len = 0.0;
@@ -908,6 +878,140 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_emit(const ot_monitor* __re
             if (lane == 0) seen[wave][m] = earlier + all;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Fluence maps (ot_fluence_map): every segment rasterised into a projected view of the table, nu x nv pixels over the edge
+// tables ue[0 .. nu], ve[0 .. nv].  k_mon_count's partition and loads (mon_load: any layout, either precision, widened in
+// registers); all arithmetic is double.  A segment is the points o + t dh, t in [0, length], dh = d / |d| (renormalised as
+// mon_hit does), in the view's coordinates u = . a_u, v = . a_v, w = . a_w (axes[9]).  Its parameter interval is clipped to
+// the box [ue[0], ue[nu]] x [ve[0], ve[nv]] x [w_lo, w_hi]; a coordinate that does not move (dh == 0 exactly) is inside under
+// mon_bin's rule, lo <= x <= hi.  The grid lines cut the clipped interval [t_a, t_b] into pieces, one pixel each, and pixel
+// (ku, kv) gets one count and intensity * (piece length) for every piece of positive length.
+// Every crossing parameter is (e[j] - o) / dh with e[j] from the table, recomputed where it is used; none is derived from a
+// step.  That expression is monotone in j, so pixels follow from parameters alone: moving up, the pixel at t is the k with
+// t(e[k]) <= t < t(e[k + 1]); moving down, t(e[k]) > t >= t(e[k + 1]) — a piece that starts on a line lies on the side it moves
+// to; a coordinate at rest is binned by mon_bin (a segment along a line lies in the upper pixel, the last one closed).  A
+// passage through a corner steps both axes and leaves no piece.
+// The walk is a counted loop: a trip deposits one piece and steps at least one axis, or is the last — nu + nv + 1 trips at most,
+// and no loop of the kernel waits on a floating-point condition (the two searches of seg_first_pixel count their trips too).
+// Deposits go to the workgroup's image in LDS (lds_pixels = nu * nv: fluence[lds_pixels] doubles, then tally[lds_pixels] int32,
+// flushed at the end, non-zero pixels only, consecutive lanes consecutive pixels) or, with lds_pixels = 0, straight to global
+// memory.  Counts are integers, exact and the same every run; the fluence is fp64 atomic adds.
+// A valid segment with a NaN in origin, direction or length, with |d| == 0, or whose clipped interval is not empty and not
+// finite (an unbounded last segment inside an infinite depth range) deposits nothing and is counted in *skipped: one atomic a
+// wave.  An empty interval (the segment misses the box) is neither.
+static constexpr int SEG_RASTER_MAX_PIXELS = 1 << 24;  // nu * nv
+struct SegRaster {
+    unsigned long long* counts;  // [nu][nv]
+    double* fluence;             // [nu][nv]
+    unsigned long long* skipped;
+    const double *ue, *ve;       // nu + 1, nv + 1 edges
+    const uint8_t* intensity;    // addressed like the fields of MonSource; NULL: weight 1
+    double axes[9];              // a_u, a_v, a_w
+    double w_lo, w_hi;
+    int32_t nu, nv, lds_pixels;
+};
+// the crossing parameter of edge j
+__device__ __forceinline__ double seg_cross(const double* __restrict__ e, int32_t j, double o, double dh) { return (e[j] - o) / dh; }
+// One axis of the clip: [t_a, t_b] cut to lo <= o + t dh <= hi.  false: the segment stays outside (dh == 0, o outside).
+__device__ __forceinline__ bool seg_clip(double lo, double hi, double o, double dh, double& t_a, double& t_b) {
+    if (dh == 0.0) return o >= lo && o <= hi;
+    const double t_lo = (lo - o) / dh, t_hi = (hi - o) / dh;
+    const double t_in = dh > 0.0 ? t_lo : t_hi, t_out = dh > 0.0 ? t_hi : t_lo;
+    t_a = t_in > t_a ? t_in : t_a;
+    t_b = t_out < t_b ? t_out : t_b;
+    return true;
+}
+// The pixel along one axis of the piece that starts at t (see above); 0 .. nb - 1 whatever the numbers.  The guess comes from
+// the position, the answer from the table's crossing parameters.
+__device__ __forceinline__ int32_t seg_first_pixel(const double* __restrict__ e, int32_t nb, double o, double dh, double t) {
+    if (dh == 0.0) {
+        const int32_t k = mon_bin(e, nb, o);
+        return k < 0 ? 0 : k;
+    }
+    const double g = (o + t * dh - e[0]) * (double)nb / (e[nb] - e[0]);
+    int32_t k = g >= 0.0 ? (g < (double)(nb - 1) ? (int32_t)g : nb - 1) : 0;  // (a NaN guess starts at 0)
+    if (dh > 0.0) {
+        for (int32_t i = 0; i < nb && k > 0 && seg_cross(e, k, o, dh) > t; ++i) --k;
+        for (int32_t i = 0; i < nb && k < nb - 1 && !(seg_cross(e, k + 1, o, dh) > t); ++i) ++k;
+    } else {
+        for (int32_t i = 0; i < nb && k < nb - 1 && seg_cross(e, k + 1, o, dh) > t; ++i) ++k;
+        for (int32_t i = 0; i < nb && k > 0 && !(seg_cross(e, k, o, dh) > t); ++i) --k;
+    }
+    return k;
+}
+__global__ __launch_bounds__(MON_THREADS) void k_seg_raster(MonSource src, int64_t n, int32_t iters, const int32_t* __restrict__ seg_count,
+                                                            int64_t n_rays, SegRaster r) {
+    extern __shared__ double seg_image[];  // fluence[lds_pixels], then tally[lds_pixels]
+    double* fluence = seg_image;
+    int32_t* tally = reinterpret_cast<int32_t*>(seg_image + r.lds_pixels);
+    for (int32_t b = threadIdx.x; b < r.lds_pixels; b += MON_THREADS) fluence[b] = 0.0, tally[b] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t first = (int64_t)blockIdx.x * iters * MON_THREADS;
+    int32_t skipped = 0;  // (wave-wide: a scalar)
+    for (int32_t it = 0; it < iters && first + (int64_t)it * MON_THREADS < n; ++it) {
+        const int64_t s = first + (int64_t)it * MON_THREADS + threadIdx.x;
+        const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
+        if (!__ballot(g.valid)) continue;
+        const double* a = r.axes;
+        const double ou = g.ox * a[0] + g.oy * a[1] + g.oz * a[2], ov = g.ox * a[3] + g.oy * a[4] + g.oz * a[5],
+                     ow = g.ox * a[6] + g.oy * a[7] + g.oz * a[8];
+        double du = g.dx * a[0] + g.dy * a[1] + g.dz * a[2], dv = g.dx * a[3] + g.dy * a[4] + g.dz * a[5],
+               dw = g.dx * a[6] + g.dy * a[7] + g.dz * a[8];
+        const double norm = sqrt(du * du + dv * dv + dw * dw);
+        const double inv = 1.0 / norm;
+        du *= inv; dv *= inv; dw *= inv;
+        // (x == x is false for a NaN only; norm > 0 refuses a zero direction and a NaN one)
+        const bool numbers = ou == ou && ov == ov && ow == ow && du == du && dv == dv && dw == dw && g.len == g.len && norm > 0.0;
+        double t_a = 0.0, t_b = g.len;
+        bool inside = g.valid && numbers;
+        inside = inside && seg_clip(r.ue[0], r.ue[r.nu], ou, du, t_a, t_b);
+        inside = inside && seg_clip(r.ve[0], r.ve[r.nv], ov, dv, t_a, t_b);
+        inside = inside && seg_clip(r.w_lo, r.w_hi, ow, dw, t_a, t_b);
+        inside = inside && t_a <= t_b;
+        const bool endless = inside && !(t_b < HUGE_VAL);
+        skipped += (int32_t)__popcll(__ballot((g.valid && !numbers) || endless));
+        if (!inside || endless) continue;
+        double w = 1.0;
+        if (r.intensity) w = mon_real(r.intensity + (s >> 6) * src.tile_stride + (s & 63) * src.width, src.width);
+        int32_t ku = seg_first_pixel(r.ue, r.nu, ou, du, t_a), kv = seg_first_pixel(r.ve, r.nv, ov, dv, t_a);
+        const int32_t su = du > 0.0 ? 1 : -1, sv = dv > 0.0 ? 1 : -1;
+        double t = t_a;
+        for (int32_t trip = 0; trip <= r.nu + r.nv; ++trip) {
+            const bool in_grid = ku >= 0 && ku < r.nu && kv >= 0 && kv < r.nv;
+            if (!in_grid) break;  // (stepped off the grid: t has reached the box's wall)
+            const double t_u = du == 0.0 ? HUGE_VAL : seg_cross(r.ue, du > 0.0 ? ku + 1 : ku, ou, du);
+            const double t_v = dv == 0.0 ? HUGE_VAL : seg_cross(r.ve, dv > 0.0 ? kv + 1 : kv, ov, dv);
+            double t_next = t_u < t_v ? t_u : t_v;
+            t_next = t_next < t_b ? t_next : t_b;
+            if (t_next > t) {
+                const int32_t pixel = ku * r.nv + kv;
+                const double piece = w * (t_next - t);
+                if (r.lds_pixels) {
+                    atomicAdd(&tally[pixel], 1);
+                    unsafeAtomicAdd(&fluence[pixel], piece);
+                } else {
+                    atomicAdd(&r.counts[pixel], 1ull);
+                    unsafeAtomicAdd(&r.fluence[pixel], piece);
+                }
+                t = t_next;
+            }
+            if (!(t_next < t_b)) break;
+            if (t_u <= t_next) ku += su;
+            if (t_v <= t_next) kv += sv;
+        }
+    }
+    if (lane == 0 && skipped) atomicAdd(r.skipped, (unsigned long long)skipped);
+    __syncthreads();
+    for (int32_t b = threadIdx.x; b < r.lds_pixels; b += MON_THREADS) {  // consecutive lanes, consecutive pixels
+        const int32_t c = tally[b];
+        if (c) {
+            atomicAdd(&r.counts[b], (unsigned long long)c);
+            unsafeAtomicAdd(&r.fluence[b], fluence[b]);
         }
     }
 }

@@ -1690,6 +1690,66 @@ int ot_trace_generation_f32(ot_ctx* c, const ot_rays* rays, const int32_t* tree,
     return trace_one_generation<float>(c, rays, tree, n, budget, out, out_capacity, seg_cursor, next, next_tree, next_capacity, n_next, counts, n_classes);
 }
 
+// What every call that reads an ot_segment_source refuses of it and of n_segments / seg_count / n_rays, in one place.
+static int check_source(const ot_segment_source* src, int64_t n, const int32_t* seg_count, int64_t n_rays) {
+    if (n < 0 || n >= (int64_t)1 << 31) return fail(OT_ERR_INVALID, "bad segment count");
+    if (src->width != 4 && src->width != 8) return fail(OT_ERR_INVALID, "segment source: width must be 4 or 8");
+    for (const void* p : src->base)
+        if (!p) return fail(OT_ERR_INVALID, "segment source has a NULL field");
+    if (!src->ray) return fail(OT_ERR_INVALID, "segment source has a NULL field");
+    if (src->tile_stride < 64 * (int64_t)src->width || src->ray_stride < 256) return fail(OT_ERR_INVALID, "segment source: a tile stride shorter than 64 slots");
+    if (n > src->capacity) return fail(OT_ERR_INVALID, "n_segments exceeds the capacity of the segment source");
+    if (seg_count && (n_rays < 1 || n % n_rays != 0)) return fail(OT_ERR_INVALID, "n_segments must be a multiple of n_rays");
+    if (!seg_count && n_rays > 0) return fail(OT_ERR_INVALID, "n_rays without seg_count: pass 0 for a list, -1 for a list with holes");
+    return 0;
+}
+static MonSource mon_source(const ot_segment_source* src) {
+    MonSource ms;
+    for (int f = 0; f < 7; ++f) ms.base[f] = (const uint8_t*)src->base[f];
+    ms.ray = (const uint8_t*)src->ray;
+    ms.tile_stride = src->tile_stride, ms.ray_stride = src->ray_stride, ms.width = src->width;
+    return ms;
+}
+
+// The launches of a checked record call with n > 0: count, scan, emit, MON_MAX monitors at a time.  first: n_monitors + 1 device
+// words, or NULL when the caller has no use for them (scratch of the call's own then).
+static int record_passes(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const MonSource& ms, int64_t n, const int32_t* seg_count,
+                         int64_t n_rays, int64_t capacity, int64_t* first, int64_t* hit_index, double* Px, double* Py, double* Pz, double* t,
+                         int64_t* n_total) {
+    // one partition of the slots for both passes: workgroups of `iters` visits of MON_THREADS slots (8 visits up to 2^25 slots: 2441
+    // workgroups for cfg 2's 5e6; more visits beyond, which keeps a launch at some 16 thousand workgroups however many slots)
+    const int32_t iters = (int32_t)std::max<int64_t>(8, n >> 22);
+    const int64_t span = (int64_t)iters * MON_THREADS, grid = (n + span - 1) / span;
+    const int32_t most = std::min<int32_t>(n_monitors, MON_MAX);
+    ot_monitor* table;
+    int32_t* count;
+    int64_t *off, *own_first;
+    const auto carve = [&](void* base) {
+        Carve cv{(uint8_t*)base};
+        table = cv.take<ot_monitor>(n_monitors), count = cv.take<int32_t>(most * grid + 1), off = cv.take<int64_t>(most * grid + 1);
+        own_first = cv.take<int64_t>(first ? 0 : n_monitors + 1);
+        return cv.used;
+    };
+    if (c->mon.ensure(carve(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of monitor scratch failed");
+    carve(c->mon.p);
+    if (!first) first = own_first;
+    if (c->scan_tmp.ensure(scan_tmp_bytes<int64_t>(most * grid + 1) + 256)) return fail(OT_ERR_HIP, "hipMalloc of scan scratch failed");
+    HIP_TRY(hipMemcpyAsync(table, mons, sizeof(ot_monitor) * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(first, 0, sizeof(int64_t), c->stream));
+    // MON_MAX monitors per launch; a launch takes the hits before it from first[m0], where the launch before it left them
+    for (int32_t m0 = 0; m0 < n_monitors; m0 += MON_MAX) {
+        const int32_t nm = std::min<int32_t>(MON_MAX, n_monitors - m0);
+        hipLaunchKernelGGL(k_mon_count, dim3((unsigned)grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, iters, seg_count, n_rays, count,
+                           MonImage{}, MonField{}, MonBeam{});
+        exclusive_scan<int32_t, int64_t>(c->scan_tmp.p, count, off, nm * grid + 1, c->stream);
+        hipLaunchKernelGGL(k_mon_emit, dim3((unsigned)grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, iters, seg_count, n_rays, off,
+                           capacity, first + m0, hit_index, Px, Py, Pz, t, n_total);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// One monitor over slot arrays: ot_monitor_record_many's passes with one monitor, room for every slot and *n_hits as the total.
 int ot_monitor_record_f64(ot_ctx* c, const ot_monitor* mon, const ot_segments* segs, int64_t n, const int32_t* seg_count,
                           int64_t n_rays, int64_t* hit_index, void* Px, void* Py, void* Pz, void* t, int64_t* n_hits) {
     if (!c || !mon || !hit_index || !Px || !Py || !Pz || !t || !n_hits) return fail(OT_ERR_INVALID, "NULL argument");
@@ -1703,24 +1763,12 @@ int ot_monitor_record_f64(ot_ctx* c, const ot_monitor* mon, const ot_segments* s
         HIP_TRY(hipMemsetAsync(n_hits, 0, sizeof(int64_t), c->stream));
         return 0;
     }
-    int32_t* hit;
-    int64_t* off;
-    double *P, *tt;
-    const auto carve = [&](void* base) {
-        Carve cv{(uint8_t*)base};
-        hit = cv.take<int32_t>(n), off = cv.take<int64_t>(n), P = cv.take<double>(3 * n), tt = cv.take<double>(n);
-        return cv.used;
-    };
-    if (c->mon.ensure(carve(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of monitor scratch failed");
-    carve(c->mon.p);
-    if (c->scan_tmp.ensure(scan_tmp_bytes<int64_t>(n) + 256)) return fail(OT_ERR_HIP, "hipMalloc of scan scratch failed");
-    const int block = 256, grid = (int)((n + block - 1) / block);
-    hipLaunchKernelGGL(k_mon_test, dim3(grid), dim3(block), 0, c->stream, *mon, view<double>(segs), n, seg_count, n_rays, hit, P, tt);
-    exclusive_scan<int32_t, int64_t>(c->scan_tmp.p, hit, off, n, c->stream);
-    hipLaunchKernelGGL(k_mon_compact, dim3(grid), dim3(block), 0, c->stream, hit, off, P, tt, n, hit_index, (double*)Px, (double*)Py,
-                       (double*)Pz, (double*)t, n_hits);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    MonSource ms;
+    const void* fields[7] = {segs->ox, segs->oy, segs->oz, segs->dx, segs->dy, segs->dz, segs->length};
+    for (int f = 0; f < 7; ++f) ms.base[f] = (const uint8_t*)fields[f];
+    ms.ray = (const uint8_t*)segs->ray;
+    ms.tile_stride = 512, ms.ray_stride = 256, ms.width = 8;  // plain arrays of doubles: 64-slot "tiles" back to back
+    return record_passes(c, mon, 1, ms, n, seg_count, n_rays, n, nullptr, hit_index, (double*)Px, (double*)Py, (double*)Pz, (double*)t, n_hits);
 }
 
 int ot_monitor_record_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const ot_segment_source* src, int64_t n,
@@ -1728,53 +1776,67 @@ int ot_monitor_record_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors
                            void* Pz, void* t, int64_t* n_total) {
     if (!c || !mons || !src || !first || !hit_index || !Px || !Py || !Pz || !t || !n_total) return fail(OT_ERR_INVALID, "NULL argument");
     if (n_monitors < 1) return fail(OT_ERR_INVALID, "n_monitors must be at least 1");
-    if (n < 0 || n >= (int64_t)1 << 31) return fail(OT_ERR_INVALID, "bad segment count");
-    if (src->width != 4 && src->width != 8) return fail(OT_ERR_INVALID, "segment source: width must be 4 or 8");
-    for (const void* p : src->base)
-        if (!p) return fail(OT_ERR_INVALID, "segment source has a NULL field");
-    if (!src->ray) return fail(OT_ERR_INVALID, "segment source has a NULL field");
-    if (src->tile_stride < 64 * (int64_t)src->width || src->ray_stride < 256) return fail(OT_ERR_INVALID, "segment source: a tile stride shorter than 64 slots");
-    if (n > src->capacity) return fail(OT_ERR_INVALID, "n_segments exceeds the capacity of the segment source");
+    if (const int rc = check_source(src, n, seg_count, n_rays)) return rc;
     if (capacity < 0) return fail(OT_ERR_INVALID, "negative output capacity");
-    if (seg_count && (n_rays < 1 || n % n_rays != 0)) return fail(OT_ERR_INVALID, "n_segments must be a multiple of n_rays");
-    if (!seg_count && n_rays > 0) return fail(OT_ERR_INVALID, "n_rays without seg_count: pass 0 for a list, -1 for a list with holes");
     HIP_TRY(hipSetDevice(c->device));
     if (n == 0) {
         HIP_TRY(hipMemsetAsync(first, 0, sizeof(int64_t) * ((size_t)n_monitors + 1), c->stream));
         HIP_TRY(hipMemsetAsync(n_total, 0, sizeof(int64_t), c->stream));
         return 0;
     }
-    // one partition of the slots for both passes: workgroups of `iters` visits of MON_THREADS slots (8 visits up to 2^25 slots: 2441
-    // workgroups for cfg 2's 5e6; more visits beyond, which keeps a launch at some 16 thousand workgroups however many slots)
-    const int32_t iters = (int32_t)std::max<int64_t>(8, n >> 22);
+    return record_passes(c, mons, n_monitors, mon_source(src), n, seg_count, n_rays, capacity, first, hit_index, (double*)Px, (double*)Py,
+                         (double*)Pz, (double*)t, n_total);
+}
+
+// Fluence maps: k_seg_raster over the segments as they lie (misc_kernels.h).  Through LDS while the image fits the budget of
+// ot_monitor_image_many (12 bytes a pixel) — on its partition, workgroups long enough to be worth an image of their own — else
+// on ot_monitor_record_many's partition with every piece a global atomic.  optable_amd/engine.py fluence_plan says the same.
+int ot_fluence_map(ot_ctx* c, const double* axes, const double* u_edges, int32_t nu, const double* v_edges, int32_t nv, double w_lo, double w_hi,
+                   const ot_segment_source* src, const void* intensity, int64_t n, const int32_t* seg_count, int64_t n_rays,
+                   unsigned long long* counts, double* fluence, unsigned long long* skipped, int32_t accumulate) {
+    if (!c || !axes || !u_edges || !v_edges || !src || !counts || !fluence || !skipped) return fail(OT_ERR_INVALID, "NULL argument");
+    if (nu < 1 || nv < 1) return fail(OT_ERR_INVALID, "nu and nv must be at least 1");
+    if ((int64_t)nu * nv > SEG_RASTER_MAX_PIXELS) return fail(OT_ERR_INVALID, "nu * nv exceeds 2^24 pixels");
+    if (accumulate != 0 && accumulate != 1) return fail(OT_ERR_INVALID, "accumulate must be 0 or 1");
+    if (const int rc = check_source(src, n, seg_count, n_rays)) return rc;
+    for (int axis = 0; axis < 2; ++axis) {
+        const double* e = axis ? v_edges : u_edges;
+        for (int32_t k = 0; k <= (axis ? nv : nu); ++k)
+            if (!std::isfinite(e[k]) || (k && !(e[k] > e[k - 1]))) return fail(OT_ERR_INVALID, "edges must be finite and strictly increasing");
+    }
+    if (!(w_lo <= w_hi)) return fail(OT_ERR_INVALID, "w_lo must not exceed w_hi");
+    for (int k = 0; k < 9; ++k)
+        if (!std::isfinite(axes[k])) return fail(OT_ERR_INVALID, "axes must be finite");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t pixels = (size_t)nu * nv;
+    if (!accumulate) {
+        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(unsigned long long) * pixels, c->stream));
+        HIP_TRY(hipMemsetAsync(fluence, 0, sizeof(double) * pixels, c->stream));
+        HIP_TRY(hipMemsetAsync(skipped, 0, sizeof(unsigned long long), c->stream));
+    }
+    if (n == 0) return 0;
+    const bool lds = pixels <= (size_t)MON_IMG_LDS_BINS;
+    const int32_t iters = (int32_t)std::max<int64_t>(8, lds ? (n + 1024 * MON_THREADS - 1) / (1024 * MON_THREADS) : n >> 22);
     const int64_t span = (int64_t)iters * MON_THREADS, grid = (n + span - 1) / span;
-    const int32_t most = std::min<int32_t>(n_monitors, MON_MAX);
-    ot_monitor* table;
-    int32_t* count;
-    int64_t* off;
+    double* d_edges;
     const auto carve = [&](void* base) {
         Carve cv{(uint8_t*)base};
-        table = cv.take<ot_monitor>(n_monitors), count = cv.take<int32_t>(most * grid + 1), off = cv.take<int64_t>(most * grid + 1);
+        d_edges = cv.take<double>((int64_t)nu + nv + 2);
         return cv.used;
     };
     if (c->mon.ensure(carve(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of monitor scratch failed");
     carve(c->mon.p);
-    if (c->scan_tmp.ensure(scan_tmp_bytes<int64_t>(most * grid + 1) + 256)) return fail(OT_ERR_HIP, "hipMalloc of scan scratch failed");
-    HIP_TRY(hipMemcpyAsync(table, mons, sizeof(ot_monitor) * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(first, 0, sizeof(int64_t), c->stream));
-    MonSource ms;
-    for (int f = 0; f < 7; ++f) ms.base[f] = (const uint8_t*)src->base[f];
-    ms.ray = (const uint8_t*)src->ray;
-    ms.tile_stride = src->tile_stride, ms.ray_stride = src->ray_stride, ms.width = src->width;
-    // MON_MAX monitors per launch; a launch takes the hits before it from first[m0], where the launch before it left them
-    for (int32_t m0 = 0; m0 < n_monitors; m0 += MON_MAX) {
-        const int32_t nm = std::min<int32_t>(MON_MAX, n_monitors - m0);
-        hipLaunchKernelGGL(k_mon_count, dim3((unsigned)grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, iters, seg_count, n_rays, count,
-                           MonImage{}, MonField{}, MonBeam{});
-        exclusive_scan<int32_t, int64_t>(c->scan_tmp.p, count, off, nm * grid + 1, c->stream);
-        hipLaunchKernelGGL(k_mon_emit, dim3((unsigned)grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, iters, seg_count, n_rays, off,
-                           capacity, first + m0, hit_index, (double*)Px, (double*)Py, (double*)Pz, (double*)t, n_total);
-    }
+    HIP_TRY(hipMemcpyAsync(d_edges, u_edges, sizeof(double) * ((size_t)nu + 1), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_edges + nu + 1, v_edges, sizeof(double) * ((size_t)nv + 1), hipMemcpyHostToDevice, c->stream));
+    SegRaster r{};
+    r.counts = counts, r.fluence = fluence, r.skipped = skipped;
+    r.ue = d_edges, r.ve = d_edges + nu + 1;
+    r.intensity = (const uint8_t*)intensity;
+    for (int k = 0; k < 9; ++k) r.axes[k] = axes[k];
+    r.w_lo = w_lo, r.w_hi = w_hi;
+    r.nu = nu, r.nv = nv, r.lds_pixels = lds ? (int32_t)pixels : 0;
+    hipLaunchKernelGGL(k_seg_raster, dim3((unsigned)grid), dim3(MON_THREADS), (size_t)r.lds_pixels * 12, c->stream, mon_source(src), n, iters, seg_count,
+                       n_rays, r);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1807,16 +1869,8 @@ static int check_image_call(const ot_ctx* c, const ot_monitor* mons, int32_t n_m
     if (nby < 1 || nbz < 1) return fail(OT_ERR_INVALID, "nby and nbz must be at least 1");
     if ((int64_t)nby * nbz > MON_IMG_MAX_BINS) return fail(OT_ERR_INVALID, "nby * nbz exceeds 2^24 bins per monitor");
     if (accumulate != 0 && accumulate != 1) return fail(OT_ERR_INVALID, "accumulate must be 0 or 1");
-    if (n < 0 || n >= (int64_t)1 << 31) return fail(OT_ERR_INVALID, "bad segment count");
-    if (src->width != 4 && src->width != 8) return fail(OT_ERR_INVALID, "segment source: width must be 4 or 8");
-    for (const void* p : src->base)
-        if (!p) return fail(OT_ERR_INVALID, "segment source has a NULL field");
-    if (!src->ray) return fail(OT_ERR_INVALID, "segment source has a NULL field");
+    if (const int rc = check_source(src, n, seg_count, n_rays)) return rc;
     if (!intensity) return fail(OT_ERR_INVALID, "NULL intensity");
-    if (src->tile_stride < 64 * (int64_t)src->width || src->ray_stride < 256) return fail(OT_ERR_INVALID, "segment source: a tile stride shorter than 64 slots");
-    if (n > src->capacity) return fail(OT_ERR_INVALID, "n_segments exceeds the capacity of the segment source");
-    if (seg_count && (n_rays < 1 || n % n_rays != 0)) return fail(OT_ERR_INVALID, "n_segments must be a multiple of n_rays");
-    if (!seg_count && n_rays > 0) return fail(OT_ERR_INVALID, "n_rays without seg_count: pass 0 for a list, -1 for a list with holes");
     const int32_t n_edges = nby + nbz + 2;
     for (int32_t m = 0; m < n_monitors; ++m) {
         const double* e = edges + (int64_t)m * n_edges;
@@ -1855,10 +1909,7 @@ static int image_passes(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, c
     HIP_TRY(hipMemcpyAsync(table, mons, sizeof(ot_monitor) * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_edges, edges, sizeof(double) * (size_t)n_monitors * n_edges, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_axes, axes, sizeof(double) * (size_t)n_monitors * 6, hipMemcpyHostToDevice, c->stream));
-    MonSource ms;
-    for (int f = 0; f < 7; ++f) ms.base[f] = (const uint8_t*)src->base[f];
-    ms.ray = (const uint8_t*)src->ray;
-    ms.tile_stride = src->tile_stride, ms.ray_stride = src->ray_stride, ms.width = src->width;
+    const MonSource ms = mon_source(src);
     for (int32_t m0 = 0; m0 < n_monitors; m0 += plan.per_pass) {
         const int32_t nm = std::min<int32_t>(plan.per_pass, n_monitors - m0);
         MonImage pass = img;

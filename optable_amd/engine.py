@@ -156,6 +156,19 @@ def wave_plan(n_monitors, nby, nbz):
     return image_plan(n_monitors, nby, nbz, WAVE_LDS_BINS)
 
 
+# -- fluence maps (ot_fluence_map) ---------------------------------------------------------------------------------------
+FLUENCE_MAX_PIXELS = 1 << 24  # misc_kernels.h SEG_RASTER_MAX_PIXELS: nu * nv
+
+
+def fluence_plan(nu, nv):
+    """How ot_fluence_map deposits into nu x nv pixels (optable_hip.hip ot_fluence_map, the same rule): {"path": "lds" when the
+    image fits a workgroup's LDS at 12 bytes a pixel (IMAGE_LDS_BINS), "global" when every piece is a global atomic}."""
+    nu, nv = int(nu), int(nv)
+    if nu < 1 or nv < 1 or nu * nv > FLUENCE_MAX_PIXELS:
+        raise ValueError(f"no fluence map of {nu} x {nv} pixels")
+    return {"path": "lds" if nu * nv <= IMAGE_LDS_BINS else "global"}
+
+
 # What a whole-trace launch writes, by library call: (the SegmentBatch made when the caller passes none, what makes a passed
 # one of the right precision unusable for `slots` = n x cap records, how the error says so)
 _APPEND_OUT = ({"block": True}, lambda out, slots: out.block is None or out.tiled,
@@ -816,6 +829,43 @@ class Engine:
                                                  None if count is None else count.data_ptr(), n_rays, counts.data_ptr(), weights.data_ptr(),
                                                  0 if into is None else 1), self.lib)
         return counts, weights
+
+    def fluence_map(self, axes, u_edges, v_edges, depth, segs: SegmentBatch, weighted=True, into=None):
+        """Fluence map of a SegmentBatch read as it lies (ot_fluence_map): every segment rasterised into the view axes = (a_u,
+        a_v, a_w) ([3, 3] doubles) over the pixels u_edges x v_edges (numpy) within depth = (w_lo, w_hi).  weighted: every
+        piece weighs its segment's intensity; False: 1 (plain path length).  Returns (counts, fluence, skipped): int64 / float64
+        [nu, nv] and a one-element int64 device tensor, zeroed by the call — or `into`, such a triple from an earlier call, with
+        this call's segments added to it."""
+        with self.lock:
+            return self._fluence_map(axes, u_edges, v_edges, depth, segs, weighted, into)
+
+    def _fluence_map(self, axes, u_edges, v_edges, depth, segs, weighted, into):
+        dev = segs.device
+        axes = np.ascontiguousarray(axes, dtype=np.float64)
+        u_edges, v_edges = np.ascontiguousarray(u_edges, dtype=np.float64), np.ascontiguousarray(v_edges, dtype=np.float64)
+        if axes.shape != (3, 3) or u_edges.ndim != 1 or v_edges.ndim != 1:
+            raise ValueError("axes must be [3, 3], u_edges and v_edges one-dimensional")
+        nu, nv = len(u_edges) - 1, len(v_edges) - 1
+        fluence_plan(nu, nv)
+        if into is None:
+            counts = torch.zeros((nu, nv), dtype=torch.int64, device=dev)
+            fluence = torch.zeros((nu, nv), dtype=torch.float64, device=dev)
+            skipped = torch.zeros(1, dtype=torch.int64, device=dev)
+        else:
+            counts, fluence, skipped = into
+            for t, dt, shape in ((counts, torch.int64, (nu, nv)), (fluence, torch.float64, (nu, nv)), (skipped, torch.int64, (1,))):
+                if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type:
+                    raise ValueError(f"into: contiguous int64 counts and float64 fluence of shape [{nu}, {nv}] and one int64 on {dev}")
+        src, n_segments, count, n_rays = segment_source(segs)
+        if n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
+            return counts, fluence, skipped
+        as_doubles = C.POINTER(C.c_double)
+        abi.check(self.lib.ot_fluence_map(self._ctx, axes.ctypes.data_as(as_doubles), u_edges.ctypes.data_as(as_doubles), nu,
+                                          v_edges.ctypes.data_as(as_doubles), nv, float(depth[0]), float(depth[1]), C.byref(src),
+                                          segs.field("intensity").data_ptr() if weighted else None, n_segments,
+                                          None if count is None else count.data_ptr(), n_rays, counts.data_ptr(), fluence.data_ptr(),
+                                          skipped.data_ptr(), 0 if into is None else 1), self.lib)
+        return counts, fluence, skipped
 
     def monitor_field_many(self, monitor_structs, axes, edges, bins, segs: SegmentBatch, wavelength, amplitude_mode=0, into=None):
         """Coherent detector images of a list of monitors over a double-precision SegmentBatch read as it lies

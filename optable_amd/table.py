@@ -270,6 +270,35 @@ class OpticalTable:
         """One monitor as an image (`image_all` for it alone): a `MonitorImage`."""
         return self.image_all(segs, bins=bins, monitors=[monitor])[0]
 
+    def fluence_map(self, segs, view="Z", roi=None, pixels=256, weight="intensity", into=None):
+        """The segments as an image of a projected view — `render(type=view, roi=roi)` as numbers: a `FluenceMap` whose pixels
+        hold the number of segment pieces inside them and the intensity-weighted path length of those pieces, rasterised on the
+        device from the segments as they lie (any layout, either precision; ot_fluence_map).  view: "Z", "X" or "Y" — the image
+        axes are the lab axes (x, y), (y, z), (z, x) and the third is the depth; roi = (x0, x1, y0, y1, z0, z1) as `render` takes
+        it (default: the table's `get_bbox()`), a depth bound may be infinite; pixels: an int or (nu, nv) equal pixels over the
+        roi's image ranges; weight: "intensity" or "none" (plain path length).  A segment that runs on without end inside the
+        box — the unbounded last segment of a ray, with an infinite depth range — deposits nothing and is counted in `skipped`.
+        `into`: the `FluenceMap` an earlier call with the same view, roi, pixels and weight returned; this call's segments are
+        added to it (the chunks of a streamed trace)."""
+        from .fluence import WEIGHTS, FluenceMap, fluence_view
+
+        if not isinstance(weight, str) or weight not in WEIGHTS:
+            raise ValueError(f'weight must be "intensity" or "none", not {weight!r}')
+        if roi is None:
+            if not self.components:
+                raise ValueError("roi=None takes the table's get_bbox(), and this table has no components: pass roi")
+            roi = self.get_bbox()
+        axes, u_edges, v_edges, depth, roi = fluence_view(view, roi, pixels)
+        stack = None
+        if into is not None:
+            if not isinstance(into, FluenceMap) or (into.view, into.roi, into.pixels, into.weight) != (view, roi, (len(u_edges) - 1, len(v_edges) - 1), weight):
+                raise ValueError("into: the FluenceMap an earlier fluence_map returned for the same view, roi, pixels and weight")
+            stack = (into.counts, into.fluence, into._skipped)
+        counts, fluence, skipped = _engine().fluence_map(axes, u_edges, v_edges, depth, segs, weighted=weight == "intensity", into=stack)
+        if into is not None:
+            return into
+        return FluenceMap(view, roi, weight, counts, fluence, skipped, u_edges, v_edges)
+
     def field_all(self, segs, wavelength=0.0, bins=30, monitors=None, into=None, amplitude="sqrt"):
         """Every monitor of the table (or those given) as a COHERENT image: one `MonitorField` per monitor, in their order — per
         bin of `image_all`'s images the count of hits and the complex sum of a exp(i phi) over them, summed on the device in the

@@ -38,7 +38,7 @@ if os.environ.get("OT_LIB"):  # an A/B build of the library, e.g. the parent com
     abi.LIB_PATH = os.path.abspath(os.environ["OT_LIB"])
     import ctypes
 
-    for newer in ("ot_monitor_image_many", "ot_monitor_field_many", "ot_monitor_beam_many", "ot_monitor_wave_many"):
+    for newer in ("ot_monitor_image_many", "ot_monitor_field_many", "ot_monitor_beam_many", "ot_monitor_wave_many", "ot_fluence_map"):
         if not hasattr(ctypes.CDLL(abi.LIB_PATH), newer):
             del abi.SYMBOLS[newer]
 
