@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <tuple>
 #include <chrono>
@@ -1703,6 +1704,12 @@ static int check_source(const ot_segment_source* src, int64_t n, const int32_t* 
     if (!seg_count && n_rays > 0) return fail(OT_ERR_INVALID, "n_rays without seg_count: pass 0 for a list, -1 for a list with holes");
     return 0;
 }
+// One table of bin edges: finite and strictly increasing
+static bool edges_ok(const double* e, int32_t count) {
+    for (int32_t k = 0; k < count; ++k)
+        if (!std::isfinite(e[k]) || (k && !(e[k] > e[k - 1]))) return false;
+    return true;
+}
 static MonSource mon_source(const ot_segment_source* src) {
     MonSource ms;
     for (int f = 0; f < 7; ++f) ms.base[f] = (const uint8_t*)src->base[f];
@@ -1711,38 +1718,46 @@ static MonSource mon_source(const ot_segment_source* src) {
     return ms;
 }
 
-// The launches of a checked record call with n > 0: count, scan, emit, MON_MAX monitors at a time.  first: n_monitors + 1 device
-// words, or NULL when the caller has no use for them (scratch of the call's own then).
+// The partition of n > 0 slots every kernel over the segments is launched on: `grid` workgroups of `iters` visits of MON_THREADS
+// slots.  Straight to global memory: 8 visits up to 2^25 slots (2441 workgroups for cfg 2's 5e6) and more beyond, which keeps a
+// launch at some 16 thousand workgroups however many slots.  through_lds: workgroups long enough to be worth an LDS image of
+// their own, a thousand of them at most (two rounds of the chip at two a CU), each of which zeroes and flushes its image once.
+struct SlotPartition { int32_t iters; int64_t grid; };
+static SlotPartition slot_partition(int64_t n, bool through_lds) {
+    const int32_t iters = (int32_t)std::max<int64_t>(8, through_lds ? (n + 1024 * MON_THREADS - 1) / (1024 * MON_THREADS) : n >> 22);
+    const int64_t span = (int64_t)iters * MON_THREADS;
+    return {iters, (n + span - 1) / span};
+}
+
+// The launches of a checked record call with n > 0: count, scan, emit, MON_MAX monitors at a time, both passes on one partition.
+// first: n_monitors + 1 device words, or NULL when the caller has no use for them (scratch of the call's own then).
 static int record_passes(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const MonSource& ms, int64_t n, const int32_t* seg_count,
                          int64_t n_rays, int64_t capacity, int64_t* first, int64_t* hit_index, double* Px, double* Py, double* Pz, double* t,
                          int64_t* n_total) {
-    // one partition of the slots for both passes: workgroups of `iters` visits of MON_THREADS slots (8 visits up to 2^25 slots: 2441
-    // workgroups for cfg 2's 5e6; more visits beyond, which keeps a launch at some 16 thousand workgroups however many slots)
-    const int32_t iters = (int32_t)std::max<int64_t>(8, n >> 22);
-    const int64_t span = (int64_t)iters * MON_THREADS, grid = (n + span - 1) / span;
+    const SlotPartition sp = slot_partition(n, false);
     const int32_t most = std::min<int32_t>(n_monitors, MON_MAX);
     ot_monitor* table;
     int32_t* count;
     int64_t *off, *own_first;
     const auto carve = [&](void* base) {
         Carve cv{(uint8_t*)base};
-        table = cv.take<ot_monitor>(n_monitors), count = cv.take<int32_t>(most * grid + 1), off = cv.take<int64_t>(most * grid + 1);
+        table = cv.take<ot_monitor>(n_monitors), count = cv.take<int32_t>(most * sp.grid + 1), off = cv.take<int64_t>(most * sp.grid + 1);
         own_first = cv.take<int64_t>(first ? 0 : n_monitors + 1);
         return cv.used;
     };
     if (c->mon.ensure(carve(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of monitor scratch failed");
     carve(c->mon.p);
     if (!first) first = own_first;
-    if (c->scan_tmp.ensure(scan_tmp_bytes<int64_t>(most * grid + 1) + 256)) return fail(OT_ERR_HIP, "hipMalloc of scan scratch failed");
+    if (c->scan_tmp.ensure(scan_tmp_bytes<int64_t>(most * sp.grid + 1) + 256)) return fail(OT_ERR_HIP, "hipMalloc of scan scratch failed");
     HIP_TRY(hipMemcpyAsync(table, mons, sizeof(ot_monitor) * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(first, 0, sizeof(int64_t), c->stream));
     // MON_MAX monitors per launch; a launch takes the hits before it from first[m0], where the launch before it left them
     for (int32_t m0 = 0; m0 < n_monitors; m0 += MON_MAX) {
         const int32_t nm = std::min<int32_t>(MON_MAX, n_monitors - m0);
-        hipLaunchKernelGGL(k_mon_count, dim3((unsigned)grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, iters, seg_count, n_rays, count,
+        hipLaunchKernelGGL(k_mon_count, dim3((unsigned)sp.grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, sp.iters, seg_count, n_rays, count,
                            MonImage{}, MonField{}, MonBeam{});
-        exclusive_scan<int32_t, int64_t>(c->scan_tmp.p, count, off, nm * grid + 1, c->stream);
-        hipLaunchKernelGGL(k_mon_emit, dim3((unsigned)grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, iters, seg_count, n_rays, off,
+        exclusive_scan<int32_t, int64_t>(c->scan_tmp.p, count, off, nm * sp.grid + 1, c->stream);
+        hipLaunchKernelGGL(k_mon_emit, dim3((unsigned)sp.grid), dim3(MON_THREADS), 0, c->stream, table + m0, nm, ms, n, sp.iters, seg_count, n_rays, off,
                            capacity, first + m0, hit_index, Px, Py, Pz, t, n_total);
     }
     HIP_TRY(hipGetLastError());
@@ -1755,20 +1770,17 @@ int ot_monitor_record_f64(ot_ctx* c, const ot_monitor* mon, const ot_segments* s
     if (!c || !mon || !hit_index || !Px || !Py || !Pz || !t || !n_hits) return fail(OT_ERR_INVALID, "NULL argument");
     int rc = check_segs(segs);
     if (rc) return rc;
-    if (n < 0 || n >= (int64_t)1 << 31) return fail(OT_ERR_INVALID, "bad segment count");
-    if (seg_count && (n_rays < 1 || n % n_rays != 0)) return fail(OT_ERR_INVALID, "n_segments must be a multiple of n_rays");
-    if (!seg_count && n_rays > 0) return fail(OT_ERR_INVALID, "n_rays without seg_count: pass 0 for a list, -1 for a list with holes");
+    // plain arrays of doubles: 64-slot "tiles" back to back, room for the n slots asked for
+    const ot_segment_source src = {{segs->ox, segs->oy, segs->oz, segs->dx, segs->dy, segs->dz, segs->length}, segs->ray, 512, 256, n, 8};
+    rc = check_source(&src, n, seg_count, n_rays);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (n == 0) {
         HIP_TRY(hipMemsetAsync(n_hits, 0, sizeof(int64_t), c->stream));
         return 0;
     }
-    MonSource ms;
-    const void* fields[7] = {segs->ox, segs->oy, segs->oz, segs->dx, segs->dy, segs->dz, segs->length};
-    for (int f = 0; f < 7; ++f) ms.base[f] = (const uint8_t*)fields[f];
-    ms.ray = (const uint8_t*)segs->ray;
-    ms.tile_stride = 512, ms.ray_stride = 256, ms.width = 8;  // plain arrays of doubles: 64-slot "tiles" back to back
-    return record_passes(c, mon, 1, ms, n, seg_count, n_rays, n, nullptr, hit_index, (double*)Px, (double*)Py, (double*)Pz, (double*)t, n_hits);
+    return record_passes(c, mon, 1, mon_source(&src), n, seg_count, n_rays, n, nullptr, hit_index, (double*)Px, (double*)Py, (double*)Pz, (double*)t,
+                         n_hits);
 }
 
 int ot_monitor_record_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const ot_segment_source* src, int64_t n,
@@ -1799,11 +1811,7 @@ int ot_fluence_map(ot_ctx* c, const double* axes, const double* u_edges, int32_t
     if ((int64_t)nu * nv > SEG_RASTER_MAX_PIXELS) return fail(OT_ERR_INVALID, "nu * nv exceeds 2^24 pixels");
     if (accumulate != 0 && accumulate != 1) return fail(OT_ERR_INVALID, "accumulate must be 0 or 1");
     if (const int rc = check_source(src, n, seg_count, n_rays)) return rc;
-    for (int axis = 0; axis < 2; ++axis) {
-        const double* e = axis ? v_edges : u_edges;
-        for (int32_t k = 0; k <= (axis ? nv : nu); ++k)
-            if (!std::isfinite(e[k]) || (k && !(e[k] > e[k - 1]))) return fail(OT_ERR_INVALID, "edges must be finite and strictly increasing");
-    }
+    if (!edges_ok(u_edges, nu + 1) || !edges_ok(v_edges, nv + 1)) return fail(OT_ERR_INVALID, "edges must be finite and strictly increasing");
     if (!(w_lo <= w_hi)) return fail(OT_ERR_INVALID, "w_lo must not exceed w_hi");
     for (int k = 0; k < 9; ++k)
         if (!std::isfinite(axes[k])) return fail(OT_ERR_INVALID, "axes must be finite");
@@ -1816,8 +1824,7 @@ int ot_fluence_map(ot_ctx* c, const double* axes, const double* u_edges, int32_t
     }
     if (n == 0) return 0;
     const bool lds = pixels <= (size_t)MON_IMG_LDS_BINS;
-    const int32_t iters = (int32_t)std::max<int64_t>(8, lds ? (n + 1024 * MON_THREADS - 1) / (1024 * MON_THREADS) : n >> 22);
-    const int64_t span = (int64_t)iters * MON_THREADS, grid = (n + span - 1) / span;
+    const SlotPartition sp = slot_partition(n, lds);
     double* d_edges;
     const auto carve = [&](void* base) {
         Carve cv{(uint8_t*)base};
@@ -1835,17 +1842,17 @@ int ot_fluence_map(ot_ctx* c, const double* axes, const double* u_edges, int32_t
     for (int k = 0; k < 9; ++k) r.axes[k] = axes[k];
     r.w_lo = w_lo, r.w_hi = w_hi;
     r.nu = nu, r.nv = nv, r.lds_pixels = lds ? (int32_t)pixels : 0;
-    hipLaunchKernelGGL(k_seg_raster, dim3((unsigned)grid), dim3(MON_THREADS), (size_t)r.lds_pixels * 12, c->stream, mon_source(src), n, iters, seg_count,
-                       n_rays, r);
+    hipLaunchKernelGGL(k_seg_raster, dim3((unsigned)sp.grid), dim3(MON_THREADS), (size_t)r.lds_pixels * 12, c->stream, mon_source(src), n, sp.iters,
+                       seg_count, n_rays, r);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// How ot_monitor_image_many / ot_monitor_field_many / ot_monitor_beam_many walk n_monitors monitors of nby x nbz bins: `passes`
-// launches of at most `per_pass` monitors each, as even as they come (8 monitors of 30 x 30: 4 + 4, not 6 + 2), through LDS when a
-// pass's bins fit `budget` (MON_IMG_LDS_BINS; MON_FIELD_LDS_BINS for a field: 8 monitors go 3 + 3 + 2; MON_BEAM_LDS_BINS for beams:
-// 6 go 3 + 3), else (one monitor alone does not fit) MON_MAX at a time straight to global memory.  optable_amd/engine.py image_plan /
-// field_plan / beam_plan say the same.
+// How the detector-image calls (ot_monitor_image_many / _field_many / _beam_many / _wave_many) walk n_monitors monitors of nby x nbz
+// bins: `passes` launches of at most `per_pass` monitors each, as even as they come (8 monitors of 30 x 30: 4 + 4, not 6 + 2),
+// through LDS when a pass's bins fit the mode's `budget` (MON_IMG_LDS_BINS; MON_FIELD_LDS_BINS: 8 monitors go 3 + 3 + 2;
+// MON_BEAM_LDS_BINS: 6 go 3 + 3; MON_WAVE_LDS_BINS: 4 go 2 + 2), else (one monitor alone does not fit) MON_MAX at a time straight
+// to global memory.  optable_amd/engine.py image_plan / field_plan / beam_plan / wave_plan say the same.
 struct ImagePlan {
     int32_t per_pass, passes;
     bool lds;
@@ -1860,100 +1867,117 @@ static ImagePlan image_plan(int32_t n_monitors, int32_t nby, int32_t nbz, int32_
     return p;
 }
 
-// What the three calls refuse alike (their own outputs apart), before anything is launched or zeroed.
-static int check_image_call(const ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, int32_t nby,
-                            int32_t nbz, const ot_segment_source* src, const void* intensity, int64_t n, const int32_t* seg_count,
-                            int64_t n_rays, int32_t accumulate) {
-    if (!c || !mons || !axes || !edges || !src) return fail(OT_ERR_INVALID, "NULL argument");
-    if (n_monitors < 1) return fail(OT_ERR_INVALID, "n_monitors must be at least 1");
-    if (nby < 1 || nbz < 1) return fail(OT_ERR_INVALID, "nby and nbz must be at least 1");
-    if ((int64_t)nby * nbz > MON_IMG_MAX_BINS) return fail(OT_ERR_INVALID, "nby * nbz exceeds 2^24 bins per monitor");
-    if (accumulate != 0 && accumulate != 1) return fail(OT_ERR_INVALID, "accumulate must be 0 or 1");
-    if (const int rc = check_source(src, n, seg_count, n_rays)) return rc;
-    if (!intensity) return fail(OT_ERR_INVALID, "NULL intensity");
-    const int32_t n_edges = nby + nbz + 2;
-    for (int32_t m = 0; m < n_monitors; ++m) {
-        const double* e = edges + (int64_t)m * n_edges;
-        for (int32_t k = 0; k < n_edges; ++k)  // (k = nby + 1 starts the z table: nothing before it to exceed)
-            if (!std::isfinite(e[k]) || (k && k != nby + 1 && !(e[k] > e[k - 1])))
-                return fail(OT_ERR_INVALID, "edges must be finite and strictly increasing");
+// What the four calls take alike, and what they refuse of it alike (their other outputs apart), before anything is launched or
+// zeroed.  counts: the [n_monitors][nby][nbz] image every mode has.
+struct ImageCall {
+    ot_ctx* c; const ot_monitor* mons; int32_t n_monitors; const double *axes, *edges; int32_t nby, nbz;
+    const ot_segment_source* src; const void* intensity; int64_t n; const int32_t* seg_count; int64_t n_rays;
+    int64_t* counts; int32_t accumulate;
+};
+static int check_image_call(const ImageCall& a) {
+    if (!a.c || !a.mons || !a.axes || !a.edges || !a.src || !a.counts) return fail(OT_ERR_INVALID, "NULL argument");
+    if (a.n_monitors < 1) return fail(OT_ERR_INVALID, "n_monitors must be at least 1");
+    if (a.nby < 1 || a.nbz < 1) return fail(OT_ERR_INVALID, "nby and nbz must be at least 1");
+    if ((int64_t)a.nby * a.nbz > MON_IMG_MAX_BINS) return fail(OT_ERR_INVALID, "nby * nbz exceeds 2^24 bins per monitor");
+    if (a.accumulate != 0 && a.accumulate != 1) return fail(OT_ERR_INVALID, "accumulate must be 0 or 1");
+    if (const int rc = check_source(a.src, a.n, a.seg_count, a.n_rays)) return rc;
+    if (!a.intensity) return fail(OT_ERR_INVALID, "NULL intensity");
+    const int32_t n_edges = a.nby + a.nbz + 2;
+    for (int32_t m = 0; m < a.n_monitors; ++m) {
+        const double* e = a.edges + (int64_t)m * n_edges;
+        if (!edges_ok(e, a.nby + 1) || !edges_ok(e + a.nby + 1, a.nbz + 1)) return fail(OT_ERR_INVALID, "edges must be finite and strictly increasing");
         for (int k = 0; k < 6; ++k)
-            if (!std::isfinite(axes[6 * (int64_t)m + k])) return fail(OT_ERR_INVALID, "axes must be finite");
+            if (!std::isfinite(a.axes[6 * (int64_t)m + k])) return fail(OT_ERR_INVALID, "axes must be finite");
     }
     return 0;
 }
+// ... and what the coherent and the beam modes refuse alike of their wavelengths and their amplitude
+static int check_wavelength_args(const double* wavelength, int64_t n_wavelengths, double wavelength_uniform) {
+    if (wavelength && (n_wavelengths < 1 || n_wavelengths >= (int64_t)1 << 31)) return fail(OT_ERR_INVALID, "n_wavelengths must be at least 1 (and below 2^31)");
+    if (!wavelength && !(std::isfinite(wavelength_uniform) && wavelength_uniform > 0.0))
+        return fail(OT_ERR_INVALID, "wavelength_uniform must be finite and > 0 when there is no wavelength array");
+    return 0;
+}
+static int check_amplitude_mode(int32_t amplitude_mode) {
+    return amplitude_mode != 0 && amplitude_mode != 1 ? fail(OT_ERR_INVALID, "amplitude_mode must be 0 (sqrt) or 1 (linear)") : 0;
+}
 
-// The launches of a checked call whose outputs are zeroed or kept: the monitors, edges and axes to the device, then k_mon_count in
-// image mode (fld.re and beam.power NULL, 12 bytes of LDS a bin), field mode (20) or beam mode (12, behind the waves' edge strips)
-// — or, with `wav`, k_mon_wave (20, behind its strips) — once per pass of the plan.  img.counts / img.weights, fld.re / fld.im and beam.power come in as the images of monitor 0 and go
-// to the kernel as those of the pass's first monitor.
-static int image_passes(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, const ot_segment_source* src,
-                        int64_t n, const int32_t* seg_count, int64_t n_rays, const ImagePlan& plan, MonImage img, MonField fld, MonBeam beam,
-                        const MonWave* wav = nullptr) {
-    const int32_t n_edges = img.nby + img.nbz + 2;
-    const size_t bins = (size_t)img.nby * img.nbz, bytes_a_bin = fld.re || wav ? 20 : 12;
-    const size_t strips = sizeof(double) * MON_WAVES * (wav ? MON_WAVE_STRIP : beam.power ? MON_BEAM_STRIP : 0);
-    // the partition of k_mon_count, with workgroups long enough to be worth an image of their own: a thousand of them at most
-    // (two rounds of the chip at two a CU), each of which zeroes and flushes its LDS image once
-    const int32_t iters = (int32_t)std::max<int64_t>(8, (n + 1024 * MON_THREADS - 1) / (1024 * MON_THREADS));
-    const int64_t span = (int64_t)iters * MON_THREADS, grid = (n + span - 1) / span;
+// A mode of the detector images, as its caller describes it to image_call: how much LDS its kernel takes (`strips` bytes in front
+// of `bytes_a_bin` for each of at most `lds_budget` bins), the outputs it has next to `counts` (`planes`: [n_monitors][nby][nbz]
+// doubles; `tallies`: one int64 each; NULL where a mode has fewer) ...
+struct ImageMode {
+    int32_t lds_budget; size_t bytes_a_bin, strips;
+    double* planes[2]; int64_t* tallies[2];
+};
+// ... and what its `launch` is handed for one pass: the pass's monitors, the partition and LDS bytes to launch on, `img` with the
+// counts, edges and axes of the pass's first monitor, and `first_bin`, where that monitor's image starts in every plane.
+struct ImagePass {
+    const ot_monitor* table; int32_t nm; MonSource ms; SlotPartition sp; size_t lds_bytes, first_bin;
+    MonImage img;
+};
+
+// The shared half of a checked call: the outputs zeroed unless they are kept, nothing more for n = 0; else the monitors, edges and
+// axes to the device and one `launch` per pass of the plan.  A new mode is a new caller: its checks, its ImageMode, its launch.
+static int image_call(const ImageCall& a, const ImageMode& mode, const std::function<void(const ImagePass&)>& launch) {
+    ot_ctx* c = a.c;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bins = (size_t)a.nby * a.nbz;
+    if (!a.accumulate) {
+        HIP_TRY(hipMemsetAsync(a.counts, 0, sizeof(int64_t) * bins * a.n_monitors, c->stream));
+        for (double* plane : mode.planes)
+            if (plane) HIP_TRY(hipMemsetAsync(plane, 0, sizeof(double) * bins * a.n_monitors, c->stream));
+        for (int64_t* tally : mode.tallies)
+            if (tally) HIP_TRY(hipMemsetAsync(tally, 0, sizeof(int64_t), c->stream));
+    }
+    if (a.n == 0) return 0;
+    const ImagePlan plan = image_plan(a.n_monitors, a.nby, a.nbz, mode.lds_budget);
+    const int32_t n_edges = a.nby + a.nbz + 2;
     ot_monitor* table;
     double *d_edges, *d_axes;
     const auto carve = [&](void* base) {
         Carve cv{(uint8_t*)base};
-        table = cv.take<ot_monitor>(n_monitors), d_edges = cv.take<double>((int64_t)n_monitors * n_edges), d_axes = cv.take<double>((int64_t)n_monitors * 6);
+        table = cv.take<ot_monitor>(a.n_monitors), d_edges = cv.take<double>((int64_t)a.n_monitors * n_edges), d_axes = cv.take<double>((int64_t)a.n_monitors * 6);
         return cv.used;
     };
     if (c->mon.ensure(carve(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of monitor scratch failed");
     carve(c->mon.p);
-    HIP_TRY(hipMemcpyAsync(table, mons, sizeof(ot_monitor) * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_edges, edges, sizeof(double) * (size_t)n_monitors * n_edges, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_axes, axes, sizeof(double) * (size_t)n_monitors * 6, hipMemcpyHostToDevice, c->stream));
-    const MonSource ms = mon_source(src);
-    for (int32_t m0 = 0; m0 < n_monitors; m0 += plan.per_pass) {
-        const int32_t nm = std::min<int32_t>(plan.per_pass, n_monitors - m0);
-        MonImage pass = img;
-        MonField pass_field = fld;
-        MonBeam pass_beam = beam;
-        pass.counts += m0 * bins;
-        if (beam.power) pass_beam.power += m0 * bins;
-        else if (fld.re) pass_field.re += m0 * bins, pass_field.im += m0 * bins;
-        else if (!wav) pass.weights += m0 * bins;
-        pass.edges = d_edges + (int64_t)m0 * n_edges, pass.axes = d_axes + (int64_t)m0 * 6;
-        pass.lds_bins = plan.lds ? (int32_t)(nm * bins) : 0;
-        if (wav) {  // a kernel of its own, on the same partition
-            MonWave pass_wave = *wav;
-            pass_wave.re += m0 * bins, pass_wave.im += m0 * bins;
-            hipLaunchKernelGGL(k_mon_wave, dim3((unsigned)grid), dim3(MON_THREADS), strips + (size_t)pass.lds_bins * bytes_a_bin, c->stream, table + m0, nm,
-                               ms, n, iters, seg_count, n_rays, pass, pass_wave);
-            continue;
-        }
-        hipLaunchKernelGGL(k_mon_count, dim3((unsigned)grid), dim3(MON_THREADS), strips + (size_t)pass.lds_bins * bytes_a_bin, c->stream, table + m0, nm,
-                           ms, n, iters, seg_count, n_rays, (int32_t*)nullptr, pass, pass_field, pass_beam);
+    HIP_TRY(hipMemcpyAsync(table, a.mons, sizeof(ot_monitor) * (size_t)a.n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_edges, a.edges, sizeof(double) * (size_t)a.n_monitors * n_edges, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_axes, a.axes, sizeof(double) * (size_t)a.n_monitors * 6, hipMemcpyHostToDevice, c->stream));
+    ImagePass pass{};
+    pass.ms = mon_source(a.src);
+    pass.sp = slot_partition(a.n, true);  // (the long workgroups on the global path too)
+    pass.img.intensity = (const uint8_t*)a.intensity;
+    pass.img.nby = a.nby, pass.img.nbz = a.nbz;
+    for (int32_t m0 = 0; m0 < a.n_monitors; m0 += plan.per_pass) {
+        pass.table = table + m0, pass.nm = std::min<int32_t>(plan.per_pass, a.n_monitors - m0);
+        pass.first_bin = m0 * bins;
+        pass.img.counts = (unsigned long long*)a.counts + pass.first_bin;
+        pass.img.edges = d_edges + (int64_t)m0 * n_edges, pass.img.axes = d_axes + (int64_t)m0 * 6;
+        pass.img.lds_bins = plan.lds ? (int32_t)(pass.nm * bins) : 0;
+        pass.lds_bytes = mode.strips + (size_t)pass.img.lds_bins * mode.bytes_a_bin;
+        launch(pass);
     }
     HIP_TRY(hipGetLastError());
     return 0;
+}
+// k_mon_count in one of its image modes (no per-workgroup counts): fld.re and beam.power NULL for plain images
+static void launch_count(const ImageCall& a, const ImagePass& p, const MonImage& img, const MonField& fld, const MonBeam& beam) {
+    hipLaunchKernelGGL(k_mon_count, dim3((unsigned)p.sp.grid), dim3(MON_THREADS), p.lds_bytes, a.c->stream, p.table, p.nm, p.ms, a.n, p.sp.iters,
+                       a.seg_count, a.n_rays, (int32_t*)nullptr, img, fld, beam);
 }
 
 int ot_monitor_image_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, int32_t nby,
                           int32_t nbz, const ot_segment_source* src, const void* intensity, int64_t n, const int32_t* seg_count,
                           int64_t n_rays, int64_t* counts, double* weights, int32_t accumulate) {
-    if (!counts || !weights) return fail(OT_ERR_INVALID, "NULL argument");
-    const int rc = check_image_call(c, mons, n_monitors, axes, edges, nby, nbz, src, intensity, n, seg_count, n_rays, accumulate);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t bins = (size_t)nby * nbz;
-    if (!accumulate) {
-        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * bins * n_monitors, c->stream));
-        HIP_TRY(hipMemsetAsync(weights, 0, sizeof(double) * bins * n_monitors, c->stream));
-    }
-    if (n == 0) return 0;
-    MonImage img{};
-    img.counts = (unsigned long long*)counts, img.weights = weights;
-    img.intensity = (const uint8_t*)intensity;
-    img.nby = nby, img.nbz = nbz;
-    return image_passes(c, mons, n_monitors, axes, edges, src, n, seg_count, n_rays, image_plan(n_monitors, nby, nbz, MON_IMG_LDS_BINS), img, MonField{},
-                        MonBeam{});
+    if (!weights) return fail(OT_ERR_INVALID, "NULL argument");
+    const ImageCall a{c, mons, n_monitors, axes, edges, nby, nbz, src, intensity, n, seg_count, n_rays, counts, accumulate};
+    if (const int rc = check_image_call(a)) return rc;
+    return image_call(a, {MON_IMG_LDS_BINS, 12, 0, {weights}, {}}, [&](const ImagePass& p) {
+        MonImage img = p.img;
+        img.weights = weights + p.first_bin;
+        launch_count(a, p, img, MonField{}, MonBeam{});
+    });
 }
 
 int ot_monitor_field_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, int32_t nby,
@@ -1961,67 +1985,40 @@ int ot_monitor_field_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors,
                           const double* wavelength, int64_t n_wavelengths, double wavelength_uniform, int32_t amplitude_mode, int64_t n,
                           const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* re, double* im, int64_t* skipped,
                           int32_t accumulate) {
-    if (!counts || !re || !im || !skipped) return fail(OT_ERR_INVALID, "NULL argument");
-    const int rc = check_image_call(c, mons, n_monitors, axes, edges, nby, nbz, src, intensity, n, seg_count, n_rays, accumulate);
-    if (rc) return rc;
+    if (!re || !im || !skipped) return fail(OT_ERR_INVALID, "NULL argument");
+    const ImageCall a{c, mons, n_monitors, axes, edges, nby, nbz, src, intensity, n, seg_count, n_rays, counts, accumulate};
+    if (const int rc = check_image_call(a)) return rc;
     if (src->width != 8) return fail(OT_ERR_INVALID, "a field needs double-precision segments: width must be 8");
     if (!n_index || !pathlength) return fail(OT_ERR_INVALID, "NULL n_index or pathlength");
-    if (wavelength && (n_wavelengths < 1 || n_wavelengths >= (int64_t)1 << 31)) return fail(OT_ERR_INVALID, "n_wavelengths must be at least 1 (and below 2^31)");
-    if (!wavelength && !(std::isfinite(wavelength_uniform) && wavelength_uniform > 0.0))
-        return fail(OT_ERR_INVALID, "wavelength_uniform must be finite and > 0 when there is no wavelength array");
-    if (amplitude_mode != 0 && amplitude_mode != 1) return fail(OT_ERR_INVALID, "amplitude_mode must be 0 (sqrt) or 1 (linear)");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t bins = (size_t)nby * nbz;
-    if (!accumulate) {
-        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * bins * n_monitors, c->stream));
-        HIP_TRY(hipMemsetAsync(re, 0, sizeof(double) * bins * n_monitors, c->stream));
-        HIP_TRY(hipMemsetAsync(im, 0, sizeof(double) * bins * n_monitors, c->stream));
-        HIP_TRY(hipMemsetAsync(skipped, 0, sizeof(int64_t), c->stream));
-    }
-    if (n == 0) return 0;
-    MonImage img{};
-    img.counts = (unsigned long long*)counts;
-    img.intensity = (const uint8_t*)intensity;
-    img.nby = nby, img.nbz = nbz;
+    if (const int rc = check_wavelength_args(wavelength, n_wavelengths, wavelength_uniform)) return rc;
+    if (const int rc = check_amplitude_mode(amplitude_mode)) return rc;
     MonField fld{};
-    fld.re = re, fld.im = im;
     fld.n_index = (const uint8_t*)n_index, fld.pathlength = (const uint8_t*)pathlength;
     fld.wavelength = wavelength, fld.n_wavelengths = (int32_t)n_wavelengths, fld.wavelength_uniform = wavelength_uniform;
     fld.skipped = (unsigned long long*)skipped, fld.amplitude_mode = amplitude_mode;
-    return image_passes(c, mons, n_monitors, axes, edges, src, n, seg_count, n_rays, image_plan(n_monitors, nby, nbz, MON_FIELD_LDS_BINS), img, fld,
-                        MonBeam{});
+    return image_call(a, {MON_FIELD_LDS_BINS, 20, 0, {re, im}, {skipped}}, [&](const ImagePass& p) {
+        fld.re = re + p.first_bin, fld.im = im + p.first_bin;
+        launch_count(a, p, p.img, fld, MonBeam{});
+    });
 }
 
 int ot_monitor_beam_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, int32_t nby,
                          int32_t nbz, const ot_segment_source* src, const void* intensity, const void* q_re, const void* q_im,
                          const void* n_index, const double* wavelength, int64_t n_wavelengths, double wavelength_uniform, int64_t n,
                          const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* power, int64_t* skipped, int32_t accumulate) {
-    if (!counts || !power || !skipped) return fail(OT_ERR_INVALID, "NULL argument");
-    const int rc = check_image_call(c, mons, n_monitors, axes, edges, nby, nbz, src, intensity, n, seg_count, n_rays, accumulate);
-    if (rc) return rc;
+    if (!power || !skipped) return fail(OT_ERR_INVALID, "NULL argument");
+    const ImageCall a{c, mons, n_monitors, axes, edges, nby, nbz, src, intensity, n, seg_count, n_rays, counts, accumulate};
+    if (const int rc = check_image_call(a)) return rc;
     if (!q_re || !q_im || !n_index) return fail(OT_ERR_INVALID, "NULL q_re, q_im or n_index");
-    if (wavelength && (n_wavelengths < 1 || n_wavelengths >= (int64_t)1 << 31)) return fail(OT_ERR_INVALID, "n_wavelengths must be at least 1 (and below 2^31)");
-    if (!wavelength && !(std::isfinite(wavelength_uniform) && wavelength_uniform > 0.0))
-        return fail(OT_ERR_INVALID, "wavelength_uniform must be finite and > 0 when there is no wavelength array");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t bins = (size_t)nby * nbz;
-    if (!accumulate) {
-        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * bins * n_monitors, c->stream));
-        HIP_TRY(hipMemsetAsync(power, 0, sizeof(double) * bins * n_monitors, c->stream));
-        HIP_TRY(hipMemsetAsync(skipped, 0, sizeof(int64_t), c->stream));
-    }
-    if (n == 0) return 0;
-    MonImage img{};
-    img.counts = (unsigned long long*)counts;
-    img.intensity = (const uint8_t*)intensity;
-    img.nby = nby, img.nbz = nbz;
+    if (const int rc = check_wavelength_args(wavelength, n_wavelengths, wavelength_uniform)) return rc;
     MonBeam beam{};
-    beam.power = power;
     beam.q_re = (const uint8_t*)q_re, beam.q_im = (const uint8_t*)q_im, beam.n_index = (const uint8_t*)n_index;
     beam.wavelength = wavelength, beam.n_wavelengths = (int32_t)n_wavelengths, beam.wavelength_uniform = wavelength_uniform;
     beam.skipped = (unsigned long long*)skipped;
-    return image_passes(c, mons, n_monitors, axes, edges, src, n, seg_count, n_rays, image_plan(n_monitors, nby, nbz, MON_BEAM_LDS_BINS), img, MonField{},
-                        beam);
+    return image_call(a, {MON_BEAM_LDS_BINS, 12, sizeof(double) * MON_WAVES * MON_BEAM_STRIP, {power}, {skipped}}, [&](const ImagePass& p) {
+        beam.power = power + p.first_bin;
+        launch_count(a, p, p.img, MonField{}, beam);
+    });
 }
 
 int ot_monitor_wave_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* edges, int32_t nby,
@@ -2029,39 +2026,25 @@ int ot_monitor_wave_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, 
                          const void* q_re, const void* q_im, const double* wavelength, int64_t n_wavelengths, double wavelength_uniform,
                          int32_t amplitude_mode, int32_t gouy, int64_t n, const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* re,
                          double* im, int64_t* skipped, int64_t* aliased, int32_t accumulate) {
-    if (!counts || !re || !im || !skipped || !aliased) return fail(OT_ERR_INVALID, "NULL argument");
-    const int rc = check_image_call(c, mons, n_monitors, axes, edges, nby, nbz, src, intensity, n, seg_count, n_rays, accumulate);
-    if (rc) return rc;
+    if (!re || !im || !skipped || !aliased) return fail(OT_ERR_INVALID, "NULL argument");
+    const ImageCall a{c, mons, n_monitors, axes, edges, nby, nbz, src, intensity, n, seg_count, n_rays, counts, accumulate};
+    if (const int rc = check_image_call(a)) return rc;
     if (src->width != 8) return fail(OT_ERR_INVALID, "a beam field needs double-precision segments: width must be 8");
     if (!n_index || !pathlength || !q_re || !q_im) return fail(OT_ERR_INVALID, "NULL n_index, pathlength, q_re or q_im");
-    if (wavelength && (n_wavelengths < 1 || n_wavelengths >= (int64_t)1 << 31)) return fail(OT_ERR_INVALID, "n_wavelengths must be at least 1 (and below 2^31)");
-    if (!wavelength && !(std::isfinite(wavelength_uniform) && wavelength_uniform > 0.0))
-        return fail(OT_ERR_INVALID, "wavelength_uniform must be finite and > 0 when there is no wavelength array");
-    if (amplitude_mode != 0 && amplitude_mode != 1) return fail(OT_ERR_INVALID, "amplitude_mode must be 0 (sqrt) or 1 (linear)");
+    if (const int rc = check_wavelength_args(wavelength, n_wavelengths, wavelength_uniform)) return rc;
+    if (const int rc = check_amplitude_mode(amplitude_mode)) return rc;
     if (gouy != 0 && gouy != 1) return fail(OT_ERR_INVALID, "gouy must be 0 or 1");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t bins = (size_t)nby * nbz;
-    if (!accumulate) {
-        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * bins * n_monitors, c->stream));
-        HIP_TRY(hipMemsetAsync(re, 0, sizeof(double) * bins * n_monitors, c->stream));
-        HIP_TRY(hipMemsetAsync(im, 0, sizeof(double) * bins * n_monitors, c->stream));
-        HIP_TRY(hipMemsetAsync(skipped, 0, sizeof(int64_t), c->stream));
-        HIP_TRY(hipMemsetAsync(aliased, 0, sizeof(int64_t), c->stream));
-    }
-    if (n == 0) return 0;
-    MonImage img{};
-    img.counts = (unsigned long long*)counts;
-    img.intensity = (const uint8_t*)intensity;
-    img.nby = nby, img.nbz = nbz;
     MonWave wav{};
-    wav.re = re, wav.im = im;
     wav.q_re = (const uint8_t*)q_re, wav.q_im = (const uint8_t*)q_im;
     wav.n_index = (const uint8_t*)n_index, wav.pathlength = (const uint8_t*)pathlength;
     wav.wavelength = wavelength, wav.n_wavelengths = (int32_t)n_wavelengths, wav.wavelength_uniform = wavelength_uniform;
     wav.skipped = (unsigned long long*)skipped, wav.aliased = (unsigned long long*)aliased;
     wav.amplitude_mode = amplitude_mode, wav.gouy = gouy;
-    return image_passes(c, mons, n_monitors, axes, edges, src, n, seg_count, n_rays, image_plan(n_monitors, nby, nbz, MON_WAVE_LDS_BINS), img, MonField{},
-                        MonBeam{}, &wav);
+    return image_call(a, {MON_WAVE_LDS_BINS, 20, sizeof(double) * MON_WAVES * MON_WAVE_STRIP, {re, im}, {skipped, aliased}}, [&](const ImagePass& p) {
+        wav.re = re + p.first_bin, wav.im = im + p.first_bin;  // a kernel of its own, on the same partition
+        hipLaunchKernelGGL(k_mon_wave, dim3((unsigned)p.sp.grid), dim3(MON_THREADS), p.lds_bytes, c->stream, p.table, p.nm, p.ms, n, p.sp.iters, seg_count,
+                           n_rays, p.img, wav);
+    });
 }
 
 int ot_debug_last_launch(ot_ctx* c, int32_t info[8]) {

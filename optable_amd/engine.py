@@ -169,6 +169,52 @@ def fluence_plan(nu, nv):
     return {"path": "lds" if nu * nv <= IMAGE_LDS_BINS else "global"}
 
 
+# -- what the private halves of monitor_*_many and fluence_map share: arguments in, outputs out -------------------------------
+def _doubles(array):
+    return array.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _image_tables(M, nby, nbz, axes, edges):
+    """axes and edges of M monitors as the contiguous float64 [M, 6] and [M, nby + 1 + nbz + 1] arrays the library reads."""
+    axes, edges = np.ascontiguousarray(axes, dtype=np.float64), np.ascontiguousarray(edges, dtype=np.float64)
+    if axes.shape != (M, 6) or edges.shape != (M, nby + nbz + 2):
+        raise ValueError(f"axes must be [{M}, 6] and edges [{M}, {nby + nbz + 2}]")
+    return axes, edges
+
+
+def _wavelength_arg(wavelength, dev):
+    """`wavelength` as the library takes it: (device pointer or None, entries, the one value for all rays)."""
+    if not torch.is_tensor(wavelength):
+        return None, 0, float(wavelength)
+    if wavelength.dtype != torch.float64 or wavelength.dim() != 1 or not wavelength.is_contiguous() or wavelength.device.type != dev.type:
+        raise ValueError(f"wavelength: a float or a contiguous float64 vector on {dev}")
+    return (wavelength.data_ptr() if wavelength.numel() else None), int(wavelength.numel()), 0.0
+
+
+def _outputs(dev, shape, planes, tallies, into, alloc, plane_error, tally_error=None):
+    """The tensors a call adds to: int64 counts and `planes` float64 images of `shape`, then `tallies` one-element int64 tensors
+    — new from `alloc`, or `into`, which must be exactly those (ValueError `plane_error` / `tally_error` for the first that is not)."""
+    specs = [(torch.int64, shape)] + [(torch.float64, shape)] * planes + [(torch.int64, (1,))] * tallies
+    if into is None:
+        return tuple(alloc(sh, dtype=dt, device=dev) for dt, sh in specs)
+    outs = tuple(into)
+    if len(outs) != len(specs):
+        raise ValueError(plane_error)
+    for k, (t, (dt, sh)) in enumerate(zip(outs, specs)):
+        if tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type:
+            raise ValueError(plane_error if k <= planes else tally_error or plane_error)
+    return outs
+
+
+def _untouched(outs, into):
+    """What a call with nothing to add returns (zero-size tensors have no address to hand over): new outputs zeroed, `into` as it is."""
+    return tuple(t.zero_() for t in outs) if into is None else outs
+
+
+def _address(tensor):
+    return None if tensor is None else tensor.data_ptr()
+
+
 # What a whole-trace launch writes, by library call: (the SegmentBatch made when the caller passes none, what makes a passed
 # one of the right precision unusable for `slots` = n x cap records, how the error says so)
 _APPEND_OUT = ({"block": True}, lambda out, slots: out.block is None or out.tiled,
@@ -808,27 +854,16 @@ class Engine:
 
     def _monitor_image_many(self, mons, axes, edges, bins, segs, into):
         dev, M, (nby, nbz) = segs.device, len(mons), bins
-        axes, edges = np.ascontiguousarray(axes, dtype=np.float64), np.ascontiguousarray(edges, dtype=np.float64)
-        if axes.shape != (M, 6) or edges.shape != (M, nby + nbz + 2):
-            raise ValueError(f"axes must be [{M}, 6] and edges [{M}, {nby + nbz + 2}]")
-        if into is None:
-            counts = torch.empty((M, nby, nbz), dtype=torch.int64, device=dev)  # (the call zeroes them)
-            weights = torch.empty((M, nby, nbz), dtype=torch.float64, device=dev)
-        else:
-            counts, weights = into
-            for t, dt in ((counts, torch.int64), (weights, torch.float64)):
-                if tuple(t.shape) != (M, nby, nbz) or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type:
-                    raise ValueError(f"into: contiguous int64 counts and float64 intensity of shape [{M}, {nby}, {nbz}] on {dev}")
+        axes, edges = _image_tables(M, nby, nbz, axes, edges)
+        outs = _outputs(dev, (M, nby, nbz), 1, 0, into, torch.empty,  # (the call zeroes them)
+                        f"into: contiguous int64 counts and float64 intensity of shape [{M}, {nby}, {nbz}] on {dev}")
         src, n_segments, count, n_rays = segment_source(segs)
-        if M == 0 or n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
-            return (counts.zero_(), weights.zero_()) if into is None else (counts, weights)
-        table = (abi.OtMonitor * M)(*mons)
-        as_doubles = C.POINTER(C.c_double)
-        abi.check(self.lib.ot_monitor_image_many(self._ctx, table, M, axes.ctypes.data_as(as_doubles), edges.ctypes.data_as(as_doubles), nby, nbz,
-                                                 C.byref(src), segs.field("intensity").data_ptr(), n_segments,
-                                                 None if count is None else count.data_ptr(), n_rays, counts.data_ptr(), weights.data_ptr(),
-                                                 0 if into is None else 1), self.lib)
-        return counts, weights
+        if M == 0 or n_segments == 0:
+            return _untouched(outs, into)
+        abi.check(self.lib.ot_monitor_image_many(self._ctx, (abi.OtMonitor * M)(*mons), M, _doubles(axes), _doubles(edges), nby, nbz, C.byref(src),
+                                                 segs.field("intensity").data_ptr(), n_segments, _address(count), n_rays,
+                                                 *(t.data_ptr() for t in outs), 0 if into is None else 1), self.lib)
+        return outs
 
     def fluence_map(self, axes, u_edges, v_edges, depth, segs: SegmentBatch, weighted=True, into=None):
         """Fluence map of a SegmentBatch read as it lies (ot_fluence_map): every segment rasterised into the view axes = (a_u,
@@ -847,25 +882,15 @@ class Engine:
             raise ValueError("axes must be [3, 3], u_edges and v_edges one-dimensional")
         nu, nv = len(u_edges) - 1, len(v_edges) - 1
         fluence_plan(nu, nv)
-        if into is None:
-            counts = torch.zeros((nu, nv), dtype=torch.int64, device=dev)
-            fluence = torch.zeros((nu, nv), dtype=torch.float64, device=dev)
-            skipped = torch.zeros(1, dtype=torch.int64, device=dev)
-        else:
-            counts, fluence, skipped = into
-            for t, dt, shape in ((counts, torch.int64, (nu, nv)), (fluence, torch.float64, (nu, nv)), (skipped, torch.int64, (1,))):
-                if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type:
-                    raise ValueError(f"into: contiguous int64 counts and float64 fluence of shape [{nu}, {nv}] and one int64 on {dev}")
+        outs = _outputs(dev, (nu, nv), 1, 1, into, torch.zeros,  # (zeros: the library is not called for nothing)
+                        f"into: contiguous int64 counts and float64 fluence of shape [{nu}, {nv}] and one int64 on {dev}")
         src, n_segments, count, n_rays = segment_source(segs)
         if n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
-            return counts, fluence, skipped
-        as_doubles = C.POINTER(C.c_double)
-        abi.check(self.lib.ot_fluence_map(self._ctx, axes.ctypes.data_as(as_doubles), u_edges.ctypes.data_as(as_doubles), nu,
-                                          v_edges.ctypes.data_as(as_doubles), nv, float(depth[0]), float(depth[1]), C.byref(src),
-                                          segs.field("intensity").data_ptr() if weighted else None, n_segments,
-                                          None if count is None else count.data_ptr(), n_rays, counts.data_ptr(), fluence.data_ptr(),
-                                          skipped.data_ptr(), 0 if into is None else 1), self.lib)
-        return counts, fluence, skipped
+            return outs
+        abi.check(self.lib.ot_fluence_map(self._ctx, _doubles(axes), _doubles(u_edges), nu, _doubles(v_edges), nv, float(depth[0]), float(depth[1]),
+                                          C.byref(src), segs.field("intensity").data_ptr() if weighted else None, n_segments, _address(count),
+                                          n_rays, *(t.data_ptr() for t in outs), 0 if into is None else 1), self.lib)
+        return outs
 
     def monitor_field_many(self, monitor_structs, axes, edges, bins, segs: SegmentBatch, wavelength, amplitude_mode=0, into=None):
         """Coherent detector images of a list of monitors over a double-precision SegmentBatch read as it lies
@@ -879,39 +904,20 @@ class Engine:
 
     def _monitor_field_many(self, mons, axes, edges, bins, segs, wavelength, amplitude_mode, into):
         dev, M, (nby, nbz) = segs.device, len(mons), bins
-        axes, edges = np.ascontiguousarray(axes, dtype=np.float64), np.ascontiguousarray(edges, dtype=np.float64)
-        if axes.shape != (M, 6) or edges.shape != (M, nby + nbz + 2):
-            raise ValueError(f"axes must be [{M}, 6] and edges [{M}, {nby + nbz + 2}]")
+        axes, edges = _image_tables(M, nby, nbz, axes, edges)
         if segs.precision != "f64":
             raise ValueError("a field needs double-precision segments")
-        if torch.is_tensor(wavelength):
-            if wavelength.dtype != torch.float64 or wavelength.dim() != 1 or not wavelength.is_contiguous() or wavelength.device.type != dev.type:
-                raise ValueError(f"wavelength: a float or a contiguous float64 vector on {dev}")
-            table_ptr, n_table, uniform = (wavelength.data_ptr() if wavelength.numel() else None), int(wavelength.numel()), 0.0
-        else:
-            table_ptr, n_table, uniform = None, 0, float(wavelength)
-        if into is None:
-            counts = torch.empty((M, nby, nbz), dtype=torch.int64, device=dev)  # (the call zeroes them)
-            re, im = (torch.empty((M, nby, nbz), dtype=torch.float64, device=dev) for _ in range(2))
-            skipped = torch.empty(1, dtype=torch.int64, device=dev)
-        else:
-            counts, re, im, skipped = into
-            for t, dt in ((counts, torch.int64), (re, torch.float64), (im, torch.float64)):
-                if tuple(t.shape) != (M, nby, nbz) or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type:
-                    raise ValueError(f"into: contiguous int64 counts and float64 re, im of shape [{M}, {nby}, {nbz}] on {dev}")
-            if tuple(skipped.shape) != (1,) or skipped.dtype != torch.int64 or skipped.device.type != dev.type:
-                raise ValueError(f"into: skipped is one int64 on {dev}")
+        wavelength = _wavelength_arg(wavelength, dev)
+        outs = _outputs(dev, (M, nby, nbz), 2, 1, into, torch.empty,  # (the call zeroes them)
+                        f"into: contiguous int64 counts and float64 re, im of shape [{M}, {nby}, {nbz}] on {dev}", f"into: skipped is one int64 on {dev}")
         src, n_segments, count, n_rays = segment_source(segs)
-        if M == 0 or n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
-            return (counts.zero_(), re.zero_(), im.zero_(), skipped.zero_()) if into is None else (counts, re, im, skipped)
-        table = (abi.OtMonitor * M)(*mons)
-        as_doubles = C.POINTER(C.c_double)
-        abi.check(self.lib.ot_monitor_field_many(self._ctx, table, M, axes.ctypes.data_as(as_doubles), edges.ctypes.data_as(as_doubles), nby, nbz,
-                                                 C.byref(src), segs.field("intensity").data_ptr(), segs.field("n").data_ptr(),
-                                                 segs.field("pathlength").data_ptr(), table_ptr, n_table, uniform, int(amplitude_mode), n_segments,
-                                                 None if count is None else count.data_ptr(), n_rays, counts.data_ptr(), re.data_ptr(),
-                                                 im.data_ptr(), skipped.data_ptr(), 0 if into is None else 1), self.lib)
-        return counts, re, im, skipped
+        if M == 0 or n_segments == 0:
+            return _untouched(outs, into)
+        abi.check(self.lib.ot_monitor_field_many(self._ctx, (abi.OtMonitor * M)(*mons), M, _doubles(axes), _doubles(edges), nby, nbz, C.byref(src),
+                                                 segs.field("intensity").data_ptr(), segs.field("n").data_ptr(), segs.field("pathlength").data_ptr(),
+                                                 *wavelength, int(amplitude_mode), n_segments, _address(count), n_rays,
+                                                 *(t.data_ptr() for t in outs), 0 if into is None else 1), self.lib)
+        return outs
 
     def monitor_beam_many(self, monitor_structs, axes, edges, bins, segs: SegmentBatch, wavelength, into=None):
         """Gaussian-beam detector images of a list of monitors over a SegmentBatch read as it lies, either precision
@@ -925,37 +931,18 @@ class Engine:
 
     def _monitor_beam_many(self, mons, axes, edges, bins, segs, wavelength, into):
         dev, M, (nby, nbz) = segs.device, len(mons), bins
-        axes, edges = np.ascontiguousarray(axes, dtype=np.float64), np.ascontiguousarray(edges, dtype=np.float64)
-        if axes.shape != (M, 6) or edges.shape != (M, nby + nbz + 2):
-            raise ValueError(f"axes must be [{M}, 6] and edges [{M}, {nby + nbz + 2}]")
-        if torch.is_tensor(wavelength):
-            if wavelength.dtype != torch.float64 or wavelength.dim() != 1 or not wavelength.is_contiguous() or wavelength.device.type != dev.type:
-                raise ValueError(f"wavelength: a float or a contiguous float64 vector on {dev}")
-            table_ptr, n_table, uniform = (wavelength.data_ptr() if wavelength.numel() else None), int(wavelength.numel()), 0.0
-        else:
-            table_ptr, n_table, uniform = None, 0, float(wavelength)
-        if into is None:
-            counts = torch.empty((M, nby, nbz), dtype=torch.int64, device=dev)  # (the call zeroes them)
-            power = torch.empty((M, nby, nbz), dtype=torch.float64, device=dev)
-            skipped = torch.empty(1, dtype=torch.int64, device=dev)
-        else:
-            counts, power, skipped = into
-            for t, dt in ((counts, torch.int64), (power, torch.float64)):
-                if tuple(t.shape) != (M, nby, nbz) or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type:
-                    raise ValueError(f"into: contiguous int64 counts and float64 power of shape [{M}, {nby}, {nbz}] on {dev}")
-            if tuple(skipped.shape) != (1,) or skipped.dtype != torch.int64 or skipped.device.type != dev.type:
-                raise ValueError(f"into: skipped is one int64 on {dev}")
+        axes, edges = _image_tables(M, nby, nbz, axes, edges)
+        wavelength = _wavelength_arg(wavelength, dev)
+        outs = _outputs(dev, (M, nby, nbz), 1, 1, into, torch.empty,  # (the call zeroes them)
+                        f"into: contiguous int64 counts and float64 power of shape [{M}, {nby}, {nbz}] on {dev}", f"into: skipped is one int64 on {dev}")
         src, n_segments, count, n_rays = segment_source(segs)
-        if M == 0 or n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
-            return (counts.zero_(), power.zero_(), skipped.zero_()) if into is None else (counts, power, skipped)
-        table = (abi.OtMonitor * M)(*mons)
-        as_doubles = C.POINTER(C.c_double)
-        abi.check(self.lib.ot_monitor_beam_many(self._ctx, table, M, axes.ctypes.data_as(as_doubles), edges.ctypes.data_as(as_doubles), nby, nbz,
-                                                C.byref(src), segs.field("intensity").data_ptr(), segs.field("q_re").data_ptr(),
-                                                segs.field("q_im").data_ptr(), segs.field("n").data_ptr(), table_ptr, n_table, uniform, n_segments,
-                                                None if count is None else count.data_ptr(), n_rays, counts.data_ptr(), power.data_ptr(),
-                                                skipped.data_ptr(), 0 if into is None else 1), self.lib)
-        return counts, power, skipped
+        if M == 0 or n_segments == 0:
+            return _untouched(outs, into)
+        abi.check(self.lib.ot_monitor_beam_many(self._ctx, (abi.OtMonitor * M)(*mons), M, _doubles(axes), _doubles(edges), nby, nbz, C.byref(src),
+                                                segs.field("intensity").data_ptr(), segs.field("q_re").data_ptr(), segs.field("q_im").data_ptr(),
+                                                segs.field("n").data_ptr(), *wavelength, n_segments, _address(count), n_rays,
+                                                *(t.data_ptr() for t in outs), 0 if into is None else 1), self.lib)
+        return outs
 
     def monitor_wave_many(self, monitor_structs, axes, edges, bins, segs: SegmentBatch, wavelength, amplitude_mode=0, gouy=0, into=None):
         """Coherent Gaussian-beam detector images of a list of monitors over a double-precision SegmentBatch read as it lies
@@ -970,41 +957,22 @@ class Engine:
 
     def _monitor_wave_many(self, mons, axes, edges, bins, segs, wavelength, amplitude_mode, gouy, into):
         dev, M, (nby, nbz) = segs.device, len(mons), bins
-        axes, edges = np.ascontiguousarray(axes, dtype=np.float64), np.ascontiguousarray(edges, dtype=np.float64)
-        if axes.shape != (M, 6) or edges.shape != (M, nby + nbz + 2):
-            raise ValueError(f"axes must be [{M}, 6] and edges [{M}, {nby + nbz + 2}]")
+        axes, edges = _image_tables(M, nby, nbz, axes, edges)
         if segs.precision != "f64":
             raise ValueError("a beam field needs double-precision segments")
-        if torch.is_tensor(wavelength):
-            if wavelength.dtype != torch.float64 or wavelength.dim() != 1 or not wavelength.is_contiguous() or wavelength.device.type != dev.type:
-                raise ValueError(f"wavelength: a float or a contiguous float64 vector on {dev}")
-            table_ptr, n_table, uniform = (wavelength.data_ptr() if wavelength.numel() else None), int(wavelength.numel()), 0.0
-        else:
-            table_ptr, n_table, uniform = None, 0, float(wavelength)
-        if into is None:
-            counts = torch.empty((M, nby, nbz), dtype=torch.int64, device=dev)  # (the call zeroes them)
-            re, im = (torch.empty((M, nby, nbz), dtype=torch.float64, device=dev) for _ in range(2))
-            skipped, aliased = (torch.empty(1, dtype=torch.int64, device=dev) for _ in range(2))
-        else:
-            counts, re, im, skipped, aliased = into
-            for t, dt in ((counts, torch.int64), (re, torch.float64), (im, torch.float64)):
-                if tuple(t.shape) != (M, nby, nbz) or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type:
-                    raise ValueError(f"into: contiguous int64 counts and float64 re, im of shape [{M}, {nby}, {nbz}] on {dev}")
-            for t in (skipped, aliased):
-                if tuple(t.shape) != (1,) or t.dtype != torch.int64 or t.device.type != dev.type:
-                    raise ValueError(f"into: skipped and aliased are one int64 each on {dev}")
+        wavelength = _wavelength_arg(wavelength, dev)
+        outs = _outputs(dev, (M, nby, nbz), 2, 2, into, torch.empty,  # (the call zeroes them)
+                        f"into: contiguous int64 counts and float64 re, im of shape [{M}, {nby}, {nbz}] on {dev}",
+                        f"into: skipped and aliased are one int64 each on {dev}")
         src, n_segments, count, n_rays = segment_source(segs)
-        if M == 0 or n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
-            return (counts.zero_(), re.zero_(), im.zero_(), skipped.zero_(), aliased.zero_()) if into is None else (counts, re, im, skipped, aliased)
-        table = (abi.OtMonitor * M)(*mons)
-        as_doubles = C.POINTER(C.c_double)
-        abi.check(self.lib.ot_monitor_wave_many(self._ctx, table, M, axes.ctypes.data_as(as_doubles), edges.ctypes.data_as(as_doubles), nby, nbz,
-                                                C.byref(src), segs.field("intensity").data_ptr(), segs.field("n").data_ptr(),
-                                                segs.field("pathlength").data_ptr(), segs.field("q_re").data_ptr(), segs.field("q_im").data_ptr(),
-                                                table_ptr, n_table, uniform, int(amplitude_mode), int(gouy), n_segments,
-                                                None if count is None else count.data_ptr(), n_rays, counts.data_ptr(), re.data_ptr(),
-                                                im.data_ptr(), skipped.data_ptr(), aliased.data_ptr(), 0 if into is None else 1), self.lib)
-        return counts, re, im, skipped, aliased
+        if M == 0 or n_segments == 0:
+            return _untouched(outs, into)
+        abi.check(self.lib.ot_monitor_wave_many(self._ctx, (abi.OtMonitor * M)(*mons), M, _doubles(axes), _doubles(edges), nby, nbz, C.byref(src),
+                                                segs.field("intensity").data_ptr(), segs.field("n").data_ptr(), segs.field("pathlength").data_ptr(),
+                                                segs.field("q_re").data_ptr(), segs.field("q_im").data_ptr(), *wavelength, int(amplitude_mode),
+                                                int(gouy), n_segments, _address(count), n_rays, *(t.data_ptr() for t in outs),
+                                                0 if into is None else 1), self.lib)
+        return outs
 
     # -- measurement ---------------------------------------------------------------------------
     def timing(self, enabled=True):

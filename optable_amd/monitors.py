@@ -362,38 +362,42 @@ def image_edges(monitor, nby, nbz):
     return (np.linspace(-monitor.width / 2, monitor.width / 2, nby + 1), np.linspace(-monitor.height / 2, monitor.height / 2, nbz + 1))
 
 
-class MonitorImage:
-    """A monitor's hits as an image, binned on the device (`OpticalTable.image_all`): `counts` (int64) and `intensity` (float64,
-    the sum of the hits' intensities), [nby, nbz] device tensors over `y_edges` x `z_edges` (numpy) of the coordinates
-    `MonitorHits.yList` / `zList` give — np.histogram2d(yList, zList, bins=[y_edges, z_edges], weights=IList).  Counts are exact
-    and the same every run; the intensity sums are atomic fp64 adds whose last bits depend on the order of arrival."""
+class _MonitorBins:
+    """What the images of a monitor share: `monitor`, int64 `counts` and the float64 planes the class names in PLANES, [nby, nbz]
+    device tensors over `y_edges` x `z_edges` (numpy)."""
 
-    def __init__(self, monitor, counts, intensity, y_edges, z_edges, stack=None):
-        self.monitor, self.counts, self.intensity, self.y_edges, self.z_edges = monitor, counts, intensity, y_edges, z_edges
-        self._stack = stack  # (counts, intensity, position) of the call's [M, nby, nbz] tensors, which `into=` adds to
+    PLANES = ()
+
+    def __init__(self, monitor, counts, planes, y_edges, z_edges, stack):
+        self.monitor, self.counts, self.y_edges, self.z_edges = monitor, counts, y_edges, z_edges
+        for name, plane in zip(self.PLANES, planes):
+            setattr(self, name, plane)
+        # the call's tensors, which `into=` adds to: its [M, nby, nbz] counts and planes, then its one-element tallies (skipped,
+        # aliased: the modes that have them), and last this monitor's position among the M
+        self._stack = stack
 
     @property
     def bins(self):
         return tuple(self.counts.shape)
+
+    def _bin_area(self):
+        """Every bin's area (y width x z width), a float64 [nby, nbz] tensor on the images' device."""
+        import torch
+
+        return torch.as_tensor(np.outer(np.diff(self.y_edges), np.diff(self.z_edges)), device=self.counts.device)
 
     def to_host(self):
-        """(counts, intensity, y_edges, z_edges) as numpy arrays."""
-        return self.counts.cpu().numpy(), self.intensity.cpu().numpy(), self.y_edges, self.z_edges
+        """(counts, the planes in the order of PLANES, y_edges, z_edges) as numpy arrays."""
+        return (self.counts.cpu().numpy(), *(getattr(self, name).cpu().numpy() for name in self.PLANES), self.y_edges, self.z_edges)
 
 
-class MonitorField:
-    """A monitor's hits as a coherent image, summed on the device (`OpticalTable.field_all`): `counts` (int64) and `re`, `im`
-    (float64), [nby, nbz] device tensors over `y_edges` x `z_edges` (numpy) — per bin the number of hits and the sum of their
-    phasors a exp(i phi), a = sqrt(IList) (or IList: amplitude="linear"), phi = `MonitorHits.phaseList`.  Counts are exact and the
-    same every run; re and im are atomic fp64 sums whose last bits depend on the order of arrival."""
+class _MonitorPhasors(_MonitorBins):
+    """The two coherent images: per bin a complex sum, kept as `re` and `im`."""
+
+    PLANES = ("re", "im")
 
     def __init__(self, monitor, counts, re, im, y_edges, z_edges, stack=None):
-        self.monitor, self.counts, self.re, self.im, self.y_edges, self.z_edges = monitor, counts, re, im, y_edges, z_edges
-        self._stack = stack  # (counts, re, im, skipped, position) of the call's [M, nby, nbz] tensors, which `into=` adds to
-
-    @property
-    def bins(self):
-        return tuple(self.counts.shape)
+        super().__init__(monitor, counts, (re, im), y_edges, z_edges, stack)
 
     @property
     def field(self):
@@ -402,43 +406,48 @@ class MonitorField:
 
         return torch.complex(self.re, self.im)
 
+
+class MonitorImage(_MonitorBins):
+    """A monitor's hits as an image, binned on the device (`OpticalTable.image_all`): `counts` (int64) and `intensity` (float64,
+    the sum of the hits' intensities), [nby, nbz] device tensors over `y_edges` x `z_edges` (numpy) of the coordinates
+    `MonitorHits.yList` / `zList` give — np.histogram2d(yList, zList, bins=[y_edges, z_edges], weights=IList).  Counts are exact
+    and the same every run; the intensity sums are atomic fp64 adds whose last bits depend on the order of arrival."""
+
+    PLANES = ("intensity",)
+
+    def __init__(self, monitor, counts, intensity, y_edges, z_edges, stack=None):
+        super().__init__(monitor, counts, (intensity,), y_edges, z_edges, stack)
+
+
+class MonitorField(_MonitorPhasors):
+    """A monitor's hits as a coherent image, summed on the device (`OpticalTable.field_all`): `counts` (int64) and `re`, `im`
+    (float64), [nby, nbz] device tensors over `y_edges` x `z_edges` (numpy) — per bin the number of hits and the sum of their
+    phasors a exp(i phi), a = sqrt(IList) (or IList: amplitude="linear"), phi = `MonitorHits.phaseList`.  Counts are exact and the
+    same every run; re and im are atomic fp64 sums whose last bits depend on the order of arrival."""
+
     def intensity(self):
         """|field|^2 = re^2 + im^2: what a detector reads."""
         return self.re**2 + self.im**2
 
-    def to_host(self):
-        """(counts, re, im, y_edges, z_edges) as numpy arrays."""
-        return self.counts.cpu().numpy(), self.re.cpu().numpy(), self.im.cpu().numpy(), self.y_edges, self.z_edges
 
-
-class MonitorBeam:
+class MonitorBeam(_MonitorBins):
     """A monitor's hits as the image their Gaussian beams make, summed on the device (`OpticalTable.beam_all`): `counts` (int64,
     the hit centres, as `MonitorImage.counts`) and `power` (float64), [nby, nbz] device tensors over `y_edges` x `z_edges` (numpy)
     — per bin the sum over the hits of IList times the share of a Gaussian spot of radius `MonitorHits.spotsizeList` around
     (yList, zList) that falls into the bin, the beam taken at normal incidence.  Counts are exact and the same every run; power
     is atomic fp64 sums whose last bits depend on the order of arrival."""
 
-    def __init__(self, monitor, counts, power, y_edges, z_edges, stack=None):
-        self.monitor, self.counts, self.power, self.y_edges, self.z_edges = monitor, counts, power, y_edges, z_edges
-        self._stack = stack  # (counts, power, skipped, position) of the call's [M, nby, nbz] tensors, which `into=` adds to
+    PLANES = ("power",)
 
-    @property
-    def bins(self):
-        return tuple(self.counts.shape)
+    def __init__(self, monitor, counts, power, y_edges, z_edges, stack=None):
+        super().__init__(monitor, counts, (power,), y_edges, z_edges, stack)
 
     def irradiance(self):
         """`power` per unit area: every bin's power over its area (y width x z width), a float64 [nby, nbz] device tensor."""
-        import torch
-
-        area = np.outer(np.diff(self.y_edges), np.diff(self.z_edges))
-        return self.power / torch.as_tensor(area, device=self.power.device)
-
-    def to_host(self):
-        """(counts, power, y_edges, z_edges) as numpy arrays."""
-        return self.counts.cpu().numpy(), self.power.cpu().numpy(), self.y_edges, self.z_edges
+        return self.power / self._bin_area()
 
 
-class MonitorWave:
+class MonitorWave(_MonitorPhasors):
     """A monitor's hits as the coherent image their Gaussian beams make, summed on the device (`OpticalTable.wave_all`): `counts`
     (int64, the hit centres, as `MonitorImage.counts`) and `re`, `im` (float64), [nby, nbz] device tensors over `y_edges` x
     `z_edges` (numpy) — per bin the sum over the hits of the beam's complex field at the bin's CENTRE: amplitude
@@ -449,20 +458,8 @@ class MonitorWave:
     and the same every run; re and im are atomic fp64 sums whose last bits depend on the order of arrival."""
 
     def __init__(self, monitor, counts, re, im, y_edges, z_edges, aliased=0, stack=None):
-        self.monitor, self.counts, self.re, self.im, self.y_edges, self.z_edges = monitor, counts, re, im, y_edges, z_edges
+        super().__init__(monitor, counts, re, im, y_edges, z_edges, stack)
         self.aliased = aliased
-        self._stack = stack  # (counts, re, im, skipped, aliased, position) of the call's [M, nby, nbz] tensors, which `into=` adds to
-
-    @property
-    def bins(self):
-        return tuple(self.counts.shape)
-
-    @property
-    def field(self):
-        """re + i im, a complex128 tensor."""
-        import torch
-
-        return torch.complex(self.re, self.im)
 
     def irradiance(self):
         """|field|^2 = re^2 + im^2: power per unit area at every bin's centre, a float64 [nby, nbz] device tensor."""
@@ -470,11 +467,4 @@ class MonitorWave:
 
     def power(self):
         """`irradiance()` times the bin's area (y width x z width): the power a bin receives, midpoint rule."""
-        import torch
-
-        area = np.outer(np.diff(self.y_edges), np.diff(self.z_edges))
-        return self.irradiance() * torch.as_tensor(area, device=self.re.device)
-
-    def to_host(self):
-        """(counts, re, im, y_edges, z_edges) as numpy arrays."""
-        return self.counts.cpu().numpy(), self.re.cpu().numpy(), self.im.cpu().numpy(), self.y_edges, self.z_edges
+        return self.irradiance() * self._bin_area()

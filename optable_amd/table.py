@@ -237,6 +237,38 @@ class OpticalTable:
         found = _engine().monitor_record_many([monitor_struct(m) for m in monitors], segs)
         return [MonitorHits(m, segs, slot, P, t) for m, (slot, P, t) in zip(monitors, found)]
 
+    def _images_all(self, cls, mode, segs, bins, monitors, into, *args, left_out=None, **kwargs):
+        """What image_all, field_all, beam_all and wave_all do alike once their own arguments are checked: the monitors' edge and
+        axes tables, `into` (the list an earlier call of the same mode returned) as that call's tensors, the engine's
+        monitor_<mode>_many with `args`, and one `cls` per monitor.  A mode that counts hits left out (its tensor follows the
+        images) raises for them, `left_out` naming the causes.  Returns (the list, the engine's tensors — None where `into` had no
+        monitors to ask for)."""
+        from .monitors import image_edges
+
+        nby, nbz = bins
+        monitors = list(self.monitors if monitors is None else monitors)
+        edges = [image_edges(m, nby, nbz) for m in monitors]
+        stack = None
+        if into is not None:
+            into = list(into)
+            if len(into) != len(monitors) or any(not isinstance(im, cls) or im.monitor is not m or im.bins != bins for im, m in zip(into, monitors)):
+                raise ValueError(f"into: the list an earlier {mode}_all returned for the same monitors and bins")
+            if any(im._stack is None or im._stack[0] is not into[0]._stack[0] or im._stack[-1] != k or len(im._stack[0]) != len(into) for k, im in enumerate(into)):
+                raise ValueError("into: the whole list of one earlier call, in its order")
+            if not monitors:
+                return into, None
+            stack = into[0]._stack[:-1]
+        axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in monitors], dtype=float).reshape(len(monitors), 6)
+        table = np.array([np.concatenate(e) for e in edges], dtype=float).reshape(len(monitors), nby + nbz + 2)
+        outs = getattr(_engine(), f"monitor_{mode}_many")([monitor_struct(m) for m in monitors], axes, table, bins, segs, *args, into=stack, **kwargs)
+        images = 1 + len(cls.PLANES)  # counts and the planes; then the tallies, the hits left out first
+        n_left_out = int(outs[images].item()) if left_out else 0
+        if n_left_out:
+            raise ValueError(f"{mode}_all: {n_left_out} hits left out — {left_out}")
+        if into is None:
+            into = [cls(m, *(t[k] for t in outs[:images]), ey, ez, stack=(*outs, k)) for k, (m, (ey, ez)) in enumerate(zip(monitors, edges))]
+        return into, outs
+
     def image_all(self, segs, bins=30, monitors=None, into=None):
         """Every monitor of the table (or those given) as an image: one `MonitorImage` per monitor, in their order — the hits
         of `record_all` binned on the device in the same pass that finds them, with no hit list (ot_monitor_image_many).  The
@@ -244,27 +276,9 @@ class OpticalTable:
         +-width / 2, +-height / 2, weighted by `IList` (Monitor.render_hist: bins=30).  `into`: the list an earlier call with the
         same monitors and bins returned; this call's hits are added to those images (a detector summed over the chunks of a
         streamed trace)."""
-        from .monitors import MonitorImage, image_bins, image_edges
+        from .monitors import MonitorImage, image_bins
 
-        nby, nbz = image_bins(bins)
-        monitors = list(self.monitors if monitors is None else monitors)
-        edges = [image_edges(m, nby, nbz) for m in monitors]
-        stack = None
-        if into is not None:
-            into = list(into)
-            if len(into) != len(monitors) or any(im.monitor is not m or im.bins != (nby, nbz) for im, m in zip(into, monitors)):
-                raise ValueError("into: the list an earlier image_all returned for the same monitors and bins")
-            if any(im._stack is None or im._stack[0] is not into[0]._stack[0] or im._stack[2] != k or len(im._stack[0]) != len(into) for k, im in enumerate(into)):
-                raise ValueError("into: the whole list of one earlier call, in its order")
-            if not monitors:
-                return into
-            stack = into[0]._stack[:2]
-        axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in monitors], dtype=float).reshape(len(monitors), 6)
-        table = np.array([np.concatenate(e) for e in edges], dtype=float).reshape(len(monitors), nby + nbz + 2)
-        counts, weights = _engine().monitor_image_many([monitor_struct(m) for m in monitors], axes, table, (nby, nbz), segs, into=stack)
-        if into is not None:
-            return into
-        return [MonitorImage(m, counts[k], weights[k], ey, ez, stack=(counts, weights, k)) for k, (m, (ey, ez)) in enumerate(zip(monitors, edges))]
+        return self._images_all(MonitorImage, "image", segs, image_bins(bins), monitors, into)[0]
 
     def image_batch(self, monitor, segs, bins=30):
         """One monitor as an image (`image_all` for it alone): a `MonitorImage`."""
@@ -309,37 +323,16 @@ class OpticalTable:
         `wavelength`: one float for all rays, or the `RayBatch` that was traced (its wavelengths by the segments' `ray`; children
         of a ray tree inherit theirs).  `segs` must be double precision: single-precision path lengths carry some 0.02 cycle of
         phase noise at table scale.  `into`: as for `image_all`."""
-        from .monitors import MonitorField, image_bins, image_edges
+        from .monitors import MonitorField, image_bins
 
-        nby, nbz = image_bins(bins)
+        bins = image_bins(bins)
         if amplitude not in ("sqrt", "linear"):
             raise ValueError(f"amplitude must be 'sqrt' or 'linear', not {amplitude!r}")
         if segs.precision != "f64":
             raise ValueError("field_all needs a double-precision SegmentBatch: a field from single-precision path lengths is refused, not approximated")
         wavelength = _wavelengths_of(wavelength, segs, "a field")
-        monitors = list(self.monitors if monitors is None else monitors)
-        edges = [image_edges(m, nby, nbz) for m in monitors]
-        stack = None
-        if into is not None:
-            into = list(into)
-            if len(into) != len(monitors) or any(f.monitor is not m or f.bins != (nby, nbz) for f, m in zip(into, monitors)):
-                raise ValueError("into: the list an earlier field_all returned for the same monitors and bins")
-            if any(f._stack is None or f._stack[0] is not into[0]._stack[0] or f._stack[4] != k or len(f._stack[0]) != len(into) for k, f in enumerate(into)):
-                raise ValueError("into: the whole list of one earlier call, in its order")
-            if not monitors:
-                return into
-            stack = into[0]._stack[:4]
-        axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in monitors], dtype=float).reshape(len(monitors), 6)
-        table = np.array([np.concatenate(e) for e in edges], dtype=float).reshape(len(monitors), nby + nbz + 2)
-        counts, re, im, skipped = _engine().monitor_field_many([monitor_struct(m) for m in monitors], axes, table, (nby, nbz), segs, wavelength,
-                                                               amplitude_mode=("sqrt", "linear").index(amplitude), into=stack)
-        left_out = int(skipped.item())
-        if left_out:
-            raise ValueError(f"field_all: {left_out} hits left out — their `ray` is no index into the wavelengths given, or its wavelength "
-                             "is not finite and > 0")
-        if into is not None:
-            return into
-        return [MonitorField(m, counts[k], re[k], im[k], ey, ez, stack=(counts, re, im, skipped, k)) for k, (m, (ey, ez)) in enumerate(zip(monitors, edges))]
+        return self._images_all(MonitorField, "field", segs, bins, monitors, into, wavelength, amplitude_mode=("sqrt", "linear").index(amplitude),
+                                left_out="their `ray` is no index into the wavelengths given, or its wavelength is not finite and > 0")[0]
 
     def field_batch(self, monitor, segs, wavelength=0.0, bins=30, amplitude="sqrt"):
         """One monitor as a coherent image (`field_all` for it alone): a `MonitorField`."""
@@ -356,32 +349,11 @@ class OpticalTable:
         edges is counted nowhere and still deposits its tails.  `wavelength`: one float for all rays, or the `RayBatch` that was
         traced, as for `field_all`.  `segs` in either precision (all arithmetic is double).  A hit without q (a batch traced
         without a Gaussian beam) or with an unusable index raises ValueError.  `into`: as for `image_all`."""
-        from .monitors import MonitorBeam, image_bins, image_edges
+        from .monitors import MonitorBeam, image_bins
 
-        nby, nbz = image_bins(bins)
+        bins = image_bins(bins)
         wavelength = _wavelengths_of(wavelength, segs, "a beam image")
-        monitors = list(self.monitors if monitors is None else monitors)
-        edges = [image_edges(m, nby, nbz) for m in monitors]
-        stack = None
-        if into is not None:
-            into = list(into)
-            if len(into) != len(monitors) or any(b.monitor is not m or b.bins != (nby, nbz) for b, m in zip(into, monitors)):
-                raise ValueError("into: the list an earlier beam_all returned for the same monitors and bins")
-            if any(b._stack is None or b._stack[0] is not into[0]._stack[0] or b._stack[3] != k or len(b._stack[0]) != len(into) for k, b in enumerate(into)):
-                raise ValueError("into: the whole list of one earlier call, in its order")
-            if not monitors:
-                return into
-            stack = into[0]._stack[:3]
-        axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in monitors], dtype=float).reshape(len(monitors), 6)
-        table = np.array([np.concatenate(e) for e in edges], dtype=float).reshape(len(monitors), nby + nbz + 2)
-        counts, power, skipped = _engine().monitor_beam_many([monitor_struct(m) for m in monitors], axes, table, (nby, nbz), segs, wavelength, into=stack)
-        left_out = int(skipped.item())
-        if left_out:
-            raise ValueError(f"beam_all: {left_out} hits left out — they carry no q (a batch traced without a Gaussian beam), or their wavelength "
-                             "or refractive index is not finite and > 0, or their `ray` is no index into the wavelengths given")
-        if into is not None:
-            return into
-        return [MonitorBeam(m, counts[k], power[k], ey, ez, stack=(counts, power, skipped, k)) for k, (m, (ey, ez)) in enumerate(zip(monitors, edges))]
+        return self._images_all(MonitorBeam, "beam", segs, bins, monitors, into, wavelength, left_out=_NO_BEAM)[0]
 
     def beam_batch(self, monitor, segs, wavelength=0.0, bins=30):
         """One monitor as a Gaussian-beam image (`beam_all` for it alone): a `MonitorBeam`."""
@@ -406,9 +378,9 @@ class OpticalTable:
         and announced by one RuntimeWarning.  `wavelength`, `into` and the double-precision `segs` as for `field_all` (a field is
         linear: chunks add).  A hit without q or with an unusable index raises ValueError, as in `beam_all`."""
         import warnings
-        from .monitors import MonitorWave, image_bins, image_edges
+        from .monitors import MonitorWave, image_bins
 
-        nby, nbz = image_bins(bins)
+        bins = image_bins(bins)
         if amplitude not in ("sqrt", "linear"):
             raise ValueError(f"amplitude must be 'sqrt' or 'linear', not {amplitude!r}")
         if not isinstance(gouy, (bool, np.bool_)):
@@ -416,37 +388,19 @@ class OpticalTable:
         if segs.precision != "f64":
             raise ValueError("wave_all needs a double-precision SegmentBatch: a field from single-precision path lengths is refused, not approximated")
         wavelength = _wavelengths_of(wavelength, segs, "a beam field")
-        monitors = list(self.monitors if monitors is None else monitors)
-        edges = [image_edges(m, nby, nbz) for m in monitors]
-        stack, before = None, 0
-        if into is not None:
-            into = list(into)
-            if len(into) != len(monitors) or any(not isinstance(f, MonitorWave) or f.monitor is not m or f.bins != (nby, nbz) for f, m in zip(into, monitors)):
-                raise ValueError("into: the list an earlier wave_all returned for the same monitors and bins")
-            if any(f._stack is None or f._stack[0] is not into[0]._stack[0] or f._stack[5] != k or len(f._stack[0]) != len(into) for k, f in enumerate(into)):
-                raise ValueError("into: the whole list of one earlier call, in its order")
-            if not monitors:
-                return into
-            stack, before = into[0]._stack[:5], into[0].aliased
-        axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in monitors], dtype=float).reshape(len(monitors), 6)
-        table = np.array([np.concatenate(e) for e in edges], dtype=float).reshape(len(monitors), nby + nbz + 2)
-        counts, re, im, skipped, aliased = _engine().monitor_wave_many([monitor_struct(m) for m in monitors], axes, table, (nby, nbz), segs, wavelength,
-                                                                       amplitude_mode=("sqrt", "linear").index(amplitude), gouy=int(gouy), into=stack)
-        left_out = int(skipped.item())
-        if left_out:
-            raise ValueError(f"wave_all: {left_out} hits left out — they carry no q (a batch traced without a Gaussian beam), or their wavelength "
-                             "or refractive index is not finite and > 0, or their `ray` is no index into the wavelengths given")
-        total = int(aliased.item())
+        waves, outs = self._images_all(MonitorWave, "wave", segs, bins, monitors, into, wavelength, amplitude_mode=("sqrt", "linear").index(amplitude),
+                                       gouy=int(gouy), left_out=_NO_BEAM)
+        if outs is None:
+            return waves
+        # the call's aliased counter runs on through every call that adds `into` it: what the images knew before is the earlier calls'
+        before, total = (waves[0].aliased if waves else 0), int(outs[4].item())
         if total > before:
             warnings.warn(f"wave_all: {total - before} hits are aliased — somewhere on their footprint the phase of their beam turns more than half "
                           "a cycle from one bin centre to the next, and the sampled field means nothing there: use a smaller monitor or more bins",
                           RuntimeWarning, stacklevel=2)
-        if into is not None:
-            for f in into:
-                f.aliased = total
-            return into
-        return [MonitorWave(m, counts[k], re[k], im[k], ey, ez, total, stack=(counts, re, im, skipped, aliased, k))
-                for k, (m, (ey, ez)) in enumerate(zip(monitors, edges))]
+        for f in waves:
+            f.aliased = total
+        return waves
 
     def wave_batch(self, monitor, segs, wavelength=0.0, bins=30, amplitude="sqrt", gouy=False):
         """One monitor as a coherent Gaussian-beam image (`wave_all` for it alone): a `MonitorWave`."""
@@ -726,6 +680,11 @@ class OpticalTable:
 # scene of fixture g25).  Only for the very ray object handed to the hook, and only while it still has the origin and direction
 # it was handed over with; any other question goes to the device.
 _HOOK_MEMO = {}
+
+
+# (what leaves a hit out of beam_all and wave_all)
+_NO_BEAM = ("they carry no q (a batch traced without a Gaussian beam), or their wavelength or refractive index is not finite and > 0, or their "
+            "`ray` is no index into the wavelengths given")
 
 
 def _wavelengths_of(wavelength, segs, what):

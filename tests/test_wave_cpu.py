@@ -240,6 +240,61 @@ def test_what_is_handed_over_and_what_comes_back(monkeypatch):
         table.wave_all(segs, rays, monitors=mons)
 
 
+class _AnyMode:
+    """Stands in for the engine in all four image modes: counts the calls, keeps `into` and hands it back, or new tensors of the
+    mode's shapes (counts, `planes` images, `tallies` one-element counters)."""
+
+    calls = 0
+
+    def _answer(self, planes, tallies, structs, bins, into):
+        self.calls, self.into = self.calls + 1, into
+        if into is not None:
+            return into
+        shape = (len(structs),) + tuple(bins)
+        return (torch.zeros(shape, dtype=torch.int64), *(torch.zeros(shape, dtype=torch.float64) for _ in range(planes)),
+                *(torch.zeros(1, dtype=torch.int64) for _ in range(tallies)))
+
+    def monitor_image_many(self, structs, axes, edges, bins, segs, into=None):
+        return self._answer(1, 0, structs, bins, into)
+
+    def monitor_field_many(self, structs, axes, edges, bins, segs, wavelength, amplitude_mode=0, into=None):
+        return self._answer(2, 1, structs, bins, into)
+
+    def monitor_beam_many(self, structs, axes, edges, bins, segs, wavelength, into=None):
+        return self._answer(1, 1, structs, bins, into)
+
+    def monitor_wave_many(self, structs, axes, edges, bins, segs, wavelength, amplitude_mode=0, gouy=0, into=None):
+        return self._answer(2, 2, structs, bins, into)
+
+
+def test_into_takes_the_list_of_its_own_mode_only(monkeypatch):
+    """Every mode hands the tensors of its own earlier list back to the engine (`_stack` less the position) and refuses the list of
+    each other mode with its own words, before the engine is asked."""
+    from optable_amd import table as table_module
+
+    rec = _AnyMode()
+    monkeypatch.setattr(table_module, "_engine", lambda: rec)
+    table = oa.OpticalTable()
+    mons = [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([1, 2, 3], 0.3, 1.7).RotZ(0.3)]
+    segs = _host_segments()
+    calls = {"image": lambda **kw: table.image_all(segs, bins=(7, 5), monitors=mons, **kw),
+             "field": lambda **kw: table.field_all(segs, 780e-7, bins=(7, 5), monitors=mons, **kw),
+             "beam": lambda **kw: table.beam_all(segs, 780e-7, bins=(7, 5), monitors=mons, **kw),
+             "wave": lambda **kw: table.wave_all(segs, 780e-7, bins=(7, 5), monitors=mons, **kw)}
+    lists = {mode: call() for mode, call in calls.items()}
+    assert [len(made[0]._stack) for made in lists.values()] == [3, 5, 4, 6] and rec.calls == 4
+    for mode, call in calls.items():
+        own, asked = lists[mode], rec.calls
+        assert call(into=own) == own and rec.calls == asked + 1
+        assert len(rec.into) == len(own[0]._stack) - 1 and all(a is b for a, b in zip(rec.into, own[0]._stack))
+        assert [f._stack[-1] for f in own] == [0, 1]
+        for other, theirs in lists.items():
+            if other != mode:
+                with pytest.raises(ValueError, match=rf"into: the list an earlier {mode}_all returned for the same monitors and bins"):
+                    call(into=theirs)
+        assert rec.calls == asked + 1  # none of the refused calls reached the engine
+
+
 def test_hit_list_accessors_against_the_package_own_ray():
     """The three slots by hand of tests/test_beam_cpu.py (n = 1, 1.5, 1; q before and behind the waist), five hits on them:
     `radiusList` is `Ray.radius_of_curvature(q)`, `gouyList` is arctan2(Re q, Im q) and `amplitudeList` is a sqrt(2 / pi) over
