@@ -218,22 +218,38 @@ struct MonSeg {
 __device__ __forceinline__ double mon_real(const uint8_t* p, int32_t width) {
     return width == 8 ? *reinterpret_cast<const double*>(p) : (double)*reinterpret_cast<const float*>(p);
 }
+// The partition, said once: the slots of workgroup blockIdx.x, visit by visit.  Visit `it` is the MON_THREADS slots from at(it).
+struct MonSpan {
+    int64_t first, n;
+    int32_t iters;
+    __device__ __forceinline__ int64_t at(int32_t it) const { return first + (int64_t)it * MON_THREADS; }
+    __device__ __forceinline__ bool has(int32_t it) const { return it < iters && at(it) < n; }
+};
+__device__ __forceinline__ MonSpan mon_span(int64_t n, int32_t iters) { return {(int64_t)blockIdx.x * iters * MON_THREADS, n, iters}; }
+// The addressing rule, said once: the byte offset of slot s in a plane of 64-slot tiles `stride` bytes apart, `width` bytes a slot
+// (a field: src.tile_stride, src.width; the ray plane: src.ray_stride, 4) ...
+__device__ __forceinline__ int64_t mon_at(int64_t s, int64_t stride, int32_t width) { return (s >> 6) * stride + (s & 63) * width; }
+// ... and its scalar form for the passes that keep few registers: the 64 slots of a wave are one tile, so its place is a scalar
+// (mon_tile, through v_readfirstlane) and the lane's within it one 32-bit offset for every plane
+__device__ __forceinline__ int64_t mon_tile(int64_t s) { return __builtin_amdgcn_readfirstlane((int32_t)(s >> 6)); }
+__device__ __forceinline__ const uint8_t* mon_in_tile(const uint8_t* plane, int64_t tile, int64_t stride, int lane, int32_t width) {
+    return plane + tile * stride + (uint32_t)(lane * width);
+}
 // slot s and whether it holds a segment: k < |seg_count[ray]| in [k][ray] slots, ray >= 0 in lists with holes (n_rays < 0)
 __device__ __forceinline__ MonSeg mon_load(const MonSource& src, int64_t s, int64_t n, const int32_t* __restrict__ seg_count, int64_t n_rays) {
     MonSeg g;
     g.ox = g.oy = g.oz = g.dx = g.dy = g.dz = g.len = 0.0;
     g.valid = s < n;
     if (!g.valid) return g;
-    const int64_t tile = s >> 6, in_tile = s & 63;
     if (seg_count) {
         const uint32_t nr = (uint32_t)n_rays, su = (uint32_t)s;  // (n < 2^31)
         const int32_t c = seg_count[su % nr];
         g.valid = (int32_t)(su / nr) < (c < 0 ? -c : c);
     } else if (n_rays < 0) {
-        g.valid = *reinterpret_cast<const int32_t*>(src.ray + tile * src.ray_stride + in_tile * 4) >= 0;
+        g.valid = *reinterpret_cast<const int32_t*>(src.ray + mon_at(s, src.ray_stride, 4)) >= 0;
     }
     if (!g.valid) return g;
-    const int64_t at = tile * src.tile_stride + in_tile * src.width;
+    const int64_t at = mon_at(s, src.tile_stride, src.width);
     g.ox = mon_real(src.base[0] + at, src.width); g.oy = mon_real(src.base[1] + at, src.width); g.oz = mon_real(src.base[2] + at, src.width);
     g.dx = mon_real(src.base[3] + at, src.width); g.dy = mon_real(src.base[4] + at, src.width); g.dz = mon_real(src.base[5] + at, src.width);
     g.len = mon_real(src.base[6] + at, src.width);
@@ -244,8 +260,8 @@ __device__ __forceinline__ MonSeg mon_load(const MonSource& src, int64_t s, int6
 // y = P . a_y[m], z = P . a_z[m] (axes[m] = a_y, a_z) and the weight intensity[s], addressed like the fields of MonSource; it
 // lands in bin (ky, kz) of the monitor's edge tables (edges[m] = nby + 1 edges of y, then nbz + 1 of z) or is dropped.
 // lds_bins = n_mon * nby * nbz when the workgroup keeps a private image of the launch's monitors in dynamic LDS (lds_bins doubles,
-// then lds_bins int32: 12 bytes a bin) and adds its non-zero bins to global memory at the end, consecutive lanes consecutive
-// bins; 0 when every hit goes to global memory at once (an image no LDS holds).  MON_IMG_LDS_BINS: what fits 64 KB of LDS a
+// then lds_bins int32: 12 bytes a bin; lds_image_zero, lds_image_flush); 0 when every hit goes to global memory at once (an
+// image no LDS holds).  MON_IMG_LDS_BINS: what fits 64 KB of LDS a
 // workgroup — the most a launch gets without a function attribute, two workgroups per CU — next to the 128 bytes of `total`.
 // Counts are integers, exact and the same every run; the weights are fp64 atomic adds, whose last bits depend on arrival order.
 static constexpr int MON_IMG_LDS_BINS = (65536 - MON_MAX * 4) / 12;  // 5450: six monitors of 30 x 30
@@ -269,101 +285,170 @@ __device__ __forceinline__ int32_t mon_bin(const double* __restrict__ e, int32_t
     while (k < nb - 1 && v >= e[k + 1]) ++k;
     return k;
 }
+// What the image passes share (the image, field and beam modes of k_mon_count, k_mon_wave, k_seg_raster) is written once, here and
+// above: the partition (MonSpan), the addressing rule (mon_at; mon_tile / mon_in_tile), the bin rule (mon_image_bin), a deposit
+// (lds_image_deposit; mon_tally, mon_add), the workgroup's LDS image (lds_image_zero, lds_image_flush) and, further down, the
+// wavelength of a ray (mon_wavelength) and the spot of a hit (mon_spot).  Each pass below says only what is its own.  The
+// expressions are the ones the passes held in copies; against those copies k_mon_count has 124 vector registers for 126 (132
+// scalar spills for 127), k_mon_wave 123 for 125, k_mon_emit 65 for 67, k_seg_raster 71 as before, and none has scratch or a
+// vector spill (times: DESIGN.md 4.6).
+// What stays in a copy of its own, marked where it stands:
+//   - THE BEAM PASS, whole (mon_beam_deposit, mon_beam_pass), but for the wavelength arguments.  Built from the pieces above it
+//     computed the same and kept its registers, and beam_all took 1.2 % (narrow spots) to 4.5 % (wide) longer: k_mon_count
+//     lives on some 130 spilled scalars, and where the allocator puts them in the loop that takes the hits one at a time decides
+//     its time.  Three partial forms (the deposit alone, with the tile addressing, with the wavelength and the spot written
+//     out) stayed 0.8 to 1.4 % behind; written out, the pass is where it was.
+//   - "the wave takes its hits one at a time" in k_mon_wave: two lines around a call whose operands are the mode's; a helper
+//     taking a callable is three lines and leaves the site as long as it is;
+//   - the chunked two-phase deposit of k_mon_wave (mon_wave_deposit).  One walk for it and mon_beam_deposit, taking "fill the
+//     strip" and "combine" as callables, was built: one code line shorter than the two copies, k_mon_wave at 127 vector
+//     registers for 123 — one short of the 128 its launch bounds and the LDS budgets stand on.  Not worth a line.
+// The bin rule: the image coordinates (y0, z0) of the local hit point P on monitor m and its bin among the launch's
+// [n_mon][nby][nbz], or -1 outside the image.
+__device__ __forceinline__ int32_t mon_image_bin(const MonImage& img, int32_t m, double Px, double Py, double Pz, double& y0, double& z0) {
+    const double* a = img.axes + 6 * m;
+    const double* e = img.edges + (int64_t)m * (img.nby + img.nbz + 2);
+    y0 = Px * a[0] + Py * a[1] + Pz * a[2];
+    z0 = Px * a[3] + Py * a[4] + Pz * a[5];
+    const int32_t ky = mon_bin(e, img.nby, y0), kz = mon_bin(e + img.nby + 1, img.nbz, z0);
+    return ky < 0 || kz < 0 ? -1 : m * (img.nby * img.nbz) + ky * img.nbz + kz;
+}
+// A deposit that spreads (k_mon_wave): the count of the centre (mon_tally) apart from v on a plane of a footprint's bin (mon_add),
+// into the workgroup's LDS image (`lds`: the launch keeps one) or straight to global memory.
+__device__ __forceinline__ void mon_tally(int32_t lds, int32_t* tally, unsigned long long* counts, int32_t bin) {
+    if (lds) atomicAdd(&tally[bin], 1);
+    else atomicAdd(&counts[bin], 1ull);
+}
+__device__ __forceinline__ void mon_add(int32_t lds, double* in_lds, double* in_global, int32_t bin, double v) {
+    if (lds) unsafeAtomicAdd(&in_lds[bin], v);
+    else unsafeAtomicAdd(&in_global[bin], v);
+}
+// The workgroup's LDS image: P planes of `bins` doubles, then `bins` int32 tallies (bins = 0: none, and both loops are empty).
+// Zeroed before the first visit; flushed after the last, consecutive lanes consecutive bins, non-zero values only.  The flush
+// rule is the mode's: a pass that deposits where it counts (image, field, raster) adds the planes of a bin when its count is not
+// zero; one that spreads a hit over a footprint (beam, wave: PER_PLANE) adds the count and each plane when itself is not zero.
+template <int P> __device__ __forceinline__ int32_t* lds_image_tally(double* planes, int32_t bins) {
+    return reinterpret_cast<int32_t*>(planes + P * bins);
+}
+template <int P> __device__ __forceinline__ void lds_image_zero(double* planes, int32_t bins) {
+    int32_t* tally = lds_image_tally<P>(planes, bins);
+    for (int32_t b = threadIdx.x; b < bins; b += MON_THREADS) {
+#pragma unroll
+        for (int p = 0; p < P; ++p) planes[p * bins + b] = 0.0;
+        tally[b] = 0;
+    }
+    __syncthreads();
+}
+// One hit or piece that deposits where it counts: a count and v0 (v1 on the second plane).  The count comes LAST in the LDS arm
+// and first in the other: where both arms end in the same add, the compiler merges the two into one add on a selected address
+// — a flat atomic, which cost the LDS path of k_seg_raster's walk 4 %.
+template <int P>
+__device__ __forceinline__ void lds_image_deposit(double* planes, int32_t bins, unsigned long long* counts, double* out0, double* out1, int32_t bin,
+                                                  double v0, double v1 = 0.0) {
+    if (bins) {
+        unsafeAtomicAdd(&planes[bin], v0);
+        if (P > 1) unsafeAtomicAdd(&planes[bins + bin], v1);
+        atomicAdd(&lds_image_tally<P>(planes, bins)[bin], 1);
+    } else {
+        atomicAdd(&counts[bin], 1ull);
+        unsafeAtomicAdd(&out0[bin], v0);
+        if (P > 1) unsafeAtomicAdd(&out1[bin], v1);
+    }
+}
+template <int P, bool PER_PLANE>
+__device__ __forceinline__ void lds_image_flush(double* planes, int32_t bins, unsigned long long* counts, double* out0, double* out1 = nullptr) {
+    int32_t* tally = lds_image_tally<P>(planes, bins);
+    __syncthreads();
+    for (int32_t b = threadIdx.x; b < bins; b += MON_THREADS) {
+        const int32_t c = tally[b];
+        if (c) atomicAdd(&counts[b], (unsigned long long)c);
+        if (!PER_PLANE && !c) continue;
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const double v = planes[p * bins + b];
+            if (!PER_PLANE || v != 0.0) unsafeAtomicAdd(&(p ? out1 : out0)[b], v);
+        }
+    }
+}
 // One workgroup's part of an image pass: k_mon_count's partition, loads and tests, every hit binned where the record mode counts it.
 __device__ __forceinline__ void mon_image_pass(const ot_monitor* __restrict__ mons, int32_t n_mon, const MonSource& src, int64_t n, int32_t iters,
-                                               const int32_t* __restrict__ seg_count, int64_t n_rays, const MonImage& img, double* weight,
-                                               int32_t* tally) {
-    for (int32_t b = threadIdx.x; b < img.lds_bins; b += MON_THREADS) weight[b] = 0.0, tally[b] = 0;
-    __syncthreads();
-    const int32_t per_mon = img.nby * img.nbz;
-    const int64_t first = (int64_t)blockIdx.x * iters * MON_THREADS;
-    for (int32_t it = 0; it < iters && first + (int64_t)it * MON_THREADS < n; ++it) {
-        const int64_t s = first + (int64_t)it * MON_THREADS + threadIdx.x;
+                                               const int32_t* __restrict__ seg_count, int64_t n_rays, const MonImage& img, double* weight) {
+    lds_image_zero<1>(weight, img.lds_bins);
+    const MonSpan span = mon_span(n, iters);
+    for (int32_t it = 0; span.has(it); ++it) {
+        const int64_t s = span.at(it) + threadIdx.x;
         const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
         if (!__ballot(g.valid)) continue;
         double w = 0.0;
         bool have_w = false;  // the intensity of a slot is read once, at its first hit inside an image
         for (int32_t m = 0; m < n_mon; ++m) {
-            double Px, Py, Pz, t;
+            double Px, Py, Pz, t, y0, z0;
             if (!(g.valid && mon_hit(mons[m], g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, g.len, Px, Py, Pz, t))) continue;
-            const double* a = img.axes + 6 * m;
-            const double* e = img.edges + (int64_t)m * (img.nby + img.nbz + 2);
-            const int32_t ky = mon_bin(e, img.nby, Px * a[0] + Py * a[1] + Pz * a[2]);
-            const int32_t kz = mon_bin(e + img.nby + 1, img.nbz, Px * a[3] + Py * a[4] + Pz * a[5]);
-            if (ky < 0 || kz < 0) continue;
+            const int32_t bin = mon_image_bin(img, m, Px, Py, Pz, y0, z0);
+            if (bin < 0) continue;
             if (!have_w) {
-                w = mon_real(img.intensity + (s >> 6) * src.tile_stride + (s & 63) * src.width, src.width);
+                w = mon_real(img.intensity + mon_at(s, src.tile_stride, src.width), src.width);
                 have_w = true;
             }
-            const int32_t bin = m * per_mon + ky * img.nbz + kz;
-            if (img.lds_bins) {
-                atomicAdd(&tally[bin], 1);
-                unsafeAtomicAdd(&weight[bin], w);
-            } else {
-                atomicAdd(&img.counts[bin], 1ull);
-                unsafeAtomicAdd(&img.weights[bin], w);
-            }
+            lds_image_deposit<1>(weight, img.lds_bins, img.counts, img.weights, nullptr, bin, w);
         }
     }
-    __syncthreads();
-    for (int32_t b = threadIdx.x; b < img.lds_bins; b += MON_THREADS) {  // consecutive lanes, consecutive bins
-        const int32_t c = tally[b];
-        if (c) {
-            atomicAdd(&img.counts[b], (unsigned long long)c);
-            unsafeAtomicAdd(&img.weights[b], weight[b]);
-        }
+    lds_image_flush<1, false>(weight, img.lds_bins, img.counts, img.weights);
+}
+// The wavelength arguments of the field, beam and wave modes, and the one rule they are read by: the wavelength of a slot is
+// table[ray[s]] or, with no table, `uniform`.  mon_wavelength is false — the hit adds nothing and the caller counts it in
+// *skipped — when the ray is outside [0, n) (nothing is read out of range) or the wavelength is not finite and > 0.
+struct MonWavelength {
+    const double* table;  // [n], or NULL: `uniform` for every ray
+    unsigned long long* skipped;
+    double uniform;
+    int32_t n;
+};
+__device__ __forceinline__ bool mon_wavelength(const MonWavelength& lam, const uint8_t* ray_of_slot, double& wl) {
+    wl = lam.uniform;
+    bool known = true;
+    if (lam.table) {
+        const int32_t ray = *reinterpret_cast<const int32_t*>(ray_of_slot);
+        known = ray >= 0 && ray < lam.n;
+        if (known) wl = lam.table[ray];
     }
+    return known && wl > 0.0 && wl < HUGE_VAL;
 }
 // The field mode of k_mon_count (ot_monitor_field_many): the image mode's partition, loads, tests and bin rule, with a phasor in
 // place of the weight.  All zero for the two other modes.  A hit of slot s at the distance t has the optical path
 // L = t * n[s] + pathlength[s] (Ray.pathlength(t)), x = L / wavelength cycles, the phase 2 pi (x - floor x) (Ray.phase(t)) and the
 // amplitude sqrt(intensity[s]) (amplitude_mode 0) or intensity[s] (1); its bin gets a cos, a sin and one count.  n and pathlength are
-// addressed like the fields of MonSource and read as doubles (the host refuses single precision); the wavelength is
-// wavelength[ray[s]] or, with no array, wavelength_uniform.  A hit inside the image whose ray is outside [0, n_wavelengths) or
-// whose wavelength is not finite and > 0 adds nothing and is counted in *skipped: nothing is read out of range.
+// addressed like the fields of MonSource and read as doubles (the host refuses single precision); the wavelength is the ray's
+// (MonWavelength).  A hit inside the image whose ray has no usable wavelength adds nothing and is counted in *lam.skipped.
 // Through LDS: re[lds_bins], im[lds_bins] (double), tally[lds_bins] (int32) — 20 bytes a bin.
 static constexpr int MON_FIELD_LDS_BINS = (65536 - MON_MAX * 4) / 20;  // 3270: three monitors of 30 x 30
 struct MonField {
     double *re, *im;  // [n_mon][nby][nbz], of the launch's first monitor on; re NULL: no field mode
     const uint8_t *n_index, *pathlength;
-    const double* wavelength;  // [n_wavelengths], or NULL: wavelength_uniform for every ray
-    unsigned long long* skipped;
-    double wavelength_uniform;
-    int32_t n_wavelengths, amplitude_mode;
+    MonWavelength lam;
+    int32_t amplitude_mode;
 };
 __device__ __forceinline__ void mon_field_pass(const ot_monitor* __restrict__ mons, int32_t n_mon, const MonSource& src, int64_t n, int32_t iters,
                                                const int32_t* __restrict__ seg_count, int64_t n_rays, const MonImage& img, const MonField& fld,
-                                               double* re, double* im, int32_t* tally) {
-    for (int32_t b = threadIdx.x; b < img.lds_bins; b += MON_THREADS) re[b] = 0.0, im[b] = 0.0, tally[b] = 0;
-    __syncthreads();
-    const int32_t per_mon = img.nby * img.nbz;
-    const int64_t first = (int64_t)blockIdx.x * iters * MON_THREADS;
+                                               double* re) {
+    lds_image_zero<2>(re, img.lds_bins);  // (re, then im)
+    const MonSpan span = mon_span(n, iters);
     int32_t skipped = 0;
-    for (int32_t it = 0; it < iters && first + (int64_t)it * MON_THREADS < n; ++it) {
-        const int64_t s = first + (int64_t)it * MON_THREADS + threadIdx.x;
+    for (int32_t it = 0; span.has(it); ++it) {
+        const int64_t s = span.at(it) + threadIdx.x;
         const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
         if (!__ballot(g.valid)) continue;
         double a = 0.0, n_index = 0.0, pl = 0.0, wl = 0.0;
         int32_t have = 0;  // amplitude, index, path and wavelength of a slot are read once, at its first hit inside an image; -1: refused
         for (int32_t m = 0; m < n_mon; ++m) {
-            double Px, Py, Pz, t;
+            double Px, Py, Pz, t, y0, z0;
             if (!(g.valid && mon_hit(mons[m], g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, g.len, Px, Py, Pz, t))) continue;
-            const double* ax = img.axes + 6 * m;
-            const double* e = img.edges + (int64_t)m * (img.nby + img.nbz + 2);
-            const int32_t ky = mon_bin(e, img.nby, Px * ax[0] + Py * ax[1] + Pz * ax[2]);
-            const int32_t kz = mon_bin(e + img.nby + 1, img.nbz, Px * ax[3] + Py * ax[4] + Pz * ax[5]);
-            if (ky < 0 || kz < 0) continue;
+            const int32_t bin = mon_image_bin(img, m, Px, Py, Pz, y0, z0);
+            if (bin < 0) continue;
             if (!have) {
-                have = 1;
-                wl = fld.wavelength_uniform;
-                if (fld.wavelength) {
-                    const int32_t ray = *reinterpret_cast<const int32_t*>(src.ray + (s >> 6) * src.ray_stride + (s & 63) * 4);
-                    if (ray >= 0 && ray < fld.n_wavelengths) wl = fld.wavelength[ray];
-                    else have = -1;
-                }
-                if (!(wl > 0.0 && wl < HUGE_VAL)) have = -1;
+                have = mon_wavelength(fld.lam, src.ray + mon_at(s, src.ray_stride, 4), wl) ? 1 : -1;
                 if (have > 0) {
-                    const int64_t at = (s >> 6) * src.tile_stride + (s & 63) * 8;
+                    const int64_t at = mon_at(s, src.tile_stride, 8);
                     a = *reinterpret_cast<const double*>(img.intensity + at);
                     if (fld.amplitude_mode == 0) a = sqrt(a);
                     n_index = *reinterpret_cast<const double*>(fld.n_index + at);
@@ -379,28 +464,11 @@ __device__ __forceinline__ void mon_field_pass(const ot_monitor* __restrict__ mo
             const double f = x - floor(x);
             double sn, cs;
             sincospi(2.0 * f, &sn, &cs);
-            const int32_t bin = m * per_mon + ky * img.nbz + kz;
-            if (img.lds_bins) {
-                atomicAdd(&tally[bin], 1);
-                unsafeAtomicAdd(&re[bin], a * cs);
-                unsafeAtomicAdd(&im[bin], a * sn);
-            } else {
-                atomicAdd(&img.counts[bin], 1ull);
-                unsafeAtomicAdd(&fld.re[bin], a * cs);
-                unsafeAtomicAdd(&fld.im[bin], a * sn);
-            }
+            lds_image_deposit<2>(re, img.lds_bins, img.counts, fld.re, fld.im, bin, a * cs, a * sn);
         }
     }
-    if (skipped) atomicAdd(fld.skipped, (unsigned long long)skipped);
-    __syncthreads();
-    for (int32_t b = threadIdx.x; b < img.lds_bins; b += MON_THREADS) {  // consecutive lanes, consecutive bins
-        const int32_t c = tally[b];
-        if (c) {
-            atomicAdd(&img.counts[b], (unsigned long long)c);
-            unsafeAtomicAdd(&fld.re[b], re[b]);
-            unsafeAtomicAdd(&fld.im[b], im[b]);
-        }
-    }
+    if (skipped) atomicAdd(fld.lam.skipped, (unsigned long long)skipped);
+    lds_image_flush<2, false>(re, img.lds_bins, img.counts, fld.re, fld.im);
 }
 // The beam mode of k_mon_count (ot_monitor_beam_many): the image mode's partition, loads, tests and bin rule for the count, with
 // the hit's power spread over its Gaussian spot.  All zero for the three other modes.  A hit of slot s at the distance t and the
@@ -410,8 +478,8 @@ __device__ __forceinline__ void mon_field_pass(const ot_monitor* __restrict__ mo
 // integral over the bin of I 2 / (pi w^2) exp(-2 r^2 / w^2), the beam taken at normal incidence.  Bins whose nearer edge lies
 // more than 5 w from the centre along an axis are left out (a share below erfc(5 sqrt2) = 1.5e-23).  All in double precision;
 // intensity, q_re, q_im and n are addressed like the fields of MonSource, in its precision; the wavelength as in the field mode.
-// A hit whose wavelength, n or qi is not finite and > 0, whose ray is no index into the wavelengths or whose w is not finite
-// and > 0 adds nothing and is counted in *skipped.
+// A hit without a usable wavelength (mon_wavelength) or whose n, qi or w is not finite and > 0 (mon_spot) adds nothing and is
+// counted in *lam.skipped.
 // One hit has a footprint of 1 to nby * nbz bins, so the deposit is the wave's work, not the lane's: every lane finds its own
 // slot's hit, counts its centre and steps out its footprint (64 searches side by side), then the wave takes the hits with a
 // footprint one at a time (the lowest set bit of their ballot; y0, z0, w, I and the footprint come through v_readlane, as
@@ -428,11 +496,16 @@ static constexpr int MON_BEAM_LDS_BINS = (65536 - MON_MAX * 4 - MON_WAVES * MON_
 struct MonBeam {
     double* power;  // [n_mon][nby][nbz], of the launch's first monitor on; NULL: no beam mode
     const uint8_t *q_re, *q_im, *n_index;
-    const double* wavelength;  // [n_wavelengths], or NULL: wavelength_uniform for every ray
-    unsigned long long* skipped;
-    double wavelength_uniform;
-    int32_t n_wavelengths;
+    MonWavelength lam;
 };
+// The spot of a hit (k_mon_wave; the beam pass below holds the same expressions written out): |q|^2, w^2 = wl |q|^2 / (n pi qi) and w.  false — the hit adds nothing and is counted
+// in *skipped — when n, qi or w is not finite and > 0.
+__device__ __forceinline__ bool mon_spot(double qr, double qi, double n_index, double wl, double& q2, double& w2, double& w) {
+    q2 = qr * qr + qi * qi;
+    w2 = wl * q2 / (n_index * M_PI * qi);
+    w = sqrt(w2);
+    return n_index > 0.0 && n_index < HUGE_VAL && qi > 0.0 && qi < HUGE_VAL && w > 0.0 && w < HUGE_VAL;
+}
 // lane `from`'s v in every lane (from is wave-uniform): a scalar
 __device__ __forceinline__ double mon_lane_value(double v, int from) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), from), __builtin_amdgcn_readlane(__double2loint(v), from));
@@ -460,6 +533,8 @@ __device__ __forceinline__ int32_t mon_beam_last(const double* __restrict__ e, i
 __device__ __noinline__ double mon_beam_erf(double x) { return erf(x); }
 // One hit, by its whole wave: centre (y0, z0), spot size w, power I and the footprint ky0 .. ky1 x kz0 .. kz1 are wave-uniform; the
 // monitor's nby x nbz bins of power are `in_lds` or, when that is NULL, `in_global`.
+// (This deposit and the pass below are WRITTEN OUT — zero, partition, tile addressing, wavelength, spot, bin, count, flush and the
+// walk that mon_wave_deposit repeats: built from the shared pieces beam_all was 1.2 to 4.5 % slower, see "What stays" above.)
 __device__ __forceinline__ void mon_beam_deposit(const double* __restrict__ ey, const double* __restrict__ ez, int32_t nbz, double y0, double z0, double w,
                                                  double I, int32_t ky0, int32_t ky1, int32_t kz0, int32_t kz1, double* strip, int lane, double* in_lds,
                                                  double* in_global) {
@@ -517,12 +592,12 @@ __device__ __forceinline__ void mon_beam_pass(const ot_monitor* __restrict__ mon
             double y0 = 0.0, z0 = 0.0, w = 0.0, I = 0.0;
             int32_t ky0 = 0, ky1 = -1, kz0 = 0, kz1 = -1;
             if (hit) {
-                double wl = beam.wavelength_uniform;
+                double wl = beam.lam.uniform;
                 bool usable = true;
-                if (beam.wavelength) {
+                if (beam.lam.table) {
                     const int32_t ray = *reinterpret_cast<const int32_t*>(src.ray + tile * src.ray_stride + (uint32_t)(lane * 4));
-                    usable = ray >= 0 && ray < beam.n_wavelengths;
-                    if (usable) wl = beam.wavelength[ray];
+                    usable = ray >= 0 && ray < beam.lam.n;
+                    if (usable) wl = beam.lam.table[ray];
                 }
                 const double qr = mon_real(beam.q_re + at_tile + at_lane, src.width) + t, qi = mon_real(beam.q_im + at_tile + at_lane, src.width);
                 const double n_index = mon_real(beam.n_index + at_tile + at_lane, src.width);
@@ -555,7 +630,7 @@ __device__ __forceinline__ void mon_beam_pass(const ot_monitor* __restrict__ mon
             }
         }
     }
-    if (skipped) atomicAdd(beam.skipped, (unsigned long long)skipped);
+    if (skipped) atomicAdd(beam.lam.skipped, (unsigned long long)skipped);
     __syncthreads();
     for (int32_t b = threadIdx.x; b < img.lds_bins; b += MON_THREADS) {  // consecutive lanes, consecutive bins
         const int32_t c = tally[b];
@@ -575,20 +650,19 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_count(const ot_monitor* __r
     if (img.counts) {
         if (beam.power)
             mon_beam_pass(mons, n_mon, src, n, iters, seg_count, n_rays, img, beam, mon_image, mon_image + MON_WAVES * MON_BEAM_STRIP,
-                          reinterpret_cast<int32_t*>(mon_image + MON_WAVES * MON_BEAM_STRIP + img.lds_bins));
+                          lds_image_tally<1>(mon_image + MON_WAVES * MON_BEAM_STRIP, img.lds_bins));
         else if (fld.re)
-            mon_field_pass(mons, n_mon, src, n, iters, seg_count, n_rays, img, fld, mon_image, mon_image + img.lds_bins,
-                           reinterpret_cast<int32_t*>(mon_image + 2 * img.lds_bins));
+            mon_field_pass(mons, n_mon, src, n, iters, seg_count, n_rays, img, fld, mon_image);
         else
-            mon_image_pass(mons, n_mon, src, n, iters, seg_count, n_rays, img, mon_image, reinterpret_cast<int32_t*>(mon_image + img.lds_bins));
+            mon_image_pass(mons, n_mon, src, n, iters, seg_count, n_rays, img, mon_image);
         return;
     }
     const int lane = threadIdx.x & 63;
     if (threadIdx.x < MON_MAX) total[threadIdx.x] = 0;
     __syncthreads();
-    const int64_t first = (int64_t)blockIdx.x * iters * MON_THREADS;
-    for (int32_t it = 0; it < iters && first + (int64_t)it * MON_THREADS < n; ++it) {
-        const MonSeg g = mon_load(src, first + (int64_t)it * MON_THREADS + threadIdx.x, n, seg_count, n_rays);
+    const MonSpan span = mon_span(n, iters);
+    for (int32_t it = 0; span.has(it); ++it) {
+        const MonSeg g = mon_load(src, span.at(it) + threadIdx.x, n, seg_count, n_rays);
         if (!__ballot(g.valid)) continue;
         for (int32_t m = 0; m < n_mon; ++m) {  // m is wave-uniform: the monitor comes through scalar loads
             double Px, Py, Pz, t;
@@ -620,8 +694,8 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_count(const ot_monitor* __r
 // normal incidence and q is not advanced across the tilt.
 // Sampling: the cycle rate along y is ry + 2 kc D, linear in D; where its largest magnitude over the footprint (at one of the two
 // end centres) times the mean bin width (e[nb] - e[0]) / nb exceeds 0.5 on either axis, the hit is counted in *aliased — and is
-// deposited all the same.  A hit whose ray lies outside [0, n_wavelengths) or whose wavelength, n, qi or w is not finite and > 0
-// adds nothing and is counted in *skipped.
+// deposited all the same.  A hit without a usable wavelength or spot (mon_wavelength, mon_spot, as in the beam pass) adds nothing
+// and is counted in *lam.skipped.
 // As in the beam pass every lane finds its own slot's hit, counts its centre and steps out its footprint; the wave then takes the
 // hits with a footprint one at a time (ballot, v_readlane), its lanes put A gy at the footprint's y centres and gz at its z
 // centres into the wave's strip of LDS — 63 x 63 bins at a time, 63 + 63 complex values — and stride over the bins with one
@@ -634,10 +708,9 @@ static constexpr int MON_WAVE_LDS_BINS = (65536 - MON_MAX * 4 - MON_WAVES * MON_
 struct MonWave {
     double *re, *im;  // [n_mon][nby][nbz], of the launch's first monitor on
     const uint8_t *q_re, *q_im, *n_index, *pathlength;
-    const double* wavelength;  // [n_wavelengths], or NULL: wavelength_uniform for every ray
-    unsigned long long *skipped, *aliased;
-    double wavelength_uniform;
-    int32_t n_wavelengths, amplitude_mode, gouy;
+    MonWavelength lam;
+    unsigned long long* aliased;
+    int32_t amplitude_mode, gouy;
 };
 // exp and the phasor of a cycle count as calls, not inlined, as the beam pass's erf: inlined, their polynomials' coefficients are
 // hoisted out of every loop of the kernel and held in vector registers from its first instruction to its last (223 registers)
@@ -653,11 +726,12 @@ __device__ __forceinline__ void mon_wave_axis(double D, double w2, double f, dou
     const double env = mon_wave_exp(-(D * D) / w2);
     re = env * p.x, im = env * p.y;
 }
-// One hit, by its whole wave: everything but `lane` is wave-uniform; the monitor's nby x nbz bins are re_lds / im_lds or, when
-// re_lds is NULL, re_global / im_global.
+// One hit, by its whole wave: everything but `lane` is wave-uniform; the monitor's nby x nbz bins are re_lds / im_lds (`lds`: the
+// launch keeps an image there) or re_global / im_global.
+// (mon_beam_deposit's walk, written again: shared, it left this kernel 1 vector register of the 5 it has to spare.)
 __device__ __forceinline__ void mon_wave_deposit(const double* __restrict__ ey, const double* __restrict__ ez, int32_t nbz, double y0, double z0, double w2,
                                                  double Are, double Aim, double f, double ry, double rz, double kc, int32_t ky0, int32_t ky1, int32_t kz0,
-                                                 int32_t kz1, double* strip, int lane, double* re_lds, double* im_lds, double* re_global,
+                                                 int32_t kz1, double* strip, int lane, int32_t lds, double* re_lds, double* im_lds, double* re_global,
                                                  double* im_global) {
     for (int32_t by = ky0; by <= ky1; by += MON_WAVE_CHUNK) {
         const int32_t ny = min(MON_WAVE_CHUNK, ky1 - by + 1);
@@ -683,13 +757,8 @@ __device__ __forceinline__ void mon_wave_deposit(const double* __restrict__ ey, 
                 const double ur = yr * zr - yi * zi, ui = yr * zi + yi * zr;
                 if (ur == 0.0 && ui == 0.0) continue;
                 const int32_t bin = (by + iy) * nbz + bz + iz;
-                if (re_lds) {
-                    unsafeAtomicAdd(&re_lds[bin], ur);
-                    unsafeAtomicAdd(&im_lds[bin], ui);
-                } else {
-                    unsafeAtomicAdd(&re_global[bin], ur);
-                    unsafeAtomicAdd(&im_global[bin], ui);
-                }
+                mon_add(lds, re_lds, re_global, bin, ur);
+                mon_add(lds, im_lds, im_global, bin, ui);
             }
         }
     }
@@ -706,27 +775,23 @@ __global__ __launch_bounds__(MON_THREADS, 4) void k_mon_wave(const ot_monitor* _
     extern __shared__ double mon_wave_lds[];  // the waves' strips, then re, im, tally
     double* re = mon_wave_lds + MON_WAVES * MON_WAVE_STRIP;
     double* im = re + img.lds_bins;
-    int32_t* tally = reinterpret_cast<int32_t*>(im + img.lds_bins);
-    for (int32_t b = threadIdx.x; b < img.lds_bins; b += MON_THREADS) re[b] = 0.0, im[b] = 0.0, tally[b] = 0;
-    __syncthreads();
+    int32_t* tally = lds_image_tally<2>(re, img.lds_bins);
+    lds_image_zero<2>(re, img.lds_bins);
     const int lane = threadIdx.x & 63;
     double* strip = mon_wave_lds + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * MON_WAVE_STRIP;
     const int32_t per_mon = img.nby * img.nbz;
-    const int64_t first = (int64_t)blockIdx.x * iters * MON_THREADS;
+    const MonSpan span = mon_span(n, iters);
     int32_t skipped = 0, aliased = 0;
-    for (int32_t it = 0; it < iters && first + (int64_t)it * MON_THREADS < n; ++it) {
+    for (int32_t it = 0; span.has(it); ++it) {
         int32_t tid = threadIdx.x;
         asm volatile("" : "+v"(tid));  // (opaque: the seven per-lane plane addresses are formed here, not held across the loop)
-        const int64_t s = first + (int64_t)it * MON_THREADS + tid;
+        const int64_t s = span.at(it) + tid;
         if (!__ballot(mon_load(src, s, n, seg_count, n_rays).valid)) continue;
-        // the 64 slots of a wave are one tile: its place is a scalar, and the lane's within it one 32-bit offset for every plane
-        const int64_t tile = __builtin_amdgcn_readfirstlane((int32_t)(s >> 6));
-        const int64_t at_tile = tile * src.tile_stride;
-        const uint32_t at_lane = (uint32_t)(lane * 8);
+        const int64_t tile = mon_tile(s);
         for (int32_t m = 0; m < n_mon; ++m) {
             // the segment again for every monitor (from the cache): held across the deposits it would cost 14 registers
             asm volatile("" : "+v"(tid));
-            const MonSeg g = mon_load(src, first + (int64_t)it * MON_THREADS + tid, n, seg_count, n_rays);
+            const MonSeg g = mon_load(src, span.at(it) + tid, n, seg_count, n_rays);
             double Px, Py, Pz, t;
             const bool hit = g.valid && mon_hit(mons[m], g.ox, g.oy, g.oz, g.dx, g.dy, g.dz, g.len, Px, Py, Pz, t);
             if (!__ballot(hit)) continue;
@@ -738,35 +803,22 @@ __global__ __launch_bounds__(MON_THREADS, 4) void k_mon_wave(const ot_monitor* _
             int32_t ky0 = 0, ky1 = -1, kz0 = 0, kz1 = -1;
             bool usable = true, alias = false;
             if (hit) {
-                double wl = wav.wavelength_uniform;
-                if (wav.wavelength) {
-                    const int32_t ray = *reinterpret_cast<const int32_t*>(src.ray + tile * src.ray_stride + (uint32_t)(lane * 4));
-                    usable = ray >= 0 && ray < wav.n_wavelengths;
-                    if (usable) wl = wav.wavelength[ray];
-                }
-                const double qr = *reinterpret_cast<const double*>(wav.q_re + at_tile + at_lane) + t;
-                const double qi = *reinterpret_cast<const double*>(wav.q_im + at_tile + at_lane);
-                const double n_index = *reinterpret_cast<const double*>(wav.n_index + at_tile + at_lane);
-                const double q2 = qr * qr + qi * qi;
-                w2 = wl * q2 / (n_index * M_PI * qi);
-                const double w = sqrt(w2);
-                usable = usable && wl > 0.0 && wl < HUGE_VAL && n_index > 0.0 && n_index < HUGE_VAL && qi > 0.0 && qi < HUGE_VAL && w > 0.0 && w < HUGE_VAL;
+                double wl, q2, w;
+                usable = mon_wavelength(wav.lam, mon_in_tile(src.ray, tile, src.ray_stride, lane, 4), wl);
+                const double qr = mon_real(mon_in_tile(wav.q_re, tile, src.tile_stride, lane, 8), 8) + t;
+                const double qi = mon_real(mon_in_tile(wav.q_im, tile, src.tile_stride, lane, 8), 8);
+                const double n_index = mon_real(mon_in_tile(wav.n_index, tile, src.tile_stride, lane, 8), 8);
+                usable = mon_spot(qr, qi, n_index, wl, q2, w2, w) && usable;
                 if (usable) {
-                    y0 = Px * ax[0] + Py * ax[1] + Pz * ax[2];
-                    z0 = Px * ax[3] + Py * ax[4] + Pz * ax[5];
-                    const int32_t ky = mon_bin(ey, img.nby, y0), kz = mon_bin(ez, img.nbz, z0);
-                    if (ky >= 0 && kz >= 0) {  // the centre is counted where the image mode counts the hit
-                        const int32_t bin = m * per_mon + ky * img.nbz + kz;
-                        if (img.lds_bins) atomicAdd(&tally[bin], 1);
-                        else atomicAdd(&img.counts[bin], 1ull);
-                    }
+                    const int32_t bin = mon_image_bin(img, m, Px, Py, Pz, y0, z0);
+                    if (bin >= 0) mon_tally(img.lds_bins, tally, img.counts, bin);  // the centre is counted where the image mode counts the hit
                     const double reach = 6.0 * w;
                     mon_wave_footprint(ey, img.nby, y0 - reach, y0 + reach, ky0, ky1);
                     mon_wave_footprint(ez, img.nbz, z0 - reach, z0 + reach, kz0, kz1);
                     if (ky0 <= ky1 && kz0 <= kz1) {
-                        double a = *reinterpret_cast<const double*>(img.intensity + at_tile + at_lane);
+                        double a = mon_real(mon_in_tile(img.intensity, tile, src.tile_stride, lane, 8), 8);
                         if (wav.amplitude_mode == 0) a = sqrt(a);
-                        const double L = t * n_index + *reinterpret_cast<const double*>(wav.pathlength + at_tile + at_lane);
+                        const double L = t * n_index + mon_real(mon_in_tile(wav.pathlength, tile, src.tile_stride, lane, 8), 8);
                         f = L / wl;
                         f -= floor(f);  // the cycles of the path ride along y: one phasor less a hit
                         Are = a * sqrt(2.0 / (M_PI * w2)), Aim = 0.0;
@@ -789,27 +841,20 @@ __global__ __launch_bounds__(MON_THREADS, 4) void k_mon_wave(const ot_monitor* _
             // (wave-wide tallies: scalars)
             skipped += (int32_t)__popcll(__ballot(hit && !usable));
             aliased += (int32_t)__popcll(__ballot(alias));
-            // the wave takes its hits one at a time
+            // the wave takes its hits one at a time (the beam pass's two lines again, around this mode's operands)
             for (unsigned long long rest = __ballot(ky0 <= ky1 && kz0 <= kz1); rest; rest &= rest - 1) {
                 const int from = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(rest));
                 mon_wave_deposit(ey, ez, img.nbz, mon_lane_value(y0, from), mon_lane_value(z0, from), mon_lane_value(w2, from), mon_lane_value(Are, from),
                                  mon_lane_value(Aim, from), mon_lane_value(f, from), mon_lane_value(ry, from), mon_lane_value(rz, from), mon_lane_value(kc, from),
                                  __builtin_amdgcn_readlane(ky0, from), __builtin_amdgcn_readlane(ky1, from), __builtin_amdgcn_readlane(kz0, from),
-                                 __builtin_amdgcn_readlane(kz1, from), strip, lane, img.lds_bins ? re + m * per_mon : nullptr, im + m * per_mon,
+                                 __builtin_amdgcn_readlane(kz1, from), strip, lane, img.lds_bins, re + m * per_mon, im + m * per_mon,
                                  wav.re + (int64_t)m * per_mon, wav.im + (int64_t)m * per_mon);
             }
         }
     }
-    if (lane == 0 && skipped) atomicAdd(wav.skipped, (unsigned long long)skipped);
+    if (lane == 0 && skipped) atomicAdd(wav.lam.skipped, (unsigned long long)skipped);
     if (lane == 0 && aliased) atomicAdd(wav.aliased, (unsigned long long)aliased);
-    __syncthreads();
-    for (int32_t b = threadIdx.x; b < img.lds_bins; b += MON_THREADS) {  // consecutive lanes, consecutive bins
-        const int32_t c = tally[b];
-        const double r = re[b], i = im[b];
-        if (c) atomicAdd(&img.counts[b], (unsigned long long)c);
-        if (r != 0.0) unsafeAtomicAdd(&wav.re[b], r);
-        if (i != 0.0) unsafeAtomicAdd(&wav.im[b], i);
-    }
+    lds_image_flush<2, true>(re, img.lds_bins, img.counts, wav.re, wav.im);
 }
 // off = the exclusive scan of count (n_mon * gridDim.x + 1 elements).  Position of a hit in the concatenated output: first[0]
 // (the hits of the monitors of earlier launches: the host walks long lists MON_MAX monitors at a time) + off[m][g] + hits of
@@ -839,9 +884,9 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_emit(const ot_monitor* __re
     if (lane < MON_MAX) seen[wave][lane] = 0;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const int64_t start = (int64_t)blockIdx.x * iters * MON_THREADS;
-    for (int32_t it = 0; it < iters && start + (int64_t)it * MON_THREADS < n; ++it) {
-        const int64_t s = start + (int64_t)it * MON_THREADS + threadIdx.x;
+    const MonSpan span = mon_span(n, iters);
+    for (int32_t it = 0; span.has(it); ++it) {
+        const int64_t s = span.at(it) + threadIdx.x;
         const int p = it & 1;
         const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
         uint32_t hits = 0;
@@ -897,9 +942,9 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_emit(const ot_monitor* __re
 // passage through a corner steps both axes and leaves no piece.
 // The walk is a counted loop: a trip deposits one piece and steps at least one axis, or is the last — nu + nv + 1 trips at most,
 // and no loop of the kernel waits on a floating-point condition (the two searches of seg_first_pixel count their trips too).
-// Deposits go to the workgroup's image in LDS (lds_pixels = nu * nv: fluence[lds_pixels] doubles, then tally[lds_pixels] int32,
-// flushed at the end, non-zero pixels only, consecutive lanes consecutive pixels) or, with lds_pixels = 0, straight to global
-// memory.  Counts are integers, exact and the same every run; the fluence is fp64 atomic adds.
+// Deposits go to the workgroup's image in LDS (lds_pixels = nu * nv: fluence[lds_pixels] doubles, then tally[lds_pixels] int32:
+// the image passes' lds_image_zero / lds_image_flush, a pixel flushed when its count is not zero) or, with lds_pixels = 0,
+// straight to global memory.  Counts are integers, exact and the same every run; the fluence is fp64 atomic adds.
 // A valid segment with a NaN in origin, direction or length, with |d| == 0, or whose clipped interval is not empty and not
 // finite (an unbounded last segment inside an infinite depth range) deposits nothing and is counted in *skipped: one atomic a
 // wave.  An empty interval (the segment misses the box) is neither.
@@ -947,14 +992,12 @@ __global__ __launch_bounds__(MON_THREADS) void k_seg_raster(MonSource src, int64
                                                             int64_t n_rays, SegRaster r) {
     extern __shared__ double seg_image[];  // fluence[lds_pixels], then tally[lds_pixels]
     double* fluence = seg_image;
-    int32_t* tally = reinterpret_cast<int32_t*>(seg_image + r.lds_pixels);
-    for (int32_t b = threadIdx.x; b < r.lds_pixels; b += MON_THREADS) fluence[b] = 0.0, tally[b] = 0;
-    __syncthreads();
+    lds_image_zero<1>(fluence, r.lds_pixels);
     const int lane = threadIdx.x & 63;
-    const int64_t first = (int64_t)blockIdx.x * iters * MON_THREADS;
+    const MonSpan span = mon_span(n, iters);
     int32_t skipped = 0;  // (wave-wide: a scalar)
-    for (int32_t it = 0; it < iters && first + (int64_t)it * MON_THREADS < n; ++it) {
-        const int64_t s = first + (int64_t)it * MON_THREADS + threadIdx.x;
+    for (int32_t it = 0; span.has(it); ++it) {
+        const int64_t s = span.at(it) + threadIdx.x;
         const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
         if (!__ballot(g.valid)) continue;
         const double* a = r.axes;
@@ -977,7 +1020,7 @@ __global__ __launch_bounds__(MON_THREADS) void k_seg_raster(MonSource src, int64
         skipped += (int32_t)__popcll(__ballot((g.valid && !numbers) || endless));
         if (!inside || endless) continue;
         double w = 1.0;
-        if (r.intensity) w = mon_real(r.intensity + (s >> 6) * src.tile_stride + (s & 63) * src.width, src.width);
+        if (r.intensity) w = mon_real(r.intensity + mon_at(s, src.tile_stride, src.width), src.width);
         int32_t ku = seg_first_pixel(r.ue, r.nu, ou, du, t_a), kv = seg_first_pixel(r.ve, r.nv, ov, dv, t_a);
         const int32_t su = du > 0.0 ? 1 : -1, sv = dv > 0.0 ? 1 : -1;
         double t = t_a;
@@ -990,14 +1033,7 @@ __global__ __launch_bounds__(MON_THREADS) void k_seg_raster(MonSource src, int64
             t_next = t_next < t_b ? t_next : t_b;
             if (t_next > t) {
                 const int32_t pixel = ku * r.nv + kv;
-                const double piece = w * (t_next - t);
-                if (r.lds_pixels) {
-                    atomicAdd(&tally[pixel], 1);
-                    unsafeAtomicAdd(&fluence[pixel], piece);
-                } else {
-                    atomicAdd(&r.counts[pixel], 1ull);
-                    unsafeAtomicAdd(&r.fluence[pixel], piece);
-                }
+                lds_image_deposit<1>(fluence, r.lds_pixels, r.counts, r.fluence, nullptr, pixel, w * (t_next - t));
                 t = t_next;
             }
             if (!(t_next < t_b)) break;
@@ -1006,12 +1042,5 @@ __global__ __launch_bounds__(MON_THREADS) void k_seg_raster(MonSource src, int64
         }
     }
     if (lane == 0 && skipped) atomicAdd(r.skipped, (unsigned long long)skipped);
-    __syncthreads();
-    for (int32_t b = threadIdx.x; b < r.lds_pixels; b += MON_THREADS) {  // consecutive lanes, consecutive pixels
-        const int32_t c = tally[b];
-        if (c) {
-            atomicAdd(&r.counts[b], (unsigned long long)c);
-            unsafeAtomicAdd(&r.fluence[b], fluence[b]);
-        }
-    }
+    lds_image_flush<1, false>(fluence, r.lds_pixels, r.counts, r.fluence);
 }

@@ -1994,8 +1994,7 @@ int ot_monitor_field_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors,
     if (const int rc = check_amplitude_mode(amplitude_mode)) return rc;
     MonField fld{};
     fld.n_index = (const uint8_t*)n_index, fld.pathlength = (const uint8_t*)pathlength;
-    fld.wavelength = wavelength, fld.n_wavelengths = (int32_t)n_wavelengths, fld.wavelength_uniform = wavelength_uniform;
-    fld.skipped = (unsigned long long*)skipped, fld.amplitude_mode = amplitude_mode;
+    fld.lam = {wavelength, (unsigned long long*)skipped, wavelength_uniform, (int32_t)n_wavelengths}, fld.amplitude_mode = amplitude_mode;
     return image_call(a, {MON_FIELD_LDS_BINS, 20, 0, {re, im}, {skipped}}, [&](const ImagePass& p) {
         fld.re = re + p.first_bin, fld.im = im + p.first_bin;
         launch_count(a, p, p.img, fld, MonBeam{});
@@ -2013,8 +2012,7 @@ int ot_monitor_beam_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, 
     if (const int rc = check_wavelength_args(wavelength, n_wavelengths, wavelength_uniform)) return rc;
     MonBeam beam{};
     beam.q_re = (const uint8_t*)q_re, beam.q_im = (const uint8_t*)q_im, beam.n_index = (const uint8_t*)n_index;
-    beam.wavelength = wavelength, beam.n_wavelengths = (int32_t)n_wavelengths, beam.wavelength_uniform = wavelength_uniform;
-    beam.skipped = (unsigned long long*)skipped;
+    beam.lam = {wavelength, (unsigned long long*)skipped, wavelength_uniform, (int32_t)n_wavelengths};
     return image_call(a, {MON_BEAM_LDS_BINS, 12, sizeof(double) * MON_WAVES * MON_BEAM_STRIP, {power}, {skipped}}, [&](const ImagePass& p) {
         beam.power = power + p.first_bin;
         launch_count(a, p, p.img, MonField{}, beam);
@@ -2037,8 +2035,7 @@ int ot_monitor_wave_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, 
     MonWave wav{};
     wav.q_re = (const uint8_t*)q_re, wav.q_im = (const uint8_t*)q_im;
     wav.n_index = (const uint8_t*)n_index, wav.pathlength = (const uint8_t*)pathlength;
-    wav.wavelength = wavelength, wav.n_wavelengths = (int32_t)n_wavelengths, wav.wavelength_uniform = wavelength_uniform;
-    wav.skipped = (unsigned long long*)skipped, wav.aliased = (unsigned long long*)aliased;
+    wav.lam = {wavelength, (unsigned long long*)skipped, wavelength_uniform, (int32_t)n_wavelengths}, wav.aliased = (unsigned long long*)aliased;
     wav.amplitude_mode = amplitude_mode, wav.gouy = gouy;
     return image_call(a, {MON_WAVE_LDS_BINS, 20, sizeof(double) * MON_WAVES * MON_WAVE_STRIP, {re, im}, {skipped, aliased}}, [&](const ImagePass& p) {
         wav.re = re + p.first_bin, wav.im = im + p.first_bin;  // a kernel of its own, on the same partition

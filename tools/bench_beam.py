@@ -11,6 +11,7 @@ rounds and their spread.  beam_all and field_all read their `skipped` counter ba
 synchronisation); image_all returns without reading anything.
 
     python tools/bench_beam.py [--rays 1000000] [--rounds 21] [--monitors 6] [--out profiles/beam_image.json]
+    env: OT_LIB = another build of the library (the parent commit's, for an A/B in one job)
     python tools/bench_beam.py --probe     the device math library's double erf against scipy.special.erf, in ulp of erf, on 1e5
                                            arguments in [-8, 8]: a one-line kernel of its own in a process of its own (what the
                                            bound of tests/test_gpu_beam.py takes for E_DEV, doubled)"""
@@ -109,6 +110,8 @@ def main():
     from optable_amd.batch import RayBatch
     from optable_amd.engine import beam_plan, field_plan, image_plan
 
+    if os.environ.get("OT_LIB"):  # an A/B build of the library, e.g. the parent commit's against this tree's
+        abi.LIB_PATH = os.path.abspath(os.environ["OT_LIB"])
     assert torch.cuda.is_available(), "bench_beam.py measures on an MI355X"
     table = oa.OpticalTable()
     table.add_components(W.cfg2_components(oa))

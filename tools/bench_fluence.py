@@ -11,7 +11,8 @@ each in the `slots` layout (neighbouring lanes hold the same segment index of ne
 engine's stream, after a warm-up; reported: the median of the rounds and their spread, the pieces deposited and the rate in
 pieces per second.  All eight figures come from one run, one process, the paths alternating round by round.
 
-    python tools/bench_fluence.py [--rays 1000000] [--rounds 11] [--out profiles/fluence.json]"""
+    python tools/bench_fluence.py [--rays 1000000] [--rounds 11] [--out profiles/fluence.json]
+    env: OT_LIB = another build of the library (the parent commit's, for an A/B in one job)"""
 import argparse
 import datetime
 import json
@@ -50,6 +51,8 @@ def main():
     from optable_amd.batch import RayBatch
     from optable_amd.engine import fluence_plan
 
+    if os.environ.get("OT_LIB"):  # an A/B build of the library, e.g. the parent commit's against this tree's
+        abi.LIB_PATH = os.path.abspath(os.environ["OT_LIB"])
     assert torch.cuda.is_available(), "bench_fluence.py measures on an MI355X"
     assert args.rounds >= 5
     table = oa.OpticalTable()

@@ -13,6 +13,7 @@ on a 6 x 6 monitor of 30 bins nearly every hit is aliased (wave_all says so; the
 the arithmetic, the image is not physics.
 
     python tools/bench_wave.py [--rays 1000000] [--rounds 11] [--monitors 8] [--out profiles/wave_image.json]
+    env: OT_LIB = another build of the library (the parent commit's, for an A/B in one job)
     python tools/bench_wave.py --probe     the device math library's double exp and sincospi against np.longdouble on 1e5 arguments
                                            each over the ranges k_mon_wave uses (exp on [-37, 0]; sincospi(2 f), f in [0, 1), half of
                                            them dense around the zeros), in a kernel of its own in a process of its own: what the
@@ -139,6 +140,8 @@ def main():
     from optable_amd.batch import RayBatch
     from optable_amd.engine import beam_plan, field_plan, wave_plan
 
+    if os.environ.get("OT_LIB"):  # an A/B build of the library, e.g. the parent commit's against this tree's
+        abi.LIB_PATH = os.path.abspath(os.environ["OT_LIB"])
     assert torch.cuda.is_available(), "bench_wave.py measures on an MI355X"
     assert args.rounds >= 5
     table = oa.OpticalTable()

@@ -5,7 +5,10 @@ Are the gfx950 kernels of two builds the same machine code?  For every *.o of bo
 translation unit, as tools/kernel_resources.sh reads them) the device code object is unbundled and disassembled
 (`llvm-objdump -d --no-show-raw-insn`), the disassembly is split per kernel symbol, and addresses and the absolute branch
 targets objdump prints behind them are stripped: what is left depends on the instructions alone, not on where the linker
-put the kernel.  Symbols of .text that are no kernels (device functions that were not inlined) are compared the same way; an
+put the kernel.  Two more things say nothing about a kernel's own instructions and are left out (`normalise`): the displacement
+literal of a PC-relative address (the s_add_u32 / s_addc_u32 pair behind a s_getpc_b64 that forms the address of a function that
+was not inlined: it moves when code in front of either changes size) and the s_nop padding after a symbol's last instruction.
+Symbols of .text that are no kernels (device functions that were not inlined) are compared the same way; an
 object without kernels, or a kernel without instructions, is an error.  Next to it, the kernel's metadata note: registers,
 spills, LDS, private segment, the kernel-argument offsets and sizes.  Prints `same` or `differs` per kernel name (-v: the first differing lines) and exits non-zero on any
 difference, or when a kernel exists on one side only.
@@ -43,8 +46,31 @@ ADDRESS = re.compile(r"^\s*[0-9a-f]+:\s*")          # (only with raw instruction
 TRAILER = re.compile(r"\s*//\s*[0-9A-Fa-f]+:.*$")   # "// 000000001A2C: <kernel+0x12c>" behind every instruction
 
 
+PC_RELATIVE_ADD = re.compile(r"^(s_addc?_u32\s+\S+\s+\S+\s+)-?(?:0x[0-9a-fA-F]+|\d+)$")
+
+
+def normalise(lines):
+    """One symbol's instruction lines without what depends on where the linker put it and its callees:
+    - the displacement of a PC-relative address (the call of a function that was not inlined): the immediate operands of the
+      s_add_u32 / s_addc_u32 pair that follows a s_getpc_b64 become `<pc-relative>`; a register operand there is left alone;
+    - the s_nop padding after the symbol's last instruction."""
+    out, pair = [], 0
+    for line in lines:
+        if line.startswith("s_getpc_b64"):
+            pair = 2
+        elif pair:
+            m = PC_RELATIVE_ADD.match(line)
+            pair = pair - 1 if m else 0
+            if m:
+                line = m.group(1) + "<pc-relative>"
+        out.append(line)
+    while out and out[-1].split()[0] == "s_nop":
+        out.pop()
+    return out
+
+
 def kernels_text(dev):
-    """{symbol: [instruction lines]} of the code object's .text"""
+    """{symbol: [instruction lines]} of the code object's .text, normalised"""
     out, cur = {}, None
     for line in tool("llvm-objdump", "-d", "--no-show-raw-insn", dev).splitlines():
         m = SYMBOL.match(line)
@@ -52,7 +78,7 @@ def kernels_text(dev):
             cur = out.setdefault(m.group(1), [])
         elif cur is not None and line.strip():
             cur.append(TRAILER.sub("", ADDRESS.sub("", line)).strip())
-    return out
+    return {name: normalise(lines) for name, lines in out.items()}
 
 
 def kernels_meta(dev):
