@@ -699,6 +699,37 @@ int ot_fluence_map(ot_ctx* ctx, const double* axes, const double* u_edges, int32
                    const int32_t* seg_count, int64_t n_rays, unsigned long long* counts, double* fluence,
                    unsigned long long* skipped, int32_t accumulate);
 
+/* Spot statistics and through-focus scans: the zeroth, first and second moments of the hit distribution of every monitor, on the
+ * monitor and on a stack of n_offsets virtual planes displaced along its normal, from one pass over the segments with no hit list
+ * and no image.  A CELL is a pair (monitor m, plane j): plane j of monitor m is the monitor moved by offsets[j] (host) along its
+ * own normal, the local x axis (column 0 of ot_monitor.M).  One list of offsets is shared by all monitors; duplicates are allowed
+ * and no order is required.
+ * The hit test is ot_monitor_record_many's with one change: once the local origin (ox, oy, oz) of the segment is formed, ox becomes
+ * ox - offsets[j].  The renormalised direction, dx == 0, |t| < 1e-9 || t < 0 || t > length and the rectangle test on Py, Pz are
+ * unchanged.  offsets[j] = 0 is the monitor itself.
+ * Coordinates of a hit at the local point P: y = P . a_y - c_y, z = P . a_z - c_z with axes[m] = a_y, a_z as for
+ * ot_monitor_image_many and centre[m] = c_y, c_z (host, 2 doubles a monitor): a centre near the spot keeps the variance of a spot
+ * far from the monitor's centre from cancelling in Wyy - Wy^2 / W.  The weight w of a hit is `intensity` (device) of its slot,
+ * addressed like src->base[f] in the source's precision; NULL: w = 1.
+ * counts: device, [n_monitors][n_offsets] int64, the hits of every cell.  sums: device, [n_monitors][n_offsets][6] double:
+ * W = sum w, Wy = sum w y, Wz = sum w z, Wyy = sum w y^2, Wzz = sum w z^2, Wyz = sum w y z.  All arithmetic is double, whatever
+ * the segments' precision (width 4 is widened exactly).  accumulate = 0 zeroes both first (also for n_segments = 0), 1 adds to
+ * what is there (the chunks of a streamed trace).
+ * Determinism: counts are exact, and the sums are BIT-IDENTICAL from run to run — no floating-point atomic takes part.  A wave
+ * sums a cell over its lanes by a butterfly, adds to a row of its own, the workgroup adds its waves in order, and the last
+ * workgroup to finish adds the workgroups' rows in ascending order: the result depends on the inputs, their layout and the grid
+ * (a function of n_segments) alone.
+ * Cell groups: a launch takes 256 cells of the list [m][j] (224 bytes of LDS a cell); longer lists are walked in groups inside the
+ * call, every group one pass over the segments.
+ * src, n_segments, seg_count, n_rays as for ot_monitor_record_many.
+ * OT_ERR_INVALID, nothing launched or zeroed: a NULL argument (intensity apart); n_monitors < 1; n_offsets < 1 or
+ * n_monitors * n_offsets > 2^20; axes, centre or offsets not finite; accumulate other than 0 / 1; everything
+ * ot_monitor_record_many refuses of src, n_segments, seg_count and n_rays. */
+int ot_monitor_spots_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* centre,
+                          const double* offsets, int32_t n_offsets, const ot_segment_source* src, const void* intensity,
+                          int64_t n_segments, const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* sums,
+                          int32_t accumulate);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled every trace launch is bracketed by hipEvents on the ctx stream. */
 int ot_timing_enable(ot_ctx* ctx, int enabled);

@@ -20,6 +20,7 @@ from .assemblies import (ComponentGroup, GlassSlab, CircleGlassSlab, MLA, MMA, M
                          ASphericParametricLens)
 from .monitors import Monitor
 from .fluence import FluenceMap
+from .spots import MonitorSpots
 from .table import OpticalTable
 from .scene import compile_scene, CompiledScene, SceneError
 from .adapter import install

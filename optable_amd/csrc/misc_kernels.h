@@ -176,9 +176,14 @@ __global__ void k_gen_counts(const int32_t* tree, const int32_t* ids, int64_t n,
 // Monitor.record
 // The plane and aperture test of one segment (monitor.py:183-193): the segment in the monitor's frame, direction renormalised
 // (ray_to_local_coordinates), the crossing of the plane x = 0 within the segment's length and the rectangle.  One definition
-// for every monitor kernel (k_mon_count / k_mon_emit, k_mon_wave): P = local hit point, t = distance.
-__device__ __forceinline__ bool mon_hit(const ot_monitor& mon, double sox, double soy, double soz, double sdx, double sdy, double sdz, double slen,
-                                        double& Px, double& Py, double& Pz, double& t) {
+// for every monitor kernel (k_mon_count / k_mon_emit, k_mon_wave, k_mon_spots): P = local hit point, t = distance.
+// In two halves, which mon_hit puts together: the segment in the monitor's frame (mon_local), and the crossing of the plane
+// x = 0 by a segment whose local origin has the x coordinate `ox` (mon_cross) — the monitor's own plane for ox = l.ox, the
+// plane moved by d along the monitor's normal (the local x axis, column 0 of M) for ox = l.ox - d (k_mon_spots).
+struct MonLocal {
+    double ox, oy, oz, dx, dy, dz;
+};
+__device__ __forceinline__ MonLocal mon_local(const ot_monitor& mon, double sox, double soy, double soz, double sdx, double sdy, double sdz) {
     const double rx = sox - mon.origin[0], ry = soy - mon.origin[1], rz = soz - mon.origin[2];
     const double* M = mon.M;
     const double ox = M[0] * rx + M[3] * ry + M[6] * rz, oy = M[1] * rx + M[4] * ry + M[7] * rz,
@@ -187,11 +192,20 @@ __device__ __forceinline__ bool mon_hit(const ot_monitor& mon, double sox, doubl
            dz = M[2] * sdx + M[5] * sdy + M[8] * sdz;
     const double inv = 1.0 / sqrt(dx * dx + dy * dy + dz * dz);  // ray_to_local_coordinates renormalises
     dx *= inv; dy *= inv; dz *= inv;
-    if (dx == 0.0) return false;
-    t = -ox / dx;
+    return {ox, oy, oz, dx, dy, dz};
+}
+__device__ __forceinline__ bool mon_cross(const ot_monitor& mon, const MonLocal& l, double ox, double slen, double& Px, double& Py, double& Pz,
+                                          double& t) {
+    if (l.dx == 0.0) return false;
+    t = -ox / l.dx;
     if (fabs(t) < 1e-9 || t < 0.0 || t > slen) return false;
-    Px = ox + t * dx; Py = oy + t * dy; Pz = oz + t * dz;
+    Px = ox + t * l.dx; Py = l.oy + t * l.dy; Pz = l.oz + t * l.dz;
     return fabs(Py) <= mon.half_width && fabs(Pz) <= mon.half_height;
+}
+__device__ __forceinline__ bool mon_hit(const ot_monitor& mon, double sox, double soy, double soz, double sdx, double sdy, double sdz, double slen,
+                                        double& Px, double& Py, double& Pz, double& t) {
+    const MonLocal l = mon_local(mon, sox, soy, soz, sdx, sdy, sdz);
+    return mon_cross(mon, l, l.ox, slen, Px, Py, Pz, t);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -924,6 +938,143 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_emit(const ot_monitor* __re
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Spot statistics (ot_monitor_spots_many): the moments of the hit distribution of every CELL (monitor m, plane j) — plane j of
+// monitor m is the monitor moved by offsets[j] along its normal, the local x axis — from one pass over the segments on
+// k_mon_count's partition and loads.  The hit test is mon_hit's with the local origin's x less offsets[j] (mon_cross).  A hit at
+// the local point P has y = P . a_y - c_y, z = P . a_z - c_z (axes[m] = a_y, a_z as in the image mode; centre[m] = c_y, c_z,
+// which keeps the variance of a spot far from the monitor's centre from cancelling) and the weight w = intensity[s], read once
+// per slot at its first hit (intensity NULL: 1).  A cell accumulates MON_SPOT_VALUES doubles: the count (an integer below 2^31,
+// exact in a double), W = sum w, Wy, Wz, Wyy, Wzz, Wyz.  All arithmetic is double.
+// NO FLOATING-POINT ATOMIC, and a fixed order of every sum: a wave reduces the seven values of a cell over its lanes by a butterfly
+// (wave_sum) — only where __ballot(hit) is not zero: in slot layout a wave holds one segment index of 64 rays and misses most
+// cells — and lanes 0..6 add the totals to the wave's OWN row of the cell in LDS, visit after visit in the order of the span; at
+// the end of the span the workgroup adds its four rows in wave order and writes partials[workgroup][cell][7]; the workgroup that
+// draws the last ticket (one atomic add on an int zeroed before the launch; nobody waits) sums the rows in ascending workgroup
+// order and adds the result to the outputs (accumulate) or stores it.  The result depends on (inputs, layout, grid) alone.
+// The hand-over of the partials is write-through stores (agent-scope relaxed atomic stores: no release fence, so no workgroup
+// writes the L2 back), every wave's wait for them, a barrier, and the ticket by one lane; the last workgroup takes ONE agent-scope
+// acquire before a barrier and reads them with plain loads.
+// LDS: MON_WAVES rows of 7 doubles a cell, 224 bytes; MON_SPOT_CELLS cells of one launch, 56 KB of the 64 KB a launch gets
+// without a function attribute.  Longer cell lists: one launch per MON_SPOT_CELLS cells of the list [m][j].
+// A launch of few cells gets MON_SPOT_LDS_MIN bytes all the same (four workgroups a CU still fit): the last workgroup reads the
+// partials through them, MON_SPOT_TILE_MIN rows at a time or more.
+static constexpr int MON_SPOT_CELLS = 256, MON_SPOT_VALUES = 7, MON_SPOT_LDS_MIN = 32768, MON_SPOT_TILE_MIN = 32;
+struct MonSpots {
+    const double* axes;        // [n_monitors][6]
+    const double* centre;      // [n_monitors][2]
+    const double* offsets;     // [n_off]
+    const uint8_t* intensity;  // addressed like the fields of MonSource; NULL: weight 1
+    double* partials;          // [gridDim.x][n_cells][7]
+    unsigned int* ticket;      // 0 before the launch
+    long long* counts;         // [n_monitors][n_off]
+    double* sums;              // [n_monitors][n_off][6]
+    int32_t n_off, cell0, n_cells, accumulate;  // the launch's cells: cell0 .. cell0 + n_cells of the list [m][j]
+    int32_t lds_doubles;                        // the launch's dynamic LDS, at least MON_WAVES * n_cells * 7 doubles
+};
+template <class V> __device__ __forceinline__ V wave_sum(V v) {  // every lane gets the sum, formed in one order
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__global__ __launch_bounds__(MON_THREADS) void k_mon_spots(const ot_monitor* __restrict__ mons, MonSource src, int64_t n, int32_t iters,
+                                                           const int32_t* __restrict__ seg_count, int64_t n_rays, MonSpots sp) {
+    extern __shared__ double spot_rows[];  // [MON_WAVES][n_cells][7]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int32_t nv = sp.n_cells * MON_SPOT_VALUES;
+    double* mine = spot_rows + wave * nv;
+    for (int32_t i = lane; i < nv; i += 64) mine[i] = 0.0;
+    __syncthreads();
+    const MonSpan span = mon_span(n, iters);
+    for (int32_t it = 0; span.has(it); ++it) {
+        const int64_t s = span.at(it) + threadIdx.x;
+        const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
+        if (!__ballot(g.valid)) continue;
+        double w = 1.0;
+        bool have_w = sp.intensity == nullptr;  // the intensity of a slot is read once, at its first hit
+        int32_t m = sp.cell0 / sp.n_off, j = sp.cell0 - m * sp.n_off;  // wave-uniform: monitor, axes and offsets come through scalar loads
+        for (int32_t k = 0; k < sp.n_cells; ++m, j = 0) {
+            const MonLocal l = mon_local(mons[m], g.ox, g.oy, g.oz, g.dx, g.dy, g.dz);
+            const double* a = sp.axes + 6 * m;
+            const double cy = sp.centre[2 * m], cz = sp.centre[2 * m + 1];
+            for (; j < sp.n_off && k < sp.n_cells; ++j, ++k) {
+                double Px, Py, Pz, t;
+                const bool hit = g.valid && mon_cross(mons[m], l, l.ox - sp.offsets[j], g.len, Px, Py, Pz, t);
+                const unsigned long long b = __ballot(hit);
+                if (!b) continue;
+                if (hit && !have_w) {
+                    w = mon_real(sp.intensity + mon_at(s, src.tile_stride, src.width), src.width);
+                    have_w = true;
+                }
+                double W = 0.0, Wy = 0.0, Wz = 0.0, Wyy = 0.0, Wzz = 0.0, Wyz = 0.0;
+                if (hit) {
+                    const double y = Px * a[0] + Py * a[1] + Pz * a[2] - cy, z = Px * a[3] + Py * a[4] + Pz * a[5] - cz;
+                    W = w, Wy = w * y, Wz = w * z;
+                    Wyy = Wy * y, Wzz = Wz * z, Wyz = Wy * z;
+                }
+                W = wave_sum(W), Wy = wave_sum(Wy), Wz = wave_sum(Wz), Wyy = wave_sum(Wyy), Wzz = wave_sum(Wzz), Wyz = wave_sum(Wyz);
+                const double v = lane == 0 ? (double)__popcll(b) : lane == 1 ? W : lane == 2 ? Wy : lane == 3 ? Wz : lane == 4 ? Wyy : lane == 5 ? Wzz : Wyz;
+                if (lane < MON_SPOT_VALUES) mine[k * MON_SPOT_VALUES + lane] += v;
+            }
+        }
+    }
+    __syncthreads();
+    double* row = sp.partials + (int64_t)blockIdx.x * nv;
+    for (int32_t i = threadIdx.x; i < nv; i += MON_THREADS)  // (write-through stores: no workgroup pays for a write-back of the L2)
+        __hip_atomic_store(&row[i], ((spot_rows[i] + spot_rows[nv + i]) + spot_rows[2 * nv + i]) + spot_rows[3 * nv + i], __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();  // the rows are read and the partials have arrived: word 0 of the rows now says whether this workgroup is the last
+    int32_t* last = reinterpret_cast<int32_t*>(spot_rows);
+    if (threadIdx.x == 0) {
+        const unsigned int drawn = __hip_atomic_fetch_add(sp.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *last = drawn == gridDim.x - 1;
+        if (*last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+    }
+    __syncthreads();
+    if (!*last) return;
+    // value i of the launch (cell i / 7, sum i % 7) belongs to thread i % MON_THREADS: at most seven a thread.  The rows are added
+    // in ascending workgroup order, one add after the other.  Few cells: the workgroups' rows lie back to back, so all threads copy
+    // `tile` rows at a time into LDS (every load of a tile in flight at once) and the owner adds them from there; many cells: a
+    // thread's own loads of a row are enough in flight, and it adds them straight from memory.
+    double sum[MON_SPOT_VALUES] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int32_t tile = sp.lds_doubles / nv;
+    if (tile >= MON_SPOT_TILE_MIN) {
+        for (uint32_t g0 = 0; g0 < gridDim.x; g0 += tile) {
+            const int32_t rows = (int32_t)min((uint32_t)tile, gridDim.x - g0);
+            __syncthreads();  // `last` and the tile before are read
+            for (int32_t e = threadIdx.x; e < rows * nv; e += MON_THREADS) spot_rows[e] = sp.partials[(int64_t)g0 * nv + e];
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < MON_SPOT_VALUES; ++q) {
+                const int32_t i = threadIdx.x + q * MON_THREADS;
+                if (i < nv)
+                    for (int32_t r = 0; r < rows; ++r) sum[q] += spot_rows[r * nv + i];
+            }
+        }
+    } else {
+        for (uint32_t grp = 0; grp < gridDim.x; ++grp) {
+#pragma unroll
+            for (int q = 0; q < MON_SPOT_VALUES; ++q) {
+                const int32_t i = threadIdx.x + q * MON_THREADS;
+                if (i < nv) sum[q] += sp.partials[(int64_t)grp * nv + i];
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < MON_SPOT_VALUES; ++q) {
+        const int32_t i = threadIdx.x + q * MON_THREADS;
+        if (i >= nv) continue;
+        const int64_t cell = sp.cell0 + i / MON_SPOT_VALUES;
+        const int32_t f = i % MON_SPOT_VALUES;
+        if (f == 0) sp.counts[cell] = (sp.accumulate ? sp.counts[cell] : 0) + (long long)sum[q];
+        else sp.sums[cell * 6 + f - 1] = sp.accumulate ? sp.sums[cell * 6 + f - 1] + sum[q] : sum[q];
     }
 }
 

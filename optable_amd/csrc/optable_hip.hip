@@ -1848,6 +1848,64 @@ int ot_fluence_map(ot_ctx* c, const double* axes, const double* u_edges, int32_t
     return 0;
 }
 
+// Spot statistics: k_mon_spots over the segments as they lie (misc_kernels.h), one launch per MON_SPOT_CELLS cells of the list
+// [monitor][offset] (optable_amd/engine.py spots_plan says the same), all on the partition of the LDS image passes: at most 1024
+// workgroups, four a CU, which bounds the partials (1024 rows of 7 doubles a cell: 14 MB for a full group) and the last
+// workgroup's loop over them.  One ticket per launch, zeroed together.
+int ot_monitor_spots_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* centre, const double* offsets,
+                          int32_t n_offsets, const ot_segment_source* src, const void* intensity, int64_t n, const int32_t* seg_count,
+                          int64_t n_rays, int64_t* counts, double* sums, int32_t accumulate) {
+    if (!c || !mons || !axes || !centre || !offsets || !src || !counts || !sums) return fail(OT_ERR_INVALID, "NULL argument");
+    if (n_monitors < 1) return fail(OT_ERR_INVALID, "n_monitors must be at least 1");
+    if (n_offsets < 1) return fail(OT_ERR_INVALID, "n_offsets must be at least 1");
+    const int64_t cells = (int64_t)n_monitors * n_offsets;
+    if (cells > (int64_t)1 << 20) return fail(OT_ERR_INVALID, "n_monitors * n_offsets exceeds 2^20 cells");
+    if (accumulate != 0 && accumulate != 1) return fail(OT_ERR_INVALID, "accumulate must be 0 or 1");
+    if (const int rc = check_source(src, n, seg_count, n_rays)) return rc;
+    for (int64_t k = 0; k < 6 * (int64_t)n_monitors; ++k)
+        if (!std::isfinite(axes[k])) return fail(OT_ERR_INVALID, "axes must be finite");
+    for (int64_t k = 0; k < 2 * (int64_t)n_monitors; ++k)
+        if (!std::isfinite(centre[k])) return fail(OT_ERR_INVALID, "centre must be finite");
+    for (int32_t k = 0; k < n_offsets; ++k)
+        if (!std::isfinite(offsets[k])) return fail(OT_ERR_INVALID, "offsets must be finite");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!accumulate) {
+        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * (size_t)cells, c->stream));
+        HIP_TRY(hipMemsetAsync(sums, 0, sizeof(double) * 6 * (size_t)cells, c->stream));
+    }
+    if (n == 0) return 0;
+    const SlotPartition sp = slot_partition(n, true);
+    const int64_t launches = (cells + MON_SPOT_CELLS - 1) / MON_SPOT_CELLS;
+    const int64_t most = std::min<int64_t>(cells, MON_SPOT_CELLS);
+    ot_monitor* table;
+    double *d_axes, *d_centre, *d_offsets, *partials;
+    unsigned int* tickets;
+    const auto carve = [&](void* base) {
+        Carve cv{(uint8_t*)base};
+        table = cv.take<ot_monitor>(n_monitors), d_axes = cv.take<double>((int64_t)n_monitors * 6), d_centre = cv.take<double>((int64_t)n_monitors * 2);
+        d_offsets = cv.take<double>(n_offsets), partials = cv.take<double>(sp.grid * most * MON_SPOT_VALUES), tickets = cv.take<unsigned int>(launches);
+        return cv.used;
+    };
+    if (c->mon.ensure(carve(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of monitor scratch failed");
+    carve(c->mon.p);
+    HIP_TRY(hipMemcpyAsync(table, mons, sizeof(ot_monitor) * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_axes, axes, sizeof(double) * 6 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_centre, centre, sizeof(double) * 2 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_offsets, offsets, sizeof(double) * (size_t)n_offsets, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(tickets, 0, sizeof(unsigned int) * (size_t)launches, c->stream));
+    MonSpots spots{d_axes, d_centre, d_offsets, (const uint8_t*)intensity, partials, tickets, (long long*)counts, sums, n_offsets, 0, 0, accumulate, 0};
+    // (the launches of a call share the partials: they run one after the other on the stream)
+    for (int64_t cell0 = 0; cell0 < cells; cell0 += MON_SPOT_CELLS, ++spots.ticket) {
+        spots.cell0 = (int32_t)cell0, spots.n_cells = (int32_t)std::min<int64_t>(MON_SPOT_CELLS, cells - cell0);
+        const size_t lds_bytes = std::max<size_t>(sizeof(double) * MON_WAVES * MON_SPOT_VALUES * (size_t)spots.n_cells, MON_SPOT_LDS_MIN);
+        spots.lds_doubles = (int32_t)(lds_bytes / sizeof(double));
+        hipLaunchKernelGGL(k_mon_spots, dim3((unsigned)sp.grid), dim3(MON_THREADS), lds_bytes, c->stream, table, mon_source(src), n, sp.iters, seg_count,
+                           n_rays, spots);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // How the detector-image calls (ot_monitor_image_many / _field_many / _beam_many / _wave_many) walk n_monitors monitors of nby x nbz
 // bins: `passes` launches of at most `per_pass` monitors each, as even as they come (8 monitors of 30 x 30: 4 + 4, not 6 + 2),
 // through LDS when a pass's bins fit the mode's `budget` (MON_IMG_LDS_BINS; MON_FIELD_LDS_BINS: 8 monitors go 3 + 3 + 2;

@@ -169,6 +169,22 @@ def fluence_plan(nu, nv):
     return {"path": "lds" if nu * nv <= IMAGE_LDS_BINS else "global"}
 
 
+# -- spot statistics (ot_monitor_spots_many) --------------------------------------------------------------------------------
+SPOT_CELLS = 256          # misc_kernels.h MON_SPOT_CELLS: cells (monitor, plane) of one launch, 224 bytes of LDS each
+SPOT_MAX_CELLS = 1 << 20  # n_monitors * n_offsets of one call
+
+
+def spots_plan(n_monitors, n_offsets):
+    """How ot_monitor_spots_many walks the cells (monitor m, plane j) of `n_monitors` monitors x `n_offsets` planes (optable_hip.hip
+    ot_monitor_spots_many, the same rule): the launches as (first cell, cells) over the list [m][j], SPOT_CELLS cells at a time —
+    every launch one pass over the segments."""
+    n_monitors, n_offsets = int(n_monitors), int(n_offsets)
+    cells = n_monitors * n_offsets
+    if n_monitors < 1 or n_offsets < 1 or cells > SPOT_MAX_CELLS:
+        raise ValueError(f"no spot statistics of {n_monitors} monitors x {n_offsets} planes")
+    return [(first, min(SPOT_CELLS, cells - first)) for first in range(0, cells, SPOT_CELLS)]
+
+
 # -- what the private halves of monitor_*_many and fluence_map share: arguments in, outputs out -------------------------------
 def _doubles(array):
     return array.ctypes.data_as(C.POINTER(C.c_double))
@@ -890,6 +906,41 @@ class Engine:
         abi.check(self.lib.ot_fluence_map(self._ctx, _doubles(axes), _doubles(u_edges), nu, _doubles(v_edges), nv, float(depth[0]), float(depth[1]),
                                           C.byref(src), segs.field("intensity").data_ptr() if weighted else None, n_segments, _address(count),
                                           n_rays, *(t.data_ptr() for t in outs), 0 if into is None else 1), self.lib)
+        return outs
+
+    def monitor_spots_many(self, monitor_structs, axes, centre, offsets, segs: SegmentBatch, weighted=True, into=None):
+        """Spot statistics of a list of monitors over a SegmentBatch read as it lies (ot_monitor_spots_many): the moments of the
+        hits of every monitor on itself and on the planes displaced by `offsets` (numpy, J) along its normal.  axes: [M, 6] doubles
+        (a_y, a_z per monitor); centre: [M, 2] doubles (c_y, c_z, subtracted from every hit's coordinates).  weighted: every hit
+        weighs its segment's intensity; False: 1.  Returns (counts, sums): int64 [M, J] and float64 [M, J, 6] (W, Wy, Wz, Wyy,
+        Wzz, Wyz) device tensors, zeroed by the call — or `into`, such a pair from an earlier call, with this call's hits added
+        to it.  The sums are the same bits every run."""
+        with self.lock:
+            return self._monitor_spots_many(list(monitor_structs), axes, centre, offsets, segs, weighted, into)
+
+    def _monitor_spots_many(self, mons, axes, centre, offsets, segs, weighted, into):
+        dev, M = segs.device, len(mons)
+        axes, centre = np.ascontiguousarray(axes, dtype=np.float64), np.ascontiguousarray(centre, dtype=np.float64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.float64)
+        if axes.shape != (M, 6) or centre.shape != (M, 2) or offsets.ndim != 1:
+            raise ValueError(f"axes must be [{M}, 6], centre [{M}, 2] and offsets one-dimensional")
+        J = len(offsets)
+        if M:
+            spots_plan(M, J)
+        specs = ((torch.int64, (M, J)), (torch.float64, (M, J, 6)))
+        if into is None:
+            outs = tuple(torch.zeros(sh, dtype=dt, device=dev) for dt, sh in specs)  # (zeros: the library is not called for nothing)
+        else:
+            outs = tuple(into)
+            if len(outs) != 2 or any(tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type
+                                     for t, (dt, sh) in zip(outs, specs)):
+                raise ValueError(f"into: contiguous int64 counts of shape [{M}, {J}] and float64 sums of shape [{M}, {J}, 6] on {dev}")
+        src, n_segments, count, n_rays = segment_source(segs)
+        if M == 0 or n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
+            return outs
+        abi.check(self.lib.ot_monitor_spots_many(self._ctx, (abi.OtMonitor * M)(*mons), M, _doubles(axes), _doubles(centre), _doubles(offsets), J,
+                                                 C.byref(src), segs.field("intensity").data_ptr() if weighted else None, n_segments, _address(count),
+                                                 n_rays, *(t.data_ptr() for t in outs), 0 if into is None else 1), self.lib)
         return outs
 
     def monitor_field_many(self, monitor_structs, axes, edges, bins, segs: SegmentBatch, wavelength, amplitude_mode=0, into=None):

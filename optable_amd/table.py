@@ -313,6 +313,44 @@ class OpticalTable:
             return into
         return FluenceMap(view, roi, weight, counts, fluence, skipped, u_edges, v_edges)
 
+    def spots_all(self, segs, offsets=(0.0,), monitors=None, weight="intensity", centre=None, into=None):
+        """Every monitor of the table (or those given) as SPOT STATISTICS: one `MonitorSpots` per monitor, in their order — the
+        count, the power and the first and second moments of the hits of `record_all`, on the monitor and on every plane displaced
+        by one of `offsets` along its normal (a through-focus scan from one trace), summed on the device in the pass that finds the
+        hits, with no hit list and no image (ot_monitor_spots_many).  A plane is tested as a monitor of the same size built at
+        the displaced pose would be.  The coordinates are the images': the local hit point on the monitor's lab tangents, less
+        `centre`.  weight: "intensity" or "none" (every hit weighs 1).  centre: None, one (y, z) for all monitors or one per
+        monitor — a point near the spot, which keeps a small spot far from the monitor's centre from losing its variance to
+        cancellation; `MonitorSpots.centroid()` adds it back.  Counts are exact and the sums the same bits every run.  `into`: the
+        list an earlier call with the same monitors, offsets, weight and centre returned; this call's hits are added to it (the
+        chunks of a streamed trace)."""
+        from .spots import WEIGHTS, MonitorSpots, spot_centres, spot_offsets
+
+        if not isinstance(weight, str) or weight not in WEIGHTS:
+            raise ValueError(f'weight must be "intensity" or "none", not {weight!r}')
+        monitors = list(self.monitors if monitors is None else monitors)
+        offsets, centres = spot_offsets(offsets), spot_centres(centre, len(monitors))
+        stack = None
+        if into is not None:
+            into = list(into)
+            if len(into) != len(monitors) or any(not isinstance(sp, MonitorSpots) or sp.monitor is not m or sp.weight != weight or sp.centre != tuple(c)
+                                                 or not np.array_equal(sp.offsets, offsets) for sp, m, c in zip(into, monitors, centres)):
+                raise ValueError("into: the list an earlier spots_all returned for the same monitors, offsets, weight and centre")
+            if any(sp._stack is None or sp._stack[0] is not into[0]._stack[0] or sp._stack[-1] != k or len(sp._stack[0]) != len(into) for k, sp in enumerate(into)):
+                raise ValueError("into: the whole list of one earlier call, in its order")
+            if not monitors:
+                return into
+            stack = into[0]._stack[:-1]
+        axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in monitors], dtype=float).reshape(len(monitors), 6)
+        counts, sums = _engine().monitor_spots_many([monitor_struct(m) for m in monitors], axes, centres, offsets, segs, weighted=weight == "intensity", into=stack)
+        if into is None:
+            into = [MonitorSpots(m, offsets, counts[k], sums[k], weight, centres[k], stack=(counts, sums, k)) for k, m in enumerate(monitors)]
+        return into
+
+    def spots_batch(self, monitor, segs, offsets=(0.0,), weight="intensity", centre=None):
+        """One monitor as spot statistics (`spots_all` for it alone): a `MonitorSpots`."""
+        return self.spots_all(segs, offsets=offsets, monitors=[monitor], weight=weight, centre=centre)[0]
+
     def field_all(self, segs, wavelength=0.0, bins=30, monitors=None, into=None, amplitude="sqrt"):
         """Every monitor of the table (or those given) as a COHERENT image: one `MonitorField` per monitor, in their order — per
         bin of `image_all`'s images the count of hits and the complex sum of a exp(i phi) over them, summed on the device in the
