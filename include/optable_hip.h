@@ -730,6 +730,51 @@ int ot_monitor_spots_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitor
                           int64_t n_segments, const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* sums,
                           int32_t accumulate);
 
+/* Wavefront error: the hits of every monitor reduced to the moments of their optical path difference over a unit pupil, from one
+ * pass over the segments with no hit list — what a least-squares fit of Zernike (or any other) polynomials up to radial order 4
+ * and the rms wavefront error need.  One cell per monitor; mons, axes, src, n_segments, seg_count, n_rays and accumulate as for
+ * ot_monitor_spots_many, and there are no plane offsets.
+ * The hit test is ot_monitor_record_many's, unchanged.  A hit of slot s on monitor m gives the local hit point P, the distance t
+ * and the renormalised local direction d.  With n = n_index[s] and L = t n + pathlength[s] (Ray.pathlength(t), as
+ * ot_monitor_field_many forms it) the optical path W is taken against an ideal wave: reference_kind is one int for the call,
+ * reference[m] three host doubles per monitor.
+ *   reference_kind 0, a spherical wave about a focus F: reference[m] = F_loc = M^T (F - origin), the focus in the monitor's frame.
+ *     W = L + n ((F_loc - P) . d): the optical path at the foot of the perpendicular from F onto the ray.  A perfect wave that
+ *     converges on F, or diverges from it, has one W for every ray.  This is the reference sphere AT INFINITY: against a sphere of
+ *     the finite radius R_s about F, W differs by n e^2 / (2 R_s) to leading order, e the ray's miss distance at F — the limit
+ *     in which the two agree is e^2 / R_s far below the error of interest.
+ *   reference_kind 1, a plane wave along the unit vector u: reference[m] = u_loc = M^T u.  W = L - n (P . u_loc).
+ * Pupil coordinates: coordinates is one int for the call, pupil[m] = (c_y, c_z, R), R > 0, host.
+ *   coordinates 1, position: (p, q) = ((y - c_y) / R, (z - c_z) / R) with y = P . a_y, z = P . a_z (axes[m] = a_y, a_z, the
+ *     images' coordinates).
+ *   coordinates 0, direction: (p, q) = ((ty - c_y) / R, (tz - c_z) / R) with ty = D . a_y, tz = D . a_z of the segment's
+ *     direction D as it is stored (MonitorHits.tYList / tZList, as ot_monitor_wave_many forms them).
+ * A hit is INSIDE the pupil when p^2 + q^2 <= 1 and W, p and q are finite; every other hit is tallied as outside and adds to no
+ * sum.  The weight w of a hit is `intensity` (device, double, addressed like src->base[f]) of its slot; NULL: w = 1.
+ * With W' = W - piston[m] (host, one double a monitor; near the mean of W it keeps Q from cancelling) monitor m accumulates 61
+ * sums, sums[m][0 .. 60], in this order:
+ *   S[a, b] = sum w p^a q^b,    a + b <= 8: 45 values, (a, b) at g (g + 1) / 2 + b with g = a + b
+ *   T[a, b] = sum w W' p^a q^b, a + b <= 4: 15 values, (a, b) at 45 + g (g + 1) / 2 + b
+ *   Q       = sum w W'^2:                     1 value, at 60
+ * (a term is (w p^a) q^b, ((w W') p^a) q^b, (w W') W', the powers by repeated multiplication) and counts[m] = (inside, outside),
+ * int64.  Both are device arrays; accumulate = 0 zeroes them first (also for n_segments = 0), 1 adds to what is there.  All
+ * arithmetic is double, and the segments must be double (src->width 8): a path length in single precision is a hundredth of a wave
+ * wrong at table scale.  n_index, pathlength: device, double, addressed like src->base[f].
+ * Determinism: as ot_monitor_spots_many — counts exact, sums bit-identical from run to run, no floating-point atomic; the result
+ * is a function of the inputs, their layout and the grid alone.
+ * Monitor groups: a launch takes OT_WAVEFRONT_MONITORS monitors (4 waves x 63 doubles of LDS each); longer lists are walked in
+ * groups inside the call, every group one pass over the segments.
+ * OT_ERR_INVALID, nothing launched or zeroed: a NULL argument (intensity apart); n_monitors < 1 or > 2^20; reference_kind or
+ * coordinates other than 0 / 1; axes, reference, pupil or piston not finite; R <= 0; u_loc = 0 (reference_kind 1); src->width
+ * other than 8; accumulate other than 0 / 1; everything ot_monitor_record_many refuses of src, n_segments, seg_count, n_rays. */
+#define OT_WAVEFRONT_MONITORS 28
+#define OT_WAVEFRONT_SUMS 61
+int ot_monitor_wavefront_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitors, const double* axes, int32_t reference_kind,
+                              const double* reference, int32_t coordinates, const double* pupil, const double* piston,
+                              const ot_segment_source* src, const void* intensity, const void* n_index, const void* pathlength,
+                              int64_t n_segments, const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* sums,
+                              int32_t accumulate);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled every trace launch is bracketed by hipEvents on the ctx stream. */
 int ot_timing_enable(ot_ctx* ctx, int enabled);

@@ -21,6 +21,7 @@ from .assemblies import (ComponentGroup, GlassSlab, CircleGlassSlab, MLA, MMA, M
 from .monitors import Monitor
 from .fluence import FluenceMap
 from .spots import MonitorSpots
+from .wavefront import MonitorWavefront
 from .table import OpticalTable
 from .scene import compile_scene, CompiledScene, SceneError
 from .adapter import install

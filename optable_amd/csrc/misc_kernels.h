@@ -968,28 +968,123 @@ struct MonSpots {
     const double* centre;      // [n_monitors][2]
     const double* offsets;     // [n_off]
     const uint8_t* intensity;  // addressed like the fields of MonSource; NULL: weight 1
-    double* partials;          // [gridDim.x][n_cells][7]
+    double* partials;          // [gridDim.x][n_cells][values]
     unsigned int* ticket;      // 0 before the launch
-    long long* counts;         // [n_monitors][n_off]
-    double* sums;              // [n_monitors][n_off][6]
+    long long* counts;         // [n_monitors][n_off]; the wavefront mode: [n_monitors][2]
+    double* sums;              // [n_monitors][n_off][6]; the wavefront mode: [n_monitors][61]
     int32_t n_off, cell0, n_cells, accumulate;  // the launch's cells: cell0 .. cell0 + n_cells of the list [m][j]
-    int32_t lds_doubles;                        // the launch's dynamic LDS, at least MON_WAVES * n_cells * 7 doubles
+    int32_t lds_doubles;                        // the launch's dynamic LDS, at least MON_WAVES * n_cells * values doubles
+    // the wavefront mode (below): values = MON_WAVEFRONT_VALUES, a cell is a monitor (n_off = 1; centre and offsets are not read)
+    int32_t values;                      // MON_SPOT_VALUES or MON_WAVEFRONT_VALUES doubles a cell
+    int32_t kind, coordinates;           // reference_kind and coordinates of ot_monitor_wavefront_many
+    const double *reference, *pupil, *piston;  // [n_monitors][3] F_loc or u_loc, [n_monitors][3] (c_y, c_z, R), [n_monitors]
+    const uint8_t *n_index, *pathlength;  // double, addressed like the fields of MonSource
 };
 template <class V> __device__ __forceinline__ V wave_sum(V v) {  // every lane gets the sum, formed in one order
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+// The wavefront mode of k_mon_spots (ot_monitor_wavefront_many): the same partition, loads, rows, partials, ticket and last
+// workgroup, with a cell of MON_WAVEFRONT_VALUES = 63 doubles per monitor — the hits inside the pupil, the hits outside, and the
+// 61 sums S[a, b] (a + b <= 8), T[a, b] (a + b <= 4), Q of the header, in its order.  A hit (mon_hit, unchanged) of slot s:
+//   L = t n[s] + pathlength[s] (as k_mon_field),  W = L + n ((F_loc - P) . d) (kind 0)  or  L - n (P . u_loc) (kind 1),
+//   (p, q) = ((u - c_y) / R, (v - c_z) / R) with (u, v) = (P . a_y, P . a_z) (coordinates 1) or (g.d . a_y, g.d . a_z) as
+//   k_mon_wave forms ty, tz (0);  inside: p^2 + q^2 <= 1 and W finite;  W' = W - piston.
+// n, pathlength and intensity of a slot are read once, at its first hit.  A lane that is not inside carries w = W' = p = q = 0 into
+// the butterflies (a zero weight alone would leave NaN 0 = NaN in the sums).  The powers p^0..p^8, q^0..q^8 are two register tables
+// indexed by the constants of a fully unrolled body; term (a, b) is (w p^a) q^b, ((w W') p^a) q^b, (w W') W'.  Every total goes
+// through wave_sum, lane 2 + i keeps total i, and lanes 0..62 add their value to the wave's row: the order of every sum is that of
+// the spot statistics.  Where no lane of the wave is inside the pupil the 61 butterflies are skipped (their totals are zero).
+// LDS: MON_WAVES rows of 63 doubles a monitor, 2,016 bytes; MON_WAVEFRONT_CELLS = 28 monitors a launch — 56,448 bytes, and
+// 28 x 63 = 1,764 values, within the 7 x MON_THREADS the last workgroup's threads own.
+static constexpr int MON_WAVEFRONT_CELLS = 28, MON_WAVEFRONT_VALUES = 63, MON_WAVEFRONT_SUMS = 61;
+static_assert(MON_WAVEFRONT_CELLS * MON_WAVEFRONT_VALUES <= MON_SPOT_CELLS * MON_SPOT_VALUES, "a launch's values: seven a thread of the last workgroup");
+__device__ __forceinline__ void mon_wavefront_visit(const ot_monitor* __restrict__ mons, const MonSource& src, const MonSeg& g, int64_t s,
+                                                    const MonSpots& sp, double* mine, int lane) {
+    double w = 1.0, n_index = 0.0, pl = 0.0;
+    bool have = false;
+    for (int32_t k = 0; k < sp.n_cells; ++k) {
+        const int32_t m = sp.cell0 + k;  // wave-uniform: monitor, axes, reference, pupil and piston come through scalar loads
+        double Px, Py, Pz, t;
+        const MonLocal l = mon_local(mons[m], g.ox, g.oy, g.oz, g.dx, g.dy, g.dz);
+        const bool hit = g.valid && mon_cross(mons[m], l, l.ox, g.len, Px, Py, Pz, t);
+        if (!__ballot(hit)) continue;
+        if (hit && !have) {
+            const int64_t at = mon_at(s, src.tile_stride, 8);
+            if (sp.intensity) w = *reinterpret_cast<const double*>(sp.intensity + at);
+            n_index = *reinterpret_cast<const double*>(sp.n_index + at);
+            pl = *reinterpret_cast<const double*>(sp.pathlength + at);
+            have = true;
+        }
+        const double* a = sp.axes + 6 * m;
+        const double *f = sp.reference + 3 * m, *c = sp.pupil + 3 * m;
+        double wi = 0.0, Wp = 0.0, p = 0.0, q = 0.0;
+        bool inside = false;
+        if (hit) {
+            const double L = t * n_index + pl;
+            const double Wv = sp.kind == 0 ? L + n_index * ((f[0] - Px) * l.dx + (f[1] - Py) * l.dy + (f[2] - Pz) * l.dz)
+                                           : L - n_index * (Px * f[0] + Py * f[1] + Pz * f[2]);
+            const double u = sp.coordinates ? Px * a[0] + Py * a[1] + Pz * a[2] : g.dx * a[0] + g.dy * a[1] + g.dz * a[2];
+            const double v = sp.coordinates ? Px * a[3] + Py * a[4] + Pz * a[5] : g.dx * a[3] + g.dy * a[4] + g.dz * a[5];
+            const double pp = (u - c[0]) / c[2], qq = (v - c[1]) / c[2];
+            inside = pp * pp + qq * qq <= 1.0 && fabs(Wv) < HUGE_VAL;  // (a NaN fails both)
+            if (inside) wi = w, Wp = Wv - sp.piston[m], p = pp, q = qq;
+        }
+        const unsigned long long bi = __ballot(inside), bo = __ballot(hit && !inside);
+        double v = lane == 0 ? (double)__popcll(bi) : lane == 1 ? (double)__popcll(bo) : 0.0;
+        if (bi) {
+            double pa[9], qa[9];
+            pa[0] = qa[0] = 1.0;
+#pragma unroll
+            for (int e = 1; e <= 8; ++e) pa[e] = pa[e - 1] * p, qa[e] = qa[e - 1] * q;
+            const double wW = wi * Wp;
+#pragma unroll
+            for (int a = 0; a <= 8; ++a) {  // (by a, so that one w p^a is alive at a time; the place of (a, b) is the header's)
+                const double wa = wi * pa[a];
+#pragma unroll
+                for (int b = 0; a + b <= 8; ++b) {
+                    const double total = wave_sum(wa * qa[b]);
+                    if (lane == 2 + (a + b) * (a + b + 1) / 2 + b) v = total;
+                    asm volatile("" : "+v"(v));         // v takes the total here, not in a chain of selects behind 61 live totals,
+                    __builtin_amdgcn_sched_barrier(0);  // and one butterfly at a time: interleaved, their operands take hundreds of registers
+                }
+            }
+#pragma unroll
+            for (int a = 0; a <= 4; ++a) {
+                const double wa = wW * pa[a];
+#pragma unroll
+                for (int b = 0; a + b <= 4; ++b) {
+                    const double total = wave_sum(wa * qa[b]);
+                    if (lane == 2 + 45 + (a + b) * (a + b + 1) / 2 + b) v = total;
+                    asm volatile("" : "+v"(v));
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            const double total = wave_sum(wW * Wp);
+            if (lane == 2 + 45 + 15) v = total;
+        }
+        if (lane < MON_WAVEFRONT_VALUES) mine[k * MON_WAVEFRONT_VALUES + lane] += v;
+    }
+}
 __global__ __launch_bounds__(MON_THREADS) void k_mon_spots(const ot_monitor* __restrict__ mons, MonSource src, int64_t n, int32_t iters,
                                                            const int32_t* __restrict__ seg_count, int64_t n_rays, MonSpots sp) {
-    extern __shared__ double spot_rows[];  // [MON_WAVES][n_cells][7]
+    extern __shared__ double spot_rows[];  // [MON_WAVES][n_cells][values]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int32_t nv = sp.n_cells * MON_SPOT_VALUES;
+    const int32_t nv = sp.n_cells * sp.values;
     double* mine = spot_rows + wave * nv;
     for (int32_t i = lane; i < nv; i += 64) mine[i] = 0.0;
     __syncthreads();
     const MonSpan span = mon_span(n, iters);
-    for (int32_t it = 0; span.has(it); ++it) {
+    // the wavefront mode walks the span in a loop of its own: one loop for both keeps the scalars of either alive through the
+    // other, and the spot statistics' test of every slot against every plane pays for the spills
+    const bool wavefront = sp.values == MON_WAVEFRONT_VALUES;  // (uniform for the launch)
+    for (int32_t it = 0; wavefront && span.has(it); ++it) {
+        const int64_t s = span.at(it) + threadIdx.x;
+        const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
+        if (__ballot(g.valid)) mon_wavefront_visit(mons, src, g, s, sp, mine, lane);
+    }
+    for (int32_t it = 0; !wavefront && span.has(it); ++it) {
         const int64_t s = span.at(it) + threadIdx.x;
         const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
         if (!__ballot(g.valid)) continue;
@@ -1071,10 +1166,12 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_spots(const ot_monitor* __r
     for (int q = 0; q < MON_SPOT_VALUES; ++q) {
         const int32_t i = threadIdx.x + q * MON_THREADS;
         if (i >= nv) continue;
-        const int64_t cell = sp.cell0 + i / MON_SPOT_VALUES;
-        const int32_t f = i % MON_SPOT_VALUES;
-        if (f == 0) sp.counts[cell] = (sp.accumulate ? sp.counts[cell] : 0) + (long long)sum[q];
-        else sp.sums[cell * 6 + f - 1] = sp.accumulate ? sp.sums[cell * 6 + f - 1] + sum[q] : sum[q];
+        // a cell's values: its counts (one; inside and outside in the wavefront mode), then its sums
+        const int32_t nc = sp.values == MON_SPOT_VALUES ? 1 : 2, ns = sp.values - nc;
+        const int64_t cell = sp.cell0 + i / sp.values;
+        const int32_t f = i % sp.values;
+        if (f < nc) sp.counts[cell * nc + f] = (sp.accumulate ? sp.counts[cell * nc + f] : 0) + (long long)sum[q];
+        else sp.sums[cell * ns + f - nc] = sp.accumulate ? sp.sums[cell * ns + f - nc] + sum[q] : sum[q];
     }
 }
 

@@ -1893,11 +1893,78 @@ int ot_monitor_spots_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors,
     HIP_TRY(hipMemcpyAsync(d_centre, centre, sizeof(double) * 2 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_offsets, offsets, sizeof(double) * (size_t)n_offsets, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(tickets, 0, sizeof(unsigned int) * (size_t)launches, c->stream));
-    MonSpots spots{d_axes, d_centre, d_offsets, (const uint8_t*)intensity, partials, tickets, (long long*)counts, sums, n_offsets, 0, 0, accumulate, 0};
+    MonSpots spots{d_axes, d_centre, d_offsets, (const uint8_t*)intensity, partials, tickets, (long long*)counts, sums, n_offsets, 0, 0, accumulate, 0,
+                   MON_SPOT_VALUES, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
     // (the launches of a call share the partials: they run one after the other on the stream)
     for (int64_t cell0 = 0; cell0 < cells; cell0 += MON_SPOT_CELLS, ++spots.ticket) {
         spots.cell0 = (int32_t)cell0, spots.n_cells = (int32_t)std::min<int64_t>(MON_SPOT_CELLS, cells - cell0);
         const size_t lds_bytes = std::max<size_t>(sizeof(double) * MON_WAVES * MON_SPOT_VALUES * (size_t)spots.n_cells, MON_SPOT_LDS_MIN);
+        spots.lds_doubles = (int32_t)(lds_bytes / sizeof(double));
+        hipLaunchKernelGGL(k_mon_spots, dim3((unsigned)sp.grid), dim3(MON_THREADS), lds_bytes, c->stream, table, mon_source(src), n, sp.iters, seg_count,
+                           n_rays, spots);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Wavefront error: k_mon_spots in its wavefront mode (misc_kernels.h), a cell per monitor of 63 doubles, one launch per
+// MON_WAVEFRONT_CELLS monitors (optable_amd/engine.py wavefront_plan says the same) on the spot statistics' partition: the partials
+// are 1024 rows of 28 x 63 doubles at most, what a full group of spots takes.
+int ot_monitor_wavefront_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, int32_t reference_kind,
+                              const double* reference, int32_t coordinates, const double* pupil, const double* piston,
+                              const ot_segment_source* src, const void* intensity, const void* n_index, const void* pathlength, int64_t n,
+                              const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* sums, int32_t accumulate) {
+    static_assert(MON_WAVEFRONT_CELLS == OT_WAVEFRONT_MONITORS && MON_WAVEFRONT_SUMS == OT_WAVEFRONT_SUMS, "the header's constants");
+    if (!c || !mons || !axes || !reference || !pupil || !piston || !src || !n_index || !pathlength || !counts || !sums)
+        return fail(OT_ERR_INVALID, "NULL argument");
+    if (n_monitors < 1 || n_monitors > 1 << 20) return fail(OT_ERR_INVALID, "n_monitors must be 1 .. 2^20");
+    if (reference_kind != 0 && reference_kind != 1) return fail(OT_ERR_INVALID, "reference_kind must be 0 (focus) or 1 (direction)");
+    if (coordinates != 0 && coordinates != 1) return fail(OT_ERR_INVALID, "coordinates must be 0 (direction) or 1 (position)");
+    if (accumulate != 0 && accumulate != 1) return fail(OT_ERR_INVALID, "accumulate must be 0 or 1");
+    if (const int rc = check_source(src, n, seg_count, n_rays)) return rc;
+    if (src->width != 8) return fail(OT_ERR_INVALID, "a wavefront needs double-precision segments: width must be 8");
+    for (int64_t k = 0; k < 6 * (int64_t)n_monitors; ++k)
+        if (!std::isfinite(axes[k])) return fail(OT_ERR_INVALID, "axes must be finite");
+    for (int64_t m = 0; m < n_monitors; ++m) {
+        const double *r = reference + 3 * m, *p = pupil + 3 * m;
+        if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2])) return fail(OT_ERR_INVALID, "reference must be finite");
+        if (reference_kind == 1 && r[0] == 0.0 && r[1] == 0.0 && r[2] == 0.0) return fail(OT_ERR_INVALID, "the direction of a plane wave must not be zero");
+        if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) return fail(OT_ERR_INVALID, "pupil must be finite");
+        if (!(p[2] > 0.0)) return fail(OT_ERR_INVALID, "the pupil's radius must be positive");
+        if (!std::isfinite(piston[m])) return fail(OT_ERR_INVALID, "piston must be finite");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    if (!accumulate) {
+        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * 2 * (size_t)n_monitors, c->stream));
+        HIP_TRY(hipMemsetAsync(sums, 0, sizeof(double) * MON_WAVEFRONT_SUMS * (size_t)n_monitors, c->stream));
+    }
+    if (n == 0) return 0;
+    const SlotPartition sp = slot_partition(n, true);
+    const int64_t launches = ((int64_t)n_monitors + MON_WAVEFRONT_CELLS - 1) / MON_WAVEFRONT_CELLS;
+    const int64_t most = std::min<int64_t>(n_monitors, MON_WAVEFRONT_CELLS);
+    ot_monitor* table;
+    double *d_axes, *d_reference, *d_pupil, *d_piston, *partials;
+    unsigned int* tickets;
+    const auto carve = [&](void* base) {
+        Carve cv{(uint8_t*)base};
+        table = cv.take<ot_monitor>(n_monitors), d_axes = cv.take<double>((int64_t)n_monitors * 6), d_reference = cv.take<double>((int64_t)n_monitors * 3);
+        d_pupil = cv.take<double>((int64_t)n_monitors * 3), d_piston = cv.take<double>(n_monitors);
+        partials = cv.take<double>(sp.grid * most * MON_WAVEFRONT_VALUES), tickets = cv.take<unsigned int>(launches);
+        return cv.used;
+    };
+    if (c->mon.ensure(carve(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of monitor scratch failed");
+    carve(c->mon.p);
+    HIP_TRY(hipMemcpyAsync(table, mons, sizeof(ot_monitor) * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_axes, axes, sizeof(double) * 6 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_reference, reference, sizeof(double) * 3 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_pupil, pupil, sizeof(double) * 3 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_piston, piston, sizeof(double) * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(tickets, 0, sizeof(unsigned int) * (size_t)launches, c->stream));
+    MonSpots spots{d_axes, nullptr, nullptr, (const uint8_t*)intensity, partials, tickets, (long long*)counts, sums, 1, 0, 0, accumulate, 0,
+                   MON_WAVEFRONT_VALUES, reference_kind, coordinates, d_reference, d_pupil, d_piston, (const uint8_t*)n_index, (const uint8_t*)pathlength};
+    for (int64_t cell0 = 0; cell0 < n_monitors; cell0 += MON_WAVEFRONT_CELLS, ++spots.ticket) {
+        spots.cell0 = (int32_t)cell0, spots.n_cells = (int32_t)std::min<int64_t>(MON_WAVEFRONT_CELLS, n_monitors - cell0);
+        const size_t lds_bytes = std::max<size_t>(sizeof(double) * MON_WAVES * MON_WAVEFRONT_VALUES * (size_t)spots.n_cells, MON_SPOT_LDS_MIN);
         spots.lds_doubles = (int32_t)(lds_bytes / sizeof(double));
         hipLaunchKernelGGL(k_mon_spots, dim3((unsigned)sp.grid), dim3(MON_THREADS), lds_bytes, c->stream, table, mon_source(src), n, sp.iters, seg_count,
                            n_rays, spots);

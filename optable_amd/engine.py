@@ -185,6 +185,21 @@ def spots_plan(n_monitors, n_offsets):
     return [(first, min(SPOT_CELLS, cells - first)) for first in range(0, cells, SPOT_CELLS)]
 
 
+# -- wavefront error (ot_monitor_wavefront_many) -----------------------------------------------------------------------------
+WAVEFRONT_MONITORS = 28           # optable_hip.h OT_WAVEFRONT_MONITORS: monitors of one launch, 4 waves x 63 doubles of LDS each
+WAVEFRONT_SUMS = 61               # optable_hip.h OT_WAVEFRONT_SUMS: S (45), T (15), Q
+WAVEFRONT_MAX_MONITORS = 1 << 20  # n_monitors of one call
+
+
+def wavefront_plan(n_monitors):
+    """How ot_monitor_wavefront_many walks `n_monitors` monitors (optable_hip.hip ot_monitor_wavefront_many, the same rule): the
+    launches as (first monitor, monitors), WAVEFRONT_MONITORS at a time — every launch one pass over the segments."""
+    n_monitors = int(n_monitors)
+    if n_monitors < 1 or n_monitors > WAVEFRONT_MAX_MONITORS:
+        raise ValueError(f"no wavefront of {n_monitors} monitors")
+    return [(first, min(WAVEFRONT_MONITORS, n_monitors - first)) for first in range(0, n_monitors, WAVEFRONT_MONITORS)]
+
+
 # -- what the private halves of monitor_*_many and fluence_map share: arguments in, outputs out -------------------------------
 def _doubles(array):
     return array.ctypes.data_as(C.POINTER(C.c_double))
@@ -941,6 +956,45 @@ class Engine:
         abi.check(self.lib.ot_monitor_spots_many(self._ctx, (abi.OtMonitor * M)(*mons), M, _doubles(axes), _doubles(centre), _doubles(offsets), J,
                                                  C.byref(src), segs.field("intensity").data_ptr() if weighted else None, n_segments, _address(count),
                                                  n_rays, *(t.data_ptr() for t in outs), 0 if into is None else 1), self.lib)
+        return outs
+
+    def monitor_wavefront_many(self, monitor_structs, axes, reference_kind, reference, coordinates, pupil, piston, segs: SegmentBatch,
+                               weighted=True, into=None):
+        """The wavefront sums of a list of monitors over a double-precision SegmentBatch read as it lies
+        (ot_monitor_wavefront_many).  axes: [M, 6] doubles (a_y, a_z per monitor); reference_kind 0: reference [M, 3] is the focus in
+        every monitor's frame, 1: the plane wave's unit direction there; coordinates 0: direction, 1: position; pupil: [M, 3]
+        (c_y, c_z, R); piston: [M].  weighted: every hit weighs its segment's intensity; False: 1.  Returns (counts, sums): int64
+        [M, 2] (inside, outside the pupil) and float64 [M, 61] (S, T, Q in the header's order) device tensors, zeroed by the call —
+        or `into`, such a pair from an earlier call, with this call's hits added to it.  The sums are the same bits every run."""
+        with self.lock:
+            return self._monitor_wavefront_many(list(monitor_structs), axes, reference_kind, reference, coordinates, pupil, piston, segs, weighted, into)
+
+    def _monitor_wavefront_many(self, mons, axes, reference_kind, reference, coordinates, pupil, piston, segs, weighted, into):
+        dev, M = segs.device, len(mons)
+        axes, reference = np.ascontiguousarray(axes, dtype=np.float64), np.ascontiguousarray(reference, dtype=np.float64)
+        pupil, piston = np.ascontiguousarray(pupil, dtype=np.float64), np.ascontiguousarray(piston, dtype=np.float64)
+        if axes.shape != (M, 6) or reference.shape != (M, 3) or pupil.shape != (M, 3) or piston.shape != (M,):
+            raise ValueError(f"axes must be [{M}, 6], reference and pupil [{M}, 3] and piston [{M}]")
+        if segs.precision != "f64":
+            raise ValueError("a wavefront needs double-precision segments")
+        if M:
+            wavefront_plan(M)
+        specs = ((torch.int64, (M, 2)), (torch.float64, (M, WAVEFRONT_SUMS)))
+        if into is None:
+            outs = tuple(torch.zeros(sh, dtype=dt, device=dev) for dt, sh in specs)  # (zeros: the library is not called for nothing)
+        else:
+            outs = tuple(into)
+            if len(outs) != 2 or any(tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type
+                                     for t, (dt, sh) in zip(outs, specs)):
+                raise ValueError(f"into: contiguous int64 counts of shape [{M}, 2] and float64 sums of shape [{M}, {WAVEFRONT_SUMS}] on {dev}")
+        src, n_segments, count, n_rays = segment_source(segs)
+        if M == 0 or n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
+            return outs
+        abi.check(self.lib.ot_monitor_wavefront_many(self._ctx, (abi.OtMonitor * M)(*mons), M, _doubles(axes), int(reference_kind), _doubles(reference),
+                                                     int(coordinates), _doubles(pupil), _doubles(piston), C.byref(src),
+                                                     segs.field("intensity").data_ptr() if weighted else None, segs.field("n").data_ptr(),
+                                                     segs.field("pathlength").data_ptr(), n_segments, _address(count), n_rays,
+                                                     *(t.data_ptr() for t in outs), 0 if into is None else 1), self.lib)
         return outs
 
     def monitor_field_many(self, monitor_structs, axes, edges, bins, segs: SegmentBatch, wavelength, amplitude_mode=0, into=None):

@@ -242,6 +242,24 @@ class MonitorHits:
         s = self.slot[order]
         return self._gather(self.segs.pathlength, s) + self.t[order] * self._gather(self.segs.n_index, s)
 
+    def wavefrontList(self, focus=None, direction=None, sort="YZ"):
+        """The optical path W of every hit against an ideal wave, hit by hit — what `OpticalTable.wavefront_all` reduces: exactly
+        one of `focus` (a lab point F: W = L + n ((F_loc - P) . d), the path at the foot of the perpendicular from F onto the ray)
+        or `direction` (a lab vector u, made unit: W = L - n (P . u_loc)), with L = `pathlengthList`, P the local hit point and d
+        the renormalised local direction of the segment (double)."""
+        import torch
+
+        from .wavefront import hit_wavefront, local_frame, wavefront_reference
+
+        kind, _, local = wavefront_reference(focus, direction, [self.monitor])
+        order = self._order(sort)
+        s = self.slot[order]
+        M = torch.as_tensor(local_frame(self.monitor)[0], device=self.slot.device)
+        d = self.directionList(sort).double() @ M  # rows: M^T D
+        d = d * (1.0 / torch.sqrt((d * d).sum(dim=1)))[:, None]
+        return hit_wavefront(kind, local[0].tolist(), self.P[order].double(), self.t[order].double(), d, self._gather(self.segs.n_index, s).double(),
+                             self._gather(self.segs.pathlength, s).double())
+
     def phaseList(self, wavelength, sort="YZ"):
         """The phase of every hit in [0, 2 pi), `Ray.phase(t)` of its segment: 2 pi (x - floor x) with x = pathlengthList / wavelength
         cycles.  `wavelength`: a float for all rays, or the `RayBatch` that was traced (its wavelengths, as double, by the hits'

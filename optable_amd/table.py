@@ -351,6 +351,71 @@ class OpticalTable:
         """One monitor as spot statistics (`spots_all` for it alone): a `MonitorSpots`."""
         return self.spots_all(segs, offsets=offsets, monitors=[monitor], weight=weight, centre=centre)[0]
 
+    def wavefront_all(self, segs, focus=None, direction=None, pupil=None, coordinates=None, monitors=None, weight="intensity", piston=None,
+                      into=None):
+        """Every monitor of the table (or those given) as a WAVEFRONT: one `MonitorWavefront` per monitor, in their order — the
+        optical path W of every hit of `record_all` against an ideal wave, reduced on the device, in the pass that finds the hits
+        and with no hit list, to the moments a Zernike fit up to radial order 4 and the rms wavefront error need
+        (ot_monitor_wavefront_many).  Exactly one of `focus` (a point F: the spherical wave that converges on F or diverges from
+        it; W is the optical path at the foot of the perpendicular from F onto the ray — the reference sphere at infinity, which
+        differs from a sphere of radius R_s by n e^2 / (2 R_s), e the ray's miss distance at F) or `direction` (a vector u: the
+        plane wave along it), in the lab frame, one for all monitors or one per monitor.  `pupil` = (c_y, c_z, R), one for all or
+        one per monitor: the hits with (p, q) = ((y - c_y) / R, (z - c_z) / R) inside the unit disc take part, the others are
+        counted in `outside`; (y, z) are the hit's `yList` / `zList` (coordinates "position" or 1, the default with `direction`,
+        where `pupil` defaults to (0, 0, min(width, height) / 2)) or its `tYList` / `tZList` ("direction" or 0, the default with
+        `focus`, where `pupil` is required).  weight: "intensity" or "none".  `piston`: a number, or one per monitor, subtracted
+        from W before it is summed; None: one extra pass — the call reduces with piston 0 and again with the mean it finds (0 for a
+        monitor without a hit).  The value is kept on the result.  `into`: the list an earlier call with the same monitors,
+        reference, pupil, coordinates and weight returned; this call's hits are added to it with ITS piston (the chunks of a
+        streamed trace use the first chunk's), which an explicit `piston` must equal.  `segs` must be double precision."""
+        from .wavefront import (COORDINATES, WEIGHTS, MonitorWavefront, wavefront_coordinates, wavefront_piston, wavefront_pupil, wavefront_reference)
+
+        if not isinstance(weight, str) or weight not in WEIGHTS:
+            raise ValueError(f'weight must be "intensity" or "none", not {weight!r}')
+        monitors = list(self.monitors if monitors is None else monitors)
+        M = len(monitors)
+        kind, lab, local = wavefront_reference(focus, direction, monitors)
+        pupils, coords = wavefront_pupil(pupil, kind, monitors), wavefront_coordinates(coordinates, kind)
+        pistons = None if piston is None else wavefront_piston(piston, M)
+        if segs.precision != "f64":
+            raise ValueError("wavefront_all needs a double-precision SegmentBatch: a path length in single precision is a hundredth of a wave wrong at table scale")
+        name = ("focus", "direction")[kind]
+        stack = None
+        if into is not None:
+            into = list(into)
+            if len(into) != M or any(not isinstance(wf, MonitorWavefront) or wf.monitor is not m or wf.weight != weight or wf.reference != (name, tuple(r))
+                                     or wf.pupil != tuple(c) or wf.coordinates != COORDINATES[coords] for wf, m, r, c in zip(into, monitors, lab, pupils)):
+                raise ValueError("into: the list an earlier wavefront_all returned for the same monitors, reference, pupil, coordinates and weight")
+            if any(wf._stack is None or wf._stack[0] is not into[0]._stack[0] or wf._stack[-1] != k or len(wf._stack[0]) != M for k, wf in enumerate(into)):
+                raise ValueError("into: the whole list of one earlier call, in its order")
+            if pistons is not None and any(wf.piston != float(v) for wf, v in zip(into, pistons)):
+                raise ValueError("into: piston must be None or the piston of the earlier call")
+            if not monitors:
+                return into
+            pistons, stack = np.array([wf.piston for wf in into], dtype=np.float64), into[0]._stack[:-1]
+        axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in monitors], dtype=float).reshape(M, 6)
+        structs = [monitor_struct(m) for m in monitors]
+
+        def reduce(p, out):
+            return _engine().monitor_wavefront_many(structs, axes, kind, local, coords, pupils, p, segs, weighted=weight == "intensity", into=out)
+
+        if pistons is None:  # the mean of W with piston 0, then the sums about it
+            _, first = reduce(np.zeros(M), None)
+            first = first.cpu().numpy()
+            with np.errstate(all="ignore"):
+                pistons = np.where(first[:, 0] != 0.0, first[:, 45] / first[:, 0], 0.0)
+            pistons = np.ascontiguousarray(np.where(np.isfinite(pistons), pistons, 0.0))
+        counts, sums = reduce(pistons, stack)
+        if into is None:
+            into = [MonitorWavefront(m, counts[k, 0], counts[k, 1], sums[k], (name, lab[k]), pupils[k], COORDINATES[coords], pistons[k], weight,
+                                     stack=(counts, sums, k)) for k, m in enumerate(monitors)]
+        return into
+
+    def wavefront_batch(self, monitor, segs, focus=None, direction=None, pupil=None, coordinates=None, weight="intensity", piston=None):
+        """One monitor as a wavefront (`wavefront_all` for it alone): a `MonitorWavefront`."""
+        return self.wavefront_all(segs, focus=focus, direction=direction, pupil=pupil, coordinates=coordinates, monitors=[monitor], weight=weight,
+                                  piston=piston)[0]
+
     def field_all(self, segs, wavelength=0.0, bins=30, monitors=None, into=None, amplitude="sqrt"):
         """Every monitor of the table (or those given) as a COHERENT image: one `MonitorField` per monitor, in their order — per
         bin of `image_all`'s images the count of hits and the complex sum of a exp(i phi) over them, summed on the device in the
