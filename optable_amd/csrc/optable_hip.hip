@@ -1848,10 +1848,77 @@ int ot_fluence_map(ot_ctx* c, const double* axes, const double* u_edges, int32_t
     return 0;
 }
 
-// Spot statistics: k_mon_spots over the segments as they lie (misc_kernels.h), one launch per MON_SPOT_CELLS cells of the list
-// [monitor][offset] (optable_amd/engine.py spots_plan says the same), all on the partition of the LDS image passes: at most 1024
-// workgroups, four a CU, which bounds the partials (1024 rows of 7 doubles a cell: 14 MB for a full group) and the last
-// workgroup's loop over them.  One ticket per launch, zeroed together.
+// What the two reductions of k_mon_spots (ot_monitor_spots_many, ot_monitor_wavefront_many; misc_kernels.h) take alike, and what
+// they refuse of it alike: after their own NULL, size and enum refusals (a size before any array of that size is read), before
+// their own tables' and before anything is zeroed or launched.
+struct ReduceCall {
+    ot_ctx* c; const ot_monitor* mons; int32_t n_monitors; const double* axes;
+    const ot_segment_source* src; const void* intensity; int64_t n; const int32_t* seg_count; int64_t n_rays;
+    int64_t* counts; double* sums; int32_t accumulate;
+};
+static int check_reduce_call(const ReduceCall& a) {
+    if (a.accumulate != 0 && a.accumulate != 1) return fail(OT_ERR_INVALID, "accumulate must be 0 or 1");
+    if (const int rc = check_source(a.src, a.n, a.seg_count, a.n_rays)) return rc;
+    for (int64_t k = 0; k < 6 * (int64_t)a.n_monitors; ++k)
+        if (!std::isfinite(a.axes[k])) return fail(OT_ERR_INVALID, "axes must be finite");
+    return 0;
+}
+// A mode, as its caller describes it to reduce_call: `cells` of the call, `cells_a_launch` of them a launch at `values` doubles each
+// (optable_amd/engine.py _cell_plan: the same list), the int64 counts and double sums a call that does not accumulate zeroes,
+// and the mode's host tables: `doubles` doubles each, whose device copy goes to MonSpots::*to (host NULL: none).
+struct ReduceTable { const double* host; int64_t doubles; const double* MonSpots::*to; };
+struct ReduceMode { int64_t cells; int32_t cells_a_launch, values; size_t n_counts, n_sums; ReduceTable tables[3]; };
+// The shared half of a checked call: counts and sums zeroed unless they are kept, nothing more for n = 0; else the monitors, axes
+// and tables to the device and one launch per `cells_a_launch` cells, all on the partition of the LDS image passes: at most 1024
+// workgroups, four a CU, which bounds the partials (1024 rows of a launch's values: 14 MB for a full group of either mode) and the
+// last workgroup's loop over them.  One ticket per launch, zeroed together.  A new mode is a new caller: its checks, its ReduceMode
+// and, in `spots`, its own MonSpots fields by name.
+static int reduce_call(const ReduceCall& a, const ReduceMode& mode, MonSpots spots) {
+    ot_ctx* c = a.c;
+    HIP_TRY(hipSetDevice(c->device));
+    if (!a.accumulate) {
+        HIP_TRY(hipMemsetAsync(a.counts, 0, sizeof(int64_t) * mode.n_counts, c->stream));
+        HIP_TRY(hipMemsetAsync(a.sums, 0, sizeof(double) * mode.n_sums, c->stream));
+    }
+    if (a.n == 0) return 0;
+    const SlotPartition sp = slot_partition(a.n, true);
+    const int64_t launches = (mode.cells + mode.cells_a_launch - 1) / mode.cells_a_launch;
+    const int64_t most = std::min<int64_t>(mode.cells, mode.cells_a_launch);
+    const ReduceTable up[4] = {{a.axes, 6 * (int64_t)a.n_monitors, &MonSpots::axes}, mode.tables[0], mode.tables[1], mode.tables[2]};
+    ot_monitor* table;
+    double *d_up[4], *partials;
+    unsigned int* tickets;
+    const auto carve = [&](void* base) {
+        Carve cv{(uint8_t*)base};
+        table = cv.take<ot_monitor>(a.n_monitors), partials = cv.take<double>(sp.grid * most * mode.values), tickets = cv.take<unsigned int>(launches);
+        for (int k = 0; k < 4; ++k) d_up[k] = cv.take<double>(up[k].doubles, up[k].host);
+        return cv.used;
+    };
+    if (c->mon.ensure(carve(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of monitor scratch failed");
+    carve(c->mon.p);
+    HIP_TRY(hipMemcpyAsync(table, a.mons, sizeof(ot_monitor) * (size_t)a.n_monitors, hipMemcpyHostToDevice, c->stream));
+    for (int k = 0; k < 4; ++k)
+        if (up[k].host) {
+            HIP_TRY(hipMemcpyAsync(d_up[k], up[k].host, sizeof(double) * (size_t)up[k].doubles, hipMemcpyHostToDevice, c->stream));
+            spots.*up[k].to = d_up[k];
+        }
+    HIP_TRY(hipMemsetAsync(tickets, 0, sizeof(unsigned int) * (size_t)launches, c->stream));
+    spots.intensity = (const uint8_t*)a.intensity, spots.partials = partials, spots.ticket = tickets;
+    spots.counts = (long long*)a.counts, spots.sums = a.sums, spots.accumulate = a.accumulate, spots.values = mode.values;
+    // (the launches of a call share the partials: they run one after the other on the stream)
+    for (int64_t cell0 = 0; cell0 < mode.cells; cell0 += mode.cells_a_launch, ++spots.ticket) {
+        spots.cell0 = (int32_t)cell0, spots.n_cells = (int32_t)std::min<int64_t>(mode.cells_a_launch, mode.cells - cell0);
+        const size_t lds_bytes = std::max<size_t>(sizeof(double) * MON_WAVES * mode.values * (size_t)spots.n_cells, MON_SPOT_LDS_MIN);
+        spots.lds_doubles = (int32_t)(lds_bytes / sizeof(double));
+        hipLaunchKernelGGL(k_mon_spots, dim3((unsigned)sp.grid), dim3(MON_THREADS), lds_bytes, c->stream, table, mon_source(a.src), a.n, sp.iters,
+                           a.seg_count, a.n_rays, spots);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Spot statistics: a cell per (monitor, plane) of the list [monitor][offset], 7 doubles, MON_SPOT_CELLS cells a launch
+// (optable_amd/engine.py spots_plan).
 int ot_monitor_spots_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* centre, const double* offsets,
                           int32_t n_offsets, const ot_segment_source* src, const void* intensity, int64_t n, const int32_t* seg_count,
                           int64_t n_rays, int64_t* counts, double* sums, int32_t accumulate) {
@@ -1860,56 +1927,20 @@ int ot_monitor_spots_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors,
     if (n_offsets < 1) return fail(OT_ERR_INVALID, "n_offsets must be at least 1");
     const int64_t cells = (int64_t)n_monitors * n_offsets;
     if (cells > (int64_t)1 << 20) return fail(OT_ERR_INVALID, "n_monitors * n_offsets exceeds 2^20 cells");
-    if (accumulate != 0 && accumulate != 1) return fail(OT_ERR_INVALID, "accumulate must be 0 or 1");
-    if (const int rc = check_source(src, n, seg_count, n_rays)) return rc;
-    for (int64_t k = 0; k < 6 * (int64_t)n_monitors; ++k)
-        if (!std::isfinite(axes[k])) return fail(OT_ERR_INVALID, "axes must be finite");
+    const ReduceCall a{c, mons, n_monitors, axes, src, intensity, n, seg_count, n_rays, counts, sums, accumulate};
+    if (const int rc = check_reduce_call(a)) return rc;
     for (int64_t k = 0; k < 2 * (int64_t)n_monitors; ++k)
         if (!std::isfinite(centre[k])) return fail(OT_ERR_INVALID, "centre must be finite");
     for (int32_t k = 0; k < n_offsets; ++k)
         if (!std::isfinite(offsets[k])) return fail(OT_ERR_INVALID, "offsets must be finite");
-    HIP_TRY(hipSetDevice(c->device));
-    if (!accumulate) {
-        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * (size_t)cells, c->stream));
-        HIP_TRY(hipMemsetAsync(sums, 0, sizeof(double) * 6 * (size_t)cells, c->stream));
-    }
-    if (n == 0) return 0;
-    const SlotPartition sp = slot_partition(n, true);
-    const int64_t launches = (cells + MON_SPOT_CELLS - 1) / MON_SPOT_CELLS;
-    const int64_t most = std::min<int64_t>(cells, MON_SPOT_CELLS);
-    ot_monitor* table;
-    double *d_axes, *d_centre, *d_offsets, *partials;
-    unsigned int* tickets;
-    const auto carve = [&](void* base) {
-        Carve cv{(uint8_t*)base};
-        table = cv.take<ot_monitor>(n_monitors), d_axes = cv.take<double>((int64_t)n_monitors * 6), d_centre = cv.take<double>((int64_t)n_monitors * 2);
-        d_offsets = cv.take<double>(n_offsets), partials = cv.take<double>(sp.grid * most * MON_SPOT_VALUES), tickets = cv.take<unsigned int>(launches);
-        return cv.used;
-    };
-    if (c->mon.ensure(carve(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of monitor scratch failed");
-    carve(c->mon.p);
-    HIP_TRY(hipMemcpyAsync(table, mons, sizeof(ot_monitor) * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_axes, axes, sizeof(double) * 6 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_centre, centre, sizeof(double) * 2 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_offsets, offsets, sizeof(double) * (size_t)n_offsets, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(tickets, 0, sizeof(unsigned int) * (size_t)launches, c->stream));
-    MonSpots spots{d_axes, d_centre, d_offsets, (const uint8_t*)intensity, partials, tickets, (long long*)counts, sums, n_offsets, 0, 0, accumulate, 0,
-                   MON_SPOT_VALUES, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
-    // (the launches of a call share the partials: they run one after the other on the stream)
-    for (int64_t cell0 = 0; cell0 < cells; cell0 += MON_SPOT_CELLS, ++spots.ticket) {
-        spots.cell0 = (int32_t)cell0, spots.n_cells = (int32_t)std::min<int64_t>(MON_SPOT_CELLS, cells - cell0);
-        const size_t lds_bytes = std::max<size_t>(sizeof(double) * MON_WAVES * MON_SPOT_VALUES * (size_t)spots.n_cells, MON_SPOT_LDS_MIN);
-        spots.lds_doubles = (int32_t)(lds_bytes / sizeof(double));
-        hipLaunchKernelGGL(k_mon_spots, dim3((unsigned)sp.grid), dim3(MON_THREADS), lds_bytes, c->stream, table, mon_source(src), n, sp.iters, seg_count,
-                           n_rays, spots);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
+    MonSpots spots{};
+    spots.n_off = n_offsets;
+    return reduce_call(a, {cells, MON_SPOT_CELLS, MON_SPOT_VALUES, (size_t)cells, 6 * (size_t)cells,
+                           {{centre, 2 * (int64_t)n_monitors, &MonSpots::centre}, {offsets, n_offsets, &MonSpots::offsets}}}, spots);
 }
 
-// Wavefront error: k_mon_spots in its wavefront mode (misc_kernels.h), a cell per monitor of 63 doubles, one launch per
-// MON_WAVEFRONT_CELLS monitors (optable_amd/engine.py wavefront_plan says the same) on the spot statistics' partition: the partials
-// are 1024 rows of 28 x 63 doubles at most, what a full group of spots takes.
+// Wavefront error: k_mon_spots in its wavefront mode, a cell per monitor of 63 doubles, MON_WAVEFRONT_CELLS monitors a launch
+// (optable_amd/engine.py wavefront_plan): 28 x 63 doubles a row of the partials, what a full group of spots takes.
 int ot_monitor_wavefront_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, int32_t reference_kind,
                               const double* reference, int32_t coordinates, const double* pupil, const double* piston,
                               const ot_segment_source* src, const void* intensity, const void* n_index, const void* pathlength, int64_t n,
@@ -1920,11 +1951,9 @@ int ot_monitor_wavefront_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monit
     if (n_monitors < 1 || n_monitors > 1 << 20) return fail(OT_ERR_INVALID, "n_monitors must be 1 .. 2^20");
     if (reference_kind != 0 && reference_kind != 1) return fail(OT_ERR_INVALID, "reference_kind must be 0 (focus) or 1 (direction)");
     if (coordinates != 0 && coordinates != 1) return fail(OT_ERR_INVALID, "coordinates must be 0 (direction) or 1 (position)");
-    if (accumulate != 0 && accumulate != 1) return fail(OT_ERR_INVALID, "accumulate must be 0 or 1");
-    if (const int rc = check_source(src, n, seg_count, n_rays)) return rc;
+    const ReduceCall a{c, mons, n_monitors, axes, src, intensity, n, seg_count, n_rays, counts, sums, accumulate};
+    if (const int rc = check_reduce_call(a)) return rc;
     if (src->width != 8) return fail(OT_ERR_INVALID, "a wavefront needs double-precision segments: width must be 8");
-    for (int64_t k = 0; k < 6 * (int64_t)n_monitors; ++k)
-        if (!std::isfinite(axes[k])) return fail(OT_ERR_INVALID, "axes must be finite");
     for (int64_t m = 0; m < n_monitors; ++m) {
         const double *r = reference + 3 * m, *p = pupil + 3 * m;
         if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2])) return fail(OT_ERR_INVALID, "reference must be finite");
@@ -1933,44 +1962,13 @@ int ot_monitor_wavefront_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monit
         if (!(p[2] > 0.0)) return fail(OT_ERR_INVALID, "the pupil's radius must be positive");
         if (!std::isfinite(piston[m])) return fail(OT_ERR_INVALID, "piston must be finite");
     }
-    HIP_TRY(hipSetDevice(c->device));
-    if (!accumulate) {
-        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * 2 * (size_t)n_monitors, c->stream));
-        HIP_TRY(hipMemsetAsync(sums, 0, sizeof(double) * MON_WAVEFRONT_SUMS * (size_t)n_monitors, c->stream));
-    }
-    if (n == 0) return 0;
-    const SlotPartition sp = slot_partition(n, true);
-    const int64_t launches = ((int64_t)n_monitors + MON_WAVEFRONT_CELLS - 1) / MON_WAVEFRONT_CELLS;
-    const int64_t most = std::min<int64_t>(n_monitors, MON_WAVEFRONT_CELLS);
-    ot_monitor* table;
-    double *d_axes, *d_reference, *d_pupil, *d_piston, *partials;
-    unsigned int* tickets;
-    const auto carve = [&](void* base) {
-        Carve cv{(uint8_t*)base};
-        table = cv.take<ot_monitor>(n_monitors), d_axes = cv.take<double>((int64_t)n_monitors * 6), d_reference = cv.take<double>((int64_t)n_monitors * 3);
-        d_pupil = cv.take<double>((int64_t)n_monitors * 3), d_piston = cv.take<double>(n_monitors);
-        partials = cv.take<double>(sp.grid * most * MON_WAVEFRONT_VALUES), tickets = cv.take<unsigned int>(launches);
-        return cv.used;
-    };
-    if (c->mon.ensure(carve(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of monitor scratch failed");
-    carve(c->mon.p);
-    HIP_TRY(hipMemcpyAsync(table, mons, sizeof(ot_monitor) * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_axes, axes, sizeof(double) * 6 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_reference, reference, sizeof(double) * 3 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_pupil, pupil, sizeof(double) * 3 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_piston, piston, sizeof(double) * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(tickets, 0, sizeof(unsigned int) * (size_t)launches, c->stream));
-    MonSpots spots{d_axes, nullptr, nullptr, (const uint8_t*)intensity, partials, tickets, (long long*)counts, sums, 1, 0, 0, accumulate, 0,
-                   MON_WAVEFRONT_VALUES, reference_kind, coordinates, d_reference, d_pupil, d_piston, (const uint8_t*)n_index, (const uint8_t*)pathlength};
-    for (int64_t cell0 = 0; cell0 < n_monitors; cell0 += MON_WAVEFRONT_CELLS, ++spots.ticket) {
-        spots.cell0 = (int32_t)cell0, spots.n_cells = (int32_t)std::min<int64_t>(MON_WAVEFRONT_CELLS, n_monitors - cell0);
-        const size_t lds_bytes = std::max<size_t>(sizeof(double) * MON_WAVES * MON_WAVEFRONT_VALUES * (size_t)spots.n_cells, MON_SPOT_LDS_MIN);
-        spots.lds_doubles = (int32_t)(lds_bytes / sizeof(double));
-        hipLaunchKernelGGL(k_mon_spots, dim3((unsigned)sp.grid), dim3(MON_THREADS), lds_bytes, c->stream, table, mon_source(src), n, sp.iters, seg_count,
-                           n_rays, spots);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
+    MonSpots spots{};
+    spots.n_off = 1;  // a cell is a monitor
+    spots.kind = reference_kind, spots.coordinates = coordinates;
+    spots.n_index = (const uint8_t*)n_index, spots.pathlength = (const uint8_t*)pathlength;
+    return reduce_call(a, {n_monitors, MON_WAVEFRONT_CELLS, MON_WAVEFRONT_VALUES, 2 * (size_t)n_monitors, MON_WAVEFRONT_SUMS * (size_t)n_monitors,
+                           {{reference, 3 * (int64_t)n_monitors, &MonSpots::reference}, {pupil, 3 * (int64_t)n_monitors, &MonSpots::pupil},
+                            {piston, n_monitors, &MonSpots::piston}}}, spots);
 }
 
 // How the detector-image calls (ot_monitor_image_many / _field_many / _beam_many / _wave_many) walk n_monitors monitors of nby x nbz

@@ -169,20 +169,25 @@ def fluence_plan(nu, nv):
     return {"path": "lds" if nu * nv <= IMAGE_LDS_BINS else "global"}
 
 
+# -- the reductions of k_mon_spots (ot_monitor_spots_many, ot_monitor_wavefront_many) -----------------------------------------------
+def _cell_plan(cells, most):
+    """How optable_hip.hip reduce_call walks a list of `cells` cells (the same rule): the launches as (first cell, cells), `most`
+    at a time — every launch one pass over the segments."""
+    return [(first, min(most, cells - first)) for first in range(0, cells, most)]
+
+
 # -- spot statistics (ot_monitor_spots_many) --------------------------------------------------------------------------------
 SPOT_CELLS = 256          # misc_kernels.h MON_SPOT_CELLS: cells (monitor, plane) of one launch, 224 bytes of LDS each
 SPOT_MAX_CELLS = 1 << 20  # n_monitors * n_offsets of one call
 
 
 def spots_plan(n_monitors, n_offsets):
-    """How ot_monitor_spots_many walks the cells (monitor m, plane j) of `n_monitors` monitors x `n_offsets` planes (optable_hip.hip
-    ot_monitor_spots_many, the same rule): the launches as (first cell, cells) over the list [m][j], SPOT_CELLS cells at a time —
-    every launch one pass over the segments."""
+    """How ot_monitor_spots_many walks the cells (monitor m, plane j) of `n_monitors` monitors x `n_offsets` planes: `_cell_plan`
+    over the list [m][j], SPOT_CELLS cells at a time."""
     n_monitors, n_offsets = int(n_monitors), int(n_offsets)
-    cells = n_monitors * n_offsets
-    if n_monitors < 1 or n_offsets < 1 or cells > SPOT_MAX_CELLS:
+    if n_monitors < 1 or n_offsets < 1 or n_monitors * n_offsets > SPOT_MAX_CELLS:
         raise ValueError(f"no spot statistics of {n_monitors} monitors x {n_offsets} planes")
-    return [(first, min(SPOT_CELLS, cells - first)) for first in range(0, cells, SPOT_CELLS)]
+    return _cell_plan(n_monitors * n_offsets, SPOT_CELLS)
 
 
 # -- wavefront error (ot_monitor_wavefront_many) -----------------------------------------------------------------------------
@@ -192,12 +197,11 @@ WAVEFRONT_MAX_MONITORS = 1 << 20  # n_monitors of one call
 
 
 def wavefront_plan(n_monitors):
-    """How ot_monitor_wavefront_many walks `n_monitors` monitors (optable_hip.hip ot_monitor_wavefront_many, the same rule): the
-    launches as (first monitor, monitors), WAVEFRONT_MONITORS at a time — every launch one pass over the segments."""
+    """How ot_monitor_wavefront_many walks `n_monitors` monitors: `_cell_plan` with a monitor a cell, WAVEFRONT_MONITORS at a time."""
     n_monitors = int(n_monitors)
     if n_monitors < 1 or n_monitors > WAVEFRONT_MAX_MONITORS:
         raise ValueError(f"no wavefront of {n_monitors} monitors")
-    return [(first, min(WAVEFRONT_MONITORS, n_monitors - first)) for first in range(0, n_monitors, WAVEFRONT_MONITORS)]
+    return _cell_plan(n_monitors, WAVEFRONT_MONITORS)
 
 
 # -- what the private halves of monitor_*_many and fluence_map share: arguments in, outputs out -------------------------------
@@ -205,12 +209,18 @@ def _doubles(array):
     return array.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _float64_tables(error, *tables):
+    """Every (array, shape) of `tables` as the contiguous float64 array of that shape the library reads (None in a shape: any
+    length).  ValueError `error` when one has another shape."""
+    out = [np.ascontiguousarray(array, dtype=np.float64) for array, _ in tables]
+    if any(t.ndim != len(shape) or any(n is not None and n != have for have, n in zip(t.shape, shape)) for t, (_, shape) in zip(out, tables)):
+        raise ValueError(error)
+    return out
+
+
 def _image_tables(M, nby, nbz, axes, edges):
-    """axes and edges of M monitors as the contiguous float64 [M, 6] and [M, nby + 1 + nbz + 1] arrays the library reads."""
-    axes, edges = np.ascontiguousarray(axes, dtype=np.float64), np.ascontiguousarray(edges, dtype=np.float64)
-    if axes.shape != (M, 6) or edges.shape != (M, nby + nbz + 2):
-        raise ValueError(f"axes must be [{M}, 6] and edges [{M}, {nby + nbz + 2}]")
-    return axes, edges
+    """axes and edges of M monitors as the [M, 6] and [M, nby + 1 + nbz + 1] arrays the library reads."""
+    return _float64_tables(f"axes must be [{M}, 6] and edges [{M}, {nby + nbz + 2}]", (axes, (M, 6)), (edges, (M, nby + nbz + 2)))
 
 
 def _wavelength_arg(wavelength, dev):
@@ -222,18 +232,25 @@ def _wavelength_arg(wavelength, dev):
     return (wavelength.data_ptr() if wavelength.numel() else None), int(wavelength.numel()), 0.0
 
 
-def _outputs(dev, shape, planes, tallies, into, alloc, plane_error, tally_error=None):
-    """The tensors a call adds to: int64 counts and `planes` float64 images of `shape`, then `tallies` one-element int64 tensors
-    — new from `alloc`, or `into`, which must be exactly those (ValueError `plane_error` / `tally_error` for the first that is not)."""
-    specs = [(torch.int64, shape)] + [(torch.float64, shape)] * planes + [(torch.int64, (1,))] * tallies
+_TALLY = (torch.int64, (1,))  # a one-element counter next to a call's images
+
+
+def _image_specs(shape, planes, tallies):
+    """The outputs of an image call: int64 counts and `planes` float64 images of `shape`, then `tallies` tallies."""
+    return [(torch.int64, shape)] + [(torch.float64, shape)] * planes + [_TALLY] * tallies
+
+
+def _outputs(dev, specs, into, alloc, error, tally_error=None):
+    """The tensors a call adds to, one per (dtype, shape) of `specs` — new from `alloc`, or `into`, which must be exactly those
+    (ValueError `error` for the first that is not, `tally_error` where that one is a tally and the caller has a message for it)."""
     if into is None:
         return tuple(alloc(sh, dtype=dt, device=dev) for dt, sh in specs)
     outs = tuple(into)
     if len(outs) != len(specs):
-        raise ValueError(plane_error)
-    for k, (t, (dt, sh)) in enumerate(zip(outs, specs)):
-        if tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type:
-            raise ValueError(plane_error if k <= planes else tally_error or plane_error)
+        raise ValueError(error)
+    for t, spec in zip(outs, specs):
+        if (t.dtype, tuple(t.shape)) != spec or not t.is_contiguous() or t.device.type != dev.type:
+            raise ValueError(tally_error if tally_error and spec is _TALLY else error)
     return outs
 
 
@@ -886,7 +903,7 @@ class Engine:
     def _monitor_image_many(self, mons, axes, edges, bins, segs, into):
         dev, M, (nby, nbz) = segs.device, len(mons), bins
         axes, edges = _image_tables(M, nby, nbz, axes, edges)
-        outs = _outputs(dev, (M, nby, nbz), 1, 0, into, torch.empty,  # (the call zeroes them)
+        outs = _outputs(dev, _image_specs((M, nby, nbz), 1, 0), into, torch.empty,  # (the call zeroes them)
                         f"into: contiguous int64 counts and float64 intensity of shape [{M}, {nby}, {nbz}] on {dev}")
         src, n_segments, count, n_rays = segment_source(segs)
         if M == 0 or n_segments == 0:
@@ -907,13 +924,11 @@ class Engine:
 
     def _fluence_map(self, axes, u_edges, v_edges, depth, segs, weighted, into):
         dev = segs.device
-        axes = np.ascontiguousarray(axes, dtype=np.float64)
-        u_edges, v_edges = np.ascontiguousarray(u_edges, dtype=np.float64), np.ascontiguousarray(v_edges, dtype=np.float64)
-        if axes.shape != (3, 3) or u_edges.ndim != 1 or v_edges.ndim != 1:
-            raise ValueError("axes must be [3, 3], u_edges and v_edges one-dimensional")
+        axes, u_edges, v_edges = _float64_tables("axes must be [3, 3], u_edges and v_edges one-dimensional", (axes, (3, 3)), (u_edges, (None,)),
+                                                 (v_edges, (None,)))
         nu, nv = len(u_edges) - 1, len(v_edges) - 1
         fluence_plan(nu, nv)
-        outs = _outputs(dev, (nu, nv), 1, 1, into, torch.zeros,  # (zeros: the library is not called for nothing)
+        outs = _outputs(dev, _image_specs((nu, nv), 1, 1), into, torch.zeros,  # (zeros: the library is not called for nothing)
                         f"into: contiguous int64 counts and float64 fluence of shape [{nu}, {nv}] and one int64 on {dev}")
         src, n_segments, count, n_rays = segment_source(segs)
         if n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
@@ -934,28 +949,27 @@ class Engine:
             return self._monitor_spots_many(list(monitor_structs), axes, centre, offsets, segs, weighted, into)
 
     def _monitor_spots_many(self, mons, axes, centre, offsets, segs, weighted, into):
-        dev, M = segs.device, len(mons)
-        axes, centre = np.ascontiguousarray(axes, dtype=np.float64), np.ascontiguousarray(centre, dtype=np.float64)
-        offsets = np.ascontiguousarray(offsets, dtype=np.float64)
-        if axes.shape != (M, 6) or centre.shape != (M, 2) or offsets.ndim != 1:
-            raise ValueError(f"axes must be [{M}, 6], centre [{M}, 2] and offsets one-dimensional")
+        M = len(mons)
+        axes, centre, offsets = _float64_tables(f"axes must be [{M}, 6], centre [{M}, 2] and offsets one-dimensional", (axes, (M, 6)), (centre, (M, 2)),
+                                                (offsets, (None,)))
         J = len(offsets)
         if M:
             spots_plan(M, J)
-        specs = ((torch.int64, (M, J)), (torch.float64, (M, J, 6)))
-        if into is None:
-            outs = tuple(torch.zeros(sh, dtype=dt, device=dev) for dt, sh in specs)  # (zeros: the library is not called for nothing)
-        else:
-            outs = tuple(into)
-            if len(outs) != 2 or any(tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type
-                                     for t, (dt, sh) in zip(outs, specs)):
-                raise ValueError(f"into: contiguous int64 counts of shape [{M}, {J}] and float64 sums of shape [{M}, {J}, 6] on {dev}")
+        return self._reduce_many("ot_monitor_spots_many", mons, (_doubles(axes), _doubles(centre), _doubles(offsets), J), segs, weighted, (),
+                                 [(torch.int64, (M, J)), (torch.float64, (M, J, 6))], into,
+                                 f"into: contiguous int64 counts of shape [{M}, {J}] and float64 sums of shape [{M}, {J}, 6] on {segs.device}")
+
+    def _reduce_many(self, call, mons, tables, segs, weighted, fields, specs, into, error):
+        """What monitor_spots_many and monitor_wavefront_many do alike once their tables are checked: the outputs of `specs`, and the
+        library's `call` with the mode's `tables` behind the monitors and its segment `fields` behind the intensity."""
+        M = len(mons)
+        outs = _outputs(segs.device, specs, into, torch.zeros, error)  # (zeros: the library is not called for nothing)
         src, n_segments, count, n_rays = segment_source(segs)
         if M == 0 or n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
             return outs
-        abi.check(self.lib.ot_monitor_spots_many(self._ctx, (abi.OtMonitor * M)(*mons), M, _doubles(axes), _doubles(centre), _doubles(offsets), J,
-                                                 C.byref(src), segs.field("intensity").data_ptr() if weighted else None, n_segments, _address(count),
-                                                 n_rays, *(t.data_ptr() for t in outs), 0 if into is None else 1), self.lib)
+        abi.check(getattr(self.lib, call)(self._ctx, (abi.OtMonitor * M)(*mons), M, *tables, C.byref(src),
+                                          segs.field("intensity").data_ptr() if weighted else None, *(segs.field(f).data_ptr() for f in fields),
+                                          n_segments, _address(count), n_rays, *(t.data_ptr() for t in outs), 0 if into is None else 1), self.lib)
         return outs
 
     def monitor_wavefront_many(self, monitor_structs, axes, reference_kind, reference, coordinates, pupil, piston, segs: SegmentBatch,
@@ -970,32 +984,17 @@ class Engine:
             return self._monitor_wavefront_many(list(monitor_structs), axes, reference_kind, reference, coordinates, pupil, piston, segs, weighted, into)
 
     def _monitor_wavefront_many(self, mons, axes, reference_kind, reference, coordinates, pupil, piston, segs, weighted, into):
-        dev, M = segs.device, len(mons)
-        axes, reference = np.ascontiguousarray(axes, dtype=np.float64), np.ascontiguousarray(reference, dtype=np.float64)
-        pupil, piston = np.ascontiguousarray(pupil, dtype=np.float64), np.ascontiguousarray(piston, dtype=np.float64)
-        if axes.shape != (M, 6) or reference.shape != (M, 3) or pupil.shape != (M, 3) or piston.shape != (M,):
-            raise ValueError(f"axes must be [{M}, 6], reference and pupil [{M}, 3] and piston [{M}]")
+        M = len(mons)
+        axes, reference, pupil, piston = _float64_tables(f"axes must be [{M}, 6], reference and pupil [{M}, 3] and piston [{M}]", (axes, (M, 6)),
+                                                         (reference, (M, 3)), (pupil, (M, 3)), (piston, (M,)))
         if segs.precision != "f64":
             raise ValueError("a wavefront needs double-precision segments")
         if M:
             wavefront_plan(M)
-        specs = ((torch.int64, (M, 2)), (torch.float64, (M, WAVEFRONT_SUMS)))
-        if into is None:
-            outs = tuple(torch.zeros(sh, dtype=dt, device=dev) for dt, sh in specs)  # (zeros: the library is not called for nothing)
-        else:
-            outs = tuple(into)
-            if len(outs) != 2 or any(tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous() or t.device.type != dev.type
-                                     for t, (dt, sh) in zip(outs, specs)):
-                raise ValueError(f"into: contiguous int64 counts of shape [{M}, 2] and float64 sums of shape [{M}, {WAVEFRONT_SUMS}] on {dev}")
-        src, n_segments, count, n_rays = segment_source(segs)
-        if M == 0 or n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
-            return outs
-        abi.check(self.lib.ot_monitor_wavefront_many(self._ctx, (abi.OtMonitor * M)(*mons), M, _doubles(axes), int(reference_kind), _doubles(reference),
-                                                     int(coordinates), _doubles(pupil), _doubles(piston), C.byref(src),
-                                                     segs.field("intensity").data_ptr() if weighted else None, segs.field("n").data_ptr(),
-                                                     segs.field("pathlength").data_ptr(), n_segments, _address(count), n_rays,
-                                                     *(t.data_ptr() for t in outs), 0 if into is None else 1), self.lib)
-        return outs
+        tables = (_doubles(axes), int(reference_kind), _doubles(reference), int(coordinates), _doubles(pupil), _doubles(piston))
+        return self._reduce_many("ot_monitor_wavefront_many", mons, tables, segs, weighted, ("n", "pathlength"),
+                                 [(torch.int64, (M, 2)), (torch.float64, (M, WAVEFRONT_SUMS))], into,
+                                 f"into: contiguous int64 counts of shape [{M}, 2] and float64 sums of shape [{M}, {WAVEFRONT_SUMS}] on {segs.device}")
 
     def monitor_field_many(self, monitor_structs, axes, edges, bins, segs: SegmentBatch, wavelength, amplitude_mode=0, into=None):
         """Coherent detector images of a list of monitors over a double-precision SegmentBatch read as it lies
@@ -1013,7 +1012,7 @@ class Engine:
         if segs.precision != "f64":
             raise ValueError("a field needs double-precision segments")
         wavelength = _wavelength_arg(wavelength, dev)
-        outs = _outputs(dev, (M, nby, nbz), 2, 1, into, torch.empty,  # (the call zeroes them)
+        outs = _outputs(dev, _image_specs((M, nby, nbz), 2, 1), into, torch.empty,  # (the call zeroes them)
                         f"into: contiguous int64 counts and float64 re, im of shape [{M}, {nby}, {nbz}] on {dev}", f"into: skipped is one int64 on {dev}")
         src, n_segments, count, n_rays = segment_source(segs)
         if M == 0 or n_segments == 0:
@@ -1038,7 +1037,7 @@ class Engine:
         dev, M, (nby, nbz) = segs.device, len(mons), bins
         axes, edges = _image_tables(M, nby, nbz, axes, edges)
         wavelength = _wavelength_arg(wavelength, dev)
-        outs = _outputs(dev, (M, nby, nbz), 1, 1, into, torch.empty,  # (the call zeroes them)
+        outs = _outputs(dev, _image_specs((M, nby, nbz), 1, 1), into, torch.empty,  # (the call zeroes them)
                         f"into: contiguous int64 counts and float64 power of shape [{M}, {nby}, {nbz}] on {dev}", f"into: skipped is one int64 on {dev}")
         src, n_segments, count, n_rays = segment_source(segs)
         if M == 0 or n_segments == 0:
@@ -1066,7 +1065,7 @@ class Engine:
         if segs.precision != "f64":
             raise ValueError("a beam field needs double-precision segments")
         wavelength = _wavelength_arg(wavelength, dev)
-        outs = _outputs(dev, (M, nby, nbz), 2, 2, into, torch.empty,  # (the call zeroes them)
+        outs = _outputs(dev, _image_specs((M, nby, nbz), 2, 2), into, torch.empty,  # (the call zeroes them)
                         f"into: contiguous int64 counts and float64 re, im of shape [{M}, {nby}, {nbz}] on {dev}",
                         f"into: skipped and aliased are one int64 each on {dev}")
         src, n_segments, count, n_rays = segment_source(segs)

@@ -7,10 +7,9 @@ the number of segment pieces inside it and their intensity-weighted path length.
 """
 import numpy as np
 
-from .monitors import image_bins
+from .monitors import WEIGHTS, image_bins  # noqa: F401  (WEIGHTS: importable from here too)
 
 VIEW_AXES = {"Z": (0, 1, 2), "X": (1, 2, 0), "Y": (2, 0, 1)}  # view -> lab axes of (u, v, depth)
-WEIGHTS = ("intensity", "none")
 
 
 def fluence_view(view, roi, pixels):

@@ -374,6 +374,14 @@ def image_bins(bins):
     return nby, nbz
 
 
+WEIGHTS = ("intensity", "none")  # what a hit or a segment piece weighs in fluence_map, spots_all and wavefront_all
+
+
+def check_weight(weight):
+    if not isinstance(weight, str) or weight not in WEIGHTS:
+        raise ValueError(f'weight must be "intensity" or "none", not {weight!r}')
+
+
 def image_edges(monitor, nby, nbz):
     """The bin edges of a monitor's image, as `Monitor.render_hist` / `_get_hist_y` bin it (monitor.py:195-200, 271-289):
     nby equal bins over +-width / 2 along y, nbz over +-height / 2 along z — what np.histogram_bin_edges gives for that range."""

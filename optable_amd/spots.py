@@ -6,7 +6,8 @@ What the reference computes hit by hit on a `Monitor` — `sum_intensity`, `avg_
 """
 import numpy as np
 
-WEIGHTS = ("intensity", "none")
+from .monitors import WEIGHTS  # noqa: F401  (importable from here too)
+
 SUMS = ("W", "Wy", "Wz", "Wyy", "Wzz", "Wyz")
 
 

@@ -23,7 +23,7 @@ from .assemblies import *  # noqa: F401,F403  (reference re-exports, optical_tab
 from .components import *  # noqa: F401,F403
 from .components import OpticalComponent
 from .geometry import base_merge_bboxs, _NO_BOX, out_of_scope
-from .monitors import Monitor
+from .monitors import Monitor, check_weight
 from .rays import Ray
 from .scene import compile_scene
 
@@ -250,15 +250,11 @@ class OpticalTable:
         edges = [image_edges(m, nby, nbz) for m in monitors]
         stack = None
         if into is not None:
-            into = list(into)
-            if len(into) != len(monitors) or any(not isinstance(im, cls) or im.monitor is not m or im.bins != bins for im, m in zip(into, monitors)):
-                raise ValueError(f"into: the list an earlier {mode}_all returned for the same monitors and bins")
-            if any(im._stack is None or im._stack[0] is not into[0]._stack[0] or im._stack[-1] != k or len(im._stack[0]) != len(into) for k, im in enumerate(into)):
-                raise ValueError("into: the whole list of one earlier call, in its order")
+            into, stack = _into_stack(into, len(monitors), lambda k, im: isinstance(im, cls) and im.monitor is monitors[k] and im.bins == bins,
+                                      f"into: the list an earlier {mode}_all returned for the same monitors and bins")
             if not monitors:
                 return into, None
-            stack = into[0]._stack[:-1]
-        axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in monitors], dtype=float).reshape(len(monitors), 6)
+        axes = _monitor_axes(monitors)
         table = np.array([np.concatenate(e) for e in edges], dtype=float).reshape(len(monitors), nby + nbz + 2)
         outs = getattr(_engine(), f"monitor_{mode}_many")([monitor_struct(m) for m in monitors], axes, table, bins, segs, *args, into=stack, **kwargs)
         images = 1 + len(cls.PLANES)  # counts and the planes; then the tallies, the hits left out first
@@ -294,10 +290,9 @@ class OpticalTable:
         box — the unbounded last segment of a ray, with an infinite depth range — deposits nothing and is counted in `skipped`.
         `into`: the `FluenceMap` an earlier call with the same view, roi, pixels and weight returned; this call's segments are
         added to it (the chunks of a streamed trace)."""
-        from .fluence import WEIGHTS, FluenceMap, fluence_view
+        from .fluence import FluenceMap, fluence_view
 
-        if not isinstance(weight, str) or weight not in WEIGHTS:
-            raise ValueError(f'weight must be "intensity" or "none", not {weight!r}')
+        check_weight(weight)
         if roi is None:
             if not self.components:
                 raise ValueError("roi=None takes the table's get_bbox(), and this table has no components: pass roi")
@@ -324,25 +319,20 @@ class OpticalTable:
         cancellation; `MonitorSpots.centroid()` adds it back.  Counts are exact and the sums the same bits every run.  `into`: the
         list an earlier call with the same monitors, offsets, weight and centre returned; this call's hits are added to it (the
         chunks of a streamed trace)."""
-        from .spots import WEIGHTS, MonitorSpots, spot_centres, spot_offsets
+        from .spots import MonitorSpots, spot_centres, spot_offsets
 
-        if not isinstance(weight, str) or weight not in WEIGHTS:
-            raise ValueError(f'weight must be "intensity" or "none", not {weight!r}')
+        check_weight(weight)
         monitors = list(self.monitors if monitors is None else monitors)
         offsets, centres = spot_offsets(offsets), spot_centres(centre, len(monitors))
         stack = None
         if into is not None:
-            into = list(into)
-            if len(into) != len(monitors) or any(not isinstance(sp, MonitorSpots) or sp.monitor is not m or sp.weight != weight or sp.centre != tuple(c)
-                                                 or not np.array_equal(sp.offsets, offsets) for sp, m, c in zip(into, monitors, centres)):
-                raise ValueError("into: the list an earlier spots_all returned for the same monitors, offsets, weight and centre")
-            if any(sp._stack is None or sp._stack[0] is not into[0]._stack[0] or sp._stack[-1] != k or len(sp._stack[0]) != len(into) for k, sp in enumerate(into)):
-                raise ValueError("into: the whole list of one earlier call, in its order")
+            into, stack = _into_stack(into, len(monitors), lambda k, sp: isinstance(sp, MonitorSpots) and sp.monitor is monitors[k] and sp.weight == weight
+                                      and sp.centre == tuple(centres[k]) and np.array_equal(sp.offsets, offsets),
+                                      "into: the list an earlier spots_all returned for the same monitors, offsets, weight and centre")
             if not monitors:
                 return into
-            stack = into[0]._stack[:-1]
-        axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in monitors], dtype=float).reshape(len(monitors), 6)
-        counts, sums = _engine().monitor_spots_many([monitor_struct(m) for m in monitors], axes, centres, offsets, segs, weighted=weight == "intensity", into=stack)
+        counts, sums = _engine().monitor_spots_many([monitor_struct(m) for m in monitors], _monitor_axes(monitors), centres, offsets, segs,
+                                                    weighted=weight == "intensity", into=stack)
         if into is None:
             into = [MonitorSpots(m, offsets, counts[k], sums[k], weight, centres[k], stack=(counts, sums, k)) for k, m in enumerate(monitors)]
         return into
@@ -368,10 +358,9 @@ class OpticalTable:
         monitor without a hit).  The value is kept on the result.  `into`: the list an earlier call with the same monitors,
         reference, pupil, coordinates and weight returned; this call's hits are added to it with ITS piston (the chunks of a
         streamed trace use the first chunk's), which an explicit `piston` must equal.  `segs` must be double precision."""
-        from .wavefront import (COORDINATES, WEIGHTS, MonitorWavefront, wavefront_coordinates, wavefront_piston, wavefront_pupil, wavefront_reference)
+        from .wavefront import COORDINATES, MonitorWavefront, wavefront_coordinates, wavefront_piston, wavefront_pupil, wavefront_reference
 
-        if not isinstance(weight, str) or weight not in WEIGHTS:
-            raise ValueError(f'weight must be "intensity" or "none", not {weight!r}')
+        check_weight(weight)
         monitors = list(self.monitors if monitors is None else monitors)
         M = len(monitors)
         kind, lab, local = wavefront_reference(focus, direction, monitors)
@@ -382,19 +371,15 @@ class OpticalTable:
         name = ("focus", "direction")[kind]
         stack = None
         if into is not None:
-            into = list(into)
-            if len(into) != M or any(not isinstance(wf, MonitorWavefront) or wf.monitor is not m or wf.weight != weight or wf.reference != (name, tuple(r))
-                                     or wf.pupil != tuple(c) or wf.coordinates != COORDINATES[coords] for wf, m, r, c in zip(into, monitors, lab, pupils)):
-                raise ValueError("into: the list an earlier wavefront_all returned for the same monitors, reference, pupil, coordinates and weight")
-            if any(wf._stack is None or wf._stack[0] is not into[0]._stack[0] or wf._stack[-1] != k or len(wf._stack[0]) != M for k, wf in enumerate(into)):
-                raise ValueError("into: the whole list of one earlier call, in its order")
+            into, stack = _into_stack(into, M, lambda k, wf: isinstance(wf, MonitorWavefront) and wf.monitor is monitors[k] and wf.weight == weight
+                                      and wf.reference == (name, tuple(lab[k])) and wf.pupil == tuple(pupils[k]) and wf.coordinates == COORDINATES[coords],
+                                      "into: the list an earlier wavefront_all returned for the same monitors, reference, pupil, coordinates and weight")
             if pistons is not None and any(wf.piston != float(v) for wf, v in zip(into, pistons)):
                 raise ValueError("into: piston must be None or the piston of the earlier call")
             if not monitors:
                 return into
-            pistons, stack = np.array([wf.piston for wf in into], dtype=np.float64), into[0]._stack[:-1]
-        axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in monitors], dtype=float).reshape(M, 6)
-        structs = [monitor_struct(m) for m in monitors]
+            pistons = np.array([wf.piston for wf in into], dtype=np.float64)
+        axes, structs = _monitor_axes(monitors), [monitor_struct(m) for m in monitors]
 
         def reduce(p, out):
             return _engine().monitor_wavefront_many(structs, axes, kind, local, coords, pupils, p, segs, weighted=weight == "intensity", into=out)
@@ -788,6 +773,22 @@ _HOOK_MEMO = {}
 # (what leaves a hit out of beam_all and wave_all)
 _NO_BEAM = ("they carry no q (a batch traced without a Gaussian beam), or their wavelength or refractive index is not finite and > 0, or their "
             "`ray` is no index into the wavelengths given")
+
+
+def _monitor_axes(monitors):
+    """The [M, 6] table of the monitors' lab tangents (a_y, a_z) that every monitor_*_many call takes."""
+    return np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in monitors], dtype=float).reshape(len(monitors), 6)
+
+
+def _into_stack(into, n, same, error):
+    """`into=` of a *_all call over `n` monitors: (it as a list, the engine's tensors it adds to — None for no monitors).  It must be
+    the list an earlier call returned for the same arguments (`same(k, item)` of every item; ValueError `error`), whole, in its order."""
+    into = list(into)
+    if len(into) != n or not all(same(k, item) for k, item in enumerate(into)):
+        raise ValueError(error)
+    if any(item._stack is None or item._stack[0] is not into[0]._stack[0] or item._stack[-1] != k or len(item._stack[0]) != n for k, item in enumerate(into)):
+        raise ValueError("into: the whole list of one earlier call, in its order")
+    return into, into[0]._stack[:-1] if into else None
 
 
 def _wavelengths_of(wavelength, segs, what):

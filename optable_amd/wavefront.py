@@ -12,7 +12,8 @@ import math
 
 import numpy as np
 
-WEIGHTS = ("intensity", "none")
+from .monitors import WEIGHTS  # noqa: F401  (importable from here too)
+
 COORDINATES = ("direction", "position")  # 0, 1 of ot_monitor_wavefront_many
 DEGREE, TERMS, N_S, N_T, N_SUMS = 4, 15, 45, 15, 61
 RCOND = 1e-12  # a Gram matrix whose reciprocal condition is below this determines no fit

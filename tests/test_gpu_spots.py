@@ -192,6 +192,29 @@ def test_more_cells_than_one_group():
     assert int(spots[1].counts.min()) > 0
 
 
+def test_more_cells_than_one_group_streamed():
+    """The 400 cells and 1,003 rays above as two chunks of 512 and 491 rays, the second added with `into=`: every launch of the
+    second call draws its own ticket, shares the call's partials and adds to what the first call left.  The hits are those of the
+    one-call test, so no ray sits on a rim; the bounds are the reference's own for the concatenated records."""
+    table = _cfg2_table()
+    mons = [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([7.0, 0, 0], 5, 5).RotZ(-0.2)]
+    offsets = np.linspace(-0.995, 0.995, 200)
+    assert spots_plan(2, 200) == [(0, 256), (256, 144)]
+    o, d = scenes.cfg2_rays(1003, 5)
+    whole = _batch(o, d)
+    chunks = []
+    for part in (slice(0, 512), slice(512, 1003)):
+        b = RayBatch.from_arrays(o[part], d[part], wavelength=scenes.WL, intensity=whole.intensity[part].cpu().numpy(),
+                                 q=1j * np.pi * scenes.W0**2 / scenes.WL, device="cuda")
+        chunks.append(table.trace_batch(b, max_segments=5, layout="slots"))
+    records = tuple(np.concatenate(parts) for parts in zip(*(_records(c) for c in chunks)))
+    spots = table.spots_all(chunks[0], offsets=offsets, monitors=mons)
+    table.spots_all(chunks[1], offsets=offsets, monitors=mons, into=spots)
+    for sp, m in zip(spots, mons):
+        _assert_spots(sp, _reference(records, m, offsets))
+    assert int(spots[1].counts.min()) > 0
+
+
 def test_lists_and_trees():
     """Ray trees of the slab with reflectivity 0.2 (every hit splits, tests/test_gpu_trees.py): the [k][tree] slots with count[i],
     the dense list with holes and the list in generation order."""

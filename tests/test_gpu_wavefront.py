@@ -180,6 +180,25 @@ def test_more_monitors_than_one_group():
     assert int(wfs[-1].counts) > 0 and int(wfs[0].outside) > 0
 
 
+def test_more_monitors_than_one_group_streamed():
+    """The 30 monitors and 1,003 rays above as two chunks of 512 and 491 rays, the second added with `into=`: every launch of the
+    second call draws its own ticket, shares the call's partials and adds to what the first call left, with the first call's pistons."""
+    assert wavefront_plan(cases.GROUP_MONITORS) == [(0, 28), (28, 2)]
+    table = cases.cfg2_table()
+    mons, pupils = cases.group_monitors()
+    o, d, intensity = cases.cfg2_arrays(1003, 5)
+    chunks = [table.trace_batch(_batch(o[part], d[part], intensity[part]), max_segments=5, layout="slots") for part in (slice(0, 512), slice(512, 1003))]
+    records = tuple(np.concatenate(parts) for parts in zip(*(_records(c) for c in chunks)))
+    kwargs = dict(direction=(1.0, 0.0, 0.0))
+    piston = np.linspace(5.0, 5.5, len(mons))
+    wfs = table.wavefront_all(chunks[0], pupil=pupils, monitors=mons, piston=piston, **kwargs)
+    table.wavefront_all(chunks[1], pupil=pupils, monitors=mons, into=wfs, **kwargs)
+    for k, (wf, m, p) in enumerate(zip(wfs, mons, pupils)):
+        assert wf.piston == piston[k]
+        _assert_wavefront(wf, cases.reference(records, m, kwargs, p, piston[k]), terms=(4, 15))
+    assert int(wfs[-1].counts) > 0
+
+
 # -- closed forms, independent of the reference: one hand-made segment per ray --------------------------------------------------------
 def _hand_batch(o, d, length, intensity=None, n_index=1.0, pathlength=0.0):
     n = len(o)
