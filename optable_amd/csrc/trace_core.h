@@ -780,8 +780,9 @@ __device__ __forceinline__ bool hit_leaf(const Scene<T>& sc, const DNode<T>& nd,
                 const T gr = sample((i == 9) ? b : a + T(i) * step);
                 // fp64: the reference's strict product test (optical_component.py:131).  fp32: |P| - R is
                 // quantised to ~2e-6 at R ~ 30, so a sample lands on g == 0 exactly for several percent of
-                // the rays and the product test would drop those roots; compare signs instead.
-                const bool crossing = sizeof(T) == 4 ? ((gl < T(0)) != (gr < T(0))) : (gl * gr < T(0));
+                // the rays and the product test would drop those roots; compare signs instead.  A NaN sample (a conic sag
+                // past its domain inside the local box) has no sign: no crossing next to it, as the product test says.
+                const bool crossing = sizeof(T) == 4 ? ((gl < T(0)) != (gr < T(0)) && !__builtin_isunordered(gl, gr)) : (gl * gr < T(0));
                 if (crossing) crossings |= 1u << i;
                 gl = gr;
             }

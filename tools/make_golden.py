@@ -22,6 +22,7 @@ import numpy as np  # noqa: E402
 import optable as ref  # noqa: E402  (the reference)
 import scenes  # noqa: E402
 import implicit_scenes  # noqa: E402
+import form_scenes  # noqa: E402
 
 assert ref.__file__.startswith("/root/reference"), ref.__file__
 OUT = os.path.join(ROOT, "tests", "golden")
@@ -62,6 +63,14 @@ def ray_rows(rays):
 
 def run(name):
     sc = {**scenes.SCENES, **scenes.HOOKED_SCENES, **implicit_scenes.IMPLICIT_SCENES}[name](ref)
+    out, line = record(sc)
+    os.makedirs(OUT, exist_ok=True)
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
+    print(f"{name}: {line}")
+
+
+def record(sc):
+    """One scene run by the reference, as the arrays of a fixture (+ a line for the log)."""
     table = ref.OpticalTable()
     table.add_components(sc["components"])
     table.add_monitors(sc["monitors"])
@@ -105,9 +114,27 @@ def run(name):
         out[f"mon{m}_I"] = np.array([d[1] for d in raw], dtype=float)
         out[f"mon{m}_t"] = np.array([d[2] for d in raw], dtype=float)
         out[f"mon{m}_seg"] = np.array([seg_index[id(d[3])] for d in raw], dtype=np.int64)
-    os.makedirs(OUT, exist_ok=True)
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
-    print(f"{name}: {len(rays)} rays, {len(leaves)} leaves, {len(groups)} groups -> {len(segs)} segments")
+    return out, f"{len(rays)} rays, {len(leaves)} leaves, {len(groups)} groups -> {len(segs)} segments"
+
+
+def forms_fixture(family):
+    """g30 - g33: the surface-form catalogue (tests/form_scenes.py), one file per family; every form in the format of
+    `run`, its arrays under `<form>/`.  (A sag whose radicand goes negative inside the local box makes the reference print a
+    RuntimeWarning and report no crossing there: part of what is recorded.)"""
+    import warnings
+
+    out = {}
+    for name in form_scenes.NAMES:
+        if form_scenes.FAMILY[name] != family:
+            continue
+        np.random.seed(12345)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            rows, line = record(form_scenes.scene(ref, name))
+        for key, val in rows.items():
+            out[f"{name}/{key}"] = val
+        print(f"{family} {name}: {line}")
+    np.savez_compressed(os.path.join(OUT, family + ".npz"), **out)
 
 
 def exports_fixture():
@@ -380,7 +407,7 @@ def adapter_fixture():
 if __name__ == "__main__":
     names = sys.argv[1:] or list(scenes.SCENES) + list(scenes.HOOKED_SCENES) + list(implicit_scenes.IMPLICIT_SCENES)
     for nm in names:
-        if nm in ("g14_slab", "g17_abcd", "g20_interact", "g22_calibrate", "g23_exports", "g27_real_example", "g28_adapter", "examples"):
+        if nm in ("g14_slab", "g17_abcd", "g20_interact", "g22_calibrate", "g23_exports", "g27_real_example", "g28_adapter", "examples") + tuple(form_scenes.FAMILIES):
             continue
         np.random.seed(12345)
         run(nm)
@@ -403,3 +430,6 @@ if __name__ == "__main__":
         interact_fixture()
     if not sys.argv[1:] or "g28_adapter" in sys.argv[1:]:
         adapter_fixture()
+    for family in form_scenes.FAMILIES:
+        if not sys.argv[1:] or family in sys.argv[1:]:
+            forms_fixture(family)
