@@ -338,7 +338,7 @@ class SegmentBatch:
         if tiled:  # 64-slot tiles (include/optable_hip.h: ot_trace_tiled_*); the fields are strided [tiles, 64] views of one block
             self.capacity = cap = (self.capacity + 63) // 64 * 64
             width = 8 if precision == "f64" else 4
-            tile_bytes = 64 * (12 * width + 8)
+            tile_bytes = 64 * (12 * width + 8)  # csrc/kernels.h SegTiles<T>::TILE_BYTES is the definition: 12 real planes of 64, then ray and surface
             self.block = torch.empty(cap // 64 * tile_bytes, dtype=torch.uint8, device=self.device)
             reals, ints = self.block.view(dt), self.block.view(torch.int32)
             rs, is_ = tile_bytes // width, tile_bytes // 4

@@ -13,7 +13,8 @@
 //                        again, ordered slots); k_gen_probe / k_gen_rank / k_gen_counts keep interact-count gates
 //                        FIFO-exact; k_gen_totals publishes the generation's totals between the two passes.
 //   k_mon_*              Monitor.record over a segment stream (monitor.py:183-193).
-// The persistent lane-per-ray kernels' shared pieces (argument-segment layout, OT_KARG, value helpers) are one block behind load_ray.
+// The segment record — field order (SegField), tile geometry (SegTiles), one store per form over the output layout — stands ahead of load_ray;
+// the persistent lane-per-ray kernels' shared pieces (argument-segment layout, OT_KARG, value helpers) are one block behind it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -36,8 +37,11 @@ template <class T> struct RaysOutT {
     T *ox, *oy, *oz, *dx, *dy, *dz, *wl, *qr, *qi, *I, *n, *pl;
     int32_t *id, *flags;
 };
+// A segment record: twelve reals in THIS order — that of ot_segments, of the planes of SegPlanes and of a tile of SegTiles —
+// then int32 ray and surface.  Every record store below names a field by its index here and asks the layout where it lies.
+enum SegField { SEG_OX, SEG_OY, SEG_OZ, SEG_DX, SEG_DY, SEG_DZ, SEG_LEN, SEG_I, SEG_QR, SEG_QI, SEG_N, SEG_PL, SEG_REALS };
 template <class T> struct SegsT {
-    T *ox, *oy, *oz, *dx, *dy, *dz, *len, *I, *qr, *qi, *n, *pl;
+    T* f[SEG_REALS];  // by SegField
     int32_t *ray, *surface;
 };
 template <class T> static RaysT<T> view(const ot_rays* r) {
@@ -50,8 +54,8 @@ template <class T> static RaysOutT<T> view_out(const ot_rays* r) {
             (T*)r->q_im, (T*)r->intensity, (T*)r->n, (T*)r->pathlength, r->id, r->flags};
 }
 template <class T> static SegsT<T> view(const ot_segments* s) {
-    return {(T*)s->ox, (T*)s->oy, (T*)s->oz, (T*)s->dx, (T*)s->dy, (T*)s->dz, (T*)s->length, (T*)s->intensity,
-            (T*)s->q_re, (T*)s->q_im, (T*)s->n, (T*)s->pathlength, s->ray, s->surface};
+    return {{(T*)s->ox, (T*)s->oy, (T*)s->oz, (T*)s->dx, (T*)s->dy, (T*)s->dz, (T*)s->length, (T*)s->intensity,
+             (T*)s->q_re, (T*)s->q_im, (T*)s->n, (T*)s->pathlength}, s->ray, s->surface};
 }
 
 // ------------------------------------------------------------------------------------------
@@ -85,16 +89,6 @@ template <bool NT, class V> __device__ __forceinline__ void st(V* p, V v) {
     if (NT) __builtin_nontemporal_store(v, p);
     else *p = v;
 }
-template <class T, bool NT = false>
-__device__ __forceinline__ void store_segment(const SegsT<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
-                                              int32_t surface) {
-    st<NT>(out.ox + slot, r.ox); st<NT>(out.oy + slot, r.oy); st<NT>(out.oz + slot, r.oz);
-    st<NT>(out.dx + slot, r.dx); st<NT>(out.dy + slot, r.dy); st<NT>(out.dz + slot, r.dz);
-    st<NT>(out.len + slot, len); st<NT>(out.I + slot, r.I);
-    st<NT>(out.qr + slot, r.qr); st<NT>(out.qi + slot, r.qi);
-    st<NT>(out.n + slot, r.n); st<NT>(out.pl + slot, r.pl);
-    st<NT>(out.ray + slot, tree); st<NT>(out.surface + slot, surface);
-}
 
 // Append layout (ot_trace_append_*): ONE allocation of 14 planes of `cap` slots — the 12 real fields in ot_segments order,
 // then int32 ray[cap], int32 surface[cap] — instead of 14 independent arrays: two scalar registers instead of 28 live
@@ -105,10 +99,10 @@ template <class T> struct SegPlanes {
 };
 // Every plane is addressed as (wave-uniform plane base) + (one 32-bit lane offset): the store takes its base from a
 // scalar register pair and the lane offset from ONE vector register computed once per record, instead of a 64-bit vector
-// add per field (the host keeps capacity below 2^30 slots so that the byte offset fits 32 bits).
+// add per field (the host keeps capacity below 2^30 slots so that the byte offset fits 32 bits).  The opaque base and the running
+// plane pointer are the point of this layout, so it keeps a store of its own: SegField order, but no field addressed by its index.
 template <class T, bool NT = false>
-__device__ __forceinline__ void store_segment(const SegPlanes<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
-                                              int32_t surface) {
+__device__ __forceinline__ void store_segment(const SegPlanes<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree, int32_t surface) {
 #ifdef OT_EXP_NOSTORE  // measurement only: what the record stores cost a kernel (never in the product library)
     if (slot != 0x7fffffffffffll) return;
 #endif
@@ -125,7 +119,7 @@ __device__ __forceinline__ void store_segment(const SegPlanes<T>& out, int64_t s
     int32_t* q = reinterpret_cast<int32_t*>(p);
     st<NT>(q + s, tree); st<NT>(q + cap + s, surface);
 }
-template <class T> __device__ __forceinline__ int32_t* ray_plane(const SegPlanes<T>& out) { return reinterpret_cast<int32_t*>(reinterpret_cast<T*>(out.base) + 12 * out.cap); }
+template <class T> __device__ __forceinline__ int32_t* ray_plane(const SegPlanes<T>& out) { return reinterpret_cast<int32_t*>(reinterpret_cast<T*>(out.base) + SEG_REALS * out.cap); }
 
 // Tiled layout (ot_trace_tiled_*): slot s lives in tile s / 64 at lane s % 64; a tile holds the 14 fields of 64 consecutive
 // slots field by field — 12 x 64 reals, then int32 ray[64], int32 surface[64] — so the 64 lanes of a wave write ONE
@@ -134,20 +128,67 @@ template <class T> __device__ __forceinline__ int32_t* ray_plane(const SegPlanes
 // 5.22 TB/s that way (tools/stream_layouts.hip).
 template <class T> struct SegTiles {
     uint8_t* base;
-    static constexpr int64_t TILE_BYTES = 64 * (12 * (int64_t)sizeof(T) + 8);
+    // the tile's geometry, stated HERE for the device (host: probe_layouts in optable_hip.hip; Python: batch.py, engine.py)
+    static constexpr int LANE_BITS = 6, LANES = 1 << LANE_BITS;                    // slots per tile = elements per plane
+    static constexpr int64_t INT_PLANES = SEG_REALS * LANES * (int64_t)sizeof(T);  // bytes of the real planes: ray[] starts there, surface[] behind it
+    static constexpr int64_t TILE_BYTES = INT_PLANES + 2 * LANES * (int64_t)sizeof(int32_t);
 };
-template <class T, bool NT = false>
-__device__ __forceinline__ void store_segment(const SegTiles<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
-                                              int32_t surface) {
-    uint8_t* tb = out.base + (slot >> 6) * SegTiles<T>::TILE_BYTES;
-    T* p = reinterpret_cast<T*>(tb) + (slot & 63);
-    st<NT>(p, r.ox); st<NT>(p + 64, r.oy); st<NT>(p + 128, r.oz);
-    st<NT>(p + 192, r.dx); st<NT>(p + 256, r.dy); st<NT>(p + 320, r.dz);
-    st<NT>(p + 384, len); st<NT>(p + 448, r.I);
-    st<NT>(p + 512, r.qr); st<NT>(p + 576, r.qi);
-    st<NT>(p + 640, r.n); st<NT>(p + 704, r.pl);
-    int32_t* q = reinterpret_cast<int32_t*>(tb + 768 * sizeof(T)) + (slot & 63);
-    st<NT>(q, tree); st<NT>(q + 64, surface);
+
+// Where the record of one slot lies, for the two layouts whose planes are pointers: real(f) is a real plane, ints() the two integer
+// planes (asked for behind the real ones), l the record's element: a field lies at plane + l.  A tile's planes start at its element 0 (the
+// paired stores address the pair's even element) or, OWN, at the record with l = 0 (one-element stores: lane first, plane offset behind).
+struct IntPlanes { int32_t *ray, *surface; };
+template <class OUT, bool OWN> struct RecAt {  // the fourteen arrays (SegsT); a tile: the specialisation below
+    const OUT& out;
+    int64_t l;  // the slot
+    __device__ __forceinline__ auto real(int f) const { return out.f[f]; }
+    __device__ __forceinline__ IntPlanes ints() const { return {out.ray, out.surface}; }
+};
+template <class T, bool OWN> struct RecAt<SegTiles<T>, OWN> {
+    using G = SegTiles<T>;
+    uint8_t* tb;
+    int64_t own, l;
+    T* p;  // plane ox, formed once and ahead of the plane tests (formed at each store, behind its test, the masked tiled stores compile differently)
+    __device__ __forceinline__ RecAt(const G& o, int64_t slot)
+        : tb(o.base + (slot >> G::LANE_BITS) * G::TILE_BYTES), own(OWN ? slot & (G::LANES - 1) : 0), l(OWN ? 0 : slot & (G::LANES - 1)),
+          p(reinterpret_cast<T*>(tb) + own) {}
+    __device__ __forceinline__ T* real(int f) const { return p + G::LANES * f; }
+    __device__ __forceinline__ IntPlanes ints() const {
+        int32_t* q = reinterpret_cast<int32_t*>(tb + G::INT_PLANES) + own;
+        return {q, q + G::LANES};
+    }
+};
+
+// THE one-element-per-lane store, both layouts.  Two scalar masks say which planes it leaves out (constant zeros: the tests fold away):
+// Resident planes (include/optable_hip.h: OT_RESIDENT_*): a plane the caller vouches the output already holds, in every slot this
+// launch would write it to, is not written again — `ray`, and `n` / `intensity` where the scene hands the batch's one value through.
+// The mask is a kernel argument: every plane test is a scalar branch.  k_trace_fused only, and only for a segment no storing lane of
+// the wave is past its old count on (the kernel decides that per wave, never per lane); everything else writes full records.
+// First-segment fields (include/optable_hip.h: ot_trace_reuse_*): segment 0 of a ray is the input ray handed through, so where the
+// batch holds one bit pattern in a field and the output's slot 0 already holds it, that plane is left unwritten as well — at k == 0
+// only.  The kernel receives those fields as OT_UNIFORM_* bits above the planes (resident >> FIRST_SHIFT) and hands the stores
+// `first`: that at k == 0, nothing at k >= 1 (scalar: k is the wave's loop counter).  A record with `first` bits goes unpaired, from
+// ONE place in the segment loop (before the ray is handed to interact, as the paired stores are).
+constexpr uint32_t FIRST_SHIFT = 8;
+template <class T, bool NT = false, class OUT>
+__device__ __forceinline__ void store_segment(const OUT& out, int64_t slot, const RayState<T>& r, T len, int32_t tree, int32_t surface,
+                                              uint32_t resident = 0u, uint32_t first = 0u) {
+    const RecAt<OUT, true> at{out, slot};
+    if (!(first & OT_UNIFORM_OX)) st<NT>(at.real(SEG_OX) + at.l, r.ox);
+    if (!(first & OT_UNIFORM_OY)) st<NT>(at.real(SEG_OY) + at.l, r.oy);
+    if (!(first & OT_UNIFORM_OZ)) st<NT>(at.real(SEG_OZ) + at.l, r.oz);
+    if (!(first & OT_UNIFORM_DX)) st<NT>(at.real(SEG_DX) + at.l, r.dx);
+    if (!(first & OT_UNIFORM_DY)) st<NT>(at.real(SEG_DY) + at.l, r.dy);
+    if (!(first & OT_UNIFORM_DZ)) st<NT>(at.real(SEG_DZ) + at.l, r.dz);
+    st<NT>(at.real(SEG_LEN) + at.l, len);
+    if (!(resident & OT_RESIDENT_INTENSITY) && !(first & OT_UNIFORM_INTENSITY)) st<NT>(at.real(SEG_I) + at.l, r.I);
+    if (!(first & OT_UNIFORM_Q_RE)) st<NT>(at.real(SEG_QR) + at.l, r.qr);
+    if (!(first & OT_UNIFORM_Q_IM)) st<NT>(at.real(SEG_QI) + at.l, r.qi);
+    if (!(resident & OT_RESIDENT_N) && !(first & OT_UNIFORM_N)) st<NT>(at.real(SEG_N) + at.l, r.n);
+    if (!(first & OT_UNIFORM_PATHLENGTH)) st<NT>(at.real(SEG_PL) + at.l, r.pl);
+    const IntPlanes q = at.ints();
+    if (!(resident & OT_RESIDENT_RAY)) st<NT>(q.ray + at.l, tree);
+    st<NT>(q.surface + at.l, surface);
 }
 
 // Paired stores: lanes 2j and 2j+1 hold records for two ADJACENT slots.  Instead of fourteen stores of one element
@@ -156,12 +197,11 @@ __device__ __forceinline__ void store_segment(const SegTiles<T>& out, int64_t sl
 // Half as many store instructions, each twice as wide: the widest coalesced form a structure-of-arrays layout allows
 // (MI355X_MICROARCH.md: 16 bytes per lane is what streaming stores want).  Needs an even slot on the even lane, both
 // lanes storing, and arrays aligned to the vector: the caller checks and falls back to store_segment otherwise.
-__device__ __forceinline__ int dpp_xor1(int v) { return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true); }  // quad_perm [1,0,3,2]
-__device__ __forceinline__ float xchg1(float v) { return __int_as_float(dpp_xor1(__float_as_int(v))); }
+__device__ __forceinline__ int32_t xchg1(int32_t v) { return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true); }  // quad_perm [1,0,3,2]
+__device__ __forceinline__ float xchg1(float v) { return __int_as_float(xchg1(__float_as_int(v))); }
 __device__ __forceinline__ double xchg1(double v) {
-    return __hiloint2double(dpp_xor1(__double2hiint(v)), dpp_xor1(__double2loint(v)));
+    return __hiloint2double(xchg1(__double2hiint(v)), xchg1(__double2loint(v)));
 }
-__device__ __forceinline__ int32_t xchg1(int32_t v) { return dpp_xor1(v); }
 template <bool NT, class V>
 __device__ __forceinline__ void store_pair(V* A, V* B, int64_t slot, V a, V b, bool odd) {
     typedef V vec2 __attribute__((ext_vector_type(2)));
@@ -169,117 +209,22 @@ __device__ __forceinline__ void store_pair(V* A, V* B, int64_t slot, V a, V b, b
     vec2 v;
     v.x = odd ? got : a;
     v.y = odd ? b : got;
-    vec2* p = reinterpret_cast<vec2*>(odd ? B + (slot - 1) : A + slot);
-    if (NT) __builtin_nontemporal_store(v, p);
-    else *p = v;
+    st<NT>(reinterpret_cast<vec2*>(odd ? B + (slot - 1) : A + slot), v);
 }
-// ... the same inside a tile: both lanes of a pair lie in one tile (64 is even), the planes are 64 elements apart
-template <class T, bool NT>
-__device__ __forceinline__ void store_segment_paired(const SegTiles<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
-                                                     int32_t surface, bool odd) {
-    uint8_t* tb = out.base + (slot >> 6) * SegTiles<T>::TILE_BYTES;
-    T* p = reinterpret_cast<T*>(tb);
-    const int64_t l = slot & 63;
-    store_pair<NT>(p, p + 64, l, r.ox, r.oy, odd);
-    store_pair<NT>(p + 128, p + 192, l, r.oz, r.dx, odd);
-    store_pair<NT>(p + 256, p + 320, l, r.dy, r.dz, odd);
-    store_pair<NT>(p + 384, p + 448, l, len, r.I, odd);
-    store_pair<NT>(p + 512, p + 576, l, r.qr, r.qi, odd);
-    store_pair<NT>(p + 640, p + 704, l, r.n, r.pl, odd);
-    int32_t* q = reinterpret_cast<int32_t*>(tb + 768 * sizeof(T));
-    store_pair<NT>(q, q + 64, l, tree, surface, odd);
+// Both lanes of a pair lie in one tile (64 is even), so the form is one for slots and tiles.
+template <class T, bool NT, class OUT>
+__device__ __forceinline__ void store_segment_paired(const OUT& out, int64_t slot, const RayState<T>& r, T len, int32_t tree, int32_t surface, bool odd) {
+    const RecAt<OUT, false> at{out, slot};
+    store_pair<NT>(at.real(SEG_OX), at.real(SEG_OY), at.l, r.ox, r.oy, odd);
+    store_pair<NT>(at.real(SEG_OZ), at.real(SEG_DX), at.l, r.oz, r.dx, odd);
+    store_pair<NT>(at.real(SEG_DY), at.real(SEG_DZ), at.l, r.dy, r.dz, odd);
+    store_pair<NT>(at.real(SEG_LEN), at.real(SEG_I), at.l, len, r.I, odd);
+    store_pair<NT>(at.real(SEG_QR), at.real(SEG_QI), at.l, r.qr, r.qi, odd);
+    store_pair<NT>(at.real(SEG_N), at.real(SEG_PL), at.l, r.n, r.pl, odd);
+    const IntPlanes q = at.ints();
+    store_pair<NT>(q.ray, q.surface, at.l, tree, surface, odd);
 }
-template <class T, bool NT>
-__device__ __forceinline__ void store_segment_paired(const SegsT<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
-                                                     int32_t surface, bool odd) {
-    store_pair<NT>(out.ox, out.oy, slot, r.ox, r.oy, odd);
-    store_pair<NT>(out.oz, out.dx, slot, r.oz, r.dx, odd);
-    store_pair<NT>(out.dy, out.dz, slot, r.dy, r.dz, odd);
-    store_pair<NT>(out.len, out.I, slot, len, r.I, odd);
-    store_pair<NT>(out.qr, out.qi, slot, r.qr, r.qi, odd);
-    store_pair<NT>(out.n, out.pl, slot, r.n, r.pl, odd);
-    store_pair<NT>(out.ray, out.surface, slot, tree, surface, odd);
-}
-
-// Resident planes (include/optable_hip.h: OT_RESIDENT_*): a plane the caller vouches the output already holds, in every slot this
-// launch would write it to, is not written again — `ray`, and `n` / `intensity` where the scene hands the batch's one value through.
-// The mask is a kernel argument: every plane test is a scalar branch.  k_trace_fused only, and only for a segment no storing lane of
-// the wave is past its old count on (the kernel decides that per wave, never per lane); everything else writes full records.
-template <class T, bool NT>
-__device__ __forceinline__ void store_segment_reduced(const SegsT<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
-                                                      int32_t surface, uint32_t resident) {
-    st<NT>(out.ox + slot, r.ox); st<NT>(out.oy + slot, r.oy); st<NT>(out.oz + slot, r.oz);
-    st<NT>(out.dx + slot, r.dx); st<NT>(out.dy + slot, r.dy); st<NT>(out.dz + slot, r.dz);
-    st<NT>(out.len + slot, len);
-    if (!(resident & OT_RESIDENT_INTENSITY)) st<NT>(out.I + slot, r.I);
-    st<NT>(out.qr + slot, r.qr); st<NT>(out.qi + slot, r.qi);
-    if (!(resident & OT_RESIDENT_N)) st<NT>(out.n + slot, r.n);
-    st<NT>(out.pl + slot, r.pl);
-    if (!(resident & OT_RESIDENT_RAY)) st<NT>(out.ray + slot, tree);
-    st<NT>(out.surface + slot, surface);
-}
-template <class T, bool NT>
-__device__ __forceinline__ void store_segment_reduced(const SegTiles<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
-                                                      int32_t surface, uint32_t resident) {
-    uint8_t* tb = out.base + (slot >> 6) * SegTiles<T>::TILE_BYTES;
-    T* p = reinterpret_cast<T*>(tb) + (slot & 63);
-    st<NT>(p, r.ox); st<NT>(p + 64, r.oy); st<NT>(p + 128, r.oz);
-    st<NT>(p + 192, r.dx); st<NT>(p + 256, r.dy); st<NT>(p + 320, r.dz);
-    st<NT>(p + 384, len);
-    if (!(resident & OT_RESIDENT_INTENSITY)) st<NT>(p + 448, r.I);
-    st<NT>(p + 512, r.qr); st<NT>(p + 576, r.qi);
-    if (!(resident & OT_RESIDENT_N)) st<NT>(p + 640, r.n);
-    st<NT>(p + 704, r.pl);
-    int32_t* q = reinterpret_cast<int32_t*>(tb + 768 * sizeof(T)) + (slot & 63);
-    if (!(resident & OT_RESIDENT_RAY)) st<NT>(q, tree);
-    st<NT>(q + 64, surface);
-}
-// First-segment fields (include/optable_hip.h: ot_trace_reuse_*): segment 0 of a ray is the input ray handed through, so where the
-// batch holds one bit pattern in a field and the output's slot 0 already holds it, that plane is left unwritten as well — at k == 0
-// only.  The kernel receives those fields as OT_UNIFORM_* bits above the planes (resident >> FIRST_SHIFT) and hands the stores
-// `first`: that at k == 0, nothing at k >= 1 (scalar: k is the wave's loop counter).  A record with `first` bits goes unpaired, from
-// ONE place in the segment loop (before the ray is handed to interact, as the paired stores are).
-constexpr uint32_t FIRST_SHIFT = 8;
-template <class T, bool NT>
-__device__ __forceinline__ void store_segment_first(const SegsT<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
-                                                    int32_t surface, uint32_t resident, uint32_t first) {
-    if (!(first & OT_UNIFORM_OX)) st<NT>(out.ox + slot, r.ox);
-    if (!(first & OT_UNIFORM_OY)) st<NT>(out.oy + slot, r.oy);
-    if (!(first & OT_UNIFORM_OZ)) st<NT>(out.oz + slot, r.oz);
-    if (!(first & OT_UNIFORM_DX)) st<NT>(out.dx + slot, r.dx);
-    if (!(first & OT_UNIFORM_DY)) st<NT>(out.dy + slot, r.dy);
-    if (!(first & OT_UNIFORM_DZ)) st<NT>(out.dz + slot, r.dz);
-    st<NT>(out.len + slot, len);
-    if (!(resident & OT_RESIDENT_INTENSITY) && !(first & OT_UNIFORM_INTENSITY)) st<NT>(out.I + slot, r.I);
-    if (!(first & OT_UNIFORM_Q_RE)) st<NT>(out.qr + slot, r.qr);
-    if (!(first & OT_UNIFORM_Q_IM)) st<NT>(out.qi + slot, r.qi);
-    if (!(resident & OT_RESIDENT_N) && !(first & OT_UNIFORM_N)) st<NT>(out.n + slot, r.n);
-    if (!(first & OT_UNIFORM_PATHLENGTH)) st<NT>(out.pl + slot, r.pl);
-    if (!(resident & OT_RESIDENT_RAY)) st<NT>(out.ray + slot, tree);
-    st<NT>(out.surface + slot, surface);
-}
-template <class T, bool NT>
-__device__ __forceinline__ void store_segment_first(const SegTiles<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
-                                                    int32_t surface, uint32_t resident, uint32_t first) {
-    uint8_t* tb = out.base + (slot >> 6) * SegTiles<T>::TILE_BYTES;
-    T* p = reinterpret_cast<T*>(tb) + (slot & 63);
-    if (!(first & OT_UNIFORM_OX)) st<NT>(p, r.ox);
-    if (!(first & OT_UNIFORM_OY)) st<NT>(p + 64, r.oy);
-    if (!(first & OT_UNIFORM_OZ)) st<NT>(p + 128, r.oz);
-    if (!(first & OT_UNIFORM_DX)) st<NT>(p + 192, r.dx);
-    if (!(first & OT_UNIFORM_DY)) st<NT>(p + 256, r.dy);
-    if (!(first & OT_UNIFORM_DZ)) st<NT>(p + 320, r.dz);
-    st<NT>(p + 384, len);
-    if (!(resident & OT_RESIDENT_INTENSITY) && !(first & OT_UNIFORM_INTENSITY)) st<NT>(p + 448, r.I);
-    if (!(first & OT_UNIFORM_Q_RE)) st<NT>(p + 512, r.qr);
-    if (!(first & OT_UNIFORM_Q_IM)) st<NT>(p + 576, r.qi);
-    if (!(resident & OT_RESIDENT_N) && !(first & OT_UNIFORM_N)) st<NT>(p + 640, r.n);
-    if (!(first & OT_UNIFORM_PATHLENGTH)) st<NT>(p + 704, r.pl);
-    int32_t* q = reinterpret_cast<int32_t*>(tb + 768 * sizeof(T)) + (slot & 63);
-    if (!(resident & OT_RESIDENT_RAY)) st<NT>(q, tree);
-    st<NT>(q + 64, surface);
-}
-// ... in lane pairs: the partners that lose their mate are paired anew where the types allow (`length` with `pathlength` when
+// ... with resident planes: the partners that lose their mate are paired anew where the types allow (`length` with `pathlength` when
 // `intensity` and `n` are both resident); one that finds none goes alone, one element per lane (`surface`: 4 bytes).
 // LEN .. SURFACE: the planes concerned, element 0 of each; l: this lane's element in them.
 template <class T, bool NT>
@@ -296,27 +241,17 @@ __device__ __forceinline__ void store_mates_reduced(T* LEN, T* I, T* N, T* PL, i
     if (resident & OT_RESIDENT_RAY) st<NT>(SURFACE + l, surface);
     else store_pair<NT>(RAY, SURFACE, l, tree, surface, odd);
 }
-template <class T, bool NT>
-__device__ __forceinline__ void store_segment_paired_reduced(const SegTiles<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
+template <class T, bool NT, class OUT>
+__device__ __forceinline__ void store_segment_paired_reduced(const OUT& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
                                                              int32_t surface, bool odd, uint32_t resident) {
-    uint8_t* tb = out.base + (slot >> 6) * SegTiles<T>::TILE_BYTES;
-    T* p = reinterpret_cast<T*>(tb);
-    const int64_t l = slot & 63;
-    store_pair<NT>(p, p + 64, l, r.ox, r.oy, odd);
-    store_pair<NT>(p + 128, p + 192, l, r.oz, r.dx, odd);
-    store_pair<NT>(p + 256, p + 320, l, r.dy, r.dz, odd);
-    store_pair<NT>(p + 512, p + 576, l, r.qr, r.qi, odd);
-    int32_t* q = reinterpret_cast<int32_t*>(tb + 768 * sizeof(T));
-    store_mates_reduced<T, NT>(p + 384, p + 448, p + 640, p + 704, q, q + 64, l, r, len, tree, surface, odd, resident);
-}
-template <class T, bool NT>
-__device__ __forceinline__ void store_segment_paired_reduced(const SegsT<T>& out, int64_t slot, const RayState<T>& r, T len, int32_t tree,
-                                                             int32_t surface, bool odd, uint32_t resident) {
-    store_pair<NT>(out.ox, out.oy, slot, r.ox, r.oy, odd);
-    store_pair<NT>(out.oz, out.dx, slot, r.oz, r.dx, odd);
-    store_pair<NT>(out.dy, out.dz, slot, r.dy, r.dz, odd);
-    store_pair<NT>(out.qr, out.qi, slot, r.qr, r.qi, odd);
-    store_mates_reduced<T, NT>(out.len, out.I, out.n, out.pl, out.ray, out.surface, slot, r, len, tree, surface, odd, resident);
+    const RecAt<OUT, false> at{out, slot};
+    store_pair<NT>(at.real(SEG_OX), at.real(SEG_OY), at.l, r.ox, r.oy, odd);
+    store_pair<NT>(at.real(SEG_OZ), at.real(SEG_DX), at.l, r.oz, r.dx, odd);
+    store_pair<NT>(at.real(SEG_DY), at.real(SEG_DZ), at.l, r.dy, r.dz, odd);
+    store_pair<NT>(at.real(SEG_QR), at.real(SEG_QI), at.l, r.qr, r.qi, odd);
+    const IntPlanes q = at.ints();
+    store_mates_reduced<T, NT>(at.real(SEG_LEN), at.real(SEG_I), at.real(SEG_N), at.real(SEG_PL), q.ray, q.surface, at.l, r, len, tree, surface, odd,
+                               resident);
 }
 
 // set bits of a wave-uniform mask below this lane (v_mbcnt: the mask comes from scalar registers, no per-lane lane-mask constant to keep)
@@ -326,21 +261,10 @@ __device__ __forceinline__ int rank_below(unsigned long long m) {
 // The caller's ray records are read exactly once per trace: non-temporal loads keep them from displacing what is
 // re-read (per-wave records, scene image in L2 mode).  Worth 1 % on cfg 4 (11.79 -> 11.67 ms, interleaved A/B), nothing on cfg 3 / 5.
 template <class V> __device__ __forceinline__ V ld_once(const V* p) { return __builtin_nontemporal_load(p); }
-template <class T> __device__ __forceinline__ RayState<T> load_ray(const RaysT<T>& in, int64_t i, int32_t flags) {
-    RayState<T> r;
-    r.ox = ld_once(in.ox + i); r.oy = ld_once(in.oy + i); r.oz = ld_once(in.oz + i);
-    r.dx = ld_once(in.dx + i); r.dy = ld_once(in.dy + i); r.dz = ld_once(in.dz + i);
-    r.wl = ld_once(in.wl + i); r.qr = ld_once(in.qr + i); r.qi = ld_once(in.qi + i);
-    r.I = ld_once(in.I + i); r.n = ld_once(in.n + i); r.pl = ld_once(in.pl + i);
-    r.len = in.len ? in.len[i] : Num<T>::inf();
-    r.has_q = (flags & OT_RAY_HAS_Q) != 0;
-    r.last = (int32_t)((uint32_t)flags >> 8) - 1;  // bits 8..31: node the ray was emitted on, plus one (generation buffers; 0 for a caller's ray)
-    return r;
-}
 // Uniform fields (include/optable_hip.h: OT_UNIFORM_*): a field the caller vouches holds ONE bit pattern in every ray of the
 // batch is not streamed per lane — the wave reads element 0, once, through the scalar cache (a load from the constant address
 // space at a wave-uniform address: s_load, not part of the non-temporal stream).  The mask is a kernel argument, so each test is a
-// scalar branch and a launch with mask 0 issues the loads of load_ray.  k_trace_fused and k_stream_ceiling only: every other
+// scalar branch and a launch with mask 0 issues the per-lane loads alone.  k_trace_fused and k_stream_ceiling only: every other
 // kernel reads the full arrays, which are always valid.
 template <class V> __device__ __forceinline__ V ld_shared(const V* p) {
     typedef const __attribute__((address_space(4))) V* ConstPtr;
@@ -374,9 +298,11 @@ template <class T> __device__ __forceinline__ RayState<T> load_ray(const RaysT<T
     r.I = ld_field(in.I, i, mask, OT_UNIFORM_INTENSITY); r.n = ld_field(in.n, i, mask, OT_UNIFORM_N); r.pl = ld_field(in.pl, i, mask, OT_UNIFORM_PATHLENGTH);
     r.len = in.len ? in.len[i] : Num<T>::inf();
     r.has_q = (flags & OT_RAY_HAS_Q) != 0;
-    r.last = (int32_t)((uint32_t)flags >> 8) - 1;
+    r.last = (int32_t)((uint32_t)flags >> 8) - 1;  // bits 8..31: node the ray was emitted on, plus one (generation buffers; 0 for a caller's ray)
     return r;
 }
+// ... with no hint: twelve non-temporal loads (the bit tests fold away)
+template <class T> __device__ __forceinline__ RayState<T> load_ray(const RaysT<T>& in, int64_t i, int32_t flags) { return load_ray(in, i, flags, 0u); }
 
 // ------------------------------------------------------------------------------------------
 // Building blocks of the persistent lane-per-ray kernels (k_trace_trees, k_trace_rolling, k_trace_refill, k_trace_pool).
@@ -391,6 +317,10 @@ template <class T> __device__ __forceinline__ RayState<T> load_ray(const RaysT<T
 // reference not tried there).  Interaction block, as advance() returning {child, used, survive}, with out-references, or as no
 // more than material cache + interact: each changes all four k_trace_refill (not tried elsewhere).  Search fork by reference:
 // changes k_trace_refill and k_trace_trees (by value not tried).  decode_lead_flags(fl, sc, r) by reference: changes k_trace_refill.
+// Segment-record stores (ahead of load_ray; were one function per form AND layout): one per form over SegsT and SegTiles, load_ray without
+// a mask as the masked one with 0 — all 174 kernels the same, but only as RecAt stands.  A slot's planes as an array of stored pointers, a
+// tile's integer planes formed ahead of the real stores, or its plane ox formed at each store behind its test: changes tiled k_trace_fused
+// (the first two: fp64 tiled k_stream_ceiling too); SegsT `ray` / `surface` offset to the slot inside ints(): seven k_trace_rolling, one k_gen_pass.
 struct AppendCtl {
     unsigned long long* cursor;  // slots claimed so far (device); the caller reads it back as *n_slots
     int64_t capacity;
@@ -568,7 +498,7 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
                                                         hit ? leaf_id_of<T, F>(sc, h.node) : -1, (threadIdx.x & 1) != 0, rm);
                 else if (active)  // (last: the two paired forms, every other segment's, keep the places they had; and the slot is
                                   // written k * n + i here too — `i` alone, equal at k == 0, costs the FA MINW = 4 kernels 8-38 vector spills)
-                    store_segment_first<T, NT>(out, (int64_t)k * n + i, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : -1, rm, fm);
+                    store_segment<T, NT>(out, (int64_t)k * n + i, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : -1, rm, fm);
             }
             if (active) {
                 const int64_t slot = (int64_t)k * n + i;
@@ -576,13 +506,13 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
                 if (h.node < 0) {  // escaped: archived unchanged (optical_table.py:132-134)
                     if (!both) {
                         if (whole) store_segment<T, NT>(out, slot, r, r.len, (int32_t)i, -1);
-                        else store_segment_reduced<T, NT>(out, slot, r, r.len, (int32_t)i, -1, rm);
+                        else store_segment<T, NT>(out, slot, r, r.len, (int32_t)i, -1, rm);
                     }
                     active = false;
                 } else {
                     if (!both) {
                         if (whole) store_segment<T, NT>(out, slot, r, h.t, (int32_t)i, leaf_id_of<T, F>(sc, h.node));
-                        else store_segment_reduced<T, NT>(out, slot, r, h.t, (int32_t)i, leaf_id_of<T, F>(sc, h.node), rm);
+                        else store_segment<T, NT>(out, slot, r, h.t, (int32_t)i, leaf_id_of<T, F>(sc, h.node), rm);
                     }
                     RayState<T> child;
                     const int nk = interact<T, F, 1>(sc, r, h, &child, mc);

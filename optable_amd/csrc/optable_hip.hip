@@ -2197,7 +2197,7 @@ template <class T> static int probe_layouts(ot_ctx* c) {
     const int pi = sizeof(T) == 8 ? 1 : 0;
     HIP_TRY(hipSetDevice(c->device));
     const size_t in_bytes = (size_t)n * (12 * sizeof(T) + 8), slots_bytes = (size_t)n * K * (12 * sizeof(T) + 8);
-    const size_t tiles_bytes = (size_t)(n * K / 64) * SegTiles<T>::TILE_BYTES;
+    const size_t tiles_bytes = (size_t)(n * K / SegTiles<T>::LANES) * SegTiles<T>::TILE_BYTES;  // (the tile's geometry: kernels.h SegTiles, the one definition)
     uint8_t* buf = nullptr;
     if (hipMalloc((void**)&buf, in_bytes + slots_bytes + tiles_bytes + 4 * n + 4096) != hipSuccess) {
         (void)hipGetLastError();

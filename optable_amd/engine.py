@@ -107,7 +107,7 @@ def segment_source(segs):
     src.ray = segs.ray.data_ptr()
     src.width = _width(segs.precision)
 
-    def tile_bytes(field):
+    def tile_bytes(field):  # (of a tiled field: SegTiles<T>::TILE_BYTES of csrc/kernels.h, read off the view's row stride)
         return (field.stride(0) if field.dim() == 2 else 64) * field.element_size()
 
     src.tile_stride, src.ray_stride, src.capacity = tile_bytes(segs.ox), tile_bytes(segs.ray), segs.capacity
