@@ -775,6 +775,50 @@ int ot_monitor_wavefront_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_mon
                               int64_t n_segments, const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* sums,
                               int32_t accumulate);
 
+/* Diffraction PSF: the plane waves of every monitor's hits summed over a grid of image samples, on the device.
+ * ot_monitor_psf_many uses the hit test of ot_monitor_record_many, unchanged.  A hit of slot s on monitor m gives the local point P,
+ * the distance t and the renormalised local direction d.  Further: n = n_index[s]; L = t n + pathlength[s]; the wavelength lambda,
+ * resolved exactly as ot_monitor_field_many resolves it (wavelength[ray[s]] from the per-ray array, or wavelength_uniform); the
+ * amplitude a = sqrt(intensity[s]) (amplitude_mode 0), intensity[s] (1) or 1 (2: intensity is not read and may be NULL).
+ * W is exactly ot_monitor_wavefront_many's: reference_kind 0: W = L + n ((F_loc - P) . d); reference_kind 1: W = L - n (P . u_loc);
+ * reference[m] holds three host doubles, axes[m] = a_y, a_z as everywhere else.
+ * Samples, not bins: grid[m] = (y0, dy, z0, dz), host, dy and dz finite and > 0; ny and nz are shared by the call; sample (k, l)
+ * lies at y_k = y0 + k dy, z_l = z0 + l dz.  Meaning of a sample, and phase of hit j there in cycles:
+ *   kind 0 (image space about a focus F): the sample is the point F + y_k a_y + z_l a_z, in the plane through F parallel to the
+ *     monitor; every ray counts as the plane wave it locally is.  x = (W + n (d . a_y) y_k + n (d . a_z) z_l) / lambda.
+ *   kind 1 (angle space about a plane wave u: the far field of an afocal system): the sample is the direction
+ *     u + y_k a_y + z_l a_z.  x = (W - n (P . a_y) y_k - n (P . a_z) z_l) / lambda.
+ * So x_j(k, l) = x0_j + gy_j y_k + gz_j z_l, and the field is U[m][k][l] = sum_j a_j exp(2 pi i frac(x_j(k, l))) over the usable
+ * hits of monitor m.
+ * Outputs, all on the device: re, im: [n_monitors][ny][nz] double; norm[m] = sum_j a_j, double; counts[m] = (used, skipped,
+ * aliased), int64.  skipped counts the hits whose ray lies outside [0, n_wavelengths), whose lambda is not finite and > 0, or whose
+ * W, gy or gz is not finite: these add nothing.  aliased counts the used hits with |gy dy| > 1/2 or |gz dz| > 1/2; they are summed
+ * all the same.  accumulate = 0 zeroes everything first, also for n_segments = 0; accumulate = 1 adds this call's result to what
+ * is there: the sum is linear, so the chunks of a streamed trace add.  All arithmetic is double, and src->width must be 8.
+ * OT_ERR_INVALID, with nothing launched or zeroed: everything ot_monitor_wavefront_many refuses of its shared arguments (ctx, mons,
+ * n_monitors, axes, reference_kind, reference, src, n_index, pathlength, n_segments, seg_count, n_rays, accumulate; a NULL
+ * output); ny or nz outside 1 .. OT_PSF_MAX_SAMPLES; grid not finite, or a step of 0 or less; an amplitude_mode outside 0 .. 2; a
+ * NULL intensity with amplitude_mode 0 or 1; the wavelength errors of ot_monitor_field_many.
+ * Determinism: like the spot statistics, re, im and norm are bit-identical from run to run.  No floating-point atomic takes part:
+ * the hits of a monitor are taken in the order of its hit list (ascending slots), in chunks whose number is a function of the
+ * monitor's hit count alone, and the chunks' partial images are added in ascending order by the workgroup that finishes last.  The
+ * result is a function of the inputs, their layout and the launch grid alone.  The counts are exact.
+ * Accuracy: the phasor of a sample comes from one direct sincospi per 8 samples of an axis and complex rotations between them, and
+ * |U_device - U_exact| <= norm (2 pi E + 2^-38), U_exact the sum above in extended precision from the segments' doubles,
+ * E = 16 x 2^-53 x max_j(|L_j| + n_j |F_loc - P_j|) / min_j lambda_j (kind 1: |P_j| in place of |F_loc - P_j|): sixteen roundings
+ * of a quantity the size of the path go into W / lambda, and 2^-38 is the budget of the recurrence.
+ * Scratch, owned by the context and kept between calls: the hit list (40 bytes a hit, sized exactly: the call counts the hits,
+ * reads the n_monitors + 1 totals back — its one synchronisation of the stream — and then writes them) and the partial images of
+ * one launch, at most OT_PSF_SCRATCH_BYTES however large the call. */
+#define OT_PSF_MAX_SAMPLES 512
+#define OT_PSF_SCRATCH_BYTES 67174400
+int ot_monitor_psf_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitors, const double* axes, int32_t reference_kind,
+                        const double* reference, const double* grid, int32_t ny, int32_t nz, const ot_segment_source* src,
+                        const void* intensity, const void* n_index, const void* pathlength, const double* wavelength,
+                        int64_t n_wavelengths, double wavelength_uniform, int32_t amplitude_mode, int64_t n_segments,
+                        const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* norm, double* re, double* im,
+                        int32_t accumulate);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled every trace launch is bracketed by hipEvents on the ctx stream. */
 int ot_timing_enable(ot_ctx* ctx, int enabled);

@@ -22,6 +22,7 @@ from .monitors import Monitor
 from .fluence import FluenceMap
 from .spots import MonitorSpots
 from .wavefront import MonitorWavefront
+from .psf import MonitorPSF
 from .table import OpticalTable
 from .scene import compile_scene, CompiledScene, SceneError
 from .adapter import install

@@ -10,7 +10,7 @@
 //   k_stream_ceiling<T>  the fused kernel's streams with no tracing (roofline companion).
 //   k_gen_pass<T>        one breadth-first generation of branching ray trees (optical_table.py:115-134) in two
 //                        streaming passes: count (rank within the tree, trace) -> scan of wave totals -> emit (trace
-//                        again, ordered slots); k_gen_probe / k_gen_rank / k_gen_counts keep interact-count gates
+//                        again, ordered slots); k_gen_probe / k_gen_per_ray (GEN_RANK) / k_gen_counts keep interact-count gates
 //                        FIFO-exact; k_gen_totals publishes the generation's totals between the two passes.
 //   k_mon_*              Monitor.record over a segment stream (monitor.py:183-193).
 // The segment record — field order (SegField), tile geometry (SegTiles), one store per form over the output layout — stands ahead of load_ray;
@@ -1755,7 +1755,7 @@ __device__ __forceinline__ int64_t tree_head(const int32_t* __restrict__ tree, i
 // k_gen_probe: the pre-pass of a generation in a scene with count-limited leaves.  It only records which limited
 // leaves each ray hits GEOMETRICALLY (probe[slot][i] = 1; no outputs, no children): a per-slot scan of these flags
 // then gives every ray the number of EARLIER rays of its tree that hit the leaf, which is what makes the gate
-// FIFO-exact inside a generation (optical_component.py:140-149, 359-362; k_gen_rank / k_gen_counts below).
+// FIFO-exact inside a generation (optical_component.py:140-149, 359-362; k_gen_per_ray (GEN_RANK) / k_gen_counts below).
 template <class T, uint32_t F, bool SCENE_IN_LDS>
 __global__ __launch_bounds__(256) void k_gen_probe(SceneBlob blob, T unit, RaysT<T> in, const int32_t* __restrict__ tree, int64_t n,
                                                    const int32_t* __restrict__ budget, int32_t* counts, int32_t n_classes, int32_t* probe) {
@@ -1975,7 +1975,7 @@ __global__ __launch_bounds__(256) void k_gen_pass(SceneBlob blob, T unit, RaysT<
 // and count and emit cannot disagree because there is only one of them.
 // Budgets (optical_table.py:138-144).  The two-pass kernels read budget[tree] in the count pass and let the tree's last ray
 // write it in the emit pass; in one pass that is a race (a tree's rays can span workgroups).  Here every RAY carries what is
-// left of its tree's budget at the start of the generation (rem[], 4 bytes per ray: seeded from budget[] by k_gen_seed_rem
+// left of its tree's budget at the start of the generation (rem[], 4 bytes per ray: seeded from budget[] by k_gen_per_ray (GEN_SEED_REM)
 // before the first generation of a call, handed to the children as rem - min(rays of the tree in this generation, rem));
 // budget[] itself is only WRITTEN (by the tree's last ray) and stays what callers read between calls.
 // Scenes with count-limited leaves keep the two-pass path (their gate needs the per-slot scans between probe and trace).

@@ -111,12 +111,6 @@ __global__ void k_gen_totals(const unsigned long long* wave_total, const unsigne
     }
 }
 
-// k_gen_one's per-ray budgets, seeded from the per-tree table before the first generation of a call (kernels.h)
-__global__ void k_gen_seed_rem(const int32_t* __restrict__ tree, const int32_t* __restrict__ budget, int64_t n, int32_t* __restrict__ rem) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) rem[i] = budget[tree[i]];
-}
-
 // k_gen_recount: the count pass of a generation whose rays were looked ahead by the emit pass that wrote them (k_gen_pass MODE 2):
 // rank within the tree, budget cut and doomed children exactly as the count pass decides them, the number of children from the
 // byte the emit pass left.  Writes the code byte in place of it and the wave totals.
@@ -150,12 +144,22 @@ __global__ __launch_bounds__(256) void k_gen_recount(const int32_t* __restrict__
     if (lane == 0 && (gwave << 6) < n) wave_total[gwave] = ((unsigned long long)n_act << 32) | (unsigned long long)kids;
 }
 
-// rank[slot][i] = how many earlier rays of i's tree (this generation) hit limited leaf `slot`
-__global__ void k_gen_rank(const int32_t* tree, int64_t n, int32_t n_slots, const int32_t* ex, int32_t* rank) {
+// The two elementwise integer passes of the generation path over tree[], one kernel with a launch-uniform mode:
+// GEN_SEED_REM: out[i] = table[tree[i]] — k_gen_one's per-ray budgets rem[], seeded from the per-tree table budget[] before the first
+//   generation of a call (kernels.h); n_slots is not read.
+// GEN_RANK: out[slot][i] = table[slot][i] - table[slot][head of i's tree] — rank[slot][i] = how many earlier rays of i's tree (this
+//   generation) hit limited leaf `slot`, from the exclusive scans ex[] of the probe pass.
+enum : int32_t { GEN_SEED_REM = 0, GEN_RANK = 1 };
+__global__ void k_gen_per_ray(int32_t mode, const int32_t* __restrict__ tree, int64_t n, int32_t n_slots, const int32_t* __restrict__ table,
+                              int32_t* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (mode == GEN_SEED_REM) {
+        out[i] = table[tree[i]];
+        return;
+    }
     const int64_t head = tree_head(tree, i);
-    for (int s = 0; s < n_slots; ++s) rank[(int64_t)s * n + i] = ex[(int64_t)s * n + i] - ex[(int64_t)s * n + head];
+    for (int s = 0; s < n_slots; ++s) out[(int64_t)s * n + i] = table[(int64_t)s * n + i] - table[(int64_t)s * n + head];
 }
 // after the trace: each tree's last ray of the generation folds the generation's hits into the table
 __global__ void k_gen_counts(const int32_t* tree, const int32_t* ids, int64_t n, int32_t n_slots, const int32_t* rank,
@@ -1172,6 +1176,245 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_spots(const ot_monitor* __r
         const int32_t f = i % sp.values;
         if (f < nc) sp.counts[cell * nc + f] = (sp.accumulate ? sp.counts[cell * nc + f] : 0) + (long long)sum[q];
         else sp.sums[cell * ns + f - nc] = sp.accumulate ? sp.sums[cell * ns + f - nc] + sum[q] : sum[q];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Diffraction PSF (ot_monitor_psf_many): U[m][k][l] = sum_j a_j exp(2 pi i (x0_j + gy_j y_k + gz_j z_l)) over the hit list of
+// monitor m (k_mon_emit's: ascending slots), as the complex product [ny x hits] . [hits x nz] that the sum separates into:
+// exp(2 pi i x_j(k, l)) = (a_j c_j Ey_j[k]) Ez_j[l].  One workgroup per (monitor, pixel tile, hit chunk):
+//   pixel tiles: an axis of n samples is ceil(n / 16) SUBTILES of 16, split as evenly as it goes into ceil(subtiles / 4) parts
+//     (mon_psf_part: 65 samples = 5 subtiles = 2 + 3, not 4 + 1), so a tile is at most 4 x 4 subtiles = 64 x 64 samples.  Subtile
+//     q = (row part) * (columns of the tile) + (column part) of a tile belongs to wave q % 4 as its slot q / 4: four slots a wave,
+//     each a 16 x 16 complex accumulator in registers (v_mfma_f64_16x16x4_f64: lane l holds column l & 15, rows (l >> 4) + 4 r).
+//   hit chunks: mon_psf_chunks(hits of the monitor) chunks of ceil(hits / chunks) consecutive hits — a function of the hit count
+//     alone, at most MON_PSF_MAX_CHUNKS.
+// A workgroup walks its chunk in rounds of MON_THREADS hits.  Per round every thread forms one hit's a c = a cis(x0), gy, gz and the
+// two rotations cis(gy dy), cis(gz dz) from the hit list and the segment planes (MonPsf: the arguments of k_mon_spots' wavefront
+// mode and of k_mon_field, read the same way) into LDS, and tallies it; a hit that is skipped, and the places past the end of the
+// chunk, carry a = 0.  Then, MON_PSF_BATCH = 16 hits at a time: every thread builds one RUN of 8 consecutive samples of one axis of
+// one hit — one direct mon_wave_cis at the run's first sample, a complex rotation per sample after it (7 roundings of 2^-53: far
+// inside the 2^-38 the contract leaves the recurrence) — into the tables tab[A re, A im, B re, B im][sample][hit], A = a c Ey, B = Ez
+// (16 hits with 64-sample tiles: more hits a batch and the tables pass the 64 KB a launch gets without a function attribute);
+// a barrier; every wave runs its slots over the batch, four hits a step in list order, four real MFMAs a step and slot
+// (re += Ar Br, re += (-Ai) Bi, im += Ar Bi, im += Ai Br); a barrier.  No transcendental per pixel and no floating-point atomic.
+// The workgroup's accumulators go to partials[workgroup] (write-through stores; in the layout the registers have: the workgroup
+// that reads them has the same lanes on the same elements) with, from the tile 0 of a monitor only, norm = sum a and the three
+// counts behind them; the hand-over, the ticket and the last workgroup's acquire are k_mon_spots'.  The workgroup that draws the
+// last ticket of its (monitor, tile) adds the chunks' partials in ascending chunk order, adds the sum to re, im (and norm, counts:
+// tile 0) — the host has zeroed them unless the call accumulates — and leaves the ticket at zero for the launch after it.
+// The result is a function of the inputs, their layout and (ny, nz) alone.
+// LDS: tables 4 x 64 x 17 doubles (the odd stride keeps the lanes of a wave on different banks, writing and reading), the hits of a
+// round 8 x 256 doubles: 51,200 bytes, three workgroups a CU.
+static constexpr int MON_PSF_BATCH = 16, MON_PSF_STRIDE = MON_PSF_BATCH + 1, MON_PSF_TILE = 64, MON_PSF_RUN = 8, MON_PSF_MAX_SAMPLES = 512;
+static constexpr int MON_PSF_CHUNK_MIN = 512, MON_PSF_MAX_CHUNKS = 256;
+static constexpr int MON_PSF_PARTIAL_ROWS = 1024;                            // partials of one launch: workgroups ...
+static constexpr int MON_PSF_ROW = 2 * MON_PSF_TILE * MON_PSF_TILE + 8;      // ... of this many doubles each (67 MB in all)
+struct MonPsf {
+    const int64_t *first, *hit_index;     // first[n_monitors + 1] into the concatenated hit list (k_mon_emit)
+    const double *Px, *Py, *Pz, *t;       // the hit list
+    const double *axes, *reference, *grid;  // [n_monitors][6], [n_monitors][3] F_loc or u_loc, [n_monitors][4] y0 dy z0 dz
+    const uint8_t *intensity, *n_index, *pathlength;  // double, addressed like the fields of MonSource
+    MonWavelength lam;                    // (lam.skipped is not used: the tally goes through the partials)
+    double* partials;                     // [gridDim.x][MON_PSF_ROW]
+    unsigned int* ticket;                 // [pairs of the launch], 0 before it and after it
+    double *re, *im, *norm;               // [n_monitors][ny][nz] twice, [n_monitors]
+    long long* counts;                    // [n_monitors][3]: used, skipped, aliased
+    int32_t kind, amplitude_mode, ny, nz;
+    int32_t pair0, max_chunks;            // the launch: (monitor, tile) pairs from pair0 on, max_chunks workgroups each
+};
+// chunks of a monitor with `hits` hits, and part `i` of the `parts` an axis of `subtiles` is split into: [first, first + count)
+__host__ __device__ inline int32_t mon_psf_chunks(int64_t hits) {
+    const int64_t c = (hits + MON_PSF_CHUNK_MIN - 1) / MON_PSF_CHUNK_MIN;
+    return (int32_t)(c < 1 ? 1 : c > MON_PSF_MAX_CHUNKS ? MON_PSF_MAX_CHUNKS : c);
+}
+__host__ __device__ inline int32_t mon_psf_parts(int32_t samples) { return ((samples + 15) / 16 + 3) / 4; }
+__host__ __device__ inline int32_t mon_psf_part(int32_t samples, int32_t i, int32_t& count) {
+    const int32_t subtiles = (samples + 15) / 16, parts = mon_psf_parts(samples), first = i * subtiles / parts;
+    count = (i + 1) * subtiles / parts - first;
+    return first;
+}
+typedef double mon_psf_acc __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(MON_THREADS) void k_mon_psf(const ot_monitor* __restrict__ mons, MonSource src, MonPsf ps) {
+    __shared__ double tab[4][MON_PSF_TILE][MON_PSF_STRIDE];
+    __shared__ double par[8][MON_THREADS];  // a c (re, im), gy, gz, cis(gy dy) (re, im), cis(gz dz) (re, im)
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int32_t parts_z = mon_psf_parts(ps.nz), n_tiles = mon_psf_parts(ps.ny) * parts_z;
+    const int32_t pair_local = blockIdx.x / ps.max_chunks, chunk = blockIdx.x % ps.max_chunks;
+    const int32_t m = (ps.pair0 + pair_local) / n_tiles, tile = (ps.pair0 + pair_local) % n_tiles;
+    const int64_t h0 = ps.first[m], hits = ps.first[m + 1] - h0;
+    const int32_t chunks = mon_psf_chunks(hits);
+    if (chunk >= chunks) return;
+    const int64_t per = (hits + chunks - 1) / chunks;
+    const int64_t j0 = h0 + (chunk * per < hits ? chunk * per : hits), j1 = h0 + ((chunk + 1) * per < hits ? (chunk + 1) * per : hits);
+    int32_t sub_y, sub_z;  // the tile: sub_y x sub_z subtiles from sample (row0, col0)
+    const int32_t row0 = 16 * mon_psf_part(ps.ny, tile / parts_z, sub_y), col0 = 16 * mon_psf_part(ps.nz, tile % parts_z, sub_z);
+    const int32_t n_sub = sub_y * sub_z, n_slot = n_sub > wave ? (n_sub - wave + 3) >> 2 : 0;  // this wave's slots
+    const double *ax = ps.axes + 6 * m, *ref = ps.reference + 3 * m, *grid = ps.grid + 4 * m;
+    const double y0 = grid[0], dy = grid[1], z0 = grid[2], dz = grid[3];
+    mon_psf_acc acc_re[4], acc_im[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc_re[q] = acc_im[q] = mon_psf_acc{0.0, 0.0, 0.0, 0.0};
+    int32_t used = 0, skipped = 0, aliased = 0;
+    double norm = 0.0;
+    for (int64_t r0 = j0; r0 < j1; r0 += MON_THREADS) {
+        {  // one hit a thread
+            const int64_t j = r0 + tid;
+            double cr = 0.0, ci = 0.0, gy = 0.0, gz = 0.0, ryr = 1.0, ryi = 0.0, rzr = 1.0, rzi = 0.0;
+            if (j < j1) {
+                const int64_t s = ps.hit_index[j];
+                const double Px = ps.Px[j], Py = ps.Py[j], Pz = ps.Pz[j], t = ps.t[j];
+                const int64_t at = mon_at(s, src.tile_stride, 8);
+                const double n_index = *reinterpret_cast<const double*>(ps.n_index + at), pl = *reinterpret_cast<const double*>(ps.pathlength + at);
+                double wl;
+                bool ok = mon_wavelength(ps.lam, src.ray + mon_at(s, src.ray_stride, 4), wl);
+                const double L = t * n_index + pl;
+                double W;
+                if (ps.kind == 0) {  // the renormalised local direction, as mon_hit formed it
+                    const MonLocal l = mon_local(mons[m], 0.0, 0.0, 0.0, *reinterpret_cast<const double*>(src.base[3] + at),
+                                                 *reinterpret_cast<const double*>(src.base[4] + at), *reinterpret_cast<const double*>(src.base[5] + at));
+                    W = L + n_index * ((ref[0] - Px) * l.dx + (ref[1] - Py) * l.dy + (ref[2] - Pz) * l.dz);
+                    gy = n_index * (l.dx * ax[0] + l.dy * ax[1] + l.dz * ax[2]);
+                    gz = n_index * (l.dx * ax[3] + l.dy * ax[4] + l.dz * ax[5]);
+                } else {
+                    W = L - n_index * (Px * ref[0] + Py * ref[1] + Pz * ref[2]);
+                    gy = -n_index * (Px * ax[0] + Py * ax[1] + Pz * ax[2]);
+                    gz = -n_index * (Px * ax[3] + Py * ax[4] + Pz * ax[5]);
+                }
+                ok = ok && fabs(W) < HUGE_VAL;
+                const double x0 = ok ? W / wl : 0.0;
+                gy = ok ? gy / wl : 0.0, gz = ok ? gz / wl : 0.0;
+                if (!(fabs(gy) < HUGE_VAL && fabs(gz) < HUGE_VAL)) ok = false, gy = gz = 0.0;
+                if (ok) {
+                    double a = 1.0;
+                    if (ps.amplitude_mode != 2) {
+                        const double I = *reinterpret_cast<const double*>(ps.intensity + at);
+                        a = ps.amplitude_mode == 0 ? sqrt(I) : I;
+                    }
+                    const double2 c = mon_wave_cis(x0), ry = mon_wave_cis(gy * dy), rz = mon_wave_cis(gz * dz);
+                    cr = a * c.x, ci = a * c.y, ryr = ry.x, ryi = ry.y, rzr = rz.x, rzi = rz.y;
+                    norm += a;
+                    ++used;
+                    if (fabs(gy * dy) > 0.5 || fabs(gz * dz) > 0.5) ++aliased;
+                } else {
+                    ++skipped;
+                }
+            }
+            par[0][tid] = cr, par[1][tid] = ci, par[2][tid] = gy, par[3][tid] = gz;
+            par[4][tid] = ryr, par[5][tid] = ryi, par[6][tid] = rzr, par[7][tid] = rzi;
+        }
+        __syncthreads();
+        const int32_t in_round = j1 - r0 < MON_THREADS ? (int32_t)(j1 - r0) : MON_THREADS;
+        for (int32_t b0 = 0; b0 < in_round; b0 += MON_PSF_BATCH) {
+            {  // one run a thread: waves 0, 1 the rows (A), waves 2, 3 the columns (B)
+                const int hb = tid & (MON_PSF_BATCH - 1), run = (tid >> 4) & 7, axis = tid >> 7;
+                if (run * MON_PSF_RUN < 16 * (axis ? sub_z : sub_y)) {
+                    const int p = b0 + hb;
+                    const double g = par[2 + axis][p], rr = par[4 + 2 * axis][p], ri = par[5 + 2 * axis][p];
+                    const double k0 = (double)((axis ? col0 : row0) + run * MON_PSF_RUN);
+                    const double v = axis ? z0 + k0 * dz : y0 + k0 * dy;
+                    const double2 e = mon_wave_cis(g * v);
+                    double er = e.x, ei = e.y;
+                    if (!axis) {
+                        const double cr = par[0][p], ci = par[1][p];
+                        er = cr * e.x - ci * e.y, ei = cr * e.y + ci * e.x;
+                    }
+#pragma unroll
+                    for (int i = 0; i < MON_PSF_RUN; ++i) {
+                        tab[2 * axis][run * MON_PSF_RUN + i][hb] = er, tab[2 * axis + 1][run * MON_PSF_RUN + i][hb] = ei;
+                        const double nr = er * rr - ei * ri, ni = er * ri + ei * rr;
+                        er = nr, ei = ni;
+                    }
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int ks = 0; ks < MON_PSF_BATCH / 4; ++ks) {
+                const int hit = 4 * ks + (lane >> 4);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if (q < n_slot) {
+                        const int sub = 4 * q + wave, row = 16 * (sub / sub_z) + (lane & 15), col = 16 * (sub % sub_z) + (lane & 15);
+                        const double ar = tab[0][row][hit], ai = tab[1][row][hit], br = tab[2][col][hit], bi = tab[3][col][hit];
+                        acc_re[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, br, acc_re[q], 0, 0, 0);
+                        acc_re[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(-ai, bi, acc_re[q], 0, 0, 0);
+                        acc_im[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bi, acc_im[q], 0, 0, 0);
+                        acc_im[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br, acc_im[q], 0, 0, 0);
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // the partials: element (slot q, re / im, register r) of lane `lane` of wave `wave` at ((sub * 2 + re / im) * 4 + r) * 64 + lane
+    double* mine = ps.partials + (int64_t)blockIdx.x * MON_PSF_ROW;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (q < n_slot) {
+            double* at = mine + (int64_t)(4 * q + wave) * 512 + lane;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                __hip_atomic_store(at + 64 * r, acc_re[q][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(at + 256 + 64 * r, acc_im[q][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+    if (tile == 0) {  // (uniform for the workgroup) the tallies: a butterfly per wave, the waves in their order
+        const double v[4] = {wave_sum(norm), (double)wave_sum(used), (double)wave_sum(skipped), (double)wave_sum(aliased)};
+        if (lane == 0)
+            for (int i = 0; i < 4; ++i) par[i][wave] = v[i];
+        __syncthreads();
+        if (tid < 4)
+            __hip_atomic_store(mine + MON_PSF_ROW - 8 + tid, ((par[tid][0] + par[tid][1]) + par[tid][2]) + par[tid][3], __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();  // the partials have arrived: word 0 of `tab` now says whether this workgroup is the last of its (monitor, tile)
+    int32_t* last = reinterpret_cast<int32_t*>(&tab[0][0][0]);
+    if (tid == 0) {
+        const unsigned int drawn = __hip_atomic_fetch_add(ps.ticket + pair_local, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *last = drawn == (unsigned int)chunks - 1;
+        if (*last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(ps.ticket + pair_local, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    if (!*last) return;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc_re[q] = acc_im[q] = mon_psf_acc{0.0, 0.0, 0.0, 0.0};
+    const double* rows = ps.partials + (int64_t)(blockIdx.x - chunk) * MON_PSF_ROW;  // the chunks of this pair, in their order
+    for (int32_t c = 0; c < chunks; ++c) {
+        const double* row = rows + (int64_t)c * MON_PSF_ROW;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (q < n_slot) {
+                const double* at = row + (int64_t)(4 * q + wave) * 512 + lane;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc_re[q][r] += at[64 * r], acc_im[q][r] += at[256 + 64 * r];
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (q < n_slot) {
+            const int sub = 4 * q + wave, col = col0 + 16 * (sub % sub_z) + (lane & 15);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = row0 + 16 * (sub / sub_z) + (lane >> 4) + 4 * r;
+                if (row < ps.ny && col < ps.nz) {
+                    const int64_t o = ((int64_t)m * ps.ny + row) * ps.nz + col;
+                    ps.re[o] += acc_re[q][r], ps.im[o] += acc_im[q][r];
+                }
+            }
+        }
+    }
+    if (tile == 0 && tid < 4) {
+        double sum = 0.0;
+        for (int32_t c = 0; c < chunks; ++c) sum += rows[(int64_t)c * MON_PSF_ROW + MON_PSF_ROW - 8 + tid];
+        if (tid == 0) ps.norm[m] += sum;
+        else ps.counts[3 * (int64_t)m + tid - 1] += (long long)sum;
     }
 }
 

@@ -142,6 +142,7 @@ struct ot_ctx {
     int32_t opt_pair = 1;  // paired 16-byte segment stores in the lane-per-ray kernel
     int32_t opt_nt = 1, opt_minw = 4, opt_blocks_per_cu = 0;  // defaults from tools/tune.py on MI355X
     Scratch gen, scan_tmp, mon, gen_rem, gen_ahead, trees;
+    Scratch psf, psf_hits;  // ot_monitor_psf_many: its tables and tickets; the hit list and the partials (sized once the hits are counted)
     int32_t opt_trees_global = 0;      // k_trace_trees: 1 = every scene through the all-features kernel that reads its image from global memory (test knob)
     int32_t opt_uniform = 1;  // the lane-per-ray kernel reads fields flagged in a call's uniform_mask once per wave (0: the mask is dropped)
     int32_t opt_resident = 1; // ... and leaves the planes of a call's resident_mask and the fields of its first_mask unwritten where the output holds them (2: planes only; 0: both masks are dropped)
@@ -612,7 +613,7 @@ int ot_ctx_destroy(ot_ctx* c) {
     for (SceneImage& im : c->image)
         if (im.blob) (void)hipFree(im.blob);
     if (c->slot_max) (void)hipFree(c->slot_max);
-    for (Scratch* s : {&c->gen, &c->gen_rem, &c->gen_ahead, &c->trees, &c->scan_tmp, &c->mon, &c->blocked})
+    for (Scratch* s : {&c->gen, &c->gen_rem, &c->gen_ahead, &c->trees, &c->scan_tmp, &c->mon, &c->psf, &c->psf_hits, &c->blocked})
         if (s->p) (void)hipFree(s->p);
     if (c->gen_mismatch) (void)hipFree(c->gen_mismatch);
     if (c->gen_chain) (void)hipFree(c->gen_chain);
@@ -1358,7 +1359,7 @@ static int trace_generation(ot_ctx* c, const GenSetup<T>& g, const GenBuf& src, 
                            s.probe);
         for (int k = 0; k < ns; ++k)
             exclusive_scan<int32_t, int32_t>(c->scan_tmp.p, s.probe + (int64_t)k * n, s.probe_ex + (int64_t)k * n, n, c->stream);
-        hipLaunchKernelGGL(k_gen_rank, dim3(g1), dim3(block), 0, c->stream, src.tree, n, ns, s.probe_ex, s.rank);
+        hipLaunchKernelGGL(k_gen_per_ray, dim3(g1), dim3(block), 0, c->stream, GEN_RANK, src.tree, n, ns, (const int32_t*)s.probe_ex, s.rank);
     }
     // count -> scan of the wave totals -> emit (kernels.h: k_gen_pass)
     if (ahead_in)
@@ -1580,7 +1581,8 @@ static int trace_tree(ot_ctx* c, const ot_rays* rays, const int32_t* tree, int64
         int src = where, dst = other(where);
         if (one_pass_ok && (c->opt_gen_onepass > 0 || cur_n <= ONE_PASS_SMALL)) {
             if (!rem_valid) {
-                hipLaunchKernelGGL(k_gen_seed_rem, dim3((unsigned)((cur_n + 255) / 256)), dim3(256), 0, c->stream, gen[src].tree, (const int32_t*)budget, cur_n, gen[src].rem);
+                hipLaunchKernelGGL(k_gen_per_ray, dim3((unsigned)((cur_n + 255) / 256)), dim3(256), 0, c->stream, GEN_SEED_REM, gen[src].tree, cur_n, 0,
+                                   (const int32_t*)budget, gen[src].rem);
                 HIP_TRY(hipGetLastError());
             }
             rc = trace_generation_one<T>(c, g, gen[src], cur_n, budget, out, out_capacity, state, gen[dst], buf_capacity, counts, n_classes, nullptr, chain_n);
@@ -2165,6 +2167,103 @@ int ot_monitor_wave_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, 
         hipLaunchKernelGGL(k_mon_wave, dim3((unsigned)p.sp.grid), dim3(MON_THREADS), p.lds_bytes, c->stream, p.table, p.nm, p.ms, n, p.sp.iters, seg_count,
                            n_rays, p.img, wav);
     });
+}
+
+// Diffraction PSF: the hit list of ot_monitor_record_many into scratch of the context's own, then k_mon_psf (misc_kernels.h) over
+// (monitor, pixel tile, hit chunk).  The hit list is sized exactly: record_passes runs once with no room (its emit pass then writes
+// first[] and nothing else), the n_monitors + 1 offsets come back to the host — the call's one synchronisation — and it runs
+// again into a list of that size.  The offsets also give every monitor's chunk count (mon_psf_chunks), the same number the kernel
+// forms on the device.  A launch takes max(1, MON_PSF_PARTIAL_ROWS / (most chunks of a monitor)) (monitor, tile) pairs, so its
+// partials stay within MON_PSF_PARTIAL_ROWS rows of MON_PSF_ROW doubles; the launches of a call follow one another on the stream
+// and share partials and tickets.  optable_amd/engine.py psf_plan says the same.
+int ot_monitor_psf_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, int32_t reference_kind, const double* reference,
+                        const double* grid, int32_t ny, int32_t nz, const ot_segment_source* src, const void* intensity, const void* n_index,
+                        const void* pathlength, const double* wavelength, int64_t n_wavelengths, double wavelength_uniform, int32_t amplitude_mode,
+                        int64_t n, const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* norm, double* re, double* im,
+                        int32_t accumulate) {
+    static_assert(MON_PSF_MAX_SAMPLES == OT_PSF_MAX_SAMPLES && MON_PSF_PARTIAL_ROWS * (int64_t)MON_PSF_ROW * 8 == OT_PSF_SCRATCH_BYTES, "the header's constants");
+    if (!c || !mons || !axes || !reference || !grid || !src || !n_index || !pathlength || !counts || !norm || !re || !im)
+        return fail(OT_ERR_INVALID, "NULL argument");
+    if (n_monitors < 1 || n_monitors > 1 << 20) return fail(OT_ERR_INVALID, "n_monitors must be 1 .. 2^20");
+    if (reference_kind != 0 && reference_kind != 1) return fail(OT_ERR_INVALID, "reference_kind must be 0 (focus) or 1 (direction)");
+    if (ny < 1 || ny > MON_PSF_MAX_SAMPLES || nz < 1 || nz > MON_PSF_MAX_SAMPLES) return fail(OT_ERR_INVALID, "ny and nz must be 1 .. 512");
+    if (amplitude_mode < 0 || amplitude_mode > 2) return fail(OT_ERR_INVALID, "amplitude_mode must be 0 (sqrt), 1 (linear) or 2 (unit)");
+    if (amplitude_mode != 2 && !intensity) return fail(OT_ERR_INVALID, "NULL intensity");
+    const ReduceCall a{c, mons, n_monitors, axes, src, intensity, n, seg_count, n_rays, counts, norm, accumulate};
+    if (const int rc = check_reduce_call(a)) return rc;
+    if (src->width != 8) return fail(OT_ERR_INVALID, "a PSF needs double-precision segments: width must be 8");
+    if (const int rc = check_wavelength_args(wavelength, n_wavelengths, wavelength_uniform)) return rc;
+    for (int64_t m = 0; m < n_monitors; ++m) {
+        const double *r = reference + 3 * m, *g = grid + 4 * m;
+        if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2])) return fail(OT_ERR_INVALID, "reference must be finite");
+        if (reference_kind == 1 && r[0] == 0.0 && r[1] == 0.0 && r[2] == 0.0) return fail(OT_ERR_INVALID, "the direction of a plane wave must not be zero");
+        if (!std::isfinite(g[0]) || !std::isfinite(g[1]) || !std::isfinite(g[2]) || !std::isfinite(g[3])) return fail(OT_ERR_INVALID, "grid must be finite");
+        if (!(g[1] > 0.0) || !(g[3] > 0.0)) return fail(OT_ERR_INVALID, "the steps of a grid must be positive");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t pixels = (size_t)n_monitors * ny * nz;
+    if (!accumulate) {
+        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * 3 * (size_t)n_monitors, c->stream));
+        HIP_TRY(hipMemsetAsync(norm, 0, sizeof(double) * (size_t)n_monitors, c->stream));
+        HIP_TRY(hipMemsetAsync(re, 0, sizeof(double) * pixels, c->stream));
+        HIP_TRY(hipMemsetAsync(im, 0, sizeof(double) * pixels, c->stream));
+    }
+    if (n == 0) return 0;
+    ot_monitor* table;
+    int64_t *first, *n_total;
+    double *d_axes, *d_reference, *d_grid;
+    unsigned int* tickets;
+    const auto carve = [&](void* base) {
+        Carve cv{(uint8_t*)base};
+        table = cv.take<ot_monitor>(n_monitors), first = cv.take<int64_t>((size_t)n_monitors + 1), n_total = cv.take<int64_t>(1);
+        d_axes = cv.take<double>(6 * (size_t)n_monitors), d_reference = cv.take<double>(3 * (size_t)n_monitors), d_grid = cv.take<double>(4 * (size_t)n_monitors);
+        tickets = cv.take<unsigned int>(MON_PSF_PARTIAL_ROWS);
+        return cv.used;
+    };
+    if (c->psf.ensure(carve(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of PSF scratch failed");
+    carve(c->psf.p);
+    const MonSource ms = mon_source(src);
+    if (const int rc = record_passes(c, mons, n_monitors, ms, n, seg_count, n_rays, 0, first, nullptr, nullptr, nullptr, nullptr, nullptr, n_total)) return rc;
+    std::vector<int64_t> host_first((size_t)n_monitors + 1);
+    HIP_TRY(hipMemcpyAsync(host_first.data(), first, sizeof(int64_t) * host_first.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int64_t total = host_first[n_monitors];
+    if (total == 0) return 0;
+    int32_t max_chunks = 1;
+    for (int32_t m = 0; m < n_monitors; ++m) max_chunks = std::max(max_chunks, mon_psf_chunks(host_first[m + 1] - host_first[m]));
+    const int64_t n_pairs = (int64_t)n_monitors * mon_psf_parts(ny) * mon_psf_parts(nz);
+    const int64_t pairs_a_launch = std::min<int64_t>(n_pairs, std::max(1, MON_PSF_PARTIAL_ROWS / max_chunks));
+    int64_t* hit_index;
+    double *Px, *Py, *Pz, *tt, *partials;
+    const auto carve_hits = [&](void* base) {
+        Carve cv{(uint8_t*)base};
+        hit_index = cv.take<int64_t>(total), Px = cv.take<double>(total), Py = cv.take<double>(total), Pz = cv.take<double>(total), tt = cv.take<double>(total);
+        partials = cv.take<double>((size_t)pairs_a_launch * max_chunks * MON_PSF_ROW);
+        return cv.used;
+    };
+    if (c->psf_hits.ensure(carve_hits(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of the PSF hit list failed");
+    carve_hits(c->psf_hits.p);
+    if (const int rc = record_passes(c, mons, n_monitors, ms, n, seg_count, n_rays, total, first, hit_index, Px, Py, Pz, tt, n_total)) return rc;
+    HIP_TRY(hipMemcpyAsync(table, mons, sizeof(ot_monitor) * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_axes, axes, sizeof(double) * 6 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_reference, reference, sizeof(double) * 3 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_grid, grid, sizeof(double) * 4 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(tickets, 0, sizeof(unsigned int) * MON_PSF_PARTIAL_ROWS, c->stream));
+    MonPsf ps{};
+    ps.first = first, ps.hit_index = hit_index, ps.Px = Px, ps.Py = Py, ps.Pz = Pz, ps.t = tt;
+    ps.axes = d_axes, ps.reference = d_reference, ps.grid = d_grid;
+    ps.intensity = (const uint8_t*)intensity, ps.n_index = (const uint8_t*)n_index, ps.pathlength = (const uint8_t*)pathlength;
+    ps.lam = {wavelength, nullptr, wavelength_uniform, (int32_t)n_wavelengths};
+    ps.partials = partials, ps.ticket = tickets;
+    ps.re = re, ps.im = im, ps.norm = norm, ps.counts = (long long*)counts;
+    ps.kind = reference_kind, ps.amplitude_mode = amplitude_mode, ps.ny = ny, ps.nz = nz, ps.max_chunks = max_chunks;
+    for (int64_t pair0 = 0; pair0 < n_pairs; pair0 += pairs_a_launch) {
+        ps.pair0 = (int32_t)pair0;
+        const int64_t pairs = std::min(pairs_a_launch, n_pairs - pair0);
+        hipLaunchKernelGGL(k_mon_psf, dim3((unsigned)(pairs * max_chunks)), dim3(MON_THREADS), 0, c->stream, table, ms, ps);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 int ot_debug_last_launch(ot_ctx* c, int32_t info[8]) {

@@ -204,6 +204,42 @@ def wavefront_plan(n_monitors):
     return _cell_plan(n_monitors, WAVEFRONT_MONITORS)
 
 
+# -- diffraction PSF (ot_monitor_psf_many) -------------------------------------------------------------------------------------
+PSF_MAX_SAMPLES = 512             # optable_hip.h OT_PSF_MAX_SAMPLES: ny, nz of one call
+PSF_CHUNK_MIN = 512               # misc_kernels.h MON_PSF_CHUNK_MIN: hits of a chunk before a monitor gets another one
+PSF_MAX_CHUNKS = 256              # MON_PSF_MAX_CHUNKS: hit chunks of one monitor
+PSF_PARTIAL_ROWS = 1024           # MON_PSF_PARTIAL_ROWS: workgroups of one launch
+PSF_ROW = 2 * 64 * 64 + 8         # MON_PSF_ROW: doubles of a workgroup's partial image (a 64 x 64 tile, re and im, and the tallies)
+PSF_SCRATCH_BYTES = PSF_PARTIAL_ROWS * PSF_ROW * 8  # optable_hip.h OT_PSF_SCRATCH_BYTES
+PSF_AMPLITUDES = ("sqrt", "linear", "unit")  # amplitude_mode 0, 1, 2
+
+
+def _psf_parts(samples):
+    """The pixel tiles along an axis of `samples` samples as (first sample, samples): the ceil(samples / 16) subtiles of 16 split as
+    evenly as it goes into ceil(subtiles / 4) parts (misc_kernels.h mon_psf_part, the same rule)."""
+    subtiles = -(-samples // 16)
+    parts = -(-subtiles // 4)
+    cuts = [i * subtiles // parts for i in range(parts + 1)]
+    return [(16 * a, min(16 * b, samples) - 16 * a) for a, b in zip(cuts, cuts[1:])]
+
+
+def psf_plan(ny, nz, hits=()):
+    """How ot_monitor_psf_many walks an image of ny x nz samples whose monitors have `hits` hits each (optable_hip.hip, the same
+    rule): {"tiles": the pixel tiles as (first row, rows, first column, columns), at most 64 x 64; "chunks": per monitor, the
+    workgroups a tile's hits are split over — ceil(hits / PSF_CHUNK_MIN), 1 .. PSF_MAX_CHUNKS, a function of the hit count alone;
+    "chunk_hits": per monitor, the hits of a chunk; "pairs_a_launch", "launches": the (monitor, tile) pairs one launch takes so that
+    its partial images stay within PSF_PARTIAL_ROWS rows (PSF_SCRATCH_BYTES), and the launches that makes}."""
+    ny, nz, hits = int(ny), int(nz), [int(h) for h in hits]
+    if not 1 <= ny <= PSF_MAX_SAMPLES or not 1 <= nz <= PSF_MAX_SAMPLES or any(h < 0 for h in hits):
+        raise ValueError(f"no PSF of {ny} x {nz} samples (1 .. {PSF_MAX_SAMPLES})")
+    tiles = [(r0, r, c0, c) for r0, r in _psf_parts(ny) for c0, c in _psf_parts(nz)]
+    chunks = [min(max(-(-h // PSF_CHUNK_MIN), 1), PSF_MAX_CHUNKS) for h in hits]
+    pairs = len(hits) * len(tiles)
+    a_launch = min(pairs, max(1, PSF_PARTIAL_ROWS // max(chunks, default=1)))
+    return {"tiles": tiles, "chunks": chunks, "chunk_hits": [-(-h // c) for h, c in zip(hits, chunks)], "pairs_a_launch": a_launch,
+            "launches": -(-pairs // a_launch) if pairs else 0}
+
+
 # -- what the private halves of monitor_*_many and fluence_map share: arguments in, outputs out -------------------------------
 def _doubles(array):
     return array.ctypes.data_as(C.POINTER(C.c_double))
@@ -995,6 +1031,38 @@ class Engine:
         return self._reduce_many("ot_monitor_wavefront_many", mons, tables, segs, weighted, ("n", "pathlength"),
                                  [(torch.int64, (M, 2)), (torch.float64, (M, WAVEFRONT_SUMS))], into,
                                  f"into: contiguous int64 counts of shape [{M}, 2] and float64 sums of shape [{M}, {WAVEFRONT_SUMS}] on {segs.device}")
+
+    def monitor_psf_many(self, monitor_structs, axes, reference_kind, reference, grid, pixels, segs: SegmentBatch, wavelength, amplitude_mode=0,
+                         into=None):
+        """The diffraction PSF of a list of monitors over a double-precision SegmentBatch read as it lies (ot_monitor_psf_many): the
+        plane waves of every monitor's hits summed over its grid of samples.  axes: [M, 6] doubles (a_y, a_z per monitor);
+        reference_kind 0: reference [M, 3] is the focus in every monitor's frame, 1: the plane wave's unit direction there; grid:
+        [M, 4] doubles (y0, dy, z0, dz); pixels = (ny, nz).  wavelength: a float for all rays, or a float64 device tensor indexed by
+        the segments' `ray`; amplitude_mode: 0 = sqrt(intensity), 1 = intensity, 2 = 1.  Returns (counts, norm, re, im): int64 [M, 3]
+        (used, skipped, aliased), float64 [M] (the summed amplitudes) and float64 [M, ny, nz] twice, device tensors zeroed by the
+        call — or `into`, such a tuple from an earlier call, with this call's hits added to it.  The same bits every run."""
+        with self.lock:
+            return self._monitor_psf_many(list(monitor_structs), axes, reference_kind, reference, grid, pixels, segs, wavelength, amplitude_mode, into)
+
+    def _monitor_psf_many(self, mons, axes, reference_kind, reference, grid, pixels, segs, wavelength, amplitude_mode, into):
+        dev, M, (ny, nz) = segs.device, len(mons), pixels
+        axes, reference, grid = _float64_tables(f"axes must be [{M}, 6], reference [{M}, 3] and grid [{M}, 4]", (axes, (M, 6)), (reference, (M, 3)),
+                                                (grid, (M, 4)))
+        if segs.precision != "f64":
+            raise ValueError("a PSF needs double-precision segments")
+        psf_plan(ny, nz)
+        wavelength = _wavelength_arg(wavelength, dev)
+        outs = _outputs(dev, [(torch.int64, (M, 3)), (torch.float64, (M,)), (torch.float64, (M, ny, nz)), (torch.float64, (M, ny, nz))], into,
+                        torch.zeros,  # (zeros: the library is not called for nothing)
+                        f"into: contiguous int64 counts of shape [{M}, 3], float64 norm of shape [{M}] and float64 re, im of shape [{M}, {ny}, {nz}] on {dev}")
+        src, n_segments, count, n_rays = segment_source(segs)
+        if M == 0 or n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
+            return outs
+        abi.check(self.lib.ot_monitor_psf_many(self._ctx, (abi.OtMonitor * M)(*mons), M, _doubles(axes), int(reference_kind), _doubles(reference),
+                                               _doubles(grid), ny, nz, C.byref(src), segs.field("intensity").data_ptr(), segs.field("n").data_ptr(),
+                                               segs.field("pathlength").data_ptr(), *wavelength, int(amplitude_mode), n_segments, _address(count), n_rays,
+                                               *(t.data_ptr() for t in outs), 0 if into is None else 1), self.lib)
+        return outs
 
     def monitor_field_many(self, monitor_structs, axes, edges, bins, segs: SegmentBatch, wavelength, amplitude_mode=0, into=None):
         """Coherent detector images of a list of monitors over a double-precision SegmentBatch read as it lies

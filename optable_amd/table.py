@@ -401,6 +401,63 @@ class OpticalTable:
         return self.wavefront_all(segs, focus=focus, direction=direction, pupil=pupil, coordinates=coordinates, monitors=[monitor], weight=weight,
                                   piston=piston)[0]
 
+    def psf_all(self, segs, wavelength, focus=None, direction=None, step=None, pixels=65, centre=(0.0, 0.0), monitors=None, amplitude="sqrt",
+                into=None):
+        """Every monitor of the table (or those given) as a DIFFRACTION IMAGE: one `MonitorPSF` per monitor, in their order — the
+        plane waves of the hits of `record_all`, every hit on every sample, summed over a grid of `pixels` samples (an int or
+        (ny, nz), 1 .. 512) `step` apart (a number or (dy, dz), required) on the device (ot_monitor_psf_many).  Exactly one of
+        `focus` (a point F, lab frame: the samples are the points F + y a_y + z a_z of the plane through F parallel to the monitor,
+        `step` is a length, and every ray counts as the plane wave it locally is) or `direction` (a vector u: the samples are the
+        directions u + y a_y + z a_z, `step` is in direction cosines — the far field of an afocal system), one for all monitors or
+        one per monitor; the optical path of a hit is `wavefront_all`'s W against the same reference.  Sample k of an axis of n lies
+        at c + (k - (n - 1) / 2) x step, c from `centre` = (y, z): an odd count puts a sample on the reference itself.
+        `wavelength`: one float for all rays, or the `RayBatch` that was traced, as for `field_all`.  amplitude: "sqrt"
+        (sqrt(intensity): intensity is a power), "linear" or "unit" (every hit 1).  The model: each ray is a plane-wave sample, so
+        the result is the diffraction PSF when the rays sample the direction cosines (`focus`) or the pupil positions
+        (`direction`) uniformly, with the intensity as weight, and that distribution's weighted sum for any other; no pi on
+        reflection; hits of different wavelengths add coherently; the image repeats with the period wavelength / (n x ray
+        spacing).  Hits whose phase turns more than half a cycle from one sample to the next are summed all the same, counted in
+        `MonitorPSF.aliased` and announced by one RuntimeWarning.  The result is the same bits every run.  `segs` must be double
+        precision.  `into`: the list an earlier call with the same monitors, reference, grid and amplitude returned; this call's
+        hits are added to it (a field is linear: the chunks of a streamed trace add)."""
+        import warnings
+        from .psf import MonitorPSF, psf_amplitude, psf_grid
+        from .wavefront import wavefront_reference
+
+        monitors = list(self.monitors if monitors is None else monitors)
+        M = len(monitors)
+        kind, lab, local = wavefront_reference(focus, direction, monitors)
+        grid, pixels, step, centres = psf_grid(step, pixels, centre, M)
+        mode = psf_amplitude(amplitude)
+        if segs.precision != "f64":
+            raise ValueError("psf_all needs a double-precision SegmentBatch: a path length in single precision is a hundredth of a wave wrong at table scale")
+        wavelength = _wavelengths_of(wavelength, segs, "a PSF")
+        name = ("focus", "direction")[kind]
+        stack = None
+        if into is not None:
+            into, stack = _into_stack(into, M, lambda k, p: isinstance(p, MonitorPSF) and p.monitor is monitors[k] and p.amplitude == amplitude
+                                      and p.reference == (name, tuple(lab[k])) and p.step == step and p.centre == tuple(centres[k])
+                                      and tuple(p.re.shape) == pixels,
+                                      "into: the list an earlier psf_all returned for the same monitors, reference, grid and amplitude")
+            if not monitors:
+                return into
+        before = 0 if stack is None else int(stack[0][:, 2].sum().item())
+        counts, norm, re, im = _engine().monitor_psf_many([monitor_struct(m) for m in monitors], _monitor_axes(monitors), kind, local, grid, pixels, segs,
+                                                          wavelength, amplitude_mode=mode, into=stack)
+        if into is None:
+            into = [MonitorPSF(m, counts[k], norm[k], re[k], im[k], (name, lab[k]), grid[k], step, centres[k], amplitude, stack=(counts, norm, re, im, k))
+                    for k, m in enumerate(monitors)]
+        aliased = (int(counts[:, 2].sum().item()) if M else 0) - before
+        if aliased > 0:
+            warnings.warn(f"psf_all: {aliased} hits are aliased — their phase turns more than half a cycle from one sample to the next, and the "
+                          "sampled image means nothing for them: use a smaller step", RuntimeWarning, stacklevel=2)
+        return into
+
+    def psf_batch(self, monitor, segs, wavelength, focus=None, direction=None, step=None, pixels=65, centre=(0.0, 0.0), amplitude="sqrt"):
+        """One monitor as a diffraction image (`psf_all` for it alone): a `MonitorPSF`."""
+        return self.psf_all(segs, wavelength, focus=focus, direction=direction, step=step, pixels=pixels, centre=centre, monitors=[monitor],
+                            amplitude=amplitude)[0]
+
     def field_all(self, segs, wavelength=0.0, bins=30, monitors=None, into=None, amplitude="sqrt"):
         """Every monitor of the table (or those given) as a COHERENT image: one `MonitorField` per monitor, in their order — per
         bin of `image_all`'s images the count of hits and the complex sum of a exp(i phi) over them, summed on the device in the

@@ -97,11 +97,13 @@ def kernels_meta(dev):
         if not m:
             continue
         indent, dash, key, val = len(m.group(1)), m.group(2), m.group(3), m.group(4).strip().strip("'")
-        if key == ".args":
+        if dash and indent < 6:  # "  - .agpr_count: ..." opens a kernel's entry: its keys, .args among them, follow in alphabetical order
             flush_arg()
             if lines or cur:
                 entries.append((cur, lines))
-            cur, lines, in_args = None, [], True
+            cur, lines, in_args = None, [], False
+        if key == ".args":
+            in_args = True
             continue
         if in_args and indent >= 6:
             if dash:
