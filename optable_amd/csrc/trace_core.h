@@ -719,7 +719,17 @@ __device__ __forceinline__ bool hit_leaf(const Scene<T>& sc, const DNode<T>& nd,
             const T disc = nd.rad2 - (cx * cx + cy * cy + cz * cz);
             if (!(disc > T(0))) return false;  // the line stays outside: g never changes sign
             const T hc = sqrt_t(disc);
-            const T r0 = tca - hc, r1 = tca + hc;
+            T r0 = tca - hc, r1 = tca + hc;
+            // fp32: a ray emitted ON this cap (own) has one root at its start point, which the |t| < EPS filter below throws
+            // away as the reference does.  The start point carries the rounding of the segment that led to it — an ulp of
+            // its coordinates, 1.5e-5 at 130 after a segment of 100 — so that root can land beyond EPS = 1e-5 and the ray would
+            // meet the cap a second time where it left it.  Away from grazing (half-chord > 0.05 R, the generic path's
+            // |dg0| > 0.05) the root nearer to zero IS the start point's when it is small against the chord: it is put at
+            // exactly 0, where exact arithmetic has it — in the first interval for the same-interval rule, dropped by the filter.
+            if (sizeof(T) == 4 && own && hc > T(0.05) * nd.p[0]) {
+                const bool first = abs_t(r0) <= abs_t(r1);
+                if (abs_t(first ? r0 : r1) < T(1e-3) * hc) { if (first) r0 = T(0); else r1 = T(0); }
+            }
             const T inv_step = qd(T(9), b - a);
             const bool in0 = r0 > a && r0 < b, in1 = r1 > a && r1 < b;
             const int i0 = min((int)((r0 - a) * inv_step), 8), i1 = min((int)((r1 - a) * inv_step), 8);

@@ -94,7 +94,8 @@ def audit(scene, s64, s32, K):
 # General divergence audit
 #
 # A ray is EXPLAINED when the decision at which its two traces part is marginal in the fp64 trace: its margin (a
-# distance for `edge`, `tie`, `guard` and `escape`; |1 - sin^2 theta_t| for `tir`) is at most C * delta + FLOOR[prec],
+# distance for `edge`, `tie`, `guard`, `escape` and the root-search causes `box`, `scan`, `cut`, `graze` of a spherical
+# cap; |1 - sin^2 theta_t| for `tir`) is at most C * delta + FLOOR[prec],
 # where delta = |dO| + L |dD| is how far apart the two traces already were where they parted.
 #
 # C: a start moved by dO and a direction turned by dD move the hit point by |dO| + L |dD| along the surface, times
@@ -110,6 +111,7 @@ C_DELTA = 10.0
 FLOOR = {"f64": 1e-10, "f32": 1e-4}
 GUARD = {"f64": 1e-9, "f32": 1e-5}  # self-hit guard: trace_core.h Num<T>::eps_t (the oracle: EPS_T)
 GUARD_FACTOR = 10.0  # `guard` explains a deciding segment shorter than this many guards ...
+CAUSES = ("edge", "tie", "tir", "guard", "escape", "box", "scan", "cut", "graze")
 _MIRROR, _REFRACT = 0, 1  # OT_INT_* (include/optable_hip.h)
 _MAT_CONST, _MAT_SELLMEIER, _MAT_CHEB = 0, 1, 2
 
@@ -229,6 +231,55 @@ class _Leaves:
         off = abs(float(surf.f(loc)))
         return off if surf.within_boundary(loc) else float(np.hypot(off, _boundary_distance(surf, loc)))
 
+    def search_margins(self, leaf, O, D, P):
+        """The decisions of the root search of a spherical cap (trace_core.h hit_leaf, optical_component.py:206-233) that are no
+        aperture edge, for the lab ray (O, D) and a hit point P on it, each with its margin in scene units, measured on
+        that ray (the fp64 trace's):
+          box    distance of P to the nearest face of the leaf's local box: the search runs over the ray's crossing of the
+                 box only, and a cap deeper than a hemisphere has its belly outside it;
+          scan   the ten samples of the crossing: distance of a root to the nearest sample (a root that changes its sample
+                 interval changes which intervals show a sign change; two roots in one interval show none) and
+                 |chord - step|;
+          cut    |t - 100| of the nearest root (|t1 - 100| when the whole crossing lies beyond): the search ends at t = 100;
+          graze  |R - distance of the line to the centre|: whether there are roots at all.
+        {} for any other leaf."""
+        surf = self.surface(leaf) if leaf >= 0 else None
+        if type(surf).__name__ != "Sphere" or not (np.all(np.isfinite(O)) and np.all(np.isfinite(D))):
+            return {}
+        nd = self.nodes[self.node[leaf]]
+        o, M = self.local(leaf, O)
+        d = M.T @ np.asarray(D, dtype=float)
+        d = d / np.linalg.norm(d)
+        box = np.asarray(nd["lbox"], dtype=float).reshape(3, 2)
+        out = {}
+        if P is not None and np.all(np.isfinite(P)):
+            loc, _ = self.local(leaf, P)
+            out["box"] = float(np.min(np.abs(loc[:, None] - box)))
+        R = float(surf.radius)
+        tca = -float(o @ d)
+        c2 = float(np.sum((o + tca * d) ** 2))
+        out["graze"] = abs(R - np.sqrt(c2))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ta, tb = (box[:, 0] - o) / d, (box[:, 1] - o) / d
+        ta, tb = np.where(np.isnan(ta), -np.inf, ta), np.where(np.isnan(tb), np.inf, tb)
+        t1, t2 = float(np.max(np.minimum(ta, tb))), float(np.min(np.maximum(ta, tb)))
+        eps = GUARD["f64"]
+        if c2 >= R * R or t2 + eps < t1:
+            return out
+        half = np.sqrt(R * R - c2)
+        roots = np.array([tca - half, tca + half])
+        if max(t1, 0.0) > 100.0:
+            out["cut"] = max(t1, 0.0) - 100.0
+            return out
+        a, b = max(t1, 0.0) - eps, min(t2, 100.0) + eps
+        samples = a + (b - a) / 9.0 * np.arange(10)
+        near = np.abs(roots[:, None] - samples[None, :])
+        if t2 > 100.0:
+            out["cut"] = float(np.min(near[:, -1]))
+            near = near[:, :-1]
+        out["scan"] = float(min(np.min(near), abs(2 * half - (b - a) / 9.0)))
+        return out
+
     def _index(self, mat, wl_m):
         m = self.scene.materials[mat]
         if m.kind == _MAT_CONST:
@@ -309,8 +360,8 @@ def audit_traces(scene, ref, got, prec="f64", tol=None, rays=None):
     direction.  rays: the input rays' host dict (their wavelengths are what `tir` needs in dispersive glass).
 
     Returns a dict of arrays over the diverged rays: ray, kstar (first differing record of the tree, FIFO order), leaf_ref
-    / leaf_got (surfaces there; -1 escaped, -2 dead), cause ("edge", "tie", "tir", "guard", "escape"; "prefix" when an
-    earlier record disagrees, "missing" when a record is absent, "unexplained" otherwise), margin, delta, bound
+    / leaf_got (surfaces there; -1 escaped, -2 dead), cause ("edge", "tie", "tir", "guard", "escape", and for a spherical cap
+    the decisions of its root search, "box", "scan", "cut", "graze": _Leaves.search_margins; "prefix" when an earlier record disagrees, "missing" when a record is absent, "unexplained" otherwise), margin, delta, bound
     (C_DELTA * delta + FLOOR[prec]) and explained; plus `same` (bool per input ray) and `n_rays`."""
     if tol is None:
         tol = 1e-9 if prec == "f64" else 2e-3
@@ -375,15 +426,26 @@ def audit_traces(scene, ref, got, prec="f64", tol=None, rays=None):
                 if a != b and max(a, b) >= 0:
                     short = min(x for x in (La[k], Lb[k]) if np.isfinite(x))
                     cand["guard"] = max(short - GUARD_FACTOR * GUARD[prec], 0.0)
+                if a != b:
+                    for leaf, P in ((a, Pa), (b, Pb)):
+                        for c, m in leaves.search_margins(leaf, Oa[k], Da[k], P).items():
+                            cand[c] = min(cand.get(c, np.inf), m)
                 if cand:
                     cause = min(cand, key=lambda c: cand[c])
                     margin = float(cand[cause])
                 break
             if not (_close(La[k], Lb[k], tol)):
-                cause = "prefix"
+                # the same leaf at another root (a cap met on its far side where the other trace met the near one)
+                cand = {}
+                for L in (La[k], Lb[k]):
+                    for c, m in leaves.search_margins(int(Sa[k]), Oa[k], Da[k], Oa[k] + L * Da[k] if np.isfinite(L) else None).items():
+                        cand[c] = min(cand.get(c, np.inf), m)
+                cand.pop("graze", None)  # (both traces found roots)
+                cause = min(cand, key=lambda c: cand[c]) if cand else "prefix"
+                margin = float(cand[cause]) if cand else np.inf
                 break
         bound = C_DELTA * delta + floor if np.isfinite(delta) else floor
-        ok = cause in ("edge", "tie", "tir", "guard", "escape") and margin <= bound
+        ok = cause in CAUSES and margin <= bound
         out["ray"].append(int(r))
         out["kstar"].append(int(k))
         out["leaf_ref"].append(int(Sa[k]) if k < len(Sa) else -9)

@@ -4,7 +4,9 @@ Random rays rarely come within 1e-9 of an aperture edge, so the differential fuz
 decide between two surfaces.  Here every ray is marginal on purpose: for each aperture family (circle, rectangle,
 polygon, cylinder theta end, sphere cap, asphere, boolean aperture), for total internal reflection at the critical
 angle and for two mirrors through one line (a tie), rays start at signed offsets of 1e-3 .. 1e-12 scene units from the
-decision.  The oracle confirms which side each ray is on.  They are traced in fp64 and fp32, by the default call and
+decision; so do rays at the decisions of a spherical cap's root search (the rim and the local box of a cap deeper than a
+hemisphere, a tangent line, a chord as long as the scan's sample step, a hit at the t = 100 cut) and at a reflex vertex and
+a vertex level of a concave polygon.  The oracle confirms which side each ray is on.  They are traced in fp64 and fp32, by the default call and
 by the forced lane-per-ray and rolling-list kernels in the slots, tiled and append layouts, in batches that are not
 multiples of 64 with the marginal rays in the last partial wave:
   - fp64 rays whose offset is above the fp64 floor match the oracle exactly (sequence; fields within 1e-9),
@@ -88,10 +90,64 @@ def _family(name):
         comps = [oa.Mirror([5, 0, 0], radius=1.0), oa.Mirror([5, 0, 0], radius=1.0).RotZ(0.1)]
         o, d = _rim_rays(OFFSETS, [0, 0, 0.3], [0, 1, 0], [1, 0, 0])
         return comps, o, d, OFFSETS, ([0, 0.5, 0], [1, 0, 0])
+    if name.startswith("sphere_") and name != "sphere_t100":
+        # a reflective cap deeper than a hemisphere: x in [R - h, R] = [-1.2, 2]; its local box has the half-width a = 1.6 < R
+        R, h = DEEP_CAP
+        cap = oa.SphereRefractive([0, 0, 0], radius=R, height=h, n1=1.0, n2=1.0, reflectivity=1.0, transmission=0.0)
+        a = cap.surface.get_bbox_local()[3]
+        eps = 1e-9  # the reference's EPS: the search interval is the box crossing widened by it at both ends
+        if name == "sphere_deep_rim":  # along +x at r = a + offset, on the diagonal (inside the box): the first root has x = -sqrt(R^2 - r^2),
+            # on the cap for r >= a; below that the ray enters through the mouth and meets the crown from inside
+            u = np.array([0, 1, 1]) / np.sqrt(2)
+            o, d = _rim_rays(OFFSETS, np.array([-6.0, 0, 0]) + a * u, u, [1, 0, 0])
+        elif name == "sphere_box_face":  # along +x at y = a + offset, z = 0.5: the belly (x = -1.09) is searched from inside the box only
+            o, d = _rim_rays(OFFSETS, [-6, a, 0.5], [0, 1, 0], [1, 0, 0])
+        elif name == "sphere_tangent":  # along +y, at R + offset from the centre; from y = -a / 2 the point of contact is sample 3 of the
+            # scan (0, a / 6, .., 1.5 a), so a chord of any length has its roots in two intervals
+            u = np.array([0.8, 0, 0.6])
+            o, d = _rim_rays(OFFSETS, R * u + [0, -a / 2, 0], u, [0, 1, 0])
+        elif name == "sphere_chord":  # along +y across the whole box, the chord centred in the middle interval: found iff chord > step
+            step = (2 * a + 2 * eps) / 9
+            x = np.sqrt(R * R - ((step + OFFSETS) / 2) ** 2)
+            o = np.stack([x, np.full_like(x, -5.0), np.zeros_like(x)], 1)
+            d = np.tile([0.0, 1.0, 0.0], (len(o), 1))
+        else:
+            raise KeyError(name)
+        return [cap], o, d, OFFSETS, ([-6, 0.3, 0.2], [1, 0, 0])
+    if name == "sphere_t100":  # a hit at t = 100 + offset (the search ends at min(t2, 100) + EPS): the crown at x = 0, centre at x = -R
+        R = T100_X - 100.0
+        cap = oa.SphereRefractive([-R, 0, 0], radius=R, height=0.5, n1=1.0, n2=1.0, reflectivity=1.0, transmission=0.0)
+        x_hit = -R + np.sqrt(R * R - 0.25)
+        o, d = _rim_rays(OFFSETS, [x_hit + 100.0 + 1e-9, 0.5, 0], [1, 0, 0], [-1, 0, 0])
+        return [cap, oa.Mirror([-3, 0, 0], radius=4.0)], o, d, OFFSETS, ([50, 0.1, 0.2], [-1, 0, 0])
+    if name.startswith("polygon_"):
+        stop = oa.BaseMirror([5, 0, 0])
+        if name == "polygon_concave_vertex":  # the reflex vertex (0, -0.2) of the arrow, along its bisector +z; |cross| <= 1e-9 counts as
+            # inside (surfaces.py:534-558): 0.9 * depth for the two edges that meet there
+            stop.surface = oa.Polygon(np.array([(0.0, 1.0), (-0.9, -0.8), (0.0, -0.2), (0.9, -0.8)]))
+            o, d = _rim_rays(OFFSETS, [0, 0.0, -0.2 - 1e-9 / 0.9], [0, 0, 1], [1, 0, 0])
+        elif name == "polygon_level_vertex":  # the edge y = -0.25 of an L, from outside (+) to inside: the even-odd test casts its ray
+            # along +z, i.e. along that edge and through the vertex (-0.25, 1) at its end; the edge has the length 1.25
+            stop.surface = oa.Polygon(np.array([(-0.75, -1.0), (0.75, -1.0), (0.75, -0.25), (-0.25, -0.25), (-0.25, 1.0), (-0.75, 1.0)]))
+            o, d = _rim_rays(OFFSETS, [0, -0.25 + 1e-9 / 1.25, 0.3], [0, 1, 0], [1, 0, 0])
+        else:
+            raise KeyError(name)
+        return [stop, back], o, d, OFFSETS, ([0, -0.5, -0.6], [1, 0, 0])
     raise KeyError(name)
 
 
-FAMILIES = ["circle", "rectangle", "polygon", "cylinder", "sphere_cap", "asphere", "boolean", "tir", "tie"]
+DEEP_CAP = (2.0, 3.2)
+T100_X = 120.0  # sphere_t100: the largest coordinate of the decision, the ray's start in the frame of the cap (its centre)
+FAMILIES = ["circle", "rectangle", "polygon", "cylinder", "sphere_cap", "asphere", "boolean", "tir", "tie",
+            "sphere_deep_rim", "sphere_box_face", "sphere_tangent", "sphere_chord", "sphere_t100", "polygon_concave_vertex", "polygon_level_vertex"]
+# fp32, "clear of the decision": 1e-4, or 16 ulp_f32(X) where the decision involves a coordinate or distance X so large that
+# this is more: an offset below a few ulp of X does not survive the rounding of the ray to single precision (t = 100 is
+# the difference of two coordinates of that size, each rounded to ulp / 2, and the root adds a few more)
+FP32_SCALE = {"sphere_t100": T100_X}
+
+
+def fp32_clear(family):
+    return max(1e-4, 16.0 * float(np.spacing(np.float32(FP32_SCALE.get(family, 1.0)))))
 
 
 def _batch(o, d, off, filler, n):
@@ -152,7 +208,7 @@ def test_marginal_rays_on_every_kernel(family, oracle):
                 except AssertionError as e:
                     raise AssertionError(f"{where}\n{e}") from None
                 # rays clear of the decision take the oracle's path exactly
-                clear = np.abs(offs) > (FLOOR["f64"] if prec == "f64" else 1e-4 - 1e-12)
+                clear = np.abs(offs) > (FLOOR["f64"] if prec == "f64" else fp32_clear(family) - 1e-12)
                 bad = [int(r) for r in rep["ray"] if clear[r]]
                 assert not bad, (where, bad, offs[bad])
                 if prec == "f64":  # ... and its fields to 1e-9

@@ -118,7 +118,7 @@ def record(sc):
 
 
 def forms_fixture(family):
-    """g30 - g33: the surface-form catalogue (tests/form_scenes.py), one file per family; every form in the format of
+    """g30 - g35: the surface-form catalogue (tests/form_scenes.py), one file per family; every form in the format of
     `run`, its arrays under `<form>/`.  (A sag whose radicand goes negative inside the local box makes the reference print a
     RuntimeWarning and report no crossing there: part of what is recorded.)"""
     import warnings
