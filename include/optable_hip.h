@@ -834,7 +834,7 @@ enum ot_option {
     OT_OPT_KERNEL = 4,         /* 0 auto; 1 lane-per-ray kernel; 2 rolling-list kernel (heavy scenes) */
     OT_OPT_LDS_LIMIT_KB = 5,   /* scene images above this many KB are read from global memory   */
     OT_OPT_LIST_CAP = 6,       /* heavy scenes: live rays per wave in the rolling list: a multiple of 64, 128..1024 (mixed lists use it only if it is a power of two) */
-    OT_OPT_PAIR_STORES = 7,    /* lane-per-ray kernel: lane pairs write two fields per 16-byte store (0/1) */
+    OT_OPT_PAIR_STORES = 7,    /* lane-per-ray kernel, slot arrays (ot_trace_*) only: lane pairs write two fields per 16-byte store (0/1); tiles are written one element per lane */
     OT_OPT_MIX_GENERATIONS = 8,/* heavy scenes: -1 auto, 0 generation-pure lists even under a top-level grid */
     OT_OPT_FLAT_QUEUE = 9,     /* planar scenes under a top-level grid: wave-wide candidate queue (0 / 1; a multiple of 64 in 192..8192:
                                   on, with room for that many (ray, leaf) pairs per round instead of 512 — lanes that do not fit wait a round) */

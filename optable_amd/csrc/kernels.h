@@ -437,6 +437,7 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
     // fields around the loads, pointers held across the loop are spilled to lanes as one sixteen-register tuple and read back whole
     // for every field.)
     using Args = FusedArgs<T, OUT>;
+    constexpr bool TILES = std::is_same<OUT, SegTiles<T>>::value;  // tiles: one element per lane, from one place; `pair` is not read
     RaysT<T> in = karg_struct<RaysT<T>>(karg_words(offsetof(Args, in)));
     extern __shared__ __align__(16) uint32_t lds[];
     const uint32_t* base = blob.words;
@@ -480,15 +481,25 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
             if (!__any(active)) break;
             const GateCtx gate = {counts, n_classes, cls, nullptr, nullptr, 0, 0};
             const Hit<T> h = nearest_hit<T, F, GATE_PLAIN>(sc, r, active, gate);
-            // segment record: pairs of lanes that both store write two fields per 16-byte store (store_segment_paired)
-            const unsigned long long storing = __ballot(active);
+            // segment record, slot arrays: pairs of lanes that both store write two fields per 16-byte store (store_segment_paired)
+            unsigned long long storing = 0;
+            if constexpr (!TILES) storing = __ballot(active);
             // resident planes are skipped for the WHOLE wave or not at all: one storing lane past its old count (a ray that lives
             // longer than last time) and every lane of the wave writes this segment's full record
             const uint32_t rm = uniform_here(resident);  // (the plane tests are made at the stores, not kept in scalar registers across the search)
             const bool whole = rm == 0 || __any(active && (uint32_t)k >= SegCount::old_count(used));
             const uint32_t fm = (k == 0 && !whole) ? rm >> FIRST_SHIFT : 0u;  // first-segment fields: a reduced record 0 that leaves any of them out goes unpaired
-            const bool both = fm != 0 || (pair && ((storing >> (threadIdx.x & 62)) & 3ull) == 3ull);  // (stored here, not below)
-            if (both) {
+            // tiles: every record is stored here (TILES stands for `both` below: nothing is left to the two branches of `active`)
+            const bool both = TILES || fm != 0 || (pair && ((storing >> (threadIdx.x & 62)) & 3ull) == 3ull);  // (stored here, not below)
+            if constexpr (TILES) {
+                // A tile's planes are 512 contiguous bytes (fp32: 256) at constant offsets from the record: one element per lane is whole
+                // 128-byte lines from every store, the plane a store's immediate offset, and no exchange, select or address per field.
+                if (active) {
+                    const bool hit = h.node >= 0;
+                    store_segment<T, NT>(out, (int64_t)k * n + i, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : -1,
+                                         whole ? 0u : rm, fm);
+                }
+            } else if (both) {
                 const bool hit = h.node >= 0;
                 if (whole)
                     store_segment_paired<T, NT>(out, (int64_t)k * n + i, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : -1,
@@ -1725,7 +1736,8 @@ __global__ __launch_bounds__(256) void k_stream_ceiling(RaysT<T> in, int64_t n, 
         const uint32_t um = uniform_here(uniform);
         RayState<T> r = load_ray(in, i, ld_flags(in.flags, i, um), um);  // uniform fields: as the trace reads them (load_ray)
         const int32_t cls = ld_id(in.id, i, um);
-        const bool both = pair && (i | 1) < n;  // n is even when `pair` is set: both lanes of a pair are in range
+        // tiles are written as the trace writes them, one element per lane; slot arrays: n is even when `pair` is set, both lanes of a pair in range
+        const bool both = !std::is_same<OUT, SegTiles<T>>::value && pair && (i | 1) < n;
         for (int32_t k = 0; k < K; ++k) {
             if (both) store_segment_paired<T, NT>(out, (int64_t)k * n + i, r, r.len, (int32_t)i, cls, (threadIdx.x & 1) != 0);
             else store_segment<T, NT>(out, (int64_t)k * n + i, r, r.len, (int32_t)i, cls);

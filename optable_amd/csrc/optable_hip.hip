@@ -724,8 +724,9 @@ static int check_segs(const ot_segments* s) {
     return 0;
 }
 
-// paired segment stores (kernels.h store_segment_paired): slot k*n + i is even on even lanes iff n is even, and every
-// segment array must be aligned to two elements
+// paired segment stores (kernels.h store_segment_paired), slot arrays only: slot k*n + i is even on even lanes iff n is even, and
+// every segment array must be aligned to two elements.  (Tiles are written one element per lane: a tile's planes are contiguous and
+// lie at constant offsets from the record, so the pair buys no wider line there and costs its exchange: trace_tiled.)
 // fp64 only: measured on cfg 4 (1.6e8 pairs) 12.73 -> 12.08 ms (5230 -> 5510 GB/s, 97 % of the stream ceiling), cfg 2
 // 0.108 -> 0.106 ms; in fp32 the pair is an 8-byte store and the kernel is VALU-bound: the exchange costs 7-13 %.
 template <class T> static int32_t pair_ok(const ot_ctx* c, const ot_segments* s, int64_t n) {
@@ -1135,8 +1136,8 @@ static int trace_tiled(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, voi
     HIP_TRY(hipSetDevice(c->device));
     if (wants_rolling<T>(c, K))
         return fail(OT_ERR_UNSUPPORTED, "the tiled layout belongs to the lane-per-ray kernel (light scenes); heavy scenes write [k][ray] slots (ot_trace_*) or the append layout (ot_trace_append_*)");
-    const int32_t pair = (c->opt_pair && !(n & 1) && sizeof(T) == 8) ? 1 : 0;  // lane pairs write 16 bytes: even slot on the even lane
-    return launch_fused<T, SegTiles<T>>(c, rays, n, K, SegTiles<T>{(uint8_t*)tiles}, pair, seg_count, counts, n_classes, uniform, resident, first);
+    // pair = 0: the tiled kernels store one element per lane and do not read the argument (OT_OPT_PAIR_STORES governs the slot arrays)
+    return launch_fused<T, SegTiles<T>>(c, rays, n, K, SegTiles<T>{(uint8_t*)tiles}, 0, seg_count, counts, n_classes, uniform, resident, first);
 }
 
 // the segment block of the append layout (ot_trace_append_*, ot_trace_trees_append_*)
@@ -2319,14 +2320,14 @@ template <class T> static int probe_layouts(ot_ctx* c) {
     uint8_t* tiles = p; p += tiles_bytes;
     int32_t* seg_count = (int32_t*)p;
     const int block = 256, grid = (int)((n + block - 1) / block);
-    const int32_t pair = (c->opt_pair && sizeof(T) == 8) ? 1 : 0;
+    const int32_t pair = (c->opt_pair && sizeof(T) == 8) ? 1 : 0;  // the slot arrays' stores, as the trace pairs them; tiles: one element per lane, as the trace
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
     double best[2] = {1e30, 1e30};
     auto launch = [&](int layout) {
         if (layout == 0) hipLaunchKernelGGL((k_stream_ceiling<T, true, SegsT<T>>), dim3(grid), dim3(block), 0, c->stream, view<T>(&in), n, K, view<T>(&sg), seg_count, pair, 0u);
-        else hipLaunchKernelGGL((k_stream_ceiling<T, true, SegTiles<T>>), dim3(grid), dim3(block), 0, c->stream, view<T>(&in), n, K, SegTiles<T>{tiles}, seg_count, pair, 0u);
+        else hipLaunchKernelGGL((k_stream_ceiling<T, true, SegTiles<T>>), dim3(grid), dim3(block), 0, c->stream, view<T>(&in), n, K, SegTiles<T>{tiles}, seg_count, 0, 0u);
     };
     int rc = 0;
     for (int round = 0; round < 3 && !rc; ++round)
@@ -2501,7 +2502,7 @@ int ot_bench_stream_uniform_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32
 }
 int ot_bench_stream_tiled_uniform_f64(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count, uint32_t uniform) {
     const int rc = check_tiles<double>(tiles, capacity, n, K);
-    return rc ? rc : bench_stream<double, SegTiles<double>>(c, rays, n, K, SegTiles<double>{(uint8_t*)tiles}, (c && c->opt_pair && !(n & 1)) ? 1 : 0, seg_count, uniform);
+    return rc ? rc : bench_stream<double, SegTiles<double>>(c, rays, n, K, SegTiles<double>{(uint8_t*)tiles}, 0, seg_count, uniform);
 }
 int ot_bench_stream_tiled_uniform_f32(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, void* tiles, int64_t capacity, int32_t* seg_count, uint32_t uniform) {
     const int rc = check_tiles<float>(tiles, capacity, n, K);
