@@ -4,8 +4,9 @@
 using T = OT_REAL;
 using namespace preset;
 
-// The 128-register cap (MINW = 4) pays for the mirror / lens kernel and for the fp32 Snell kernel; the fp64 Snell kernel
-// wants 145 registers and would spill: that combination is not compiled.  FE / FM (everyday parts: polygons, spheres, aspheres,
+// The 128-register cap (MINW = 4) is stated for the mirror / lens kernel and for the fp32 Snell kernel.  The fp64 Snell kernel is
+// not compiled with it: uncapped it takes 120 (tiles) / 123 (slots) registers since the ray advances in place (152 before), which
+// is four waves per SIMD already, so the cap would only build the same kernel twice.  FE / FM (everyday parts: polygons, spheres, aspheres,
 // count gates; + the rarer shapes) exist in both precisions; the all-features kernel in single precision only (in double it
 // needs more than 256 registers; those scenes take the rolling lists), with non-temporal stores only, and is also the one
 // that reads images beyond the LDS limit from L2.  Every kernel in two output layouts:

@@ -278,6 +278,12 @@ __device__ __forceinline__ uint32_t uniform_here(uint32_t mask) {
     asm volatile("" : "+s"(mask));
     return mask;
 }
+// a wave-uniform 64-bit value, held in a scalar register pair HERE: what is computed from it per lane starts from the pair (a product
+// left to the compiler is folded into the lanes' own arithmetic: k * n + i becomes a 64-bit vector multiply-add)
+__device__ __forceinline__ int64_t scalar_here(int64_t v) {
+    asm volatile("" : "+s"(v));
+    return v;
+}
 template <class V> __device__ __forceinline__ V ld_field(const V* p, int64_t i, uint32_t mask, uint32_t bit) {
     if (mask & bit) return ld_shared(p);
     return ld_once(p + i);
@@ -438,6 +444,10 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
     // for every field.)
     using Args = FusedArgs<T, OUT>;
     constexpr bool TILES = std::is_same<OUT, SegTiles<T>>::value;  // tiles: one element per lane, from one place; `pair` is not read
+    // The all-features kernel (fp32 only) keeps the loop counter and the staged child it had, and with them its registers (152-164):
+    // it lives on scalars kept in vector lanes (116-171 of them), and the scalar counter with the ray advanced in place, which give
+    // it back up to 17 vector registers, make that up to 251 (tests/test_build_resources.py pins it as the presets' yardstick).
+    constexpr bool SCALAR_K = F != F_ALL;
     RaysT<T> in = karg_struct<RaysT<T>>(karg_words(offsetof(Args, in)));
     extern __shared__ __align__(16) uint32_t lds[];
     const uint32_t* base = blob.words;
@@ -456,7 +466,9 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
         uint32_t used = 0;  // segments written, and with resident planes the ray's old count beside it (SegCount)
         MatCache<T> mc = {T(1)};
         if (active) {
-            if (resident) {  // (this lane writes the element at the end, and no other lane touches it)
+            // (this lane writes the element at the end, and no other lane touches it; tested HERE, a scalar compare per grid-stride
+            // iteration: hoisted, the test is a lane mask in a register pair across the loop)
+            if (SCALAR_K ? uniform_here(resident) : resident) {
                 used = SegCount::start(seg_count[i]);
             }
             const uint32_t um = uniform_here(uniform);
@@ -477,10 +489,15 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
                 active = false;
             }
         }
-        for (int32_t k = 0; k < K; ++k) {  // wave-uniform trip count: lanes never leave the loop alone
+        // Wave-uniform trip count: lanes never leave the loop alone.  The counter is kept in a scalar register BY CONSTRUCTION (the
+        // increment goes through readfirstlane): left to the compiler, k + 1 is formed once, inside the divergent `if (active)` below,
+        // and k becomes a per-lane value — the slot base a 64-bit vector multiply, `fm` a vector value and every plane test of the
+        // reduced stores a vector compare and an exec-mask branch.  Everything below derives from the scalar: k * n, k == 0, k + 1.
+        for (int32_t k = 0; k < K; k = SCALAR_K ? uniform_t(k + 1) : k + 1) {
             if (!__any(active)) break;
             const GateCtx gate = {counts, n_classes, cls, nullptr, nullptr, 0, 0};
             const Hit<T> h = nearest_hit<T, F, GATE_PLAIN>(sc, r, active, gate);
+            const int64_t kn = SCALAR_K ? scalar_here((int64_t)k * n) : (int64_t)k * n;  // the segment's slot base, formed behind the search: scalar arithmetic, one 64-bit add per lane
             // segment record, slot arrays: pairs of lanes that both store write two fields per 16-byte store (store_segment_paired)
             unsigned long long storing = 0;
             if constexpr (!TILES) storing = __ballot(active);
@@ -496,23 +513,23 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
                 // 128-byte lines from every store, the plane a store's immediate offset, and no exchange, select or address per field.
                 if (active) {
                     const bool hit = h.node >= 0;
-                    store_segment<T, NT>(out, (int64_t)k * n + i, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : -1,
+                    store_segment<T, NT>(out, kn + i, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : -1,
                                          whole ? 0u : rm, fm);
                 }
             } else if (both) {
                 const bool hit = h.node >= 0;
                 if (whole)
-                    store_segment_paired<T, NT>(out, (int64_t)k * n + i, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : -1,
+                    store_segment_paired<T, NT>(out, kn + i, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : -1,
                                                 (threadIdx.x & 1) != 0);
                 else if (fm == 0)
-                    store_segment_paired_reduced<T, NT>(out, (int64_t)k * n + i, r, hit ? h.t : r.len, (int32_t)i,
+                    store_segment_paired_reduced<T, NT>(out, kn + i, r, hit ? h.t : r.len, (int32_t)i,
                                                         hit ? leaf_id_of<T, F>(sc, h.node) : -1, (threadIdx.x & 1) != 0, rm);
                 else if (active)  // (last: the two paired forms, every other segment's, keep the places they had; and the slot is
                                   // written k * n + i here too — `i` alone, equal at k == 0, costs the FA MINW = 4 kernels 8-38 vector spills)
-                    store_segment<T, NT>(out, (int64_t)k * n + i, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : -1, rm, fm);
+                    store_segment<T, NT>(out, kn + i, r, hit ? h.t : r.len, (int32_t)i, hit ? leaf_id_of<T, F>(sc, h.node) : -1, rm, fm);
             }
             if (active) {
-                const int64_t slot = (int64_t)k * n + i;
+                const int64_t slot = kn + i;
                 used = SegCount::written(used, k + 1, resident != 0);
                 if (h.node < 0) {  // escaped: archived unchanged (optical_table.py:132-134)
                     if (!both) {
@@ -525,10 +542,17 @@ __global__ __launch_bounds__(256, MINW) void k_trace_fused(SceneBlob blob, T uni
                         if (whole) store_segment<T, NT>(out, slot, r, h.t, (int32_t)i, leaf_id_of<T, F>(sc, h.node));
                         else store_segment<T, NT>(out, slot, r, h.t, (int32_t)i, leaf_id_of<T, F>(sc, h.node), rm);
                     }
-                    RayState<T> child;
-                    const int nk = interact<T, F, 1>(sc, r, h, &child, mc);
-                    if (nk == 1) r = child;
-                    else {
+                    // the ray advances in place: with one outgoing ray `r` is that ray; otherwise the lane goes inactive, and what
+                    // `r` holds then is neither stored nor traced
+                    int nk;
+                    if constexpr (!SCALAR_K) {
+                        RayState<T> child;
+                        nk = interact<T, F, 1>(sc, r, h, &child, mc);
+                        if (nk == 1) r = child;
+                    } else {
+                        nk = advance<T, F>(sc, r, h, mc);
+                    }
+                    if (nk != 1) {
                         active = false;
                         if (nk > 1) used = SegCount::branched(used, k + 1, resident != 0);  // the tree branches here: not representable in [k][ray] slots
                     }

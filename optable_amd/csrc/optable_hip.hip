@@ -1082,8 +1082,9 @@ static int launch_fused(ot_ctx* c, const ot_rays* rays, int64_t n, int32_t K, co
     if (c->opt_blocks_per_cu > 0) per_cu = c->opt_blocks_per_cu;
     const int64_t cap = (int64_t)c->n_cus * per_cu;
     const int grid = (int)(blocks_needed < cap ? blocks_needed : cap);
-    // smallest instantiation that covers the scene's features; the 128-register cap pays for the mirror / lens kernel
-    // and the fp32 Snell kernel only (the fp64 Snell kernel would spill: 145 VGPRs)
+    // smallest instantiation that covers the scene's features; the 128-register cap is stated for the mirror / lens kernel
+    // and the fp32 Snell kernel only (the fp64 Snell kernel stays within 128 registers uncapped: inst_fused.hip; nothing in
+    // the grid rule above depends on the waves a SIMD holds)
     const bool mw = c->opt_minw == 4 && (fi == 0 || (fi == 1 && !f64));
     FusedKern<T, OUT> kern = fused_kernel<T, OUT>(fi, lds, mw, c->opt_nt != 0);
     if (!kern) return fail(OT_ERR_UNSUPPORTED, "no kernel instantiation for this scene / option combination");

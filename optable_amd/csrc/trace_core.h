@@ -1664,10 +1664,16 @@ __device__ __forceinline__ void surf_normal(const Scene<T>& sc, const DNode<T>& 
 // branches" and hands the ray back to the host, see k_trace_fused).
 // SINK (MAXK > 1): a callable that takes every outgoing ray the moment it is complete, instead of `kids` — the lane-per-tree
 // kernel queues the first child before the second is formed, so that the two are never live together (k_trace_trees).
+// IN_PLACE (MAXK = 1, through advance() below): `kids` IS the incoming ray.  The first outgoing ray is written over it field by
+// field — what rides along at the emit that forms it, origin and direction behind the branches — with no staged copy, and nothing
+// is zeroed ahead of the branches: out_x .. out_z are read only after an emit has set them.  The arithmetic is the text below
+// either way, so both forms fuse and round alike.  A later emit of the same hit reads the fields the first one wrote, but its
+// values are dropped (nk > 0): with two or more outgoing rays the caller has to give the ray up anyway.
 struct NoSink {};
-template <class T, uint32_t F, int MAXK, class SINK = NoSink>
+template <class T, uint32_t F, int MAXK, class SINK = NoSink, bool IN_PLACE = false>
 __device__ __forceinline__ int interact(const Scene<T>& sc, const RayState<T>& r, const Hit<T>& h, RayState<T>* kids,
                                         const MatCache<T>& mc, SINK* sink = nullptr) {
+    static_assert(!IN_PLACE || (MAXK == 1 && std::is_same<SINK, NoSink>::value), "in place: one outgoing ray, no sink");
     const NodeRef<T> nr = node_ref<T, F>(sc, h.node);
     const DNode<T>& nd = *nr.nd;
     if (nd.inter == OT_INT_BLOCK) return 0;
@@ -1684,9 +1690,12 @@ __device__ __forceinline__ int interact(const Scene<T>& sc, const RayState<T>& r
     // leaf frame and what rides along; normalising, turning it into the lab frame and filling the record happen ONCE behind
     // them.  With `emit` expanded inside every branch a pass whose rays meet a lens, a mirror and a glass face ran that
     // tail three times at partial lanes.  Same expressions in the same order either way: the same bits.
-    T out_x = T(0), out_y = T(0), out_z = T(0), out_I = T(0), out_qr = T(0), out_qi = T(0), out_n = T(0), out_pl = T(0);
+    T out_x, out_y, out_z, out_I, out_qr, out_qi, out_n, out_pl;
+    if constexpr (!IN_PLACE) { out_x = T(0); out_y = T(0); out_z = T(0); out_I = T(0); out_qr = T(0); out_qi = T(0); out_n = T(0); out_pl = T(0); }
     auto emit = [&](T lx, T ly, T lz, T I, T qr, T qi, T n, T pl) {
-        if constexpr (MAXK == 1) {
+        if constexpr (IN_PLACE) {
+            if (nk == 0) { out_x = lx; out_y = ly; out_z = lz; kids->I = I; kids->qr = qr; kids->qi = qi; kids->n = n; kids->pl = pl; }
+        } else if constexpr (MAXK == 1) {
             if (nk == 0) { out_x = lx; out_y = ly; out_z = lz; out_I = I; out_qr = qr; out_qi = qi; out_n = n; out_pl = pl; }
         } else if (nk < MAXK) {
             RayState<T> k;
@@ -1704,7 +1713,14 @@ __device__ __forceinline__ int interact(const Scene<T>& sc, const RayState<T>& r
         ++nk;
     };
     auto finish = [&]() -> int {
-        if constexpr (MAXK == 1) {
+        if constexpr (IN_PLACE) {
+            if (nk > 0) {  // wl and has_q are the incoming ray's: they stay
+                const T inv = rsqrt_t(out_x * out_x + out_y * out_y + out_z * out_z);
+                to_lab(nd, out_x * inv, out_y * inv, out_z * inv, kids->dx, kids->dy, kids->dz);
+                kids->ox = Ox; kids->oy = Oy; kids->oz = Oz;
+                kids->len = Num<T>::inf(); kids->last = h.node;
+            }
+        } else if constexpr (MAXK == 1) {
             if (nk > 0) {
                 RayState<T> k;
                 const T inv = rsqrt_t(out_x * out_x + out_y * out_y + out_z * out_z);
@@ -1779,6 +1795,14 @@ __device__ __forceinline__ int interact(const Scene<T>& sc, const RayState<T>& r
             emit(dx - T(2) * ci * nx, dy - T(2) * ci * ny, dz - T(2) * ci * nz, r.I * nd.refl, qrr, qri, r.n, pl_hit);
     }
     return finish();
+}
+
+// The hit's interaction applied to the ray itself (k_trace_fused): returns how many rays leave the hit.  Exactly one: `r` is that
+// ray.  None: `r` is as it came.  More: `r` holds the first of them — the tree branches, and the caller neither traces nor stores
+// `r` again.
+template <class T, uint32_t F>
+__device__ __forceinline__ int advance(const Scene<T>& sc, RayState<T>& r, const Hit<T>& h, const MatCache<T>& mc) {
+    return interact<T, F, 1, NoSink, true>(sc, r, h, &r, mc);
 }
 
 }  // namespace ot
