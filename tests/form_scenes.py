@@ -16,10 +16,23 @@ scenes.SCENES: the existing parametrised tests and g28_adapter.npz stay as they 
     scene(ns, name)              the object-API scene of the fixtures (<= 40 Ray objects of the same fan, cap <= 12)
     form_leaves(scene, name)     indices of the leaves that carry the form under test
     curved_scene, curved_scene_deep_caps, curved_deep_case   random curved scenes whose parts are drawn from the catalogue
+    named(form)                  a context in which every failure names the form
 """
+import contextlib
+
 import numpy as np
 
 from optable_amd.workloads import WL, W0
+
+
+@contextlib.contextmanager
+def named(form):
+    """Every failure names the form."""
+    try:
+        yield
+    except AssertionError as exc:
+        raise AssertionError(f"surface form {form!r}: {exc}") from exc
+
 
 # -- aspheres: ASphericParametricLens([4, 0.1, 0], CT=0.6, diameter=2.4, n=1.5, **form), as built and turned by RotZ(pi) ------
 ASPHERES = {

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import optable_amd as oa
+import support
 from optable_amd import abi
 from optable_amd.batch import RayBatch, SegmentBatch
 from optable_amd.engine import Engine
@@ -60,18 +61,6 @@ def test_budget_and_pass_planner():
             plan(n, nby, nbz)
 
 
-def _host_segments(n_rays=4, k=2, precision="f64"):
-    segs = SegmentBatch(n_rays * k, precision, "cpu")
-    segs.count, segs.n_rays = torch.full((n_rays,), k, dtype=torch.int32), n_rays
-    return segs
-
-
-def _host_rays(n):
-    o = np.zeros((n, 3))
-    d = np.tile([1.0, 0.0, 0.0], (n, 1))
-    return RayBatch.from_arrays(o, d, wavelength=780e-7, device="cpu")
-
-
 def test_refused_before_the_engine_is_asked(monkeypatch):
     from optable_amd import table as table_module
 
@@ -81,9 +70,9 @@ def test_refused_before_the_engine_is_asked(monkeypatch):
     monkeypatch.setattr(table_module, "_engine", refuse)
     table = oa.OpticalTable()
     mon = oa.Monitor([1, 0, 0], 2, 2)
-    good, rays = _host_segments(), _host_rays(4)
+    good, rays = support.host_segments(), support.host_rays(4)
     with pytest.raises(ValueError, match="double-precision"):
-        table.field_all(_host_segments(precision="f32"), 780e-7, monitors=[mon])
+        table.field_all(support.host_segments(precision="f32"), 780e-7, monitors=[mon])
     with pytest.raises(ValueError, match=r"wavelength=0\.0"):
         table.field_all(good, monitors=[mon])  # the default
     for bad in (0.0, -780e-7, float("nan"), float("inf"), "red", None):
@@ -92,9 +81,9 @@ def test_refused_before_the_engine_is_asked(monkeypatch):
         with pytest.raises(ValueError, match="wavelength"):
             table.field_batch(mon, good, bad)
     with pytest.raises(ValueError, match="RayBatch of 5 rays"):
-        table.field_all(good, _host_rays(5), monitors=[mon])
+        table.field_all(good, support.host_rays(5), monitors=[mon])
     for value in (0.0, -1.0, float("nan"), float("inf")):
-        dark = _host_rays(4)
+        dark = support.host_rays(4)
         dark.wavelength[2] = value
         with pytest.raises(ValueError, match="finite wavelength > 0"):
             table.field_all(good, dark, monitors=[mon])
@@ -129,7 +118,7 @@ def test_what_is_handed_over_and_what_comes_back(monkeypatch):
     monkeypatch.setattr(table_module, "_engine", lambda: rec)
     table = oa.OpticalTable()
     mons = [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([1, 2, 3], 0.3, 1.7).RotZ(0.3)]
-    segs, rays = _host_segments(), _host_rays(4)
+    segs, rays = support.host_segments(), support.host_rays(4)
     fields = table.field_all(segs, 780e-7, bins=(7, 5), monitors=mons)
     assert rec.wavelength == 780e-7 and rec.mode == 0 and rec.bins == (7, 5) and rec.into is None
     assert rec.edges.shape == (2, 14) and rec.axes.shape == (2, 6)

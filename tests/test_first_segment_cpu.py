@@ -1,6 +1,7 @@
 """CPU: the first-segment token of a SegmentBatch (batch.py), on host tensors — what sets it, what every entry of it is compared
 with, what ends it, and that the resident-plane token beside it answers as before.  No engine and no device: `engine` and
 `stream` are whatever objects the caller compares by."""
+import functools
 import os
 import re
 
@@ -8,8 +9,9 @@ import numpy as np
 import pytest
 import torch
 
+import support
 from optable_amd import abi
-from optable_amd.batch import RayBatch, SegmentBatch
+from optable_amd.batch import RayBatch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RAY, N, I, ALL = abi.RESIDENT_RAY, abi.RESIDENT_N, abi.RESIDENT_INTENSITY, abi.RESIDENT_ALL
@@ -20,15 +22,9 @@ ONE32 = int(np.float32(1.0).view(np.int32))
 NEG0 = int(np.float64(-0.0).view(np.uint64))
 ENGINE, STREAM = object(), 1234
 n, K = 130, 5
+_out = functools.partial(support.host_out, n, K)
 POINT = {"ox": 0, "oy": 0, "oz": 0, "q_re": 0, "q_im": ONE64, "pathlength": 0, "n": ONE64, "intensity": ONE64}  # a point source (cfg 2)
 POINT_MASK = sum(BIT[f] for f in POINT)
-
-
-def _out(precision="f64", tiled=False):
-    out = SegmentBatch(n * K, precision, "cpu", tiled=tiled)
-    out.count = torch.full((n,), K, dtype=torch.int32)
-    out.n_rays = n
-    return out
 
 
 def _values(**change):

@@ -12,8 +12,8 @@ import torch
 
 import optable_amd as oa
 from fluence_reference import U, fluence_reference
+import support
 from optable_amd import abi
-from optable_amd.batch import SegmentBatch
 from optable_amd.engine import Engine
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -65,12 +65,6 @@ def test_planner_and_its_constants():
             engine.fluence_plan(nu, nv)
 
 
-def _host_segments(n_rays=4, k=2, precision="f64"):
-    segs = SegmentBatch(n_rays * k, precision, "cpu")
-    segs.count, segs.n_rays = torch.full((n_rays,), k, dtype=torch.int32), n_rays
-    return segs
-
-
 ROI = (-1.0, 9.0, -3.01, 2.97, -0.5, float("inf"))
 
 
@@ -81,7 +75,7 @@ def test_refused_before_the_engine_is_asked(monkeypatch):
         raise AssertionError("the engine was asked for")
 
     monkeypatch.setattr(table_module, "_engine", refuse)
-    table, segs = oa.OpticalTable(), _host_segments()
+    table, segs = oa.OpticalTable(), support.host_segments()
     for view in ("z", "3D", "XY", 2, None, ""):
         with pytest.raises(ValueError, match="view"):
             table.fluence_map(segs, view=view, roi=ROI)
@@ -126,7 +120,7 @@ def test_what_is_handed_over_and_what_comes_back(monkeypatch):
 
     rec = _Recorder()
     monkeypatch.setattr(table_module, "_engine", lambda: rec)
-    table, segs = oa.OpticalTable(), _host_segments()
+    table, segs = oa.OpticalTable(), support.host_segments()
     roi = (-1.0, 9.0, -3.01, 2.97, -0.5, 0.75)
     ranges = {"x": roi[0:2], "y": roi[2:4], "z": roi[4:6]}
     for view, (u, v, w), lab in (("Z", "xyz", [0, 1, 2]), ("X", "yzx", [1, 2, 0]), ("Y", "zxy", [2, 0, 1])):

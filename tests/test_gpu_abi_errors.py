@@ -9,19 +9,11 @@ import pytest
 import scenes
 from optable_amd import abi
 from optable_amd import shapes as sh
+from support import ctx  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 ERR_INVALID, ERR_UNSUPPORTED, ERR_NOSCENE = -1, -3, -5
-
-
-@pytest.fixture()
-def ctx():
-    lib = abi.load()
-    c = C.c_void_p()
-    assert lib.ot_ctx_create(0, None, C.byref(c)) == 0
-    yield lib, c
-    assert lib.ot_ctx_destroy(c) == 0
 
 
 def _compiled(builder):

@@ -9,6 +9,7 @@ import torch
 
 import optable_amd as oa
 import scenes
+import support
 from optable_amd import abi
 from optable_amd import workloads as W
 from optable_amd.batch import RayBatch
@@ -38,17 +39,6 @@ def _both(scene, batch, cap, onepass=0, **kw):
     assert torch.equal(ahead.capped, plain.capped)
     assert eng.generation_mismatches() == before
     return ahead
-
-
-def _lattice():
-    comps = []
-    for k in range(5):
-        comps.append(oa.BeamSplitter([2.0 * (k + 1), 0, 0], width=6, height=2, eta=0.5).RotZ(np.pi / 4))
-        comps.append(oa.Mirror([2.0 * (k + 1), 3.0 + 0.1 * k, 0], radius=2).RotZ(-np.pi / 2))
-        comps.append(oa.BeamSplitter([2.0 * (k + 1) + 1.0, 1.5, 0], width=6, height=2, eta=0.3).RotZ(-np.pi / 4))
-    t = oa.OpticalTable()
-    t.add_components(comps)
-    return t.compile()
 
 
 def _lattice_rays(n, seed):
@@ -89,8 +79,8 @@ def test_look_ahead_equals_count_pass_on_bushy_trees(cap, drop):
     eng = get_engine()
     try:
         eng.set_option(abi.OPT_GEN_DROP_DOOMED, drop)
-        _both(_lattice(), _lattice_rays(3000 if cap != 40 else 12_000, 5), cap)
-        _both(_lattice(), _lattice_rays(3000, 6), cap, onepass=-1)  # small generations in one pass, large ones with look-ahead: both change-overs
+        _both(support.lattice(5), _lattice_rays(3000 if cap != 40 else 12_000, 5), cap)
+        _both(support.lattice(5), _lattice_rays(3000, 6), cap, onepass=-1)  # small generations in one pass, large ones with look-ahead: both change-overs
     finally:
         eng.set_option(abi.OPT_GEN_DROP_DOOMED, 1)
 
@@ -114,7 +104,7 @@ def test_look_ahead_equals_count_pass_on_the_cavity(precision):
 def test_look_ahead_resumes_after_its_buffers_grow():
     """Segment arrays and generation buffers that are too small at first: the pending generation comes back as the caller's
     input, and a caller's rays always get a count pass of their own."""
-    scene = _lattice()
+    scene = support.lattice(5)
     batch = _lattice_rays(2000, 6)
     eng = get_engine()
     eng.upload(scene)

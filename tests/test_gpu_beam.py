@@ -32,6 +32,7 @@ beam_image_erf_probe.json; doubled for the arguments not sampled)
 Every comparison prints the largest error beside its bound, and asserts that no bin's bound exceeds 1e-10 of the monitor's total hit
 intensity: a loose bound cannot hide a misplaced deposit."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -40,28 +41,19 @@ from scipy.special import erf
 
 import optable_amd as oa
 import scenes
+import support
 from optable_amd import abi
 from optable_amd.batch import RayBatch, SegmentBatch
 from optable_amd.engine import beam_plan, get_engine, segment_source
 from optable_amd.monitors import MonitorHits, image_edges
 from optable_amd.table import monitor_struct
+from support import ctx  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-ERR_INVALID = -1
 U = 2.0**-53
 REL, E_REF, E_DEV = 20, 2, 6
 EMPTY, DROPS, SPREAD = 2, 6, 7
-
-
-def _host(t):
-    return t.double().cpu().numpy()
-
-
-def _wavelengths(wavelength, h):
-    if isinstance(wavelength, RayBatch):
-        return _host(wavelength.wavelength)[h.ray_index(None).cpu().numpy()]
-    return np.full(len(h), float(wavelength))
 
 
 def _reference(h, wavelength, y_edges, z_edges):
@@ -69,10 +61,10 @@ def _reference(h, wavelength, y_edges, z_edges):
     nby, nbz = len(y_edges) - 1, len(z_edges) - 1
     if len(h) == 0:
         return np.zeros((nby, nbz), dtype=np.int64), np.zeros((nby, nbz)), np.zeros((nby, nbz)), 0.0
-    y, z, I, t, P = _host(h.yList(None)), _host(h.zList(None)), _host(h.IList(None)), _host(h.t), _host(h.P)
-    lam = _wavelengths(wavelength, h)
-    qr = _host(h._gather(h.segs.q_re, h.slot)) + t
-    qi, n = _host(h._gather(h.segs.q_im, h.slot)), _host(h._gather(h.segs.n_index, h.slot))
+    y, z, I, t, P = support.host(h.yList(None)), support.host(h.zList(None)), support.host(h.IList(None)), support.host(h.t), support.host(h.P)
+    lam = support.hit_wavelengths(wavelength, h)
+    qr = support.host(h._gather(h.segs.q_re, h.slot)) + t
+    qi, n = support.host(h._gather(h.segs.q_im, h.slot)), support.host(h._gather(h.segs.n_index, h.slot))
     w = np.sqrt(lam * (qr * qr + qi * qi) / (n * np.pi * qi))
     assert np.all(np.isfinite(w) & (w > 0))
     clear = min(np.abs(y[:, None] - y_edges[None, :]).min(), np.abs(z[:, None] - z_edges[None, :]).min())
@@ -172,7 +164,7 @@ def test_hand_built_footprints_from_one_bin_to_the_whole_image():
     table, mon = oa.OpticalTable(), oa.Monitor([5, 0, 0], 6, 6)
     h = table.record_all(segs, monitors=[mon])[0]
     assert sorted(h.slot.tolist()) == list(range(64)) + [64, 70, 100, 127]
-    np.testing.assert_allclose(_host(h.spotsizeList(WL_HAND, None)), w[h.slot.cpu().numpy()], rtol=1e-12)
+    np.testing.assert_allclose(support.host(h.spotsizeList(WL_HAND, None)), w[h.slot.cpu().numpy()], rtol=1e-12)
     b = table.beam_batch(mon, segs, WL_HAND, bins=(7, 5))
     c = _assert_beam(b, h, WL_HAND)
     assert c.sum() == 68 and torch.equal(b.counts, table.image_batch(mon, segs, bins=(7, 5)).counts)
@@ -208,37 +200,16 @@ def test_more_edges_than_lanes():
 
 
 # -- 3: cfg 2 ---------------------------------------------------------------------------------------------------------------
-def _batch(o, d, precision="f64", seed=7):
-    """cfg 2's rays with per-ray intensities 0.25 + 0.75 u and per-ray waists w0 log-uniform in [0.005, 2]."""
-    rng = np.random.default_rng(seed)
-    intensity = 0.25 + 0.75 * rng.random(len(o))
-    w0 = np.exp(rng.uniform(np.log(0.005), np.log(2.0), len(o)))
-    return RayBatch.from_arrays(o, d, wavelength=scenes.WL, intensity=intensity, q=1j * np.pi * w0**2 / scenes.WL, precision=precision, device="cuda")
-
-
-def _cfg2_table():
-    t = oa.OpticalTable()
-    t.add_components(scenes.cfg2_components(oa))
-    return t
-
-
-def _eight_monitors():
-    """The eight of tests/test_gpu_image.py."""
-    return [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([6.5, 0, 0], 6, 6), oa.Monitor([7.5, 40, 0], 6, 6), oa.Monitor([8.5, 0, 0], 6, 6),
-            oa.Monitor([7.5, 0, 0], 6, 6).RotZ(0.3), oa.Monitor([7.5, 0, 0], 0.5, 0.5), oa.Monitor([7.5, 0, 0], 0.4, 6).RotX(0.5),
-            oa.Monitor([7.5, 0, 0], 2, 2)]
-
-
 @pytest.fixture(scope="module")
 def case3():
     """cfg 2, 5,003 rays, 5 segments, eight monitors: (table, monitors, {(layout, precision): (batch, segs, record_all hits)}), traced
     and recorded on first use."""
-    table, mons, made = _cfg2_table(), _eight_monitors(), {}
+    table, mons, made = support.cfg2_table(), support.eight_monitors(), {}
     o, d = scenes.cfg2_rays(5003, 0)
 
     def get(layout, precision):
         if (layout, precision) not in made:
-            batch = _batch(o, d, precision)
+            batch = support.waisted_batch(o, d, precision)
             segs = table.trace_batch(batch, max_segments=5, layout=layout)
             assert segs.layout == layout and segs.precision == precision
             made[layout, precision] = (batch, segs, table.record_all(segs, monitors=mons))
@@ -288,7 +259,7 @@ def test_tails_of_centres_off_the_image(case3):
     _, segs, hits = get("slots", "f64")
     h = hits[DROPS]
     ey, ez = image_edges(mons[DROPS], 30, 30)
-    y, z = _host(h.yList(None)), _host(h.zList(None))
+    y, z = support.host(h.yList(None)), support.host(h.zList(None))
     outside = (y < ey[0]) | (y > ey[-1]) | (z < ez[0]) | (z > ez[-1])
     assert 0 < outside.sum() < len(h)
     b = table.beam_batch(mons[DROPS], segs, scenes.WL)
@@ -308,15 +279,15 @@ def test_tails_of_centres_off_the_image(case3):
 def test_global_path_and_accumulation():
     """(80, 80): 6,400 bins, more than the LDS budget — every deposit a global atomic, narrow beams and beams as wide as the image.
     And `into=` over the two chunks of a batch against the whole batch in one call, on either path."""
-    table = _cfg2_table()
+    table = support.cfg2_table()
     mon = oa.Monitor([7.5, 0, 0], 2, 2)
     assert beam_plan(1, 80, 80)["path"] == "global" and beam_plan(1, 30, 30)["path"] == "lds"
-    whole = _batch(*scenes.cfg2_rays(2049, 3))
+    whole = support.waisted_batch(*scenes.cfg2_rays(2049, 3))
     segs = table.trace_batch(whole, max_segments=5, layout="slots")
     h = table.record_all(segs, monitors=[mon])[0]
     full = table.beam_all(segs, whole, bins=(80, 80), monitors=[mon])
     assert int(_assert_beam(full[0], h, whole).sum()) == len(h) >= 2049
-    w = _host(h.spotsizeList(whole, None))
+    w = support.host(h.spotsizeList(whole, None))
     assert w.min() < 2 / 80 and w.max() > 0.5  # less than a bin across, and a spot as wide as the monitor
     for bins in ((80, 80), (30, 30)):
         chunks = [whole.slice(0, 1024), whole.slice(1024, 2049)]
@@ -356,7 +327,7 @@ def test_ray_trees_inherit_the_wavelength():
     b = table.beam_batch(mon, segs, batch, bins=(9, 4))
     assert int(_assert_beam(b, h, batch).sum()) == 2 * 257
     # the two arms differ in length, and the colours in spot size: one wavelength for all is another image
-    w = _host(h.spotsizeList(batch, None))
+    w = support.host(h.spotsizeList(batch, None))
     assert len(set(np.round(w, 7))) == 4
     g = table.beam_batch(mon, segs, 780e-7, bins=(9, 4))
     _assert_beam(g, h, 780e-7)
@@ -364,29 +335,17 @@ def test_ray_trees_inherit_the_wavelength():
 
 
 # -- 7, 8: hits left out, refusals --------------------------------------------------------------------------------------------
-def _tables(mons, nby, nbz):
-    axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in mons], dtype=float)
-    edges = np.array([np.concatenate(image_edges(m, nby, nbz)) for m in mons], dtype=float)
-    return axes, edges
-
-
-class _Out:
+class _Out(support.Sentinel):
     """counts / power of M monitors of nby x nbz bins and `skipped` for ot_monitor_beam_many, filled with a sentinel."""
 
-    def __init__(self, M, nby, nbz, fill=-7):
-        self.fill = fill
-        self.counts = torch.full((M, nby, nbz), fill, dtype=torch.int64, device="cuda")
-        self.power = torch.full((M, nby, nbz), float(fill), dtype=torch.float64, device="cuda")
-        self.skipped = torch.full((1,), fill, dtype=torch.int64, device="cuda")
-
-    def untouched(self):
-        return all(bool((t == self.fill).all()) for t in (self.counts, self.power, self.skipped))
+    def __init__(self, M, nby, nbz):
+        super().__init__(counts=(torch.int64, (M, nby, nbz)), power=(torch.float64, (M, nby, nbz)), skipped=(torch.int64, (1,)))
 
 
 def _call(lib, ctx, mons, segs, nby, nbz, out, wavelength=None, n_wavelengths=0, uniform=0.0, accumulate=0, source=None, **planes):
     src, n, count, n_rays = segment_source(segs)
     table = (abi.OtMonitor * len(mons))(*[monitor_struct(m) for m in mons])
-    axes, edges = _tables(mons, nby, nbz)
+    axes, edges = support.image_tables(mons, nby, nbz)
     dp = C.POINTER(C.c_double)
     plane = {f: planes.get(f, segs.field(f).data_ptr()) for f in ("intensity", "q_re", "q_im", "n")}
     return lib.ot_monitor_beam_many(ctx, table, len(mons), axes.ctypes.data_as(dp), edges.ctypes.data_as(dp), nby, nbz,
@@ -426,15 +385,6 @@ def test_a_batch_without_q_is_refused(case3):
     assert 0 < known < len(hits[0]) and int(out.skipped.item()) == len(hits[0]) - known and int(out.counts.sum()) == known
 
 
-@pytest.fixture()
-def ctx():
-    lib = abi.load()
-    c = C.c_void_p()
-    assert lib.ot_ctx_create(0, None, C.byref(c)) == 0
-    yield lib, c
-    assert lib.ot_ctx_destroy(c) == 0
-
-
 def test_abi_errors(ctx):
     lib, c = ctx
     y = np.linspace(-2.5, 2.5, 130) + 0.0123
@@ -447,17 +397,7 @@ def test_abi_errors(ctx):
         kw.setdefault("uniform", WL_HAND)
         return _call(lib, c, [mon], segs, 7, 5, out, **kw)
 
-    def expect(status, needle):
-        msg = lib.ot_last_error().decode()
-        assert status == ERR_INVALID and needle in msg, (status, msg, needle)
-
-    src = segment_source(segs)[0]
-
-    def altered(**fields):
-        other = abi.OtSegmentSource.from_buffer_copy(src)
-        for k, v in fields.items():
-            setattr(other, k, v)
-        return other
+    expect, altered = functools.partial(support.expect_invalid, lib), functools.partial(support.altered, segment_source(segs)[0])
 
     expect(call(source=altered(width=2)), "width")
     for plane in ("intensity", "q_re", "q_im", "n", "counts", "power", "skipped"):

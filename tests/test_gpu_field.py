@@ -18,6 +18,7 @@ either library is within 1 ulp (u each), the product a cos phi rounds once on ei
 both — 16 u covers it.  The second term is the image test's bound for two summation orders of the same c doubles, |terms| <= a_j.
 Every comparison prints the largest error next to its bound."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -25,46 +26,20 @@ import torch
 
 import optable_amd as oa
 import scenes
+import support
 from optable_amd import abi
 from optable_amd.batch import RayBatch, SegmentBatch
 from optable_amd.engine import field_plan, get_engine, segment_source
 from optable_amd.monitors import image_edges
 from optable_amd.table import monitor_struct
+from support import ctx  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-ERR_INVALID = -1
 U = 2.0**-53
 
 
-def _batch(o, d, seed=7):
-    """cfg 2's rays with per-ray intensities 0.25 + 0.75 u: the amplitude is no constant."""
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
-    intensity = 0.25 + 0.75 * np.random.default_rng(seed).random(len(o))
-    return RayBatch.from_arrays(o, d, wavelength=scenes.WL, intensity=intensity, q=q, precision="f64", device="cuda")
-
-
-def _cfg2_table():
-    t = oa.OpticalTable()
-    t.add_components(scenes.cfg2_components(oa))
-    return t
-
-
-def _eight_monitors():
-    """The eight of tests/test_gpu_image.py."""
-    return [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([6.5, 0, 0], 6, 6), oa.Monitor([7.5, 40, 0], 6, 6), oa.Monitor([8.5, 0, 0], 6, 6),
-            oa.Monitor([7.5, 0, 0], 6, 6).RotZ(0.3), oa.Monitor([7.5, 0, 0], 0.5, 0.5), oa.Monitor([7.5, 0, 0], 0.4, 6).RotX(0.5),
-            oa.Monitor([7.5, 0, 0], 2, 2)]
-
-
 EMPTY, DROPS, SPREAD = 2, 6, 7
-
-
-def _wavelengths(wavelength, h):
-    """The wavelength of every hit of `h` (reference order): a float, or the traced RayBatch's by the hits' ray."""
-    if isinstance(wavelength, RayBatch):
-        return wavelength.wavelength.double().cpu().numpy()[h.ray_index(None).cpu().numpy()]
-    return np.full(len(h), float(wavelength))
 
 
 def _reference(h, wavelength, y_edges, z_edges, amplitude="sqrt", keep=None):
@@ -74,7 +49,7 @@ def _reference(h, wavelength, y_edges, z_edges, amplitude="sqrt", keep=None):
         return t.double().cpu().numpy()
 
     y, z, I = host(h.yList(None)), host(h.zList(None)), host(h.IList(None))
-    L, lam = host(h.pathlengthList(None)), _wavelengths(wavelength, h)
+    L, lam = host(h.pathlengthList(None)), support.hit_wavelengths(wavelength, h)
     parts = np.abs(host(h._gather(h.segs.pathlength, h.slot))) + np.abs(host(h.t) * host(h._gather(h.segs.n_index, h.slot)))
     if keep is not None:
         y, z, I, L, lam, parts = (v[keep] for v in (y, z, I, L, lam, parts))
@@ -116,17 +91,9 @@ def _assert_field(f, h, wavelength, amplitude="sqrt"):
 def case1():
     """cfg 2, 5,003 rays, 5 segments, eight monitors, f64: (table, monitors, batch, {layout: (segs, record_all hits)}), traced and
     recorded on first use."""
-    table, mons, made = _cfg2_table(), _eight_monitors(), {}
-    batch = _batch(*scenes.cfg2_rays(5003, 0))
-
-    def get(layout):
-        if layout not in made:
-            segs = table.trace_batch(batch, max_segments=5, layout=layout)
-            assert segs.layout == layout and segs.precision == "f64"
-            made[layout] = (segs, table.record_all(segs, monitors=mons))
-        return made[layout]
-
-    return table, mons, batch, get
+    table, mons = support.cfg2_table(), support.eight_monitors()
+    batch = support.weighted_batch(*scenes.cfg2_rays(5003, 0))
+    return table, mons, batch, support.traced(table, lambda precision: batch, 5, lambda segs: table.record_all(segs, monitors=mons))
 
 
 @pytest.mark.parametrize("layout", ["slots", "tiled", "append"])
@@ -179,7 +146,7 @@ def test_per_ray_wavelengths_through_a_dispersive_slab():
     jit = rng.uniform(-0.3, 0.3, (40, 2))
     o = np.stack([np.full(40, -3.0), 2 + jit[:, 0], jit[:, 1]], axis=1)
     d = np.tile([np.cos(np.pi / 6), -np.sin(np.pi / 6), 0.0], (40, 1))
-    base = RayBatch.from_arrays(o, d, wavelength=scenes.WL, intensity=0.25 + 0.75 * rng.random(40), q=1j * np.pi * scenes.W0**2 / scenes.WL, device="cuda")
+    base = RayBatch.from_arrays(o, d, wavelength=scenes.WL, intensity=0.25 + 0.75 * rng.random(40), q=support.Q, device="cuda")
     batch = base.multiplexed_in_wavelength([780e-7, 560e-7, 400e-7])
     assert batch.n == 120 and len(set(batch.wavelength.tolist())) == 3
     table = oa.OpticalTable()
@@ -199,10 +166,10 @@ def test_per_ray_wavelengths_through_a_dispersive_slab():
 def test_global_path_and_accumulation():
     """(80, 80): 6,400 bins, more than the LDS budget — every hit a global atomic.  And `into=` over the two chunks of a batch
     against the whole batch in one call: counts equal, the field within the sum of the two chunks' bounds."""
-    table = _cfg2_table()
+    table = support.cfg2_table()
     mon = oa.Monitor([7.5, 0, 0], 2, 2)
     assert field_plan(1, 80, 80)["path"] == "global"
-    whole = _batch(*scenes.cfg2_rays(2049, 3))
+    whole = support.weighted_batch(*scenes.cfg2_rays(2049, 3))
     segs = table.trace_batch(whole, max_segments=5, layout="slots")
     h = table.record_all(segs, monitors=[mon])[0]
     full = table.field_all(segs, whole, bins=(80, 80), monitors=[mon])
@@ -267,30 +234,18 @@ def test_michelson_known_answer(amplitude):
     assert np.all(got < 1e-6 * a * c)
 
 
-def _tables(mons, nby, nbz):
-    axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in mons], dtype=float)
-    edges = np.array([np.concatenate(image_edges(m, nby, nbz)) for m in mons], dtype=float)
-    return axes, edges
-
-
-class _Out:
+class _Out(support.Sentinel):
     """counts / re / im of M monitors of nby x nbz bins and `skipped` for ot_monitor_field_many, filled with a sentinel."""
 
-    def __init__(self, M, nby, nbz, fill=-7):
-        self.fill = fill
-        self.counts = torch.full((M, nby, nbz), fill, dtype=torch.int64, device="cuda")
-        self.re = torch.full((M, nby, nbz), float(fill), dtype=torch.float64, device="cuda")
-        self.im = torch.full((M, nby, nbz), float(fill), dtype=torch.float64, device="cuda")
-        self.skipped = torch.full((1,), fill, dtype=torch.int64, device="cuda")
-
-    def untouched(self):
-        return all(bool((t == self.fill).all()) for t in (self.counts, self.re, self.im, self.skipped))
+    def __init__(self, M, nby, nbz):
+        image = (torch.float64, (M, nby, nbz))
+        super().__init__(counts=(torch.int64, (M, nby, nbz)), re=image, im=image, skipped=(torch.int64, (1,)))
 
 
 def _call(lib, ctx, mons, segs, nby, nbz, out, wavelength=None, n_wavelengths=0, uniform=0.0, mode=0, accumulate=0, source=None, **planes):
     src, n, count, n_rays = segment_source(segs)
     table = (abi.OtMonitor * len(mons))(*[monitor_struct(m) for m in mons])
-    axes, edges = _tables(mons, nby, nbz)
+    axes, edges = support.image_tables(mons, nby, nbz)
     dp = C.POINTER(C.c_double)
     plane = {f: planes.get(f, segs.field(f).data_ptr()) for f in ("intensity", "n", "pathlength")}
     return lib.ot_monitor_field_many(ctx, table, len(mons), axes.ctypes.data_as(dp), edges.ctypes.data_as(dp), nby, nbz,
@@ -331,17 +286,7 @@ def test_the_guard_on_the_wavelength_gather(case1):
 
 def _list_of_segments(n):
     """n segments (0, 0, 0) + t (1, 0, 0) of length 10 as a list, `ray` = 0 .. n - 1: the monitor at x = 5 sees every one at P = 0."""
-    segs = SegmentBatch(n, "f64", "cuda")
-    for f in abi.SEG_FIELDS:
-        segs.field(f).zero_()
-    segs.dx.fill_(1.0)
-    segs.length.fill_(10.0)
-    segs.intensity.fill_(0.25)
-    segs.n_index.fill_(1.0)
-    segs.pathlength.copy_(torch.arange(n, dtype=torch.float64) / 8)
-    segs.ray.copy_(torch.arange(n, dtype=torch.int32))
-    segs.n_valid = n
-    return segs
+    return support.list_segments(n, dx=1.0, length=10.0, intensity=0.25, n=1.0, pathlength=np.arange(n) / 8)
 
 
 def test_field_all_refuses_a_field_with_hits_left_out():
@@ -361,15 +306,6 @@ def test_field_all_refuses_a_field_with_hits_left_out():
         table.field_batch(mon, segs, RayBatch.from_arrays(o[:100], d[:100], wavelength=0.5, device="cuda"), bins=(7, 5))
 
 
-@pytest.fixture()
-def ctx():
-    lib = abi.load()
-    c = C.c_void_p()
-    assert lib.ot_ctx_create(0, None, C.byref(c)) == 0
-    yield lib, c
-    assert lib.ot_ctx_destroy(c) == 0
-
-
 def test_abi_errors(ctx):
     lib, c = ctx
     segs, mon = _list_of_segments(130), oa.Monitor([5, 0, 0], 2, 2)
@@ -380,17 +316,7 @@ def test_abi_errors(ctx):
         kw.setdefault("uniform", 0.5)
         return _call(lib, c, [mon], segs, 7, 5, out, **kw)
 
-    def expect(status, needle):
-        msg = lib.ot_last_error().decode()
-        assert status == ERR_INVALID and needle in msg, (status, msg, needle)
-
-    src = segment_source(segs)[0]
-
-    def altered(**fields):
-        other = abi.OtSegmentSource.from_buffer_copy(src)
-        for k, v in fields.items():
-            setattr(other, k, v)
-        return other
+    expect, altered = functools.partial(support.expect_invalid, lib), functools.partial(support.altered, segment_source(segs)[0])
 
     expect(call(source=altered(width=4)), "width must be 8")  # single-precision segments: refused, not approximated
     expect(call(source=altered(width=2)), "width")

@@ -14,6 +14,7 @@ at table scale, so no piece can change pixel or vanish.  The ROIs' grid lines av
 2.97, not -3 to 3); the CPU oracle's cfg 2 segments give a shortest piece of 6.5e-8 over the views and shapes below.
 The pixel rule itself is checked on exact coordinates, lines and their neighbouring doubles included, with no such condition."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -21,37 +22,18 @@ import torch
 
 import optable_amd as oa
 import scenes
+import support
 from fluence_reference import fluence_reference
 from optable_amd import abi
 from optable_amd import workloads as W
 from optable_amd.batch import RayBatch, SegmentBatch
 from optable_amd.engine import fluence_plan, get_engine, segment_source
 from optable_amd.fluence import fluence_view
+from support import ctx  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-ERR_INVALID = -1
 ROI = (-1.03, 12.9, -3.01, 2.97, -2.83, 3.07)  # cfg 2: source at the origin, lens at x = 5, mirror pair at x = 10; finite depth in every view
-
-
-def _batch(o, d, precision="f64", seed=7):
-    """cfg 2's rays with per-ray intensities 0.25 + 0.75 u: the fluence channel is no copy of the counts."""
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
-    intensity = 0.25 + 0.75 * np.random.default_rng(seed).random(len(o))
-    return RayBatch.from_arrays(o, d, wavelength=scenes.WL, intensity=intensity, q=q, precision=precision, device="cuda")
-
-
-def _cfg2_table():
-    t = oa.OpticalTable()
-    t.add_components(scenes.cfg2_components(oa))
-    return t
-
-
-def _records(segs):
-    """The valid segment records of a batch, copied from the device: (o [n, 3], d [n, 3], length, intensity) as doubles."""
-    h = segs.to_host(reference_order=False)
-    col = lambda f: np.asarray(h[f], dtype=np.float64)  # noqa: E731  (single precision widens exactly)
-    return np.stack([col("ox"), col("oy"), col("oz")], 1), np.stack([col("dx"), col("dy"), col("dz")], 1), col("length"), col("intensity")
 
 
 def _reference(records, view, roi, pixels, weight="intensity"):
@@ -78,17 +60,9 @@ def _assert_map(fm, ref, traced=True):
 @pytest.fixture(scope="module")
 def case1():
     """cfg 2, 5,003 rays, 5 segments: (table, {(layout, precision): (segs, records)}), traced on first use."""
-    table, made = _cfg2_table(), {}
+    table = support.cfg2_table()
     o, d = scenes.cfg2_rays(5003, 0)
-
-    def get(layout, precision):
-        if (layout, precision) not in made:
-            segs = table.trace_batch(_batch(o, d, precision), max_segments=5, layout=layout)
-            assert segs.layout == layout and segs.precision == precision
-            made[layout, precision] = (segs, _records(segs))
-        return made[layout, precision]
-
-    return table, get
+    return table, support.traced(table, lambda precision: support.weighted_batch(o, d, precision), 5, support.host_records)
 
 
 @pytest.mark.parametrize("precision", ["f64", "f32"])
@@ -154,35 +128,13 @@ def test_shapes(case1, pixels):
 
 
 # -- exact coordinates ----------------------------------------------------------------------------------------------------------
-def _list_batch(o, d, length, intensity):
-    n = len(o)
-    segs = SegmentBatch(n, "f64", "cuda")
-    for f in abi.SEG_FIELDS:
-        segs.field(f).zero_()
-    for k, f in enumerate(("ox", "oy", "oz")):
-        segs.field(f).copy_(torch.from_numpy(np.ascontiguousarray(o[:, k])))
-    for k, f in enumerate(("dx", "dy", "dz")):
-        segs.field(f).copy_(torch.from_numpy(np.ascontiguousarray(d[:, k])))
-    segs.length.copy_(torch.from_numpy(np.asarray(length, dtype=np.float64)))
-    segs.intensity.copy_(torch.from_numpy(np.asarray(intensity, dtype=np.float64)))
-    segs.ray.copy_(torch.arange(n, dtype=torch.int32))
-    segs.n_valid = n
-    assert segs.layout == "list"
-    return segs
-
-
-def _around(edges):
-    """Every line, and the doubles just below and above every one of them (the outer lines' outer neighbours lie outside)."""
-    return np.unique(np.concatenate([edges, np.nextafter(edges, -np.inf), np.nextafter(edges, np.inf)]))
-
-
 def _exact_segments():
     """Axis-parallel segments on the grid of the integer lines 0 .. 7 x 0 .. 5: along u and along v, both ways, at rest on every line
     of the other axis and on the doubles next to it, starting and ending on lines (1 -> 4) and inside pixels (0.5 -> 4.5; all
     lengths whole, all pieces multiples of 1 / 2), of no length, unbounded, along the depth, outside, and with a NaN origin."""
     ue, ve = np.arange(8.0), np.arange(6.0)
     o, d, length = [], [], []
-    for rest, along, lines, reach in ((1, 0, _around(ve), 7.0), (0, 1, _around(ue), 5.0)):
+    for rest, along, lines, reach in ((1, 0, support.around(ve), 7.0), (0, 1, support.around(ue), 5.0)):
         for x in lines:
             for start, sign, L in ((1.0, 1, 3.0), (4.0, -1, 3.0), (0.5, 1, 4.0), (4.5, -1, 4.0), (2.0, 1, 0.0), (0.5, 1, np.inf), (reach - 0.5, -1, np.inf),
                                    (-2.0, 1, 4.0), (reach, -1, 2.0), (0.0, 1, reach)):
@@ -202,8 +154,8 @@ def test_pixel_rule_on_exact_coordinates():
     reference with NO precondition; inside a finite and inside an infinite depth range."""
     table = oa.OpticalTable()
     o, d, length = _exact_segments()
-    segs = _list_batch(o, d, length, np.full(len(o), 0.5))
-    many = _list_batch(np.tile(o, (7, 1)), np.tile(d, (7, 1)), np.tile(length, 7), np.full(7 * len(o), 0.5))
+    segs = support.list_batch(o, d, length, np.full(len(o), 0.5))
+    many = support.list_batch(np.tile(o, (7, 1)), np.tile(d, (7, 1)), np.tile(length, 7), np.full(7 * len(o), 0.5))
     assert 7 * len(o) > 2048  # more than one workgroup's slots
     for z1, skipped in ((1.0, 3), (np.inf, 4)):  # the NaN origin, the zero direction, the NaN length; and the ray leaving along z
         roi = (0.0, 7.0, 0.0, 5.0, -1.0, z1)
@@ -219,10 +171,10 @@ def test_pixel_rule_on_exact_coordinates():
         seven = table.fluence_map(many, view="Z", roi=roi, pixels=(7, 5))
         assert torch.equal(seven.counts, 7 * fm.counts) and torch.equal(seven.fluence, 7 * fm.fluence) and seven.skipped == 7 * skipped
     # the other precision and a view whose depth is x: the same rule on the same numbers
-    single = _list_batch(o, d, length, np.full(len(o), 0.5)).astype("f32")
+    single = support.list_batch(o, d, length, np.full(len(o), 0.5)).astype("f32")
     assert single.precision == "f32"
     roi = (0.0, 7.0, 0.0, 5.0, -1.0, 1.0)
-    host = _records(single)
+    host = support.host_records(single)
     fm = table.fluence_map(single, view="Z", roi=roi, pixels=(7, 5))
     ref = _reference(host, "Z", roi, (7, 5))
     assert torch.equal(fm.counts.cpu(), torch.from_numpy(ref.counts)) and fm.skipped == ref.skipped == 3
@@ -247,33 +199,21 @@ def test_uneven_walks_in_one_wave():
     intensity = 0.25 + 0.75 * rng.random(n)
     roi = (0.0, 512.0, 0.0, 512.0, -1.0, 1.0)
     assert fluence_plan(512, 512)["path"] == "global"
-    fm = oa.OpticalTable().fluence_map(_list_batch(o, d, length, intensity), view="Z", roi=roi, pixels=512)
+    fm = oa.OpticalTable().fluence_map(support.list_batch(o, d, length, intensity), view="Z", roi=roi, pixels=512)
     ref = _reference((o, d, length, intensity), "Z", roi, 512)
     assert len(ref.pieces) == 255 + 1023 and ref.skipped == 0
     _assert_map(fm, ref)
 
 
-class _Maps:
+class _Maps(support.Sentinel):
     """counts / fluence / skipped of nu x nv pixels for ot_fluence_map, with a guard region on either side of each."""
-    GUARD = 64
 
-    def __init__(self, nu, nv, fill=-7):
-        G, self.size, self.fill = self.GUARD, nu * nv, fill
-        self.c = torch.full((self.size + 2 * G,), fill, dtype=torch.int64, device="cuda")
-        self.f = torch.full((self.size + 2 * G,), float(fill), dtype=torch.float64, device="cuda")
-        self.s = torch.full((1 + 2 * G,), fill, dtype=torch.int64, device="cuda")
-        self.counts, self.fluence, self.skipped = self.c[G:G + self.size].view(nu, nv), self.f[G:G + self.size].view(nu, nv), self.s[G:G + 1]
+    def __init__(self, nu, nv):
+        super().__init__(guard=64, counts=(torch.int64, (nu, nv)), fluence=(torch.float64, (nu, nv)), skipped=(torch.int64, (1,)))
 
     def zero_(self):
         self.counts.zero_(), self.fluence.zero_(), self.skipped.zero_()
         return self
-
-    def guards_untouched(self):
-        G = self.GUARD
-        return all(bool((t[:G] == self.fill).all()) and bool((t[G + size:] == self.fill).all()) for t, size in ((self.c, self.size), (self.f, self.size), (self.s, 1)))
-
-    def untouched(self):
-        return all(bool((t == self.fill).all()) for t in (self.c, self.f, self.s))
 
 
 def _call(lib, ctx, segs, view, roi, pixels, out, accumulate=0):
@@ -286,23 +226,23 @@ def _call(lib, ctx, segs, view, roi, pixels, out, accumulate=0):
 
 
 def test_edges_of_the_partition():
-    table, eng = _cfg2_table(), get_engine()
+    table, eng = support.cfg2_table(), get_engine()
     # one ray, one segment (origin -> lens)
     for layout in ("slots", "tiled", "append"):
-        segs = table.trace_batch(_batch(*scenes.cfg2_rays(1, 0)), max_segments=1, layout=layout)
+        segs = table.trace_batch(support.weighted_batch(*scenes.cfg2_rays(1, 0)), max_segments=1, layout=layout)
         fm = table.fluence_map(segs, view="Z", roi=ROI, pixels=(40, 30))
-        ref = _reference(_records(segs), "Z", ROI, (40, 30))
+        ref = _reference(support.host_records(segs), "Z", ROI, (40, 30))
         assert 10 < ref.counts.sum() < 60
         _assert_map(fm, ref)
     # slot counts of 64 k + 1: 65 slots, and 2,049 = one more than a workgroup's 2,048
     for n, K in ((13, 5), (2049, 1)):
-        segs = table.trace_batch(_batch(*scenes.cfg2_rays(n, 3)), max_segments=K, layout="slots")
+        segs = table.trace_batch(support.weighted_batch(*scenes.cfg2_rays(n, 3)), max_segments=K, layout="slots")
         assert segment_source(segs)[1] % 64 == 1
         guarded = _Maps(40, 30).zero_()
         axes, ue, ve, depth, _ = fluence_view("Z", ROI, (40, 30))
         eng.fluence_map(axes, ue, ve, depth, segs, into=(guarded.counts, guarded.fluence, guarded.skipped))
         fm = table.fluence_map(segs, view="Z", roi=ROI, pixels=(40, 30))
-        ref = _reference(_records(segs), "Z", ROI, (40, 30))
+        ref = _reference(support.host_records(segs), "Z", ROI, (40, 30))
         _assert_map(fm, ref)
         torch.cuda.synchronize()
         assert guarded.guards_untouched() and torch.equal(guarded.counts, fm.counts) and int(guarded.skipped.item()) == 0
@@ -312,7 +252,7 @@ def test_edges_of_the_partition():
     axes, ue, ve, depth, _ = fluence_view("Z", ROI, (96, 80))
     eng.fluence_map(axes, ue, ve, depth, segs, into=(guarded.counts, guarded.fluence, guarded.skipped))
     torch.cuda.synchronize()
-    ref = _reference(_records(segs), "Z", ROI, (96, 80))
+    ref = _reference(support.host_records(segs), "Z", ROI, (96, 80))
     assert ref.pieces.min() > 1e-9
     assert guarded.guards_untouched() and np.array_equal(guarded.counts.cpu().numpy(), ref.counts)
     assert np.all(np.abs(guarded.fluence.cpu().numpy() - ref.fluence) <= ref.bound)
@@ -338,17 +278,17 @@ def test_edges_of_the_partition():
 
 def test_accumulation():
     """A map summed over the chunks of a trace: the two halves of a batch with `into=` against the whole batch in one call."""
-    table = _cfg2_table()
+    table = support.cfg2_table()
     o, d = scenes.cfg2_rays(2049, 3)
-    whole = _batch(o, d)
+    whole = support.weighted_batch(o, d)
     segs = table.trace_batch(whole, max_segments=5, layout="slots")
-    ref = _reference(_records(segs), "Z", ROI, (40, 30))
+    ref = _reference(support.host_records(segs), "Z", ROI, (40, 30))
     full = table.fluence_map(segs, view="Z", roi=ROI, pixels=(40, 30))
     _assert_map(full, ref)
     halves = []
     for part in (slice(0, 1024), slice(1024, 2049)):
         b = RayBatch.from_arrays(o[part], d[part], wavelength=scenes.WL, intensity=whole.intensity[part].cpu().numpy(),
-                                 q=1j * np.pi * scenes.W0**2 / scenes.WL, device="cuda")
+                                 q=support.Q, device="cuda")
         halves.append(table.trace_batch(b, max_segments=5, layout="slots"))
     fm = table.fluence_map(halves[0], view="Z", roi=ROI, pixels=(40, 30))
     first = fm.counts.clone()
@@ -373,19 +313,10 @@ def test_lists_and_trees():
     for segs, layout in ((eng.trace_trees(batch, 12, layout="slots"), "slots"), (eng.trace_trees(batch, 12, layout="append"), "append"),
                          (eng.trace_tree(batch, 12), "list")):
         assert segs.layout == layout
-        records = _records(segs)
+        records = support.host_records(segs)
         assert len(records[2]) >= 3 * 320
         for view in ("Z", "X"):
             _assert_map(table.fluence_map(segs, view=view, roi=roi, pixels=(40, 30)), _reference(records, view, roi, (40, 30)))
-
-
-@pytest.fixture()
-def ctx():
-    lib = abi.load()
-    c = C.c_void_p()
-    assert lib.ot_ctx_create(0, None, C.byref(c)) == 0
-    yield lib, c
-    assert lib.ot_ctx_destroy(c) == 0
 
 
 def test_abi_errors(ctx):
@@ -413,15 +344,7 @@ def test_abi_errors(ctx):
         return lib.ot_fluence_map(ctx_, as_ptr(axes), as_ptr(ue), u, as_ptr(ve), v, w_lo, w_hi, None if source is None else C.byref(source), intensity,
                                   n_seg, cnt, rays, counts, fluence, skipped, acc)
 
-    def expect(status, needle):
-        msg = lib.ot_last_error().decode()
-        assert status == ERR_INVALID and needle in msg, (status, msg, needle)
-
-    def altered(**fields):
-        other = abi.OtSegmentSource.from_buffer_copy(src)
-        for k, v in fields.items():
-            setattr(other, k, v)
-        return other
+    expect, altered = functools.partial(support.expect_invalid, lib), functools.partial(support.altered, src)
 
     def with_value(a, at, value):
         b = np.array(a, dtype=float)

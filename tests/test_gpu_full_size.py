@@ -8,17 +8,10 @@ import numpy as np
 import pytest
 
 import scenes
+import support
 from optable_amd import abi
 
 pytestmark = pytest.mark.gpu
-
-
-def _table(components):
-    import optable_amd as oa
-
-    t = oa.OpticalTable()
-    t.add_components(components)
-    return t
 
 
 def _chain_properties(segs, n, K, tol, unit_tol):
@@ -71,9 +64,9 @@ def test_cfg3_full_size_fp32():
     from optable_amd.batch import RayBatch
 
     n, K = 10_000_000, 20
-    table = _table(scenes.cfg3_components(oa))
+    table = support.table_of(scenes.cfg3_components(oa))
     o, d = scenes.cfg3_rays(n, 2)
-    batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=1j * np.pi * scenes.W0**2 / scenes.WL, precision="f32")
+    batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=support.Q, precision="f32")
     del o, d
     from optable_amd.engine import get_engine
 
@@ -112,12 +105,12 @@ def test_cfg4_shard_closed_form_fp64(nb):
     o = np.stack([np.full(nb, -3.0), 2 + jit[:, 0], jit[:, 1]], 1)
     d = np.tile([np.cos(np.pi / 6), -np.sin(np.pi / 6), 0.0], (nb, 1))
     wls = np.linspace(400e-7, 1100e-7, nwl)
-    base = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=1j * np.pi * scenes.W0**2 / scenes.WL)
+    base = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=support.Q)
     batch = base.multiplexed_in_wavelength(wls)
     del base, o, d
     n = nb * nwl
     glass = oa.Glass_NBK7()
-    table = _table([oa.GlassSlab([0, 0, 0], width=2, height=2, thickness=thickness, n1=oa.Vacuum(), n2=glass, reflectivity=0)])
+    table = support.table_of([oa.GlassSlab([0, 0, 0], width=2, height=2, thickness=thickness, n1=oa.Vacuum(), n2=glass, reflectivity=0)])
     segs = table.trace_batch(batch, max_segments=K)  # the DEFAULT call: tiles or slot arrays, whichever this device streams faster
     assert segs.layout in ("tiled", "slots")
     assert int(segs.count.min()) == K and int(segs.count.max()) == K
@@ -167,9 +160,9 @@ def test_cfg5_shard_fp32():
     from optable_amd.batch import RayBatch
 
     n, K = 12_500_000, 50
-    table = _table(scenes.cfg5_components(oa))
+    table = support.table_of(scenes.cfg5_components(oa))
     o, d = scenes.cfg5_rays(n, 3)
-    batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=1j * np.pi * scenes.W0**2 / scenes.WL, precision="f32")
+    batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=support.Q, precision="f32")
     del o, d
     from optable_amd.engine import get_engine
 
@@ -201,7 +194,7 @@ def test_cfg4_ray_trees_full_size_fp64():
     from optable_amd.batch import RayBatch
     from optable_amd.engine import get_engine
 
-    table = _table(W.cfg4_components(oa, reflectivity=0.2))
+    table = support.table_of(W.cfg4_components(oa, reflectivity=0.2))
     scene = table.compile()
     eng = get_engine()
     eng.upload(scene)

@@ -10,6 +10,7 @@ first asserts, from the REFERENCE values, that no y or z lies within 1e-9 of a b
 oracle gives a smallest distance of 3e-7 for the cfg 2 inputs below, all eight monitors, all four bin shapes).
 The bin rule itself is checked on exact coordinates, edges and their neighbouring doubles included, with no such condition."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -17,41 +18,17 @@ import torch
 
 import optable_amd as oa
 import scenes
+import support
 from optable_amd import abi
 from optable_amd import workloads as W
 from optable_amd.batch import RayBatch, SegmentBatch
 from optable_amd.engine import get_engine, image_plan, segment_source
-from optable_amd.monitors import image_edges
 from optable_amd.table import monitor_struct
+from support import ctx  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-ERR_INVALID = -1
 U = 2.0**-53
-
-
-def _batch(o, d, precision="f64", seed=7):
-    """cfg 2's rays with per-ray intensities 0.25 + 0.75 u: the weight channel is no copy of the counts."""
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
-    intensity = 0.25 + 0.75 * np.random.default_rng(seed).random(len(o))
-    return RayBatch.from_arrays(o, d, wavelength=scenes.WL, intensity=intensity, q=q, precision=precision, device="cuda")
-
-
-def _cfg2_table():
-    t = oa.OpticalTable()
-    t.add_components(scenes.cfg2_components(oa))
-    return t
-
-
-def _eight_monitors():
-    return [oa.Monitor([7.5, 0, 0], 6, 6),             # the six of tests/test_gpu_record_all.py
-            oa.Monitor([6.5, 0, 0], 6, 6),
-            oa.Monitor([7.5, 40, 0], 6, 6),            # where no segment passes: an all-zero image
-            oa.Monitor([8.5, 0, 0], 6, 6),
-            oa.Monitor([7.5, 0, 0], 6, 6).RotZ(0.3),
-            oa.Monitor([7.5, 0, 0], 0.5, 0.5),         # clips
-            oa.Monitor([7.5, 0, 0], 0.4, 6).RotX(0.5),  # the lab-tangent projection leaves the image range: the drop rule runs
-            oa.Monitor([7.5, 0, 0], 2, 2)]             # the beam over some 430 bins instead of 60
 
 
 EMPTY, DROPS, SPREAD = 2, 6, 7
@@ -86,17 +63,9 @@ def _assert_image(im, h):
 def case1():
     """cfg 2, 5,003 rays, 5 segments, eight monitors: (table, monitors, {(layout, precision): (segs, record_all hits)}), traced and
     recorded on first use."""
-    table, mons, made = _cfg2_table(), _eight_monitors(), {}
+    table, mons = support.cfg2_table(), support.eight_monitors()
     o, d = scenes.cfg2_rays(5003, 0)
-
-    def get(layout, precision):
-        if (layout, precision) not in made:
-            segs = table.trace_batch(_batch(o, d, precision), max_segments=5, layout=layout)
-            assert segs.layout == layout and segs.precision == precision
-            made[layout, precision] = (segs, table.record_all(segs, monitors=mons))
-        return made[layout, precision]
-
-    return table, mons, get
+    return table, mons, support.traced(table, lambda precision: support.weighted_batch(o, d, precision), 5, lambda segs: table.record_all(segs, monitors=mons))
 
 
 @pytest.mark.parametrize("precision", ["f64", "f32"])
@@ -145,9 +114,9 @@ def test_bin_shapes(case1, bins):
 
 
 def test_more_than_one_group_of_monitors():
-    table = _cfg2_table()
+    table = support.cfg2_table()
     mons = [oa.Monitor([5.5 + 0.125 * k, 0, 0], 6, 6) for k in range(32)] + [oa.Monitor([5.5, 0, 0], 6, 6)]  # 33: positions 0 and 32 alike
-    segs = table.trace_batch(_batch(*scenes.cfg2_rays(2003, 0)), max_segments=5, layout="slots")
+    segs = table.trace_batch(support.weighted_batch(*scenes.cfg2_rays(2003, 0)), max_segments=5, layout="slots")
     assert image_plan(33, 7, 5)["passes"] == 2
     images = table.image_all(segs, bins=(7, 5), monitors=mons)
     hits = table.record_all(segs, monitors=mons)
@@ -177,36 +146,18 @@ def test_lists_and_trees():
             assert int(_assert_image(im, h).sum()) == len(h)
 
 
-class _Images:
+class _Images(support.Sentinel):
     """counts / weights of M monitors of nby x nbz bins for ot_monitor_image_many, with a guard region on either side."""
-    GUARD = 64
 
-    def __init__(self, M, nby, nbz, fill=-7):
-        self.size, self.fill = M * nby * nbz, fill
-        self.c = torch.full((self.size + 2 * self.GUARD,), fill, dtype=torch.int64, device="cuda")
-        self.w = torch.full((self.size + 2 * self.GUARD,), float(fill), dtype=torch.float64, device="cuda")
-        self.counts = self.c[self.GUARD:self.GUARD + self.size].view(M, nby, nbz)
-        self.weights = self.w[self.GUARD:self.GUARD + self.size].view(M, nby, nbz)
-
-    def guards_untouched(self):
-        G = self.GUARD
-        return all(bool((t[:G] == self.fill).all()) and bool((t[G + self.size:] == self.fill).all()) for t in (self.c, self.w))
-
-    def untouched(self):
-        return bool((self.c == self.fill).all()) and bool((self.w == self.fill).all())
-
-
-def _tables(mons, nby, nbz):
-    axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in mons], dtype=float)
-    edges = np.array([np.concatenate(image_edges(m, nby, nbz)) for m in mons], dtype=float)
-    return axes, edges
+    def __init__(self, M, nby, nbz):
+        super().__init__(guard=64, counts=(torch.int64, (M, nby, nbz)), weights=(torch.float64, (M, nby, nbz)))
 
 
 def test_accumulation():
     """A detector summed over the chunks of a trace: the two halves of a batch with `into=` against the whole batch in one call."""
-    table = _cfg2_table()
+    table = support.cfg2_table()
     o, d = scenes.cfg2_rays(2049, 3)
-    whole = _batch(o, d)
+    whole = support.weighted_batch(o, d)
     mons = [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([7.5, 0, 0], 2, 2), oa.Monitor([7.5, 40, 0], 6, 6)]
     segs = table.trace_batch(whole, max_segments=5, layout="slots")
     hits = table.record_all(segs, monitors=mons)
@@ -216,7 +167,7 @@ def test_accumulation():
     halves = []
     for part in (slice(0, 1024), slice(1024, 2049)):
         b = RayBatch.from_arrays(o[part], d[part], wavelength=scenes.WL, intensity=whole.intensity[part].cpu().numpy(),
-                                 q=1j * np.pi * scenes.W0**2 / scenes.WL, device="cuda")
+                                 q=support.Q, device="cuda")
         halves.append(table.trace_batch(b, max_segments=5, layout="slots"))
     images = table.image_all(halves[0], monitors=mons)
     first = [im.counts.clone() for im in images]
@@ -225,7 +176,7 @@ def test_accumulation():
     guarded = _Images(len(mons), 30, 30)
     guarded.counts.zero_()
     guarded.weights.zero_()
-    axes, edges = _tables(mons, 30, 30)
+    axes, edges = support.image_tables(mons, 30, 30)
     for half in halves:
         eng.monitor_image_many(structs, axes, edges, (30, 30), half, into=(guarded.counts, guarded.weights))
     torch.cuda.synchronize()
@@ -244,7 +195,7 @@ def test_accumulation():
 def _call(lib, ctx, mons, segs, nby, nbz, images, accumulate=0):
     src, n, count, n_rays = segment_source(segs)
     table = (abi.OtMonitor * len(mons))(*[monitor_struct(m) for m in mons])
-    axes, edges = _tables(mons, nby, nbz)
+    axes, edges = support.image_tables(mons, nby, nbz)
     dp = C.POINTER(C.c_double)
     return lib.ot_monitor_image_many(ctx, table, len(mons), axes.ctypes.data_as(dp), edges.ctypes.data_as(dp), nby, nbz, C.byref(src),
                                      segs.field("intensity").data_ptr(), n, None if count is None else count.data_ptr(), n_rays,
@@ -252,19 +203,19 @@ def _call(lib, ctx, mons, segs, nby, nbz, images, accumulate=0):
 
 
 def test_edges_of_the_partition():
-    table = _cfg2_table()
+    table = support.cfg2_table()
     eng = get_engine()
     # one ray, one segment (origin -> lens): the first monitor sees it, the second does not
     mons = [oa.Monitor([2.5, 0, 0], 6, 6), oa.Monitor([7.5, 0, 0], 6, 6)]
     for layout in ("slots", "tiled", "append"):
-        segs = table.trace_batch(_batch(*scenes.cfg2_rays(1, 0)), max_segments=1, layout=layout)
+        segs = table.trace_batch(support.weighted_batch(*scenes.cfg2_rays(1, 0)), max_segments=1, layout=layout)
         images = table.image_all(segs, monitors=mons)
         assert (int(images[0].counts.sum()), int(images[1].counts.sum())) == (1, 0)
         for im, h in zip(images, table.record_all(segs, monitors=mons)):
             _assert_image(im, h)
     # slot counts of 64 k + 1: 65 slots, and 2,049 = one more than a workgroup's 2,048
     for n, K in ((13, 5), (2049, 1)):
-        segs = table.trace_batch(_batch(*scenes.cfg2_rays(n, 3)), max_segments=K, layout="slots")
+        segs = table.trace_batch(support.weighted_batch(*scenes.cfg2_rays(n, 3)), max_segments=K, layout="slots")
         assert segment_source(segs)[1] % 64 == 1
         images = table.image_all(segs, monitors=mons)
         assert int(images[0].counts.sum()) >= n  # every ray's first segment, the one in the slot behind the boundary among them
@@ -290,27 +241,11 @@ def test_edges_of_the_partition():
     assert kept.untouched()
 
 
-def _around(edges):
-    """Every edge, and the doubles just below and above every one of them (the outer edges' outer neighbours lie outside)."""
-    return np.unique(np.concatenate([edges, np.nextafter(edges, -np.inf), np.nextafter(edges, np.inf)]))
-
-
 def _exact_segments(ys, zs, intensity):
     """A list of len(ys) x len(zs) segments (0, y, z) + t (1, 0, 0) of length 10: the unrotated monitor at x = 5 sees P = (0, y, z)
     exactly."""
     y, z = (a.ravel() for a in np.meshgrid(ys, zs, indexing="ij"))
-    n = len(y)
-    segs = SegmentBatch(n, "f64", "cuda")
-    for f in abi.SEG_FIELDS:
-        segs.field(f).zero_()
-    segs.oy.copy_(torch.from_numpy(y))
-    segs.oz.copy_(torch.from_numpy(z))
-    segs.dx.fill_(1.0)
-    segs.length.fill_(10.0)
-    segs.intensity.copy_(torch.from_numpy(intensity))
-    segs.ray.copy_(torch.arange(n, dtype=torch.int32))
-    segs.n_valid = n
-    return segs, y, z
+    return support.list_segments(len(y), oy=y, oz=z, dx=1.0, length=10.0, intensity=intensity), y, z
 
 
 def test_bin_rule_on_exact_coordinates():
@@ -319,7 +254,7 @@ def test_bin_rule_on_exact_coordinates():
     table = oa.OpticalTable()
     mon = oa.Monitor([5, 0, 0], 2, 2)
     y_edges, z_edges = np.linspace(-1, 1, 8), np.linspace(-1, 1, 6)
-    ys, zs = _around(y_edges), _around(z_edges)
+    ys, zs = support.around(y_edges), support.around(z_edges)
     assert -1.0 in ys and 1.0 in ys and len(ys) == 24 and len(zs) == 18
     rng = np.random.default_rng(11)
     segs, y, z = _exact_segments(ys, zs, 0.25 + 0.75 * rng.random(len(ys) * len(zs)))
@@ -340,15 +275,6 @@ def test_bin_rule_on_exact_coordinates():
     assert torch.equal(im.counts.cpu(), torch.from_numpy(7 * ref)) and torch.equal(im.intensity.cpu(), torch.from_numpy(3.5 * ref))  # (halves add exactly)
 
 
-@pytest.fixture()
-def ctx():
-    lib = abi.load()
-    c = C.c_void_p()
-    assert lib.ot_ctx_create(0, None, C.byref(c)) == 0
-    yield lib, c
-    assert lib.ot_ctx_destroy(c) == 0
-
-
 def test_abi_errors(ctx):
     lib, c = ctx
     n, nby, nbz = 130, 7, 5
@@ -365,7 +291,7 @@ def test_abi_errors(ctx):
     out = _Images(1, nby, nbz)
     src, n_segments, count, n_rays = segment_source(segs)
     assert (n_segments, n_rays) == (2 * n, n)
-    good_axes, good_edges = _tables([m], nby, nbz)
+    good_axes, good_edges = support.image_tables([m], nby, nbz)
     dp = C.POINTER(C.c_double)
 
     def call(ctx_=c, mons=C.byref(mon), M=1, axes=good_axes, edges=good_edges, by=nby, bz=nbz, source=src, intensity=segs.intensity.data_ptr(),
@@ -373,15 +299,7 @@ def test_abi_errors(ctx):
         return lib.ot_monitor_image_many(ctx_, mons, M, None if axes is None else axes.ctypes.data_as(dp), None if edges is None else edges.ctypes.data_as(dp),
                                          by, bz, None if source is None else C.byref(source), intensity, n_seg, cnt, rays, counts, weights, acc)
 
-    def expect(status, needle):
-        msg = lib.ot_last_error().decode()
-        assert status == ERR_INVALID and needle in msg, (status, msg, needle)
-
-    def altered(**fields):
-        other = abi.OtSegmentSource.from_buffer_copy(src)
-        for k, v in fields.items():
-            setattr(other, k, v)
-        return other
+    expect, altered = functools.partial(support.expect_invalid, lib), functools.partial(support.altered, src)
 
     def edges_with(at, value):
         e = good_edges.copy()

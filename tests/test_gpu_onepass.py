@@ -9,6 +9,7 @@ import torch
 
 import optable_amd as oa
 import scenes
+import support
 from optable_amd import abi
 from optable_amd import workloads as W
 from optable_amd.batch import RayBatch
@@ -39,17 +40,6 @@ def _both(scene, batch, cap, **kw):
     return one
 
 
-def _lattice():
-    comps = []
-    for k in range(5):
-        comps.append(oa.BeamSplitter([2.0 * (k + 1), 0, 0], width=6, height=2, eta=0.5).RotZ(np.pi / 4))
-        comps.append(oa.Mirror([2.0 * (k + 1), 3.0 + 0.1 * k, 0], radius=2).RotZ(-np.pi / 2))
-        comps.append(oa.BeamSplitter([2.0 * (k + 1) + 1.0, 1.5, 0], width=6, height=2, eta=0.3).RotZ(-np.pi / 4))
-    t = oa.OpticalTable()
-    t.add_components(comps)
-    return t.compile()
-
-
 @pytest.mark.parametrize("precision", ["f64", "f32"])
 def test_one_pass_equals_two_pass_on_cfg4_with_reflectivity(precision, oracle):
     table = oa.OpticalTable()
@@ -78,7 +68,7 @@ def test_one_pass_equals_two_pass_on_cfg4_with_reflectivity(precision, oracle):
 def test_one_pass_equals_two_pass_on_bushy_trees(cap, drop):
     """A lattice of beam splitters: trees that double every generation, spanning many tiles of a generation, capped in their
     largest generation — the per-ray budgets, the doomed-children rule and the look-back across hundreds of tiles."""
-    scene = _lattice()
+    scene = support.lattice(5)
     n = 3000 if cap != 40 else 12_000  # (cap 40 at 12 000 trees: generations grow past 65 536 rays and shrink again — both change-overs of the default mode)
     rng = np.random.default_rng(5)
     o = np.stack([np.zeros(n), rng.uniform(-0.3, 0.3, n), rng.uniform(-0.2, 0.2, n)], 1)
@@ -123,7 +113,7 @@ def test_tiny_trees_take_every_route_of_the_generation_loop(n):
     generation is a chain link; a segment array of 16 slots ends the chains on its bound and the call re-enters with the
     pending generation wherever it was; at 64 trees the generations outgrow the buffers of 1024 rays.  Whatever the kernel
     and however often the call comes back: the list of the two-pass run with room for everything, element by element."""
-    scene = _lattice()
+    scene = support.lattice(5)
     rng = np.random.default_rng(7)
     o = np.stack([np.zeros(n), rng.uniform(-0.3, 0.3, n), rng.uniform(-0.2, 0.2, n)], 1)
     d = np.stack([np.ones(n), rng.uniform(-0.02, 0.02, n), rng.uniform(-0.01, 0.01, n)], 1)
@@ -151,7 +141,7 @@ def test_one_pass_resumes_after_its_buffers_grow():
     """Segment arrays and generation buffers that are too small at first: the library hands the pending generation back, the
     engine grows the buffers and calls again — the per-ray budgets of the one-pass kernels are re-seeded from the tree
     table on re-entry and the trace continues where it stopped."""
-    scene = _lattice()
+    scene = support.lattice(5)
     n = 2000
     rng = np.random.default_rng(6)
     o = np.stack([np.zeros(n), rng.uniform(-0.3, 0.3, n), rng.uniform(-0.2, 0.2, n)], 1)

@@ -9,6 +9,7 @@ import pytest
 
 import helpers
 import scenes
+import support
 from optable_amd import abi
 from optable_amd.fp32_audit import assert_explained, audit_traces
 
@@ -57,16 +58,8 @@ def test_ray_tracing_matches_reference_fixture(name, capsys):
 def _batch(o, d, device="cuda"):
     from optable_amd.batch import RayBatch
 
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
+    q = support.Q
     return RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q, device=device)
-
-
-def _table(components):
-    import optable_amd as oa
-
-    t = oa.OpticalTable()
-    t.add_components(components)
-    return t
 
 
 # q tolerance: 1e-9 until a ray's q has passed an aspheric interface.  ASphere.roc is a 3-point finite difference
@@ -88,7 +81,7 @@ def test_batch_trace_matches_oracle(case, oracle):
     import optable_amd as oa
 
     comps, gen, n, K = CASES[case]
-    table = _table(comps(oa))
+    table = support.table_of(comps(oa))
     o, d = gen(n)
     batch = _batch(o, d)
     segs = table.trace_batch(batch, max_segments=K, layout="slots")
@@ -121,7 +114,7 @@ def test_cfg4_dispersion_matches_oracle(oracle):
     d = np.tile([np.cos(np.pi / 6), -np.sin(np.pi / 6), 0.0], (nb, 1))
     wl = np.repeat(np.linspace(400e-7, 1100e-7, nwl), nb)  # wavelength-major (ray.py:441-444)
     o, d = np.tile(o, (nwl, 1)), np.tile(d, (nwl, 1))
-    table = _table([oa.GlassSlab([0, 0, 0], width=2, height=2, thickness=0.5, n1=oa.Vacuum(), n2=oa.Glass_NBK7(), reflectivity=0)])
+    table = support.table_of([oa.GlassSlab([0, 0, 0], width=2, height=2, thickness=0.5, n1=oa.Vacuum(), n2=oa.Glass_NBK7(), reflectivity=0)])
     batch = RayBatch.from_arrays(o, d, wavelength=wl, q=1j * np.pi * scenes.W0**2 / wl)
     got = table.trace_batch(batch, max_segments=8, layout="slots").to_host(reference_order=True)
     ref = oracle.trace(table.compile(), batch.to_host(), max_trace_num=8)
@@ -138,7 +131,7 @@ def test_branching_batch_matches_oracle(oracle):
     rng = np.random.default_rng(7)
     o = np.stack([np.full(n, -3.0), 2 + rng.uniform(-0.3, 0.3, n), rng.uniform(-0.3, 0.3, n)], 1)
     d = np.tile([np.cos(np.pi / 6), -np.sin(np.pi / 6), 0.0], (n, 1))
-    table = _table([oa.GlassSlab([0, 0, 0], width=2, height=2, thickness=0.5, n1=1, n2=1.5, reflectivity=0.2),
+    table = support.table_of([oa.GlassSlab([0, 0, 0], width=2, height=2, thickness=0.5, n1=1, n2=1.5, reflectivity=0.2),
                     oa.BeamSplitter([3, 0, 0], width=3, height=3, eta=0.4).RotZ(0.3)])
     batch = _batch(o, d)
     segs = table.trace_batch(batch, max_segments=40, layout="slots")
@@ -158,7 +151,7 @@ def test_cfg2_full_size_properties():
     import optable_amd as oa
 
     n, K = 1_000_000, 5
-    table = _table(scenes.cfg2_components(oa))
+    table = support.table_of(scenes.cfg2_components(oa))
     o, d = scenes.cfg2_rays(n, 0)
     batch = _batch(o, d)
     segs = table.trace_batch(batch, max_segments=K, layout="slots")
@@ -192,7 +185,7 @@ def test_cfg2_full_size_properties():
 def test_empty_and_ragged_inputs():
     import optable_amd as oa
 
-    table = _table(scenes.cfg2_components(oa))
+    table = support.table_of(scenes.cfg2_components(oa))
     assert table.ray_tracing([]) == []
     for n in (1, 63, 65, 257):  # partial waves / partial blocks
         o, d = scenes.cfg2_rays(n, 5)
@@ -207,9 +200,9 @@ def test_fp32_trace_tracks_fp64():
     from optable_amd.batch import RayBatch
 
     n, K = 50000, 5
-    table = _table(scenes.cfg2_components(oa))
+    table = support.table_of(scenes.cfg2_components(oa))
     o, d = scenes.cfg2_rays(n, 0)
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
+    q = support.Q
     b64 = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q)
     b32 = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q, precision="f32")
     s64 = table.trace_batch(b64, max_segments=K, layout="slots").to_host()
@@ -277,7 +270,7 @@ def test_launch_options_do_not_change_results():
     from optable_amd.engine import get_engine
 
     n, K = 100_003, 5
-    table = _table(scenes.cfg2_components(oa))
+    table = support.table_of(scenes.cfg2_components(oa))
     o, d = scenes.cfg2_rays(n, 1)
     batch = _batch(o, d)
     eng = get_engine()
@@ -306,7 +299,7 @@ def test_blocked_kernel_equals_lane_per_ray_kernel(case):
 
     comps, gen, n, K = CASES[case]
     n = min(n, 5000) + 37  # ragged last chunk
-    table = _table(comps(oa))
+    table = support.table_of(comps(oa))
     o, d = gen(n)
     batch = _batch(o, d)
     eng = get_engine()
@@ -335,9 +328,9 @@ def test_heavy_kernel_edge_sizes_dead_rays_and_finite_lengths(case, prec):
     from optable_amd.engine import get_engine
 
     comps, gen, _, K = CASES[case]
-    table = _table(comps(oa))
+    table = support.table_of(comps(oa))
     eng = get_engine()
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
+    q = support.Q
     try:
         for n, cap in ((1, K), (63, K), (64, 1), (65, 3), (129, K), (1000, K)):
             o, d = gen(n)
@@ -375,9 +368,9 @@ def test_pair_queue_walk_equals_per_lane_walk(prec):
     from optable_amd.engine import get_engine
 
     comps, gen, _, K = CASES["cfg3"]
-    table = _table(comps(oa))
+    table = support.table_of(comps(oa))
     eng = get_engine()
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
+    q = support.Q
     try:
         eng.set_option(abi.OPT_KERNEL, 2)
         for n in (64, 4097, 200_003):
@@ -423,9 +416,9 @@ def test_pair_queue_round_that_does_not_fit_defers_lanes(prec):
     from optable_amd.engine import get_engine
 
     comps, gen, _, K = CASES["cfg3"]
-    table = _table(comps(oa))
+    table = support.table_of(comps(oa))
     eng = get_engine()
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
+    q = support.Q
     o, d = gen(50_003)
     batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q, precision=prec)
     try:
@@ -461,14 +454,14 @@ def test_pair_queue_room_does_not_cost_resident_waves():
 
     comps, gen, _, K = CASES["cfg3"]
     eng = get_engine()
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
+    q = support.Q
     o, d = gen(200_003)
     batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q, precision="f32")
-    a = _table(comps(oa)).trace_batch(batch, max_segments=K, layout="append")
+    a = support.table_of(comps(oa)).trace_batch(batch, max_segments=K, layout="append")
     waves_default = eng.last_launch()["threads"] // 64 * eng.last_launch()["workgroups_per_cu"]
     try:
         scene_mod.ROOT_GRID_DIMS = (8, 3)
-        table = _table(comps(oa))
+        table = support.table_of(comps(oa))
         b = table.trace_batch(batch, max_segments=K, layout="append")
     finally:
         scene_mod.ROOT_GRID_DIMS = None
@@ -494,7 +487,7 @@ def test_pair_queue_winner_that_fails_its_own_box_takes_the_per_lane_walk(prec, 
     from optable_amd.engine import get_engine
 
     comps, gen, _, K = CASES["cfg3"]
-    table = _table(comps(oa))
+    table = support.table_of(comps(oa))
     honest = table.compile()
     scene = table.compile()
     nodes = scene.node_table()
@@ -504,7 +497,7 @@ def test_pair_queue_winner_that_fails_its_own_box_takes_the_per_lane_walk(prec, 
         nodes["aabb"][i][5] = 0.1
     n = 20_011
     o, d = gen(n)
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
+    q = support.Q
     batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q, precision=prec)
     eng = get_engine()
     try:
@@ -545,7 +538,7 @@ def test_acceleration_grids_do_not_change_results(case):
     n = min(n, 6000)
     o, d = gen(n)
     batch = _batch(o, d)
-    table = _table(comps(oa))
+    table = support.table_of(comps(oa))
     fast = table.trace_batch(batch, max_segments=K, layout="slots")
     table.accelerate = False
     plain = table.trace_batch(batch, max_segments=K, layout="slots")
@@ -567,9 +560,9 @@ def test_fp32_heavy_scenes_track_fp64(case, min_same):
 
     comps, gen, n, K = CASES[case]
     n = min(n, 8000)
-    table = _table(comps(oa))
+    table = support.table_of(comps(oa))
     o, d = gen(n)
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
+    q = support.Q
     s64 = table.trace_batch(RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q), max_segments=K, layout="slots")
     s32 = table.trace_batch(RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q, precision="f32"), max_segments=K, layout="slots")
     c64, c32 = s64.count.cpu().numpy(), s32.count.cpu().numpy()
@@ -598,9 +591,9 @@ def test_segment_chain_is_continuous(case, prec, tol):
 
     comps, gen, n, K = CASES[case]
     n = min(n, 6000)
-    table = _table(comps(oa))
+    table = support.table_of(comps(oa))
     o, d = gen(n)
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
+    q = support.Q
     segs = table.trace_batch(RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q, precision=prec), max_segments=K, layout="slots")
     cnt = segs.count.cpu().numpy()
     assert (cnt > 0).all()
@@ -622,7 +615,7 @@ def test_fused_path_honours_input_length_and_dead_flags(oracle):
     import optable_amd as oa
 
     n, K = 4096, 5
-    table = _table(scenes.cfg2_components(oa))
+    table = support.table_of(scenes.cfg2_components(oa))
     o, d = scenes.cfg2_rays(n, 9)
     batch = _batch(o, d)
     rng = np.random.default_rng(9)
@@ -646,7 +639,7 @@ def test_zero_rays_and_empty_scene():
     import optable_amd as oa
     from optable_amd.batch import RayBatch
 
-    table = _table(scenes.cfg2_components(oa))
+    table = support.table_of(scenes.cfg2_components(oa))
     empty = table.trace_batch(RayBatch(0), max_segments=5, layout="slots")
     assert empty.to_host()["ox"].size == 0
     void = oa.OpticalTable()  # no components: every ray escapes unchanged
@@ -686,7 +679,7 @@ def test_sorted_spatially_is_a_pure_reordering():
 
     comps, gen, n, K = CASES["cfg3"]
     n = 5000
-    table = _table(comps(oa))
+    table = support.table_of(comps(oa))
     o, d = gen(n)
     batch = _batch(o, d)
     ordered, order = batch.sorted_spatially()
@@ -716,14 +709,14 @@ def test_batch_limited_scene_with_shared_ids(branching, oracle):
              oa.Mirror([14, 0, 0], radius=3, max_interact_count=1).RotZ(np.pi)]
     if branching:
         comps.append(oa.BeamSplitter([3, 0, 0], width=4, height=4, eta=0.5).RotZ(0.3))
-    table = _table(comps)
+    table = support.table_of(comps)
     scene = table.compile()
     assert len(scene.limited) >= 3 and scene.max_children == (2 if branching else 1)
     nb, K = 400, 14
     o = np.stack([np.zeros(nb), rng.uniform(-1, 1, nb), rng.uniform(-0.2, 0.2, nb)], 1)
     d = np.stack([np.ones(nb), rng.uniform(-0.05, 0.05, nb), rng.uniform(-0.01, 0.01, nb)], 1)
     ids = 1000 + 7 * rng.permutation(nb)               # arbitrary, unordered, not 0..n-1
-    base = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=1j * np.pi * scenes.W0**2 / scenes.WL, ids=ids)
+    base = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=support.Q, ids=ids)
     batch = base.multiplexed_in_wavelength([780e-7, 560e-7, 400e-7])
     segs = table.trace_batch(batch, max_segments=K, layout="slots")
     got = segs.to_host(reference_order=True)
@@ -748,10 +741,10 @@ def test_fp32_ray_trees_track_fp64():
     import optable_amd as oa
     from optable_amd.batch import RayBatch
 
-    table = _table([oa.BeamSplitter([3, 0, 0], width=3, height=3, eta=0.4).RotZ(0.3), oa.Mirror([6, 0, 0], radius=2).RotZ(np.pi),
+    table = support.table_of([oa.BeamSplitter([3, 0, 0], width=3, height=3, eta=0.4).RotZ(0.3), oa.Mirror([6, 0, 0], radius=2).RotZ(np.pi),
                     oa.GlassSlab([-2, 0, 0], width=3, height=3, thickness=0.4, n1=1, n2=1.5, reflectivity=0.2).RotZ(0.1)])
     o, d = scenes.cfg2_rays(2000, 3)
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
+    q = support.Q
     s32 = table.trace_batch(RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q, precision="f32"), max_segments=10, layout="slots")
     s64 = table.trace_batch(RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q, precision="f64"), max_segments=10, layout="slots")
     assert s32.precision == "f32" and s64.precision == "f64"
@@ -778,7 +771,7 @@ def test_compiled_scene_can_be_reused_and_is_not_uploaded_twice():
     from optable_amd.engine import get_engine
 
     comps = scenes.cfg2_components(oa)
-    table = _table(comps)
+    table = support.table_of(comps)
     o, d = scenes.cfg2_rays(2000, 1)
     batch = _batch(o, d)
     scene = table.compile()
@@ -901,7 +894,7 @@ def test_exact_ties_go_to_the_first_component(many, oracle):
     comps = [oa.Mirror([-2, 0, 0], radius=2.0).RotZ(np.pi), near_a, near_b, pair]
     if many:
         comps += [oa.Block([10 + k, 5 + (k % 3), 0], width=0.5, height=0.5) for k in range(14)]
-    table = _table(comps)
+    table = support.table_of(comps)
     scene = table.compile()
     assert (scene.root_grid >= 0) == many
     o = np.tile([[0.0, 0.0, 0.0]], (64, 1)) + np.linspace(-0.3, 0.3, 64)[:, None] * np.array([[0, 1, 0]])
@@ -924,7 +917,7 @@ def test_group_tie_keeps_the_first_child(oracle):
     pair = oa.ComponentGroup([6, 0, 0])
     pair.add_component(oa.Lens([6, 0, 0], focal_length=4.0, radius=1.0))
     pair.add_component(oa.Mirror([6, 0, 0], radius=1.0))
-    table = _table([pair])
+    table = support.table_of([pair])
     o, d = np.array([[0.0, 0.2, 0.0]]), np.array([[1.0, 0.0, 0.0]])
     got = table.trace_batch(_batch(o, d), max_segments=3, layout="slots").to_host()
     ref = oracle.trace(table.compile(), _batch(o, d).to_host(), max_trace_num=3)
@@ -943,7 +936,7 @@ def test_axis_parallel_rays_and_flat_boxes_match_oracle(oracle):
              oa.MirrorPair([9, 0, 0], 4, 4),
              oa.GlassSlab([4, 3, 0], width=2, height=2, thickness=0.5, n1=1, n2=1.5).RotZ(np.pi / 2),  # faces normal to y
              oa.Prism([-4, 0, 0], width=1.5, height=2, n1=1, n2=1.5).RotZ(np.pi)]
-    table = _table(comps)
+    table = support.table_of(comps)
     rng = np.random.default_rng(8)
     n = 4000
     o = np.stack([rng.uniform(-6, 12, n), rng.uniform(-2, 5, n), rng.uniform(-1.2, 1.2, n)], 1)
@@ -957,7 +950,7 @@ def test_axis_parallel_rays_and_flat_boxes_match_oracle(oracle):
     o[5::20, 1] = 1.0                           # ... on its side plane (y = +1 edge of the 2 x 2 aperture)
     o[10::20, 2] = 1.0                          # ... on the top edge plane
     d /= np.linalg.norm(d, axis=1, keepdims=True)
-    batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=1j * np.pi * scenes.W0**2 / scenes.WL, normalize=False)
+    batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=support.Q, normalize=False)
     got = table.trace_batch(batch, max_segments=10, layout="slots").to_host(reference_order=True)
     ref = oracle.trace(table.compile(), batch.to_host(), max_trace_num=10)
     seq = lambda x: [tuple(x["surface"][x["ray"] == i].tolist()) for i in range(n)]
@@ -978,7 +971,7 @@ def test_two_threads_sharing_the_engine_do_not_interleave():
     import optable_amd as oa
 
     o, d = scenes.cfg2_rays(20000, 4)
-    tables = [_table(scenes.cfg2_components(oa)), _table([oa.Mirror([3, 0, 0], radius=2.0).RotZ(np.pi)])]
+    tables = [support.table_of(scenes.cfg2_components(oa)), support.table_of([oa.Mirror([3, 0, 0], radius=2.0).RotZ(np.pi)])]
     expect = [t.trace_batch(_batch(o, d), max_segments=5, layout="slots").count.clone() for t in tables]
     assert not torch.equal(expect[0], expect[1])
     errors = []
@@ -1011,9 +1004,9 @@ def test_streamed_host_api_equals_the_resident_batch(precision):
     from optable_amd import dist as odist
 
     n, K = 50_000, 5
-    table = _table(scenes.cfg2_components(oa))
+    table = support.table_of(scenes.cfg2_components(oa))
     o, d = scenes.cfg2_rays(n, 2)
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
+    q = support.Q
     segs = table.trace_batch(RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q, precision=precision), max_segments=K, layout="slots")
     final = odist.final_state(segs).cpu().numpy()
     tol = 1e-11 if precision == "f64" else 2e-4
@@ -1032,7 +1025,7 @@ def test_streamed_host_api_equals_the_resident_batch(precision):
     for f in odist.FINAL_FIELDS:
         np.testing.assert_array_equal(a["final"][f], b["final"][f], err_msg=f)
     with pytest.raises(NotImplementedError):
-        _table([oa.BeamSplitter([3, 0, 0], width=3, height=3)]).trace_host(o[:10], d[:10], max_segments=3)
+        support.table_of([oa.BeamSplitter([3, 0, 0], width=3, height=3)]).trace_host(o[:10], d[:10], max_segments=3)
 
 
 def test_large_image_with_every_feature_reads_the_scene_from_l2(oracle):
@@ -1043,13 +1036,13 @@ def test_large_image_with_every_feature_reads_the_scene_from_l2(oracle):
     from optable_amd.batch import RayBatch
 
     comps = scenes.cfg5_components(oa) + [oa.CylMirror([8, 3.5, 0], radius=1.2, height=2.0, theta_range=(np.pi / 2, np.pi)).RotZ(0.4)]
-    table = _table(comps)
+    table = support.table_of(comps)
     scene = table.compile()
     assert scene.n_nodes > 200
     n, K = 3000, 30
     o, d = scenes.cfg5_rays(n, 5)
     d = d + np.array([0.0, 0.02, 0.0]) * np.linspace(-1, 1, n)[:, None]      # fan out so that some rays reach the cylinder
-    batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=1j * np.pi * scenes.W0**2 / scenes.WL)
+    batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=support.Q)
     got = table.trace_batch(batch, max_segments=K, layout="slots").to_host(reference_order=True)
     ref = oracle.trace(scene, batch.to_host(), max_trace_num=K)
     np.testing.assert_array_equal(got["ray"], ref["ray"])
@@ -1069,14 +1062,14 @@ def test_very_large_scene_image(oracle):
     from optable_amd.batch import RayBatch
 
     comps = scenes.cfg5_components(oa, N=(24, 24))
-    table = _table(comps)
+    table = support.table_of(comps)
     scene = table.compile()
     assert scene.n_nodes > 570
     n, K = 4000, 24
     rng = np.random.default_rng(11)
     o = np.stack([np.zeros(n), rng.uniform(-2.2, 2.2, n), rng.uniform(-2.2, 2.2, n)], 1)
     d = np.tile([[1.0, 0.0, 0.0]], (n, 1))
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
+    q = support.Q
     batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q)
     got = table.trace_batch(batch, max_segments=K, layout="slots").to_host(reference_order=True)
     ref = oracle.trace(scene, batch.to_host(), max_trace_num=K)
@@ -1146,7 +1139,7 @@ def test_stale_cached_boxes_gate_but_never_prune(kernel, oracle):
 
     lens = oa.Lens([7, 0, 0], focal_length=6, radius=1.5)
     pair = oa.MirrorPair([10, 0, 0], 4, 4)
-    table = _table([lens, pair])
+    table = support.table_of([lens, pair])
     o, d = scenes.cfg2_rays(4000, 0)
     d = np.stack([np.ones(len(d)), 0.3 * d[:, 1], 0.3 * d[:, 2]], 1)
     batch = _batch(o, d)
@@ -1199,13 +1192,13 @@ def test_repeated_hits_on_one_curved_surface(shape, oracle):
         o = np.stack([np.full(n, -6.0), yz[:, 0], yz[:, 1]], 1)       # inside the bowl x = -r^2 / 2, travelling towards its bottom
         d = np.tile([1.0, 0.0, 0.0], (n, 1))
         K, min_repeats = 6, 2
-    table = _table([comp])
+    table = support.table_of([comp])
     out = {}
     for prec in ("f64", "f32"):
-        b = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=1j * np.pi * scenes.W0**2 / scenes.WL, precision=prec)
+        b = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=support.Q, precision=prec)
         out[prec] = table.trace_batch(b, max_segments=K, layout="slots")
     got = out["f64"].to_host(reference_order=True)
-    host = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=1j * np.pi * scenes.W0**2 / scenes.WL, device="cpu").to_host()
+    host = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=support.Q, device="cpu").to_host()
     ref = oracle.trace(table.compile(), host, max_trace_num=K)
     np.testing.assert_array_equal(got["surface"], ref["surface"])
     for f in ("ox", "oy", "oz", "dx", "dy", "dz", "length"):
@@ -1226,9 +1219,9 @@ def test_generation_emit_pass_reuses_the_count_pass_decision(prec):
     from optable_amd.engine import get_engine
 
     n, cap = 20000, 20
-    table = _table(W.cfg3_components(oa, slab_reflectivity=0.1))
+    table = support.table_of(W.cfg3_components(oa, slab_reflectivity=0.1))
     o, d = scenes.cfg3_rays(n, 2)
-    batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=1j * np.pi * scenes.W0**2 / scenes.WL, precision=prec)
+    batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=support.Q, precision=prec)
     eng = get_engine()
     got = {}
     for reuse in (0, 1):

@@ -7,6 +7,7 @@ numpy, the phases in np.longdouble.  Every case first asserts, from the REFERENC
 boundary.  Counts (used, skipped, aliased) must then be EQUAL and every sample of the field within the accuracy contract's bound,
 norm (2 pi E + 2^-38), which the reference computes from the data; norm itself within the roundings of its sum."""
 import ctypes as C
+import functools
 import math
 import os
 import subprocess
@@ -19,6 +20,7 @@ import torch
 
 import optable_amd as oa
 import scenes
+import support
 import wavefront_cases as cases
 from optable_amd import abi
 from optable_amd import workloads as W
@@ -28,25 +30,22 @@ from optable_amd.psf import psf_grid
 from optable_amd.table import monitor_struct
 from optable_amd.wavefront import wavefront_reference as reference_tables
 from psf_reference import airy, disc_grid, psf_reference
+from support import ctx  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-ERR_INVALID = -1
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WL = scenes.WL
 WORST = [0.0]  # the largest device-against-reference error of the session, as a fraction of its bound
 
 
 def _batch(o, d, intensity, precision="f64", wavelength=WL):
-    return RayBatch.from_arrays(o, d, wavelength=wavelength, intensity=intensity, q=1j * np.pi * scenes.W0**2 / WL, precision=precision, device="cuda")
+    return RayBatch.from_arrays(o, d, wavelength=wavelength, intensity=intensity, q=support.Q, precision=precision, device="cuda")
 
 
 def _records(segs):
-    """The valid segment records of a batch, copied from the device."""
-    h = segs.to_host(reference_order=False)
-    col = lambda f: np.asarray(h[f], dtype=np.float64)  # noqa: E731
-    return dict(o=np.stack([col("ox"), col("oy"), col("oz")], 1), d=np.stack([col("dx"), col("dy"), col("dz")], 1), length=col("length"),
-                intensity=col("intensity"), n=col("n"), pathlength=col("pathlength"), ray=np.asarray(h["ray"], dtype=np.int64))
+    """The valid segment records of a batch, copied from the device, by name."""
+    return dict(zip(("o", "d", "length", "intensity", "n", "pathlength", "ray"), support.host_records(segs, "n", "pathlength", "ray")))
 
 
 def _reference(rec, mon, kwargs, step, pixels, wavelength=WL, centre=(0.0, 0.0), amplitude="sqrt"):
@@ -83,17 +82,9 @@ STEP = {"focus": 0.5 * WL, "direction": 2e-5}
 @pytest.fixture(scope="module")
 def case1():
     """cfg 2, 130 rays, 5 segments, traced once per layout: (table, get(layout) -> (segs, records))."""
-    table, made = cases.cfg2_table(), {}
+    table = support.cfg2_table()
     o, d, intensity = cases.cfg2_arrays(130, 3)
-
-    def get(layout):
-        if layout not in made:
-            segs = table.trace_batch(_batch(o, d, intensity), max_segments=5, layout=layout)
-            assert segs.layout == layout and segs.precision == "f64"
-            made[layout] = (segs, _records(segs))
-        return made[layout]
-
-    return table, get
+    return table, support.traced(table, lambda precision: _batch(o, d, intensity, precision), 5, _records)
 
 
 @pytest.mark.parametrize("setup", ["focus", "direction"])
@@ -125,7 +116,7 @@ def test_layouts(case1, layout, setup, monkeypatch):
 def test_ray_counts(n):
     """Every ray of cfg 2 crosses the monitor at x = 7.5: n hits or more — a partial batch of 16, a full and an overfull wave, a round
     of 256 and one more hit, and at 1,027 rays three chunks or more with a ragged last one."""
-    table = cases.cfg2_table()
+    table = support.cfg2_table()
     segs = table.trace_batch(_batch(*cases.cfg2_arrays(n, 3)), max_segments=5, layout="slots")
     rec, mon, kwargs = _records(segs), oa.Monitor([7.5, 0, 0], 6, 6), dict(direction=(1.0, 0.0, 0.0))
     ref = _reference(rec, mon, kwargs, 2e-5, (19, 21))
@@ -137,7 +128,7 @@ def test_ray_counts(n):
 def test_more_than_one_hit_chunk(case1):
     """The plan's smallest chunk is 512 hits: the 514 of 257 rays (each crosses the monitor on its way to the mirrors and back) are two
     chunks of 257, whose partial images the last workgroup adds."""
-    table = cases.cfg2_table()
+    table = support.cfg2_table()
     segs = table.trace_batch(_batch(*cases.cfg2_arrays(257, 4)), max_segments=5, layout="append")
     rec, mon, kwargs = _records(segs), oa.Monitor([7.5, 0, 0], 6, 6), dict(direction=(1.0, 0.0, 0.0))
     ref = _reference(rec, mon, kwargs, 2e-5, (33, 17))
@@ -247,7 +238,7 @@ def test_a_grid_coarse_enough_to_alias(case1):
 def test_determinism_and_streaming():
     """The same call twice: the same bits.  Two chunks of the rays through `into=`: counts added, the field within the bound of the
     one-call reference."""
-    table = cases.cfg2_table()
+    table = support.cfg2_table()
     o, d, intensity = cases.cfg2_arrays(1027, 3)
     su = cases.SETUPS["direction"]
     mons = cases.monitors_at(su["x"])
@@ -272,7 +263,7 @@ def test_determinism_and_streaming():
 
 
 def test_single_precision_is_refused():
-    table = cases.cfg2_table()
+    table = support.cfg2_table()
     o, d, intensity = cases.cfg2_arrays(130, 3)
     segs = table.trace_batch(_batch(o, d, intensity, precision="f32"), max_segments=3)
     assert segs.precision == "f32"
@@ -285,7 +276,7 @@ def test_single_precision_is_refused():
 
 
 def test_no_segments():
-    table, eng = cases.cfg2_table(), get_engine()
+    table, eng = support.cfg2_table(), get_engine()
     eng.upload(table.compile())
     none = eng.trace_tree(RayBatch(0, "f64", "cuda"), 5)
     assert none.layout == "list" and none.n_valid == 0
@@ -295,32 +286,12 @@ def test_no_segments():
 
 
 # -- the C ABI -------------------------------------------------------------------------------------------------------------------------
-class _Out:
+class _Out(support.Sentinel):
     """counts / norm / re / im of M monitors of ny x nz samples, with a guard region on either side of each."""
-    GUARD = 64
 
-    def __init__(self, M, ny, nz, fill=-7):
-        self.fill, G = fill, self.GUARD
-        self.c = torch.full((3 * M + 2 * G,), fill, dtype=torch.int64, device="cuda")
-        self.n, self.r, self.i = (torch.full((k + 2 * G,), float(fill), dtype=torch.float64, device="cuda") for k in (M, M * ny * nz, M * ny * nz))
-        self.counts, self.norm = self.c[G:G + 3 * M].view(M, 3), self.n[G:G + M]
-        self.re, self.im = self.r[G:-G].view(M, ny, nz), self.i[G:-G].view(M, ny, nz)
-
-    def guards_untouched(self):
-        G = self.GUARD
-        return all(bool((t[:G] == self.fill).all()) and bool((t[-G:] == self.fill).all()) for t in (self.c, self.n, self.r, self.i))
-
-    def untouched(self):
-        return all(bool((t == self.fill).all()) for t in (self.c, self.n, self.r, self.i))
-
-
-@pytest.fixture()
-def ctx():
-    lib = abi.load()
-    c = C.c_void_p()
-    assert lib.ot_ctx_create(0, None, C.byref(c)) == 0
-    yield lib, c
-    assert lib.ot_ctx_destroy(c) == 0
+    def __init__(self, M, ny, nz):
+        field = (torch.float64, (M, ny, nz))
+        super().__init__(guard=64, counts=(torch.int64, (M, 3)), norm=(torch.float64, (M,)), re=field, im=field)
 
 
 def test_abi_errors(ctx):
@@ -353,15 +324,7 @@ def test_abi_errors(ctx):
         return lib.ot_monitor_psf_many(ctx_, mons, M, ptr(axes), kind, ptr(ref), ptr(grid), ny_, nz_, None if source is None else C.byref(source), intensity,
                                        n_index, pathlength, wavelength, n_wl, uniform, mode, n_seg, cnt, rays, counts, norm, re, im, acc)
 
-    def expect(status, needle):
-        msg = lib.ot_last_error().decode()
-        assert status == ERR_INVALID and needle in msg, (status, msg, needle)
-
-    def altered(**fields):
-        other = abi.OtSegmentSource.from_buffer_copy(src)
-        for k, v in fields.items():
-            setattr(other, k, v)
-        return other
+    expect, altered = functools.partial(support.expect_invalid, lib), functools.partial(support.altered, src)
 
     def with_value(good, at, value):
         a = good.copy()
@@ -425,7 +388,7 @@ def test_a_converging_cone_gives_the_airy_pattern():
     NA, F = 0.1, np.array([30.0, 0.0, 0.0])
     t = disc_grid(41, NA)
     d = np.stack([np.sqrt(1.0 - (t * t).sum(axis=1)), t[:, 0], t[:, 1]], axis=1)
-    table = cases.cfg2_table()
+    table = support.cfg2_table()
     segs = table.trace_batch(RayBatch.from_arrays(F - 2.0 * d, d, wavelength=WL, device="cuda"), max_segments=2, layout="slots")
     mon = oa.Monitor([29.0, 0, 0], 1, 1)
     step = 6 * 0.61 * WL / NA / 32

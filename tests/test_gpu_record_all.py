@@ -7,6 +7,7 @@ within 1e-9 of the monitor's half-width or half-height or of the limits on t.
 Shapes: 5,003 rays x 5 slots (a ragged last wave, 13 workgroups of 2,048 slots, 391 tiles), 33 monitors (two launches of the
 kernels), slot counts of 64 k + 1."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -14,39 +15,18 @@ import torch
 
 import optable_amd as oa
 import scenes
+import support
 from optable_amd import abi
 from optable_amd import workloads as W
 from optable_amd.batch import RayBatch, SegmentBatch
 from optable_amd.engine import get_engine, segment_source
 from optable_amd.table import monitor_struct
+from support import ctx  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 TOL = dict(rtol=1e-12, atol=1e-12)
-ERR_INVALID = -1
-
-
-def _batch(o, d, precision="f64"):
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
-    return RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=q, precision=precision, device="cuda")
-
-
-def _cfg2_table():
-    t = oa.OpticalTable()
-    t.add_components(scenes.cfg2_components(oa))
-    return t
-
-
-def _six_monitors():
-    return [oa.Monitor([7.5, 0, 0], 6, 6),             # the one tests/test_gpu_append.py shows is hit
-            oa.Monitor([6.5, 0, 0], 6, 6),
-            oa.Monitor([7.5, 40, 0], 6, 6),            # where no segment passes: an empty list in the middle
-            oa.Monitor([8.5, 0, 0], 6, 6),
-            oa.Monitor([7.5, 0, 0], 6, 6).RotZ(0.3),
-            oa.Monitor([7.5, 0, 0], 0.5, 0.5)]         # clips
-
-
-EMPTY = 2  # (its place in the list above)
+EMPTY = 2  # (its place among support.six_monitors())
 
 
 def _gather(field, slot):
@@ -78,17 +58,9 @@ def _assert_same_hits(got, ref):
 def case1():
     """cfg 2, 5,003 rays, 5 segments, six monitors: (table, monitors, {(layout, precision): (segs, record_batch per monitor)}),
     traced and recorded on first use."""
-    table, mons, made = _cfg2_table(), _six_monitors(), {}
+    table, mons = support.cfg2_table(), support.six_monitors()
     o, d = scenes.cfg2_rays(5003, 0)
-
-    def get(layout, precision):
-        if (layout, precision) not in made:
-            segs = table.trace_batch(_batch(o, d, precision), max_segments=5, layout=layout)
-            assert segs.layout == layout and segs.precision == precision
-            made[layout, precision] = (segs, [table.record_batch(m, segs) for m in mons])
-        return made[layout, precision]
-
-    return table, mons, get
+    return table, mons, support.traced(table, lambda precision: support.batch(o, d, precision), 5, lambda segs: [table.record_batch(m, segs) for m in mons])
 
 
 @pytest.mark.parametrize("precision", ["f64", "f32"])
@@ -124,9 +96,9 @@ def test_no_conversion_copy(case1, monkeypatch):
 
 
 def test_more_than_one_chunk_of_monitors():
-    table = _cfg2_table()
+    table = support.cfg2_table()
     mons = [oa.Monitor([5.5 + 0.125 * k, 0, 0], 6, 6) for k in range(32)] + [oa.Monitor([5.5, 0, 0], 6, 6)]  # 33: positions 0 and 32 alike
-    segs = table.trace_batch(_batch(*scenes.cfg2_rays(2003, 0)), max_segments=5, layout="slots")
+    segs = table.trace_batch(support.batch(*scenes.cfg2_rays(2003, 0)), max_segments=5, layout="slots")
     hits = table.record_all(segs, monitors=mons)
     assert len(hits) == 33 and sum(len(h) > 0 for h in hits) >= 3
     for m, got in zip(mons, hits):
@@ -193,19 +165,19 @@ def _call(lib, ctx, mons, segs, out):
 
 
 def test_edges():
-    table = _cfg2_table()
+    table = support.cfg2_table()
     eng = get_engine()
     # one ray, one segment (origin -> lens): the first monitor sees it, the second does not
     mons = [oa.Monitor([2.5, 0, 0], 6, 6), oa.Monitor([7.5, 0, 0], 6, 6)]
     for layout in ("slots", "tiled", "append"):
-        segs = table.trace_batch(_batch(*scenes.cfg2_rays(1, 0)), max_segments=1, layout=layout)
+        segs = table.trace_batch(support.batch(*scenes.cfg2_rays(1, 0)), max_segments=1, layout=layout)
         hits = table.record_all(segs, monitors=mons)
         assert (len(hits[0]), len(hits[1])) == (1, 0)
         for m, got in zip(mons, hits):
             _assert_same_hits(got, table.record_batch(m, segs))
     # slot counts of 64 k + 1: 65 slots, and 2,049 = one more than a workgroup's 2,048
     for n, K in ((13, 5), (2049, 1)):
-        segs = table.trace_batch(_batch(*scenes.cfg2_rays(n, 3)), max_segments=K, layout="slots")
+        segs = table.trace_batch(support.batch(*scenes.cfg2_rays(n, 3)), max_segments=K, layout="slots")
         assert segment_source(segs)[1] % 64 == 1
         mons = [oa.Monitor([2.5, 0, 0], 6, 6), oa.Monitor([7.5, 0, 0], 6, 6)]
         hits = table.record_all(segs, monitors=mons)
@@ -249,15 +221,6 @@ def test_capacity(case1):
     assert torch.equal(out.idx[:out.capacity], everything[:out.capacity])  # what fits is the front of the full result
 
 
-@pytest.fixture()
-def ctx():
-    lib = abi.load()
-    c = C.c_void_p()
-    assert lib.ot_ctx_create(0, None, C.byref(c)) == 0
-    yield lib, c
-    assert lib.ot_ctx_destroy(c) == 0
-
-
 def test_abi_errors(ctx):
     lib, c = ctx
     n = 130
@@ -276,15 +239,7 @@ def test_abi_errors(ctx):
     def call(mons=C.byref(mon), M=1, source=src, n_seg=n_segments, cnt=count.data_ptr(), rays=n_rays, args=None):
         return lib.ot_monitor_record_many(c, mons, M, None if source is None else C.byref(source), n_seg, cnt, rays, *(args or out.args()))
 
-    def expect(status, needle):
-        msg = lib.ot_last_error().decode()
-        assert status == ERR_INVALID and needle in msg, (status, msg)
-
-    def altered(**fields):
-        other = abi.OtSegmentSource.from_buffer_copy(src)
-        for k, v in fields.items():
-            setattr(other, k, v)
-        return other
+    expect, altered = functools.partial(support.expect_invalid, lib), functools.partial(support.altered, src)
 
     expect(lib.ot_monitor_record_many(None, C.byref(mon), 1, C.byref(src), n_segments, count.data_ptr(), n_rays, *out.args()), "NULL")
     expect(call(mons=None), "NULL")

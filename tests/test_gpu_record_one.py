@@ -12,6 +12,7 @@ import torch
 
 import optable_amd as oa
 import scenes
+import support
 from optable_amd.batch import RayBatch, SegmentBatch
 from optable_amd.engine import get_engine
 from optable_amd.table import monitor_struct
@@ -19,15 +20,6 @@ from optable_amd.table import monitor_struct
 pytestmark = pytest.mark.gpu
 
 TOL = dict(rtol=1e-12, atol=1e-12)
-
-
-def _six_monitors():
-    return [oa.Monitor([7.5, 0, 0], 6, 6),             # the six of tests/test_gpu_record_all.py
-            oa.Monitor([6.5, 0, 0], 6, 6),
-            oa.Monitor([7.5, 40, 0], 6, 6),            # where no segment passes
-            oa.Monitor([8.5, 0, 0], 6, 6),
-            oa.Monitor([7.5, 0, 0], 6, 6).RotZ(0.3),
-            oa.Monitor([7.5, 0, 0], 0.5, 0.5)]         # clips
 
 
 EMPTY = 2
@@ -39,7 +31,7 @@ def test_against_the_oracle(oracle, layout):
     table = oa.OpticalTable()
     table.add_components(scenes.cfg2_components(oa))
     o, d = scenes.cfg2_rays(5003, 0)
-    batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=1j * np.pi * scenes.W0**2 / scenes.WL, device="cuda")
+    batch = RayBatch.from_arrays(o, d, wavelength=scenes.WL, q=support.Q, device="cuda")
     segs = table.trace_batch(batch, max_segments=5, layout=layout)
     assert segs.layout == layout and segs.precision == "f64"
     if layout == "append":
@@ -48,7 +40,7 @@ def test_against_the_oracle(oracle, layout):
     slot_of = torch.nonzero(segs.valid_mask()).flatten().cpu().numpy()  # ... and the slot each of them lies in
     assert len(slot_of) == len(host["ox"]) == 5003 * 5
     found = []
-    for m in _six_monitors():
+    for m in support.six_monitors():
         got = table.record_batch(m, segs)
         idx, P, t = oracle.monitor_record(monitor_struct(m), host)
         P = P.reshape(-1, 3)

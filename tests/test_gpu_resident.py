@@ -3,57 +3,31 @@ output that an earlier trace of the same engine wrote leaves the planes `ray`, `
 reach and the scene keeps them invariant; the records must be the ones a trace into a FRESH output writes, bit for bit, in every
 slot k < |count|.  That the skip ran is shown through the documented hole: a plane poisoned through `.data` (torch does not see
 the write) keeps its poison.  n = 130: even (paired 16-byte stores), two full waves and a partial one; n = 129: odd (unpaired)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 import scenes
+import support
 from optable_amd import abi
 
 pytestmark = pytest.mark.gpu
 
 RAY, N, I = abi.RESIDENT_RAY, abi.RESIDENT_N, abi.RESIDENT_INTENSITY
 PLANES = {RAY: "ray", N: "n", I: "intensity"}
-Q = 1j * np.pi * scenes.W0**2 / scenes.WL
 SIZES = (130, 129)
 GRID = [(p, lay) for p in ("f64", "f32") for lay in ("slots", "tiled")]
-
-
-def _half_mirror(ns):
-    return [ns.Lens([5, 0, 0], focal_length=5, radius=1.0), ns.MirrorPair([10, 0, 0], 4, 4, reflectivity_1=0.5)]
 
 
 # scene -> (components, the planes the library must report for a batch with uniform n and intensity)
 SCENES = {
     "cfg2": (scenes.cfg2_components, RAY | N | I),
-    "half": (_half_mirror, RAY | N),              # a mirror with reflectivity 0.5: the intensity changes on the way
+    "half": (support.half_mirror, RAY | N),       # a mirror with reflectivity 0.5: the intensity changes on the way
     "snell": (scenes.cfg4_components, RAY),       # refracting (preset FB): n changes on the way
     "cfg3": (scenes.cfg3_components, 0),          # 56 leaves: the rolling lists
 }
-_compiled = {}
-
-
 def _engine(name):
-    import optable_amd as oa
-    from optable_amd.engine import get_engine
-
-    if name not in _compiled:
-        table = oa.OpticalTable()
-        table.add_components(SCENES[name][0](oa))
-        _compiled[name] = table.compile()
-    eng = get_engine()
-    eng.upload(_compiled[name])
-    return eng
-
-
-def _batch(o, d, precision, **kw):
-    from optable_amd.batch import RayBatch
-
-    kw.setdefault("wavelength", scenes.WL)
-    kw.setdefault("q", Q)
-    return RayBatch.from_arrays(o, d, precision=precision, device="cuda", **kw)
+    return support.engine_for(SCENES[name][0], (__name__, name))
 
 
 def _long(n, seed=0):
@@ -61,47 +35,15 @@ def _long(n, seed=0):
     return scenes.cfg2_rays(n, seed)
 
 
-def _short(n):
-    """`_long` with the rays of wave 0 and every other ray of wave 1 aimed past the lens: they miss everything (1 segment) or meet
-    the roof mirrors alone (2 or 3).  Wave 0 is a whole wave of short rays, wave 1 a mixed one, the rest stays long."""
-    o, d = _long(n)
-    idx = np.concatenate([np.arange(0, 64), np.arange(64, 128, 2)])
-    idx = idx[idx < n]
-    tan = np.linspace(0.21, 0.6, idx.size)  # past the lens's rim (radius 1 at x = 5) from tan = 0.2 on
-    d[idx] = np.stack([np.ones(idx.size), tan, np.zeros(idx.size)], axis=1)
-    d[idx[::4]] = [0.0, 1.0, 0.0]  # and straight up: nothing there
-    return o, d, idx
-
-
 def _snell_rays(n, seed=0):
     o, d, _ = scenes.cfg4_rays(n, seed, n_wavelengths=1)
     return o, d
-
-
-def _bits(t):
-    return t.view({8: torch.int64, 4: torch.int32}[t.element_size()])
-
-
-def _records(segs, n, K):
-    """every field of the valid slots as bit patterns, plus count"""
-    s = segs.to_slots()
-    count = segs.count.clone()
-    valid = torch.arange(K, device=count.device)[:, None] < count.abs()[None, :]
-    out = {f: _bits(s.field(f)[: K * n]).view(K, n)[valid].clone() for f in abi.SEG_FIELDS + ("ray", "surface")}
-    out["count"] = count
-    return out
 
 
 def _same(a, b, what="", but=()):
     for f in a:
         if f not in but:
             assert torch.equal(a[f], b[f]), (what, f)
-
-
-def _new_out(n, K, precision, layout):
-    from optable_amd.batch import SegmentBatch
-
-    return SegmentBatch(n * K, precision, "cuda", tiled=(layout == "tiled"))
 
 
 POISON = {"ray": -7, "n": 123.0, "intensity": 77.0}
@@ -127,17 +69,17 @@ def test_second_trace_into_the_same_output(precision, layout):
     eng = _engine("cfg2")
     K = 5
     for n in SIZES:
-        batch, again = _batch(*_long(n, 0), precision), _batch(*_long(n, 1), precision)
-        fresh = _records(eng.trace(again, K, layout=layout), n, K)
+        batch, again = support.batch(*_long(n, 0), precision), support.batch(*_long(n, 1), precision)
+        fresh = support.valid_records(eng.trace(again, K, layout=layout), n, K)
         assert int(fresh["count"].min()) == K and eng.last_launch()["kernel"] == 1
-        out = eng.trace(batch, K, out=_new_out(n, K, precision, layout), layout=layout)
+        out = eng.trace(batch, K, out=support.new_out(n, K, precision, layout), layout=layout)
         assert out.resident_mask(n, layout, {N: again.uniform_bits("n"), I: again.uniform_bits("intensity")}, eng, eng._stream) == RAY | N | I
         assert eng.trace(again, K, out=out, layout=layout) is out
-        _same(_records(out, n, K), fresh, (n, "second"))
+        _same(support.valid_records(out, n, K), fresh, (n, "second"))
         # the skip ran: poison written where torch does not see it survives in the three planes, and nowhere else
         _poison(out)
         eng.trace(again, K, out=out, layout=layout)
-        rec = _records(out, n, K)
+        rec = support.valid_records(out, n, K)
         _same(rec, fresh, (n, "poisoned"), but=("ray", "n", "intensity"))
         for f in ("ray", "n", "intensity"):
             assert _poisoned(rec, f), (n, f)
@@ -145,7 +87,7 @@ def test_second_trace_into_the_same_output(precision, layout):
         eng.set_option(abi.OPT_RESIDENT, 0)
         try:
             eng.trace(again, K, out=out, layout=layout)
-            _same(_records(out, n, K), fresh, (n, "option off"))
+            _same(support.valid_records(out, n, K), fresh, (n, "option off"))
             assert out._resident is None
         finally:
             eng.set_option(abi.OPT_RESIDENT, 1)
@@ -154,17 +96,17 @@ def test_second_trace_into_the_same_output(precision, layout):
         _poison(out)
         out.ray.fill_(-7)
         eng.trace(again, K, out=out, layout=layout)
-        _same(_records(out, n, K), fresh, (n, "visible write"))
+        _same(support.valid_records(out, n, K), fresh, (n, "visible write"))
         # ... and after forget_resident()
         _poison(out)
         eng.trace(again, K, out=out.forget_resident(), layout=layout)
-        _same(_records(out, n, K), fresh, (n, "forgotten"))
+        _same(support.valid_records(out, n, K), fresh, (n, "forgotten"))
         # a batch with another intensity: that plane is written again, the other two stay
-        dim = _batch(*_long(n, 1), precision, intensity=0.5)
-        fresh_dim = _records(eng.trace(dim, K, layout=layout), n, K)
+        dim = support.batch(*_long(n, 1), precision, intensity=0.5)
+        fresh_dim = support.valid_records(eng.trace(dim, K, layout=layout), n, K)
         _poison(out)
         eng.trace(dim, K, out=out, layout=layout)
-        rec = _records(out, n, K)
+        rec = support.valid_records(out, n, K)
         _same(rec, fresh_dim, (n, "dim"), but=("ray", "n"))
         assert _poisoned(rec, "ray") and _poisoned(rec, "n")
         # a batch that does not know its values (no host comparison): `ray` alone
@@ -174,7 +116,7 @@ def test_second_trace_into_the_same_output(precision, layout):
         eng.trace(unknown, K, out=out, layout=layout)   # whole records; the token it leaves holds `ray` only
         _poison(out)
         eng.trace(unknown, K, out=out, layout=layout)
-        rec = _records(out, n, K)
+        rec = support.valid_records(out, n, K)
         _same(rec, fresh, (n, "unknown"), but=("ray",))
         assert _poisoned(rec, "ray")
 
@@ -186,61 +128,61 @@ def test_rays_that_live_longer_than_last_time(precision, layout):
     eng = _engine("cfg2")
     K = 5
     for n in SIZES:
-        o, d, idx = _short(n)
-        short, long_ = _batch(o, d, precision), _batch(*_long(n), precision)
+        o, d, idx = support.short_rays(n)
+        short, long_ = support.batch(o, d, precision), support.batch(*_long(n), precision)
         assert short.uniform_bits("n") == long_.uniform_bits("n") and short.uniform_bits("intensity") == long_.uniform_bits("intensity")
         long_out = eng.trace(long_, K, layout=layout)
-        fresh_long = _records(long_out, n, K)
-        fresh_short = _records(eng.trace(short, K, layout=layout), n, K)
+        fresh_long = support.valid_records(long_out, n, K)
+        fresh_short = support.valid_records(eng.trace(short, K, layout=layout), n, K)
         c = fresh_short["count"].abs().cpu().numpy()
         print("segments of the short rays:", np.bincount(c[idx], minlength=K + 1).tolist())
         assert c[idx].max() <= 3 and c[idx].min() == 1 and len(set(c[idx].tolist())) >= 2, np.bincount(c[idx]).tolist()
         assert (c[np.setdiff1d(np.arange(n), idx)] == K).all()
         assert (c[:64] < K).all() and (c[64:128] < K).any() and (c[64:128] == K).any()  # a whole wave, a mixed wave
-        out = eng.trace(short, K, out=_new_out(n, K, precision, layout), layout=layout)
-        _same(_records(out, n, K), fresh_short, (n, "short"))
+        out = eng.trace(short, K, out=support.new_out(n, K, precision, layout), layout=layout)
+        _same(support.valid_records(out, n, K), fresh_short, (n, "short"))
         _poison(out)  # whatever the old records do not cover must be written, whatever they cover may stay
         eng.trace(long_, K, out=out, layout=layout)
-        rec = _records(out, n, K)
+        rec = support.valid_records(out, n, K)
         _same(rec, fresh_long, (n, "long after short"), but=("ray", "n", "intensity"))
         got, want = out.to_slots(), long_out.to_slots()
         old = torch.arange(K, device="cuda")[:, None] < torch.as_tensor(c, device="cuda")[None, :]  # slots the first launch wrote
         for f in ("ray", "n", "intensity"):
-            g, w = _bits(got.field(f)[: K * n]).view(K, n), _bits(want.field(f)[: K * n]).view(K, n)
+            g, w = support.bits(got.field(f)[: K * n]).view(K, n), support.bits(want.field(f)[: K * n]).view(K, n)
             assert torch.equal(g[~old], w[~old]), (n, f, "slots past the old count")
-            poison = _bits(torch.full((1,), POISON[f], dtype=got.field(f).dtype, device="cuda"))
+            poison = support.bits(torch.full((1,), POISON[f], dtype=got.field(f).dtype, device="cuda"))
             assert bool(((g[old] == w[old]) | (g[old] == poison)).all()), (n, f)  # (what the old records cover may stay as it was)
             assert bool((g[0] == poison).all()), (n, f)  # segment 0: no ray is past its old count, every wave skips
         # the same without poison: equal everywhere
-        out = eng.trace(short, K, out=_new_out(n, K, precision, layout), layout=layout)
+        out = eng.trace(short, K, out=support.new_out(n, K, precision, layout), layout=layout)
         eng.trace(long_, K, out=out, layout=layout)
-        _same(_records(out, n, K), fresh_long, (n, "long after short, clean"))
+        _same(support.valid_records(out, n, K), fresh_long, (n, "long after short, clean"))
         # ... and back: shorter than last time
         eng.trace(short, K, out=out, layout=layout)
-        _same(_records(out, n, K), fresh_short, (n, "short after long"))
+        _same(support.valid_records(out, n, K), fresh_short, (n, "short after long"))
         eng.trace(long_, K, out=out, layout=layout)
-        _same(_records(out, n, K), fresh_long, (n, "long again"))
+        _same(support.valid_records(out, n, K), fresh_long, (n, "long again"))
 
 
 @pytest.mark.parametrize("precision, layout", GRID)
 def test_dead_rays_and_a_larger_cap(precision, layout):
     eng = _engine("cfg2")
     for n in SIZES:
-        o, d, idx = _short(n)
-        first, second = _batch(o, d, precision), _batch(*_long(n), precision)
+        o, d, idx = support.short_rays(n)
+        first, second = support.batch(o, d, precision), support.batch(*_long(n), precision)
         for b, step in ((first, 3), (second, 5)):
             flags = b.flags.cpu()
             flags[::step] |= abi.RAY_DEAD
             b.flags.copy_(flags)
         K1, K2 = 5, 7
-        fresh = _records(eng.trace(second, K2, layout=layout), n, K2)
+        fresh = support.valid_records(eng.trace(second, K2, layout=layout), n, K2)
         assert torch.equal(fresh["count"][::5], torch.ones_like(fresh["count"][::5]))  # returned as they came: one record
-        out = eng.trace(first, K1, out=_new_out(n, K2, precision, layout), layout=layout)
+        out = eng.trace(first, K1, out=support.new_out(n, K2, precision, layout), layout=layout)
         assert out._resident is not None
         eng.trace(second, K2, out=out, layout=layout)
-        _same(_records(out, n, K2), fresh, (n, "dead"))
+        _same(support.valid_records(out, n, K2), fresh, (n, "dead"))
         eng.trace(first, K1, out=out, layout=layout)
-        _same(_records(out, n, K1), _records(eng.trace(first, K1, layout=layout), n, K1), (n, "dead, back"))
+        _same(support.valid_records(out, n, K1), support.valid_records(eng.trace(first, K1, layout=layout), n, K1), (n, "dead, back"))
 
 
 @pytest.mark.parametrize("name", ["half", "snell"])
@@ -252,56 +194,43 @@ def test_planes_the_scene_changes_are_written(name, precision, layout):
     planes = SCENES[name][1]
     K = 5 if name == "half" else 3
     for n in SIZES:
-        batch = _batch(*(_long(n) if name == "half" else _snell_rays(n)), precision)
+        batch = support.batch(*(_long(n) if name == "half" else _snell_rays(n)), precision)
         assert eng.resident_plan(precision, batch.uniform_mask, n, K) == planes
         assert eng.resident_plan(precision, 0, n, K) == RAY  # without the hint: `ray` alone
-        fresh = _records(eng.trace(batch, K, layout=layout), n, K)
+        fresh = support.valid_records(eng.trace(batch, K, layout=layout), n, K)
         assert int(fresh["count"].abs().min()) >= 2 and eng.last_launch()["kernel"] == 1
-        out = eng.trace(batch, K, out=_new_out(n, K, precision, layout), layout=layout)
+        out = eng.trace(batch, K, out=support.new_out(n, K, precision, layout), layout=layout)
         assert out._resident["planes"] == planes
         _poison(out)
         eng.trace(batch, K, out=out, layout=layout)
-        rec = _records(out, n, K)
+        rec = support.valid_records(out, n, K)
         kept = tuple(f for bit, f in PLANES.items() if planes & bit)
         _same(rec, fresh, (name, n), but=kept)
         for f in kept:
             assert _poisoned(rec, f), (name, n, f)
         # a caller's mask that is wrong for the scene skips nothing that changes: the library masks it
         _poison(out)
-        _call(eng, "resident", batch, K, out, layout, batch.uniform_mask, abi.RESIDENT_ALL)
-        rec = _records(out, n, K)
+        support.trace_call(eng, "resident", batch, K, out, layout, batch.uniform_mask, abi.RESIDENT_ALL)
+        rec = support.valid_records(out, n, K)
         _same(rec, fresh, (name, n, "all bits"), but=kept)
 
 
 def test_rolling_list_scene_has_no_plan():
     eng = _engine("cfg3")
     n, K = 130, 20
-    batch = _batch(*scenes.cfg3_rays(n, 2), "f32")
+    batch = support.batch(*scenes.cfg3_rays(n, 2), "f32")
     assert eng.resident_plan("f32", batch.uniform_mask, n, K) == 0
-    fresh = _records(eng.trace(batch, K), n, K)
+    fresh = support.valid_records(eng.trace(batch, K), n, K)
     assert eng.last_launch()["kernel"] == 2
-    out = eng.trace(batch, K, out=_new_out(n, K, "f32", "slots"))
+    out = eng.trace(batch, K, out=support.new_out(n, K, "f32", "slots"))
     assert out._resident is None
     _poison(out)
     eng.trace(batch, K, out=out)
-    _same(_records(out, n, K), fresh, "rolling")
+    _same(support.valid_records(out, n, K), fresh, "rolling")
     # and for the light scenes: no rays, or a cap the kernel's packed counts do not hold
     eng = _engine("cfg2")
     assert eng.resident_plan("f64", abi.UNIFORM_ALL, 0, 5) == 0 and eng.resident_plan("f64", abi.UNIFORM_ALL, n, 1 << 15) == 0
     assert eng.resident_plan("f64", abi.UNIFORM_ALL, n, (1 << 15) - 1) == RAY | N | I
-
-
-def _call(eng, family, batch, K, out, layout, *masks):
-    """ot_trace[_tiled]_<family>_f64/_f32 on `out`, straight through the C ABI; returns the status"""
-    rs = batch.c_struct()
-    if layout == "tiled":
-        where = (out.block.data_ptr(), out.capacity)
-        fn = eng._fn("ot_trace_tiled_" + family, batch.precision)
-    else:
-        ss = out.c_struct()
-        where = (C.byref(ss),)
-        fn = eng._fn("ot_trace_" + family, batch.precision)
-    return fn(eng._ctx, C.byref(rs), batch.n, K, *where, out.count.data_ptr(), None, 0, *masks)
 
 
 @pytest.mark.parametrize("precision, layout", GRID)
@@ -309,18 +238,18 @@ def test_old_entry_points_write_the_records_of_the_new_ones_with_an_empty_mask(p
     eng = _engine("cfg2")
     K = 5
     for n in SIZES:
-        o, d, _ = _short(n)
-        batch = _batch(o, d, precision)
+        o, d, _ = support.short_rays(n)
+        batch = support.batch(o, d, precision)
         recs = []
         for family, masks in (("uniform", (batch.uniform_mask,)), ("resident", (batch.uniform_mask, 0)), ("resident", (0, 0))):
-            out = _new_out(n, K, precision, layout)
+            out = support.new_out(n, K, precision, layout)
             out.count = torch.zeros(n, dtype=torch.int32, device="cuda")
             out.n_rays = n
-            assert _call(eng, family, batch, K, out, layout, *masks) == 0
-            recs.append(_records(out, n, K))
+            assert support.trace_call(eng, family, batch, K, out, layout, *masks) == 0
+            recs.append(support.valid_records(out, n, K))
         _same(recs[0], recs[1], (n, "uniform / resident"))
         _same(recs[0], recs[2], (n, "no masks"))
-        out = _new_out(n, K, precision, layout)
+        out = support.new_out(n, K, precision, layout)
         out.count = torch.zeros(n, dtype=torch.int32, device="cuda")
-        assert _call(eng, "resident", batch, K, out, layout, 0, abi.RESIDENT_ALL + 1) < 0  # bits outside the mask
+        assert support.trace_call(eng, "resident", batch, K, out, layout, 0, abi.RESIDENT_ALL + 1) < 0  # bits outside the mask
         assert b"resident_mask" in eng.lib.ot_last_error()

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import scenes
+import support
 from optable_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -15,10 +16,6 @@ pytestmark = pytest.mark.gpu
 ALL_FIELDS = abi.SEG_FIELDS + ("ray", "surface")
 RESIDENT = ("ray", "n", "intensity")
 POINT = ("ox", "oy", "oz", "q_re", "q_im", "pathlength")  # what cfg 2's point source adds to the resident n and intensity at k = 0
-Q = 1j * np.pi * scenes.W0**2 / scenes.WL
-POISON_BYTE = 0xA5
-POISON_REAL, POISON_INT = 123.0, -7
-_compiled = {}
 
 
 def _components(name, oa):
@@ -37,84 +34,7 @@ def _components(name, oa):
 
 
 def _engine(name):
-    import optable_amd as oa
-    from optable_amd.engine import get_engine
-
-    if name not in _compiled:
-        table = oa.OpticalTable()
-        table.add_components(_components(name, oa))
-        _compiled[name] = table.compile()
-    eng = get_engine()
-    eng.upload(_compiled[name])
-    return eng
-
-
-def _batch(o, d, precision="f64", **kw):
-    from optable_amd.batch import RayBatch
-
-    kw.setdefault("wavelength", scenes.WL)
-    kw.setdefault("q", Q)
-    return RayBatch.from_arrays(o, d, precision=precision, device="cuda", **kw)
-
-
-def _new_out(n, K, precision, layout):
-    """a fresh output with every byte poisoned, a tile's padding included (a write torch sees: there is no token yet)"""
-    from optable_amd.batch import SegmentBatch
-
-    out = SegmentBatch(n * K, precision, "cuda", tiled=(layout == "tiled"))
-    if out.tiled:
-        out.block.fill_(POISON_BYTE)
-    else:
-        for f in ALL_FIELDS:
-            out.field(f).view(torch.uint8).fill_(POISON_BYTE)
-    return out
-
-
-def _bits(t):
-    return t.view({8: torch.int64, 4: torch.int32}[t.element_size()])
-
-
-def _byte_poison(plane):
-    return _bits(torch.full((plane.element_size(),), POISON_BYTE, dtype=torch.uint8, device=plane.device).view(plane.dtype))
-
-
-def _value_poison(plane, f):
-    dt = torch.int32 if f in ("ray", "surface") else {torch.int64: torch.float64, torch.int32: torch.float32}[plane.dtype]
-    return _bits(torch.full((1,), POISON_INT if dt == torch.int32 else POISON_REAL, dtype=dt, device=plane.device))
-
-
-def _poison_behind_torch(out):
-    """through .data: torch does not see the write, the tokens of a reused output stay"""
-    for f in ALL_FIELDS:
-        out.field(f).data.fill_(POISON_INT if f in ("ray", "surface") else POISON_REAL)
-
-
-def _planes(segs, n, K):
-    """every field as bit patterns [K, n], `count`, and which slots hold records"""
-    s = segs.to_slots()
-    out = {f: _bits(s.field(f)[: K * n]).view(K, n).clone() for f in ALL_FIELDS}
-    count = segs.count.clone()
-    return out, count, torch.arange(K, device=count.device)[:, None] < count.abs()[None, :]
-
-
-def _same_records(got, want, what):
-    (g, gc, valid), (w, wc, wvalid) = got, want
-    assert torch.equal(gc, wc), (what, "count", gc.cpu().tolist(), wc.cpu().tolist())
-    assert torch.equal(valid, wvalid), (what, "slots in use")
-    for f in ALL_FIELDS:
-        assert torch.equal(g[f][valid], w[f][valid]), (what, f)
-
-
-def _untouched_beyond_the_counts(out, n, K, what):
-    """an output poisoned byte by byte before its first trace: slots k >= |count| and a tiled block's padding hold the poison"""
-    valid = (torch.arange(K, device="cuda")[:, None] < out.count.abs()[None, :]).reshape(-1)
-    for f in ALL_FIELDS:
-        flat = _bits(out.field(f).reshape(-1))
-        poison = _byte_poison(flat)
-        assert bool((flat[: K * n][~valid] == poison).all()), (what, f, "a slot past a ray's count was written")
-        if out.tiled:
-            assert out.capacity % 64 == 0 and flat.numel() == out.capacity
-            assert bool((flat[K * n:] == poison).all()), (what, f, "the last tile's padding was written")
+    return support.engine_for(lambda oa: _components(name, oa), (__name__, name))
 
 
 def _forced(eng, kernel, fn):
@@ -130,12 +50,12 @@ def _forced(eng, kernel, fn):
 def _rolling(eng, batch, K, precision="f64"):
     """THE yardstick: the rolling-lists kernel, [k][ray] slots, into a fresh output"""
     n = batch.n
-    return _planes(_forced(eng, 2, lambda: eng.trace(batch, K, out=_new_out(n, K, precision, "slots"), layout="slots")), n, K)
+    return support.planes(_forced(eng, 2, lambda: eng.trace(batch, K, out=support.new_out(n, K, precision, "slots", support.POISON_BYTE), layout="slots")), n, K)
 
 
 def _fused(eng, batch, K, layout, precision="f64", out=None):
     n = batch.n
-    out = _new_out(n, K, precision, layout) if out is None else out
+    out = support.new_out(n, K, precision, layout, support.POISON_BYTE) if out is None else out
     return _forced(eng, 1, lambda: eng.trace(batch, K, out=out, layout=layout))
 
 
@@ -145,23 +65,23 @@ def _fused(eng, batch, K, layout, precision="f64", out=None):
 def test_cfg2_every_cap_equals_the_rolling_lists(n, layout):
     """K = 1, 2, 5; 7 exceeds every ray's life: the loop ends because no lane of the wave is active"""
     eng = _engine("cfg2")
-    batch = _batch(*scenes.cfg2_rays(n, 0))
+    batch = support.batch(*scenes.cfg2_rays(n, 0))
     for K in (1, 2, 5, 7):
         want = _rolling(eng, batch, K)
         assert int(want[1].min()) == int(want[1].max()) == min(K, 5)
         out = _fused(eng, batch, K, layout)
-        _same_records(_planes(out, n, K), want, (n, K, layout))
-        _untouched_beyond_the_counts(out, n, K, (n, K, layout))
+        support.same_records(support.planes(out, n, K), want, (n, K, layout))
+        support.untouched_beyond_the_counts(out, n, K, (n, K, layout))
 
 
 @pytest.mark.parametrize("layout", ["tiled", "slots"])
 def test_cfg2_single_precision(layout):
     eng = _engine("cfg2")
     n, K = 130, 5
-    batch = _batch(*scenes.cfg2_rays(n, 0), "f32")
+    batch = support.batch(*scenes.cfg2_rays(n, 0), "f32")
     out = _fused(eng, batch, K, layout, "f32")
-    _same_records(_planes(out, n, K), _rolling(eng, batch, K, "f32"), layout)
-    _untouched_beyond_the_counts(out, n, K, layout)
+    support.same_records(support.planes(out, n, K), _rolling(eng, batch, K, "f32"), layout)
+    support.untouched_beyond_the_counts(out, n, K, layout)
 
 
 def _aimed(n, idx, target):
@@ -191,7 +111,7 @@ def test_one_wave_mixing_every_way_a_ray_ends(layout):
     eng = _engine("ends")
     n = 130
     o, d, rim, up, plate, dead = _every_end(n)
-    batch = _batch(o, d)
+    batch = support.batch(o, d)
     flags = batch.flags.cpu()
     flags[dead] |= abi.RAY_DEAD
     batch.flags.copy_(flags)
@@ -207,8 +127,8 @@ def test_one_wave_mixing_every_way_a_ray_ends(layout):
         assert {1, 2, 3, 5} <= set(c[64:128].tolist()), np.bincount(c[64:128]).tolist()  # escapes at k = 0, 1 and 2, and the cap
         assert (c[128:] == 5).all() and (c[:64] == 5).all()
         out = _fused(eng, batch, K, layout)
-        _same_records(_planes(out, n, K), want, (K, layout))
-        _untouched_beyond_the_counts(out, n, K, (K, layout))
+        support.same_records(support.planes(out, n, K), want, (K, layout))
+        support.untouched_beyond_the_counts(out, n, K, (K, layout))
 
 
 @pytest.mark.parametrize("layout", ["tiled", "slots"])
@@ -218,7 +138,7 @@ def test_a_half_silvered_mirror_at_the_first_an_inner_and_the_last_segment(layou
     n = 130
     first = np.array([3, 64, 77, 126, 129])  # aimed at the half-silvered mirror beside the lens: a branching hit at k = 0
     o, d = _aimed(n, first, [2.0, 1.5, 0.0])
-    batch = _batch(o, d)
+    batch = support.batch(o, d)
     for K, behind_the_lens in ((1, None), (2, "the last segment"), (5, "an inner segment")):
         want = _rolling(eng, batch, K)
         c = want[1].cpu().numpy()
@@ -231,44 +151,35 @@ def test_a_half_silvered_mirror_at_the_first_an_inner_and_the_last_segment(layou
             for lo, hi in ((0, 64), (64, 128)):
                 assert (c[lo:hi] == -2).any() and (c[lo:hi] == K).any(), "every full wave mixes the two"
         out = _fused(eng, batch, K, layout)
-        _same_records(_planes(out, n, K), want, (K, layout, behind_the_lens))
-        _untouched_beyond_the_counts(out, n, K, (K, layout))
+        support.same_records(support.planes(out, n, K), want, (K, layout, behind_the_lens))
+        support.untouched_beyond_the_counts(out, n, K, (K, layout))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _short(n):
-    """cfg 2's rays with those of wave 0 and every other ray of wave 1 aimed past the lens: 1 to 3 records instead of 5"""
-    o, d = scenes.cfg2_rays(n, 0)
-    idx = np.concatenate([np.arange(0, 64), np.arange(64, 128, 2)])
-    d[idx] = np.stack([np.ones(idx.size), np.linspace(0.21, 0.6, idx.size), np.zeros(idx.size)], axis=1)
-    d[idx[::4]] = [0.0, 1.0, 0.0]
-    return o, d
-
-
 @pytest.mark.parametrize("layout", ["tiled", "slots"])
 def test_reuse_second_and_third_trace_equal_a_fresh_output(layout):
     eng = _engine("cfg2")
     n, K = 130, 5
-    first, again = _batch(*scenes.cfg2_rays(n, 0)), _batch(*scenes.cfg2_rays(n, 1))
-    want = _planes(_fused(eng, again, K, layout), n, K)
-    _same_records(want, _rolling(eng, again, K), "a fresh output against the rolling lists")
+    first, again = support.batch(*scenes.cfg2_rays(n, 0)), support.batch(*scenes.cfg2_rays(n, 1))
+    want = support.planes(_fused(eng, again, K, layout), n, K)
+    support.same_records(want, _rolling(eng, again, K), "a fresh output against the rolling lists")
     out = _fused(eng, first, K, layout)
     for turn in ("second", "third"):
         assert _fused(eng, again, K, layout, out=out) is out
-        _same_records(_planes(out, n, K), want, (turn, layout))
-        _untouched_beyond_the_counts(out, n, K, (turn, layout))
+        support.same_records(support.planes(out, n, K), want, (turn, layout))
+        support.untouched_beyond_the_counts(out, n, K, (turn, layout))
     if layout != "tiled":
         return
     # both masks ran (fm at k = 0 and `whole` come from the scalar counter): poison survives in the resident planes at every k,
     # in the first-segment fields at k = 0, and nowhere else
     assert out._resident["planes"] == abi.RESIDENT_RAY | abi.RESIDENT_N | abi.RESIDENT_INTENSITY
     assert set(out._first["values"]) == set(POINT + ("n", "intensity"))
-    _poison_behind_torch(out)
+    support.poison_behind_torch(out)
     _fused(eng, again, K, layout, out=out)
-    g, gc, _ = _planes(out, n, K)
+    g, gc, _ = support.planes(out, n, K)
     assert torch.equal(gc, want[1])
     for f in ALL_FIELDS:
-        poison = _value_poison(g[f], f)
+        poison = support.value_poison(g[f], f)
         if f in RESIDENT:
             assert bool((g[f] == poison).all()), (f, "a resident plane was written")
             continue
@@ -284,21 +195,21 @@ def test_reuse_a_ray_that_lives_longer_than_last_time():
     before that, and in the other waves, the skip runs: poison survives exactly there"""
     eng = _engine("cfg2")
     n, K, layout = 130, 5, "tiled"
-    short, long_ = _batch(*_short(n)), _batch(*scenes.cfg2_rays(n, 0))
+    short, long_ = support.batch(*support.short_rays(n)[:2]), support.batch(*scenes.cfg2_rays(n, 0))
     want, wc, wvalid = _rolling(eng, long_, K)
     assert int(wc.min()) == K
     out = _fused(eng, short, K, layout)
-    _same_records(_planes(out, n, K), _rolling(eng, short, K), "the short rays")
+    support.same_records(support.planes(out, n, K), _rolling(eng, short, K), "the short rays")
     old = out.count.abs().cpu().numpy()
     assert old[:64].max() <= 3 and old[:64].min() == 1 and (old[64:128] < K).any() and (old[64:128] == K).any() and (old[128:] == K).all()
-    _poison_behind_torch(out)
+    support.poison_behind_torch(out)
     _fused(eng, long_, K, layout, out=out)
-    g, gc, _ = _planes(out, n, K)
+    g, gc, _ = support.planes(out, n, K)
     assert torch.equal(gc, wc)
     for lo, hi in ((0, 64), (64, 128), (128, n)):
         whole_from = min(int(old[lo:hi].min()), K)
         for f in ALL_FIELDS:
-            poison = _value_poison(g[f], f)
+            poison = support.value_poison(g[f], f)
             assert torch.equal(g[f][whole_from:, lo:hi], want[f][whole_from:, lo:hi]), (lo, f, "full records once a ray lives longer")
             for k in range(whole_from):
                 if f in RESIDENT or (k == 0 and f in POINT):
@@ -308,9 +219,9 @@ def test_reuse_a_ray_that_lives_longer_than_last_time():
     # and without poison, there and back: what a fresh output holds
     out = _fused(eng, short, K, layout)
     _fused(eng, long_, K, layout, out=out)
-    _same_records(_planes(out, n, K), (want, wc, wvalid), "long after short")
+    support.same_records(support.planes(out, n, K), (want, wc, wvalid), "long after short")
     _fused(eng, short, K, layout, out=out)
-    _same_records(_planes(out, n, K), _rolling(eng, short, K), "short after long")
+    support.same_records(support.planes(out, n, K), _rolling(eng, short, K), "short after long")
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -330,7 +241,7 @@ def test_the_refracting_scene_with_total_internal_reflection_fresh_and_reused(la
     o, d, wl, inside = _snell_rays()
     n = len(o)
     assert n == 130
-    batch = _batch(o, d, wavelength=wl, q=1j * np.pi * scenes.W0**2 / wl)
+    batch = support.batch(o, d, wavelength=wl, q=1j * np.pi * scenes.W0**2 / wl)
     for K in (3, 6):
         want = _rolling(eng, batch, K)
         c = want[1].cpu().numpy()
@@ -341,12 +252,12 @@ def test_the_refracting_scene_with_total_internal_reflection_fresh_and_reused(la
         assert bool((nn[: min(K, 5), inside] == nn[0, inside]).all()), "total internal reflection keeps the ray's n"
         assert int(np.delete(c, inside).min()) >= 2
         out = _fused(eng, batch, K, layout)
-        _same_records(_planes(out, n, K), want, (K, layout, "fresh"))
-        _untouched_beyond_the_counts(out, n, K, (K, layout, "fresh"))
+        support.same_records(support.planes(out, n, K), want, (K, layout, "fresh"))
+        support.untouched_beyond_the_counts(out, n, K, (K, layout, "fresh"))
         for turn in ("second", "third"):
             _fused(eng, batch, K, layout, out=out)
-            _same_records(_planes(out, n, K), want, (K, layout, turn))
-            _untouched_beyond_the_counts(out, n, K, (K, layout, turn))
+            support.same_records(support.planes(out, n, K), want, (K, layout, turn))
+            support.untouched_beyond_the_counts(out, n, K, (K, layout, turn))
 
 
 @pytest.mark.parametrize("layout", ["tiled", "slots"])
@@ -354,14 +265,14 @@ def test_a_scene_with_spherical_faces(layout):
     """the preset with curved surfaces and count gates shares the loop"""
     eng = _engine("sphere")
     n, K = 130, 6
-    batch = _batch(*scenes.cfg2_rays(n, 0))
+    batch = support.batch(*scenes.cfg2_rays(n, 0))
     want = _rolling(eng, batch, K)
     c = want[1].cpu().numpy()
     print("segments per ray:", np.bincount(c, minlength=K + 1).tolist())
     assert (c >= 1).all() and c.max() >= 5, "through both faces, off the mirror and back through both"
     out = _fused(eng, batch, K, layout)
-    _same_records(_planes(out, n, K), want, layout)
-    _untouched_beyond_the_counts(out, n, K, layout)
+    support.same_records(support.planes(out, n, K), want, layout)
+    support.untouched_beyond_the_counts(out, n, K, layout)
 
 
 @pytest.mark.parametrize("layout", ["tiled", "slots"])
@@ -371,7 +282,7 @@ def test_the_grid_stride_path_equals_the_default_grid(layout):
     eng = _engine("cfg2")
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     n, K = 2 * cus * 256 + 130, 5
-    batch = _batch(*scenes.cfg2_rays(n, 3))
+    batch = support.batch(*scenes.cfg2_rays(n, 3))
     want = _fused(eng, batch, K, layout)
     full_grid = eng.last_launch()["workgroups"]
     eng.set_option(abi.OPT_BLOCKS_PER_CU, 1)
@@ -383,4 +294,4 @@ def test_the_grid_stride_path_equals_the_default_grid(layout):
     assert launch["workgroups"] == cus and launch["workgroups"] * 256 * 2 < n <= full_grid * 256, (launch, full_grid)
     assert torch.equal(out.count, want.count) and int(want.count.min()) == K
     for f in ALL_FIELDS:
-        assert torch.equal(_bits(out.field(f).reshape(-1)), _bits(want.field(f).reshape(-1))), (layout, f)
+        assert torch.equal(support.bits(out.field(f).reshape(-1)), support.bits(want.field(f).reshape(-1))), (layout, f)

@@ -17,6 +17,7 @@ centre = 0 the bound of Wyy / W is 2 |y| d = 1e-13 from the coordinates alone, a
 the radius to better than percents, whatever the kernel does.  With centre on the spot |y| is 1e-6 and the same d bounds the
 variance to 1e-6 of itself."""
 import ctypes as C
+import functools
 import math
 
 import numpy as np
@@ -25,47 +26,25 @@ import torch
 
 import optable_amd as oa
 import scenes
+import support
 from optable_amd import abi
 from optable_amd import workloads as W
 from optable_amd.batch import RayBatch, SegmentBatch
 from optable_amd.engine import get_engine, segment_source, spots_plan
 from optable_amd.table import monitor_struct
 from spots_reference import U, radius_interval, spots_reference, variance_bound
+from support import ctx  # noqa: F401  (the fixture)
+from wavefront_cases import axes_of
 
 pytestmark = pytest.mark.gpu
 
-ERR_INVALID = -1
 OFFSETS = np.array([-0.9, -0.3, 0.0, 0.45, 0.9])
-
-
-def _batch(o, d, precision="f64", seed=7):
-    """cfg 2's rays with per-ray intensities 0.25 + 0.75 u: the weighted sums are no multiple of the counts."""
-    q = 1j * np.pi * scenes.W0**2 / scenes.WL
-    intensity = 0.25 + 0.75 * np.random.default_rng(seed).random(len(o))
-    return RayBatch.from_arrays(o, d, wavelength=scenes.WL, intensity=intensity, q=q, precision=precision, device="cuda")
-
-
-def _cfg2_table():
-    t = oa.OpticalTable()
-    t.add_components(scenes.cfg2_components(oa))
-    return t
-
-
-def _records(segs):
-    """The valid segment records of a batch, copied from the device: (o [n, 3], d [n, 3], length, intensity) as doubles."""
-    h = segs.to_host(reference_order=False)
-    col = lambda f: np.asarray(h[f], dtype=np.float64)  # noqa: E731  (single precision widens exactly)
-    return np.stack([col("ox"), col("oy"), col("oz")], 1), np.stack([col("dx"), col("dy"), col("dz")], 1), col("length"), col("intensity")
-
-
-def _axes(m):
-    return np.concatenate([m.tangent_Y, m.tangent_Z]).astype(float)
 
 
 def _reference(records, mon, offsets, weight="intensity", centre=(0.0, 0.0)):
     o, d, length, intensity = records
     s = monitor_struct(mon)
-    ref = spots_reference(o, d, length, intensity if weight == "intensity" else None, list(s.M), list(s.origin), s.half_width, s.half_height, _axes(mon),
+    ref = spots_reference(o, d, length, intensity if weight == "intensity" else None, list(s.M), list(s.origin), s.half_width, s.half_height, axes_of(mon),
                           centre, offsets)
     print(f"  margin {ref.margin:.3g}, hits per plane {ref.counts.min()} .. {ref.counts.max()}")
     assert ref.margin > 1e-7  # a condition on the inputs
@@ -106,26 +85,22 @@ EMPTY = 2
 @pytest.fixture(scope="module")
 def case1():
     """cfg 2, 5,003 rays, 5 segments — 25,015 slots: 13 workgroups of 2,048 with a ragged tail — four monitors, five planes:
-    (table, monitors, {(layout, precision): (segs, records, [reference per monitor])}), traced and reduced on the host on first use."""
-    table, mons, made = _cfg2_table(), _monitors(), {}
+    (table, monitors, {(layout, precision): (segs, (records, [reference per monitor]))}), traced and reduced on the host on first use."""
+    table, mons = support.cfg2_table(), _monitors()
     o, d = scenes.cfg2_rays(5003, 0)
 
-    def get(layout, precision):
-        if (layout, precision) not in made:
-            segs = table.trace_batch(_batch(o, d, precision), max_segments=5, layout=layout)
-            assert segs.layout == layout and segs.precision == precision
-            records = _records(segs)
-            made[layout, precision] = (segs, records, [_reference(records, m, OFFSETS) for m in mons])
-        return made[layout, precision]
+    def derive(segs):
+        records = support.host_records(segs)
+        return records, [_reference(records, m, OFFSETS) for m in mons]
 
-    return table, mons, get
+    return table, mons, support.traced(table, lambda precision: support.weighted_batch(o, d, precision), 5, derive)
 
 
 @pytest.mark.parametrize("precision", ["f64", "f32"])
 @pytest.mark.parametrize("layout", ["slots", "tiled", "append"])
 def test_layouts_and_precisions(case1, layout, precision, monkeypatch):
     table, mons, get = case1
-    segs, records, refs = get(layout, precision)
+    segs, (records, refs) = get(layout, precision)
     table.monitors = []
     table.add_monitors(mons)
 
@@ -156,10 +131,10 @@ def test_layouts_agree(case1):
     table, mons, get = case1
     got = {}
     for layout in ("slots", "tiled", "append"):
-        segs, _, refs = get(layout, "f64")
+        segs, (_, refs) = get(layout, "f64")
         got[layout] = [sp.to_host()[:2] for sp in table.spots_all(segs, offsets=OFFSETS, monitors=mons)]
     for layout in ("tiled", "append"):
-        for (c0, s0), (c1, s1), ref in zip(got["slots"], got[layout], get("slots", "f64")[2]):
+        for (c0, s0), (c1, s1), ref in zip(got["slots"], got[layout], get("slots", "f64")[1][1]):
             np.testing.assert_array_equal(c0, c1)
             assert np.all(np.abs(s0 - s1) <= 2 * ref.bound)
 
@@ -167,10 +142,10 @@ def test_layouts_agree(case1):
 @pytest.mark.parametrize("n,K", [(130, 3), (1027, 5), (1, 1)])
 def test_batch_sizes(n, K):
     """130 x 3 = 390 slots: a partial wave in a partial workgroup; 1,027 x 5 = 5,135: three workgroups, the last one ragged; 1 x 1."""
-    table = _cfg2_table()
+    table = support.cfg2_table()
     mons = [oa.Monitor([2.5, 0, 0], 6, 6), oa.Monitor([7.5, 0, 0], 6, 6)]
-    segs = table.trace_batch(_batch(*scenes.cfg2_rays(n, 3)), max_segments=K, layout="slots")
-    records = _records(segs)
+    segs = table.trace_batch(support.weighted_batch(*scenes.cfg2_rays(n, 3)), max_segments=K, layout="slots")
+    records = support.host_records(segs)
     offsets = [-0.5, 0.0, 0.25]
     spots = table.spots_all(segs, offsets=offsets, monitors=mons)
     for sp, m in zip(spots, mons):
@@ -180,12 +155,12 @@ def test_batch_sizes(n, K):
 
 def test_more_cells_than_one_group():
     """2 monitors x 200 planes = 400 cells: two launches, the first ending inside the second monitor's planes."""
-    table = _cfg2_table()
+    table = support.cfg2_table()
     mons = [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([7.0, 0, 0], 5, 5).RotZ(-0.2)]  # (wide: 400 planes of a clipping aperture put some ray on a rim)
     offsets = np.linspace(-0.995, 0.995, 200)
     assert spots_plan(2, 200) == [(0, 256), (256, 144)]
-    segs = table.trace_batch(_batch(*scenes.cfg2_rays(1003, 5)), max_segments=5, layout="slots")
-    records = _records(segs)
+    segs = table.trace_batch(support.weighted_batch(*scenes.cfg2_rays(1003, 5)), max_segments=5, layout="slots")
+    records = support.host_records(segs)
     spots = table.spots_all(segs, offsets=offsets, monitors=mons)
     for sp, m in zip(spots, mons):
         _assert_spots(sp, _reference(records, m, offsets))
@@ -196,18 +171,18 @@ def test_more_cells_than_one_group_streamed():
     """The 400 cells and 1,003 rays above as two chunks of 512 and 491 rays, the second added with `into=`: every launch of the
     second call draws its own ticket, shares the call's partials and adds to what the first call left.  The hits are those of the
     one-call test, so no ray sits on a rim; the bounds are the reference's own for the concatenated records."""
-    table = _cfg2_table()
+    table = support.cfg2_table()
     mons = [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([7.0, 0, 0], 5, 5).RotZ(-0.2)]
     offsets = np.linspace(-0.995, 0.995, 200)
     assert spots_plan(2, 200) == [(0, 256), (256, 144)]
     o, d = scenes.cfg2_rays(1003, 5)
-    whole = _batch(o, d)
+    whole = support.weighted_batch(o, d)
     chunks = []
     for part in (slice(0, 512), slice(512, 1003)):
         b = RayBatch.from_arrays(o[part], d[part], wavelength=scenes.WL, intensity=whole.intensity[part].cpu().numpy(),
-                                 q=1j * np.pi * scenes.W0**2 / scenes.WL, device="cuda")
+                                 q=support.Q, device="cuda")
         chunks.append(table.trace_batch(b, max_segments=5, layout="slots"))
-    records = tuple(np.concatenate(parts) for parts in zip(*(_records(c) for c in chunks)))
+    records = tuple(np.concatenate(parts) for parts in zip(*(support.host_records(c) for c in chunks)))
     spots = table.spots_all(chunks[0], offsets=offsets, monitors=mons)
     table.spots_all(chunks[1], offsets=offsets, monitors=mons, into=spots)
     for sp, m in zip(spots, mons):
@@ -230,7 +205,7 @@ def test_lists_and_trees():
     for segs, layout in ((eng.trace_trees(batch, 12, layout="slots"), "slots"), (eng.trace_trees(batch, 12, layout="append"), "append"),
                          (eng.trace_tree(batch, 12), "list")):
         assert segs.layout == layout
-        records = _records(segs)
+        records = support.host_records(segs)
         for sp, m in zip(table.spots_all(segs, offsets=offsets, monitors=mons), mons):
             ref = _reference(records, m, offsets)
             _assert_spots(sp, ref)
@@ -247,7 +222,7 @@ def test_planes_are_displaced_monitors(case1):
     """Offset 0 is the monitor: the moments of its `record_all` hits.  Offset d is a Monitor built at the displaced pose.  torch sums
     in an order of its own and rounds its own P: twice the tolerance."""
     table, mons, get = case1
-    segs, _, refs = get("slots", "f64")
+    segs, (_, refs) = get("slots", "f64")
     for k in (0, 1, 3):
         mon, ref = mons[k], refs[k]
         normal = np.asarray(mon.transform_matrix, dtype=float)[:, 0]
@@ -286,16 +261,16 @@ def test_determinism(case1):
 
 def test_streaming():
     """Two chunks of a trace with `into=` against the reference of their concatenation."""
-    table = _cfg2_table()
+    table = support.cfg2_table()
     o, d = scenes.cfg2_rays(2049, 3)
-    whole = _batch(o, d)
+    whole = support.weighted_batch(o, d)
     mons = [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([7.5, 0, 0], 0.7, 0.7), oa.Monitor([7.5, 40, 0], 6, 6)]
     halves = []
     for part in (slice(0, 1024), slice(1024, 2049)):
         b = RayBatch.from_arrays(o[part], d[part], wavelength=scenes.WL, intensity=whole.intensity[part].cpu().numpy(),
-                                 q=1j * np.pi * scenes.W0**2 / scenes.WL, device="cuda")
+                                 q=support.Q, device="cuda")
         halves.append(table.trace_batch(b, max_segments=5, layout="slots"))
-    records = tuple(np.concatenate(parts) for parts in zip(*(_records(h) for h in halves)))
+    records = tuple(np.concatenate(parts) for parts in zip(*(support.host_records(h) for h in halves)))
     spots = table.spots_all(halves[0], offsets=OFFSETS, monitors=mons)
     first = [sp.counts.clone() for sp in spots]
     assert table.spots_all(halves[1], offsets=OFFSETS, monitors=mons, into=spots) is not None
@@ -304,23 +279,6 @@ def test_streaming():
         assert int(before.sum()) < int(sp.counts.sum()) or not sp.counts.any()
     again = table.spots_all(halves[0], offsets=OFFSETS, monitors=mons)  # without `into=` a call starts from zero again
     assert all(torch.equal(a.counts, b) for a, b in zip(again, first))
-
-
-def _list_batch(o, d, length, intensity):
-    n = len(o)
-    segs = SegmentBatch(n, "f64", "cuda")
-    for f in abi.SEG_FIELDS:
-        segs.field(f).zero_()
-    for k, f in enumerate(("ox", "oy", "oz")):
-        segs.field(f).copy_(torch.from_numpy(np.ascontiguousarray(o[:, k])))
-    for k, f in enumerate(("dx", "dy", "dz")):
-        segs.field(f).copy_(torch.from_numpy(np.ascontiguousarray(d[:, k])))
-    segs.length.copy_(torch.from_numpy(np.asarray(length, dtype=np.float64)))
-    segs.intensity.copy_(torch.from_numpy(np.asarray(intensity, dtype=np.float64)))
-    segs.ray.copy_(torch.arange(n, dtype=torch.int32))
-    segs.n_valid = n
-    assert segs.layout == "list"
-    return segs
 
 
 def test_weight_none_and_centre():
@@ -333,7 +291,7 @@ def test_weight_none_and_centre():
     d = np.tile(tilt / np.sqrt(tilt @ tilt), (n, 1))
     o = np.stack([np.zeros(n), 0.4 + 1e-6 * rng.normal(size=n), 1e-6 * rng.normal(size=n)], axis=1)
     intensity = 0.25 + 0.75 * rng.random(n)
-    segs = _list_batch(o, d, np.full(n, 8.0), intensity)
+    segs = support.list_batch(o, d, np.full(n, 8.0), intensity)
     records = (o, d, np.full(n, 8.0), intensity)
     table, mon = oa.OpticalTable(), oa.Monitor([5, 0, 0], 2, 2)
     offsets = [-0.5, 0.0, 0.5]
@@ -368,13 +326,13 @@ def test_best_focus_of_a_thin_lens():
     rng = np.random.default_rng(23)
     r, phi = 0.5 * np.sqrt(rng.random(n)), rng.uniform(0, 2 * np.pi, n)
     o = np.stack([np.zeros(n), r * np.cos(phi), r * np.sin(phi)], axis=1)
-    batch = RayBatch.from_arrays(o, np.tile([1.0, 0.0, 0.0], (n, 1)), wavelength=scenes.WL, q=1j * np.pi * scenes.W0**2 / scenes.WL, device="cuda")
+    batch = RayBatch.from_arrays(o, np.tile([1.0, 0.0, 0.0], (n, 1)), wavelength=scenes.WL, q=support.Q, device="cuda")
     table, mon = oa.OpticalTable(), oa.Monitor([10.3, 0, 0], 2, 2)
     table.add_components([oa.Lens([5, 0, 0], focal_length=5, radius=1.0)])
     segs = table.trace_batch(batch, max_segments=3)
     offsets = np.linspace(-0.6, 0.6, 25)
     sp = table.spots_batch(mon, segs, offsets=offsets)
-    ref = _reference(_records(segs), mon, offsets)
+    ref = _reference(support.host_records(segs), mon, offsets)
     _assert_spots(sp, ref)
     assert (ref.counts == n).all()
     var, e = zip(*(variance_bound(ref.sums[j], ref.bound[j]) for j in range(25)))
@@ -397,9 +355,9 @@ def test_best_focus_of_a_thin_lens():
 def test_power_is_the_sum_of_the_image():
     """cfg 2 at small n: `power()` on its monitor against `image_all(...).intensity.sum()`.  Both add the same c weights in orders of
     their own ((c - 1) U sum |w| each), torch then the 900 bins: (2 c + 900) U sum |w|."""
-    table = _cfg2_table()
+    table = support.cfg2_table()
     mon = oa.Monitor([7.5, 0, 0], 6, 6)
-    segs = table.trace_batch(_batch(*scenes.cfg2_rays(2003, 1)), max_segments=5, layout="slots")
+    segs = table.trace_batch(support.weighted_batch(*scenes.cfg2_rays(2003, 1)), max_segments=5, layout="slots")
     sp = table.spots_batch(mon, segs)
     im = table.image_batch(mon, segs)
     c = int(sp.counts[0])
@@ -420,28 +378,17 @@ def test_the_example_runs():
     assert "41 planes" in out.stdout and "best focus: offset -0.500000 (x = 10.000000)" in out.stdout, out.stdout
 
 
-class _Out:
+class _Out(support.Sentinel):
     """counts / sums of M monitors x J planes for ot_monitor_spots_many, with a guard region on either side of each."""
-    GUARD = 64
 
-    def __init__(self, M, J, fill=-7):
-        self.cells, self.fill, G = M * J, fill, self.GUARD
-        self.c = torch.full((self.cells + 2 * G,), fill, dtype=torch.int64, device="cuda")
-        self.s = torch.full((6 * self.cells + 2 * G,), float(fill), dtype=torch.float64, device="cuda")
-        self.counts, self.sums = self.c[G:G + self.cells].view(M, J), self.s[G:G + 6 * self.cells].view(M, J, 6)
-
-    def guards_untouched(self):
-        G = self.GUARD
-        return all(bool((t[:G] == self.fill).all()) and bool((t[-G:] == self.fill).all()) for t in (self.c, self.s))
-
-    def untouched(self):
-        return bool((self.c == self.fill).all()) and bool((self.s == self.fill).all())
+    def __init__(self, M, J):
+        super().__init__(guard=64, counts=(torch.int64, (M, J)), sums=(torch.float64, (M, J, 6)))
 
 
 def _call(lib, ctx, mons, segs, offsets, out, accumulate=0, weighted=True):
     src, n, count, n_rays = segment_source(segs)
     table = (abi.OtMonitor * len(mons))(*[monitor_struct(m) for m in mons])
-    axes, centre, offsets = np.array([_axes(m) for m in mons]), np.zeros((len(mons), 2)), np.asarray(offsets, dtype=np.float64)
+    axes, centre, offsets = np.array([axes_of(m) for m in mons]), np.zeros((len(mons), 2)), np.asarray(offsets, dtype=np.float64)
     dp = C.POINTER(C.c_double)
     return lib.ot_monitor_spots_many(ctx, table, len(mons), axes.ctypes.data_as(dp), centre.ctypes.data_as(dp), offsets.ctypes.data_as(dp), len(offsets),
                                      C.byref(src), segs.field("intensity").data_ptr() if weighted else None, n, None if count is None else count.data_ptr(),
@@ -449,7 +396,7 @@ def _call(lib, ctx, mons, segs, offsets, out, accumulate=0, weighted=True):
 
 
 def test_no_segments_and_the_guards():
-    table, eng = _cfg2_table(), get_engine()
+    table, eng = support.cfg2_table(), get_engine()
     mons = [oa.Monitor([2.5, 0, 0], 6, 6), oa.Monitor([7.5, 0, 0], 6, 6)]
     eng.upload(table.compile())
     none = eng.trace_tree(RayBatch(0, "f64", "cuda"), 5)
@@ -469,25 +416,16 @@ def test_no_segments_and_the_guards():
     torch.cuda.synchronize()
     assert kept.untouched()
     # a real batch into guarded outputs, 300 planes (two launches): nothing outside them is written
-    segs = table.trace_batch(_batch(*scenes.cfg2_rays(257, 2)), max_segments=5, layout="append")
+    segs = table.trace_batch(support.weighted_batch(*scenes.cfg2_rays(257, 2)), max_segments=5, layout="append")
     offsets = np.linspace(-0.9, 0.9, 300)
     wide = _Out(2, 300)
     with eng.lock:
         assert _call(eng.lib, eng._ctx, mons, segs, offsets, wide) == 0
     torch.cuda.synchronize()
     assert wide.guards_untouched()
-    records = _records(segs)
+    records = support.host_records(segs)
     for k, m in enumerate(mons):
         _assert_sums(wide.counts[k].cpu().numpy(), wide.sums[k].cpu().numpy(), _reference(records, m, offsets))
-
-
-@pytest.fixture()
-def ctx():
-    lib = abi.load()
-    c = C.c_void_p()
-    assert lib.ot_ctx_create(0, None, C.byref(c)) == 0
-    yield lib, c
-    assert lib.ot_ctx_destroy(c) == 0
 
 
 def test_abi_errors(ctx):
@@ -506,7 +444,7 @@ def test_abi_errors(ctx):
     out = _Out(1, J)
     src, n_segments, count, n_rays = segment_source(segs)
     assert (n_segments, n_rays) == (2 * n, n)
-    good_axes, good_centre, good_offsets = _axes(m).reshape(1, 6), np.array([[0.25, -0.5]]), np.array([-1.0, 0.0, 6.0])
+    good_axes, good_centre, good_offsets = axes_of(m).reshape(1, 6), np.array([[0.25, -0.5]]), np.array([-1.0, 0.0, 6.0])
     dp = C.POINTER(C.c_double)
     ptr = lambda a: None if a is None else a.ctypes.data_as(dp)  # noqa: E731
 
@@ -516,15 +454,7 @@ def test_abi_errors(ctx):
         return lib.ot_monitor_spots_many(ctx_, mons, M, ptr(axes), ptr(centre), ptr(offsets), n_off, None if source is None else C.byref(source), intensity,
                                          n_seg, cnt, rays, counts, sums, acc)
 
-    def expect(status, needle):
-        msg = lib.ot_last_error().decode()
-        assert status == ERR_INVALID and needle in msg, (status, msg, needle)
-
-    def altered(**fields):
-        other = abi.OtSegmentSource.from_buffer_copy(src)
-        for k, v in fields.items():
-            setattr(other, k, v)
-        return other
+    expect, altered = functools.partial(support.expect_invalid, lib), functools.partial(support.altered, src)
 
     def with_value(good, at, value):
         a = good.copy()

@@ -10,8 +10,6 @@ per ray against the rolling lists bit for bit in both precisions and in every ou
 trees against the oracle, the fp32 default launch against the oracle with every diverging ray explained, and the object
 API against what the reference recorded (tests/golden/g30-g35).  Only launch options that other suites already set; what
 ran is read back from last_launch()."""
-import contextlib
-
 import numpy as np
 import pytest
 
@@ -26,15 +24,6 @@ from optable_amd.fp32_audit import assert_explained, audit_traces
 pytestmark = pytest.mark.gpu
 Q = 1j * np.pi * FS.W0**2 / FS.WL
 N, K = 4099, 12  # not a multiple of 64, more than one workgroup
-
-
-@contextlib.contextmanager
-def named(form):
-    """Every failure names the form."""
-    try:
-        yield
-    except AssertionError as exc:
-        raise AssertionError(f"surface form {form!r}: {exc}") from exc
 
 
 _CASES = {}
@@ -75,7 +64,7 @@ def test_form_fp64_default_launch_matches_oracle(name, oracle):
     table, scene, o, d, host, ref = _case(name, oracle)
     segs = table.trace_batch(_batch(o, d), max_segments=K, scene=scene)
     got = segs.to_host(reference_order=True)
-    with named(name):
+    with FS.named(name):
         clean = _assert_matches_oracle(oracle, scene, host, ref, got, K)
         assert clean.all() or name in FS.LENSES or name in FS.BOWLS  # without an asphere the bound on q IS 1e-9
         np.testing.assert_array_equal(segs.count.abs().cpu().numpy() >= K, ref["capped"].astype(bool))
@@ -93,7 +82,7 @@ def test_form_lane_per_ray_equals_rolling_lists_in_every_layout(name, precision)
     eng = get_engine()
     out = {}
     try:
-        with named(name):
+        with FS.named(name):
             eng.set_option(abi.OPT_KERNEL, 1)
             out["lane per ray, slots"] = table.trace_batch(batch, max_segments=K, layout="slots", scene=scene)
             assert eng.last_launch()["kernel"] == 1, eng.last_launch()
@@ -110,7 +99,7 @@ def test_form_lane_per_ray_equals_rolling_lists_in_every_layout(name, precision)
         eng.set_option(abi.OPT_KERNEL, 0)
     host = {k: v.to_host(reference_order=True) for k, v in out.items()}
     base = host.pop("lane per ray, slots")
-    with named(name):
+    with FS.named(name):
         assert len(base["ray"]) > N
         for variant, got in host.items():
             for f in abi.SEG_FIELDS + ("ray", "surface", "count"):
@@ -130,7 +119,7 @@ def test_form_splitting_variant_matches_oracle(name, oracle):
     host = batch.to_host()
     got = table.trace_batch(batch, max_segments=K, scene=scene).to_host(reference_order=True)
     ref = oracle.trace(scene, host, max_trace_num=K)
-    with named(name):
+    with FS.named(name):
         assert scene.max_children == 2 and len(ref["ray"]) > 2.5 * n  # (a narrow arc is met once: 3 segments per ray, less the misses)
         _assert_matches_oracle(oracle, scene, host, ref, got, K)
 
@@ -153,7 +142,7 @@ def test_form_fp32_default_launch_against_oracle(name, oracle):
     b, bb = _sequences(got, N)
     same = np.array([np.array_equal(x, y) for x, y in zip(a, b)])
     print(f"fp32 share {name}: {same.mean():.5f} ({int((~same).sum())} of {N} rays diverge)")
-    with named(name):
+    with FS.named(name):
         assert_explained(audit_traces(scene, ref, got, prec="f32", tol=2e-3, rays=host))
         assert same.mean() > 0.999, f"{int((~same).sum())} of {N} rays diverge (all explained)"
         ia = np.concatenate([np.arange(ba[i], ba[i + 1]) for i in np.flatnonzero(same)])
@@ -174,7 +163,7 @@ def test_form_object_api_matches_reference_fixture(name):
     out = table.ray_tracing(sc["rays"], perfomance_limit=sc["limit"])
     got = rays_to_segs(out)
     got["ray"] = gold["seg_tree"]  # Ray objects carry no tree index; order is checked field by field
-    with named(name):
+    with FS.named(name):
         assert len(out) == len(gold["seg_tree"])
         np.testing.assert_array_equal(got["has_q"], gold["seg_has_q"])
         helpers.assert_segments_match(got, gold, gold["in_has_q"])
@@ -234,7 +223,7 @@ def test_curved_scenes_of_catalogue_forms_match_oracle(seed, oracle):
     host = batch.to_host()
     got = table.trace_batch(batch, max_segments=cap, scene=scene).to_host(reference_order=True)
     ref = oracle.trace(scene, host, max_trace_num=cap)
-    with named(f"curved scene {seed}"):
+    with FS.named(f"curved scene {seed}"):
         _assert_matches_oracle(oracle, scene, host, ref, got, cap)
 
 
@@ -289,7 +278,7 @@ def test_curved_scenes_of_deep_caps_match_oracle(seed, oracle):
     host = batch.to_host()
     got = table.trace_batch(batch, max_segments=cap, scene=scene).to_host(reference_order=True)
     ref = oracle.trace(scene, host, max_trace_num=cap)
-    with named(f"curved scene of deep caps {seed}"):
+    with FS.named(f"curved scene of deep caps {seed}"):
         caps = [k for k, leaf in enumerate(scene.leaves) if type(leaf.surface).__name__ == "Sphere" and leaf.surface.height >= leaf.surface.radius]
         assert np.isin(ref["surface"], caps).sum() > 0.25 * n  # the deep caps are met
         _assert_matches_oracle(oracle, scene, host, ref, got, cap)

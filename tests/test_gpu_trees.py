@@ -7,6 +7,7 @@ import torch
 
 import optable_amd as oa
 import scenes
+import support
 from optable_amd import abi
 from optable_amd import workloads as W
 from optable_amd.batch import RayBatch
@@ -15,17 +16,6 @@ from optable_amd.fp32_audit import assert_explained, audit_traces
 
 pytestmark = pytest.mark.gpu
 Q = 1j * np.pi * W.W0**2 / W.WL
-
-
-def _lattice(k_max=3):
-    comps = []
-    for k in range(k_max):
-        comps.append(oa.BeamSplitter([2.0 * (k + 1), 0, 0], width=6, height=2, eta=0.5).RotZ(np.pi / 4))
-        comps.append(oa.Mirror([2.0 * (k + 1), 3.0 + 0.1 * k, 0], radius=2).RotZ(-np.pi / 2))
-        comps.append(oa.BeamSplitter([2.0 * (k + 1) + 1.0, 1.5, 0], width=6, height=2, eta=0.3).RotZ(-np.pi / 4))
-    t = oa.OpticalTable()
-    t.add_components(comps)
-    return t.compile()
 
 
 def _lattice_rays(n, seed, precision="f64"):
@@ -77,7 +67,7 @@ def test_trees_equal_generations_on_cfg4_with_reflectivity(precision, oracle):
 def test_trees_equal_generations_on_bushy_trees(cap, precision):
     """Beam-splitter lattice: trees that double every generation and are cut by the cap in their widest one — the queue bound
     ceil(cap / 2) and the rule that drops children no budget is left for."""
-    _same_as_generations(_lattice(), _lattice_rays(3000, 5, precision), cap)
+    _same_as_generations(support.lattice(), _lattice_rays(3000, 5, precision), cap)
 
 
 @pytest.mark.parametrize("lds_entries", [1, 2, 3, 8])
@@ -88,7 +78,7 @@ def test_deep_queues_spill_into_the_scratch_ring_and_keep_their_order(lds_entrie
     eng = get_engine()
     try:
         eng.set_option(abi.OPT_TREES_LDS_ENTRIES, lds_entries)
-        _same_as_generations(_lattice(), _lattice_rays(20_000, 11, precision), 48)
+        _same_as_generations(support.lattice(), _lattice_rays(20_000, 11, precision), 48)
         plan = eng.trees_plan(precision, 48)
         assert plan["lds_entries"] == min(lds_entries, 6 if precision == "f64" else 13) and plan["queue"] == plan["lds_entries"] + 24
     finally:
@@ -97,7 +87,7 @@ def test_deep_queues_spill_into_the_scratch_ring_and_keep_their_order(lds_entrie
 
 def test_trees_whose_rays_all_escape_or_die():
     """Trees of one ray (a miss), of dead input rays, and a batch that is not a multiple of the wave."""
-    scene = _lattice()
+    scene = support.lattice()
     batch = _lattice_rays(1001, 7)
     batch.dz.fill_(0.9)  # most rays leave the table at once
     batch.flags[::5] |= abi.RAY_DEAD
@@ -107,7 +97,7 @@ def test_trees_whose_rays_all_escape_or_die():
 def test_a_queue_that_is_too_small_reports_its_trees():
     """A cap whose queue bound does not fit the CU's LDS: the plan says so, small trees still come out right, and a tree
     that overflows its queue is reported (negative count), never silently truncated."""
-    scene = _lattice()
+    scene = support.lattice()
     eng = get_engine()
     eng.upload(scene)
     batch = _lattice_rays(2000, 8)
@@ -226,7 +216,7 @@ def test_append_layout_of_the_tree_kernel_holds_the_same_records(precision, away
     """ot_trace_trees_append_*: the records of a step go to consecutive slots of the wave's chunk whatever trees the lanes are on
     (a batch in which nine trees of ten are a single ray: lanes refill from their wave's share all the time) — the same
     records as the [k][tree] slots, in the reference's order after the stable sort by tree."""
-    scene = _lattice()
+    scene = support.lattice()
     batch = _lattice_rays(30_000, 13, precision)
     if away:
         gone = torch.rand(batch.n, device=batch.device) < away
@@ -252,7 +242,7 @@ def test_append_layout_of_the_tree_kernel_holds_the_same_records(precision, away
 def test_default_call_sizes_the_dense_list_from_a_sample():
     """Engine.trace_branching on a large batch: rays per tree from a 1 % sample; the append block is that x 1.15 + the launch's
     slack, not every tree at its cap — also for few long trees under a large cap."""
-    scene = _lattice()
+    scene = support.lattice()
     eng = get_engine()
     eng.upload(scene)
     batch = _lattice_rays(400_000, 17, "f32")
@@ -332,7 +322,7 @@ def test_trees_in_a_scene_of_grids_and_curved_optics(precision, oracle):
 @pytest.mark.parametrize("refill_at", [1, 40, 64])
 def test_records_do_not_depend_on_when_lanes_refill(refill_at):
     """OT_OPT_TREES_REFILL_AT: lanes that take their next tree one by one, in groups, or 64 to a wave at a time — the same records."""
-    scene = _lattice()
+    scene = support.lattice()
     batch = _lattice_rays(20_000, 19)
     gone = torch.rand(batch.n, device=batch.device) < 0.6
     batch.dx[gone] = -1.0
@@ -364,7 +354,7 @@ def test_default_call_keeps_moderately_uneven_trees_in_step():
     (rpr, refill_at), = eng._records_per_ray.values()
     assert segs.layout == "append" and 13 < rpr < 30 and refill_at == 64
     assert int(segs.count.min()) >= 8 and int(segs.count.max()) < 48
-    eng.upload(_lattice())
+    eng.upload(support.lattice())
     skew = _lattice_rays(400_000, 17, "f32")
     gone = torch.rand(skew.n, device=skew.device) < 0.9
     skew.dx[gone] = -1.0

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import scenes
+import support
 from optable_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -16,27 +17,14 @@ SCALARS = BIT["wavelength"] | BIT["q_re"] | BIT["q_im"] | BIT["intensity"] | BIT
 ORIGIN = BIT["ox"] | BIT["oy"] | BIT["oz"]
 DIRECTION = BIT["dx"] | BIT["dy"] | BIT["dz"]
 IDF = BIT["id"] | BIT["flags"]
-Q = 1j * np.pi * scenes.W0**2 / scenes.WL
 
 # scene -> (components, segments per ray, a ray that hits: origin, direction)
 SCENES = {
     "cfg2": (scenes.cfg2_components, 5, np.array([0.0, 0.0, 0.0]), np.array([1.0, 0.0, 0.0])),
     "snell": (scenes.cfg4_components, 3, np.array([-3.0, 2.0, 0.0]), np.array([np.cos(np.pi / 6), -np.sin(np.pi / 6), 0.0])),
 }
-_compiled = {}
-
-
 def _engine(name):
-    import optable_amd as oa
-    from optable_amd.engine import get_engine
-
-    if name not in _compiled:
-        table = oa.OpticalTable()
-        table.add_components(SCENES[name][0](oa))
-        _compiled[name] = table.compile()
-    eng = get_engine()
-    eng.upload(_compiled[name])
-    return eng
+    return support.engine_for(SCENES[name][0], (__name__, name))
 
 
 def _rays(name, n, spread_origin, spread_direction, seed=7):
@@ -54,43 +42,21 @@ def _rays(name, n, spread_origin, spread_direction, seed=7):
 def _varying(n):
     """the six 'scalar' fields as arrays with no two elements alike"""
     j = np.arange(n)
-    return dict(wavelength=scenes.WL * (1 + 1e-3 * j / n), intensity=1.0 - 0.5 * j / n, q=Q * (1 + 1e-3 * j / n) + 1e-3 * (j + 1),
+    return dict(wavelength=scenes.WL * (1 + 1e-3 * j / n), intensity=1.0 - 0.5 * j / n, q=support.Q * (1 + 1e-3 * j / n) + 1e-3 * (j + 1),
                 n_index=1.0 + 1e-3 * (j + 1) / n, pathlength=1e-3 * (j + 1))
-
-
-def _batch(o, d, precision, **kw):
-    from optable_amd.batch import RayBatch
-
-    kw.setdefault("wavelength", scenes.WL)
-    kw.setdefault("q", Q)
-    return RayBatch.from_arrays(o, d, precision=precision, device="cuda", **kw)
 
 
 # mask class -> (batch maker, the mask it must have)
 def _classes(name, n, precision):
     rev = np.arange(n, dtype=np.int32)[::-1].copy()
     return {
-        "none": (lambda: _batch(*_rays(name, n, True, True), precision, ids=rev, **_varying(n)), BIT["flags"]),  # (flags: dropped below)
-        "scalars": (lambda: _batch(*_rays(name, n, True, True), precision), SCALARS | IDF),
-        "scalars+origin": (lambda: _batch(*_rays(name, n, False, True), precision), SCALARS | ORIGIN | IDF),
-        "direction": (lambda: _batch(*_rays(name, n, True, False), precision, ids=rev, **_varying(n)), DIRECTION | BIT["flags"]),
-        "flags+id": (lambda: _batch(*_rays(name, n, True, True), precision, **_varying(n)), IDF),
-        "everything": (lambda: _batch(*_rays(name, n, False, False), precision), abi.UNIFORM_ALL),
+        "none": (lambda: support.batch(*_rays(name, n, True, True), precision, ids=rev, **_varying(n)), BIT["flags"]),  # (flags: dropped below)
+        "scalars": (lambda: support.batch(*_rays(name, n, True, True), precision), SCALARS | IDF),
+        "scalars+origin": (lambda: support.batch(*_rays(name, n, False, True), precision), SCALARS | ORIGIN | IDF),
+        "direction": (lambda: support.batch(*_rays(name, n, True, False), precision, ids=rev, **_varying(n)), DIRECTION | BIT["flags"]),
+        "flags+id": (lambda: support.batch(*_rays(name, n, True, True), precision, **_varying(n)), IDF),
+        "everything": (lambda: support.batch(*_rays(name, n, False, False), precision), abi.UNIFORM_ALL),
     }
-
-
-def _bits(t):
-    return t.view({8: torch.int64, 4: torch.int32}[t.element_size()])
-
-
-def _records(segs, n, K):
-    """every field of the valid slots as bit patterns, plus count"""
-    s = segs.to_slots()
-    count = segs.count.clone()
-    valid = torch.arange(K, device=count.device)[:, None] < count.abs()[None, :]
-    out = {f: _bits(s.field(f)[: K * n]).view(K, n)[valid].clone() for f in abi.SEG_FIELDS + ("ray", "surface")}
-    out["count"] = count
-    return out
 
 
 def _same(a, b, what=""):
@@ -101,10 +67,10 @@ def _same(a, b, what=""):
 def _trace_both(eng, batch, K, layout):
     """(records with the hint, records with OT_OPT_UNIFORM = 0) of the same batch"""
     n = batch.n
-    hinted = _records(eng.trace(batch, K, layout=layout), n, K)
+    hinted = support.valid_records(eng.trace(batch, K, layout=layout), n, K)
     eng.set_option(abi.OPT_UNIFORM, 0)
     try:
-        plain = _records(eng.trace(batch, K, layout=layout), n, K)
+        plain = support.valid_records(eng.trace(batch, K, layout=layout), n, K)
     finally:
         eng.set_option(abi.OPT_UNIFORM, 1)
     return hinted, plain
@@ -136,7 +102,7 @@ def test_dead_rays_and_foreign_ids(name, precision):
     eng = _engine(name)
     K = SCENES[name][1]
     for n in (130, 129):
-        batch = _batch(*_rays(name, n, False, True), precision)
+        batch = support.batch(*_rays(name, n, False, True), precision)
         flags = batch.flags.cpu()
         flags[::3] |= abi.RAY_DEAD
         batch.flags.copy_(flags)
@@ -147,7 +113,7 @@ def test_dead_rays_and_foreign_ids(name, precision):
             assert torch.equal(hinted["count"][::3], torch.ones_like(hinted["count"][::3]))  # returned as they came: one record
         # ids that are not arange(n) are not flagged, and the records do not depend on them
         ids = (np.arange(n, dtype=np.int32) * 7) % n
-        other = _batch(*_rays(name, n, False, True), precision, ids=ids)
+        other = support.batch(*_rays(name, n, False, True), precision, ids=ids)
         assert other.uniform_mask == SCALARS | ORIGIN | BIT["flags"]
         hinted, plain = _trace_both(eng, other, K, "slots")
         _same(hinted, plain, ("ids", n))
@@ -158,7 +124,7 @@ def test_the_kernel_reads_a_flagged_field_once():
     counter, so the field stays flagged and every ray is traced with element 0 of it; `forget_uniform()` is the way out."""
     eng = _engine("cfg2")
     n = 130
-    batch = _batch(*_rays("cfg2", n, False, True), "f64")
+    batch = support.batch(*_rays("cfg2", n, False, True), "f64")
     batch.intensity.data[5] = 3.0
     assert batch.uniform_mask & BIT["intensity"]
     first = eng.trace(batch, 5).intensity[:n].clone()
@@ -174,7 +140,7 @@ def test_in_place_edits_are_followed(precision):
     """The CPU rules on device tensors, and the traced records after an edit."""
     eng = _engine("cfg2")
     n = 130
-    batch = _batch(*_rays("cfg2", n, False, True), precision)
+    batch = support.batch(*_rays("cfg2", n, False, True), precision)
     assert batch.uniform_mask == SCALARS | ORIGIN | IDF
     batch.intensity.mul_(0.5)  # a row of the staging block: every real field's entry goes with it
     assert batch.uniform_mask == IDF
@@ -183,7 +149,7 @@ def test_in_place_edits_are_followed(precision):
     for layout in ("slots", "tiled"):
         _same(*_trace_both(eng, batch, 5, layout), what=layout)
     # slices, clones and wavelength copies pass the hint on; gathers do not
-    batch = _batch(*_rays("cfg2", n, False, True), precision)
+    batch = support.batch(*_rays("cfg2", n, False, True), precision)
     full = batch.uniform_mask
     assert batch.slice(0, 64).uniform_mask == full and batch.slice(3, 64).uniform_mask == full & ~BIT["id"]
     assert batch.clone().uniform_mask == full
@@ -198,16 +164,16 @@ def test_in_place_edits_are_followed(precision):
 def test_one_wavelength_edit_changes_one_ray():
     eng = _engine("snell")
     n, K = 130, 3
-    batch = _batch(*_rays("snell", n, True, False), "f64")
+    batch = support.batch(*_rays("snell", n, True, False), "f64")
     assert batch.uniform_mask == SCALARS | DIRECTION | IDF
     before = eng.trace(batch, K)
     assert int(before.count.min()) == K  # every slot compared below is a written one
-    before = {f: _bits(before.field(f)[: K * n]).view(K, n).clone() for f in abi.SEG_FIELDS}
+    before = {f: support.bits(before.field(f)[: K * n]).view(K, n).clone() for f in abi.SEG_FIELDS}
     batch.wavelength[7] = 500e-7
     assert not batch.uniform_mask & BIT["wavelength"]
     after = eng.trace(batch, K)
     assert int(after.count.min()) == K
-    after = {f: _bits(after.field(f)[: K * n]).view(K, n).clone() for f in abi.SEG_FIELDS}
+    after = {f: support.bits(after.field(f)[: K * n]).view(K, n).clone() for f in abi.SEG_FIELDS}
     others = torch.arange(n, device="cuda") != 7
     for f in abi.SEG_FIELDS:
         assert torch.equal(before[f][:, others], after[f][:, others]), f
@@ -222,7 +188,7 @@ def test_stream_ceiling_honours_the_hint(precision, tiled):
     eng = _engine("cfg2")
     K = 5
     for n in (130, 129):
-        batch = _batch(*_rays("cfg2", n, False, True), precision)
+        batch = support.batch(*_rays("cfg2", n, False, True), precision)
         assert batch.uniform_mask == SCALARS | ORIGIN | IDF
         got = []
         for option in (1, 0):
@@ -233,7 +199,7 @@ def test_stream_ceiling_honours_the_hint(precision, tiled):
             finally:
                 eng.set_option(abi.OPT_UNIFORM, 1)
             out.n_rays = n
-            got.append(_records(out, n, K))
+            got.append(support.valid_records(out, n, K))
         _same(got[0], got[1], (n, tiled))
         assert int(got[0]["count"].min()) == K
 
@@ -248,12 +214,12 @@ def test_heavy_scene_ignores_the_hint():
     eng = get_engine()
     eng.upload(table.compile())
     n, K = 1030, 20
-    batch = _batch(*scenes.cfg3_rays(n, 2), "f32")
+    batch = support.batch(*scenes.cfg3_rays(n, 2), "f32")
     plain = batch.clone().forget_uniform()
     assert batch.uniform_mask == SCALARS | BIT["ox"] | IDF and plain.uniform_mask == 0
-    a = _records(eng.trace(batch, K), n, K)
+    a = support.valid_records(eng.trace(batch, K), n, K)
     assert eng.last_launch()["kernel"] != 1
-    b = _records(eng.trace(plain, K), n, K)
+    b = support.valid_records(eng.trace(plain, K), n, K)
     _same(a, b)
 
 
@@ -263,7 +229,7 @@ def test_mask_bits_outside_the_set_are_refused():
     from optable_amd.batch import SegmentBatch
 
     eng = _engine("cfg2")
-    batch = _batch(*_rays("cfg2", 130, False, True), "f64")
+    batch = support.batch(*_rays("cfg2", 130, False, True), "f64")
     out = SegmentBatch(130 * 5, "f64", "cuda")
     out.count = torch.empty(130, dtype=torch.int32, device="cuda")
     rs, ss = batch.c_struct(), out.c_struct()
@@ -283,10 +249,10 @@ def _only(field, n, precision):
         (o if field[0] == "o" else d)[:, "xyz".index(field[1])] = SCENES["snell"][2 if field[0] == "o" else 3]["xyz".index(field[1])]
     elif field in ("q_re", "q_im"):
         q = kw["q"]
-        kw["q"] = (Q.imag * 0 + 0.25) + 1j * q.imag if field == "q_re" else q.real + 1j * Q.imag
+        kw["q"] = (support.Q.imag * 0 + 0.25) + 1j * q.imag if field == "q_re" else q.real + 1j * support.Q.imag
     else:
         kw[_KW[field]] = {"wavelength": scenes.WL, "intensity": 0.75, "n": 1.0, "pathlength": 0.5}[field]
-    batch = _batch(o, d, precision, ids=np.arange(n, dtype=np.int32)[::-1].copy(), normalize=False, **kw)
+    batch = support.batch(o, d, precision, ids=np.arange(n, dtype=np.int32)[::-1].copy(), normalize=False, **kw)
     batch.flags.copy_(batch.flags.clone())
     return batch
 

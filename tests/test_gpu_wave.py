@@ -45,6 +45,7 @@ n qr D / (wavelength |q|^2) at its two end centres, times the mean bin width, ab
 without a footprint is not).  The reference counts them, and asserts that every hit is at least 1e-6 away from the threshold and
 that moving the 6 w limit by 1e-9 either way changes no hit's verdict."""
 import ctypes as C
+import functools
 import warnings
 
 import numpy as np
@@ -53,29 +54,19 @@ import torch
 
 import optable_amd as oa
 import scenes
+import support
 from optable_amd import abi
 from optable_amd.batch import RayBatch, SegmentBatch
 from optable_amd.engine import get_engine, segment_source, wave_plan
-from optable_amd.monitors import image_edges
 from optable_amd.table import monitor_struct
+from support import ctx  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-ERR_INVALID = -1
 U = 2.0**-53
 K, E_EXP, E_SC = 24, 2, 2
 CAP = 3e-8
 EMPTY, DROPS, SPREAD = 2, 6, 7
-
-
-def _host(t):
-    return t.double().cpu().numpy()
-
-
-def _wavelengths(wavelength, h):
-    if isinstance(wavelength, RayBatch):
-        return _host(wavelength.wavelength)[h.ray_index(None).cpu().numpy()]
-    return np.full(len(h), float(wavelength))
 
 
 class _Ref:
@@ -103,12 +94,12 @@ def _reference(h, wavelength, y_edges, z_edges, amplitude="sqrt", gouy=False, qu
     nby, nbz = len(y_edges) - 1, len(z_edges) - 1
     if len(h) == 0:
         return _Ref(np.zeros((nby, nbz), dtype=np.int64), np.zeros((nby, nbz), dtype=complex), np.zeros((nby, nbz)), 0.0, 0)
-    y, z, I, t, P = _host(h.yList(None)), _host(h.zList(None)), _host(h.IList(None)), _host(h.t), _host(h.P)
-    ty, tz, direction = _host(h.tYList(None)), _host(h.tZList(None)), _host(h.directionList(None))
-    lam = _wavelengths(wavelength, h)
-    qr = _host(h._gather(h.segs.q_re, h.slot)) + t
-    qi, n = _host(h._gather(h.segs.q_im, h.slot)), _host(h._gather(h.segs.n_index, h.slot))
-    L = _host(h._gather(h.segs.pathlength, h.slot)) + t * n
+    y, z, I, t, P = support.host(h.yList(None)), support.host(h.zList(None)), support.host(h.IList(None)), support.host(h.t), support.host(h.P)
+    ty, tz, direction = support.host(h.tYList(None)), support.host(h.tZList(None)), support.host(h.directionList(None))
+    lam = support.hit_wavelengths(wavelength, h)
+    qr = support.host(h._gather(h.segs.q_re, h.slot)) + t
+    qi, n = support.host(h._gather(h.segs.q_im, h.slot)), support.host(h._gather(h.segs.n_index, h.slot))
+    L = support.host(h._gather(h.segs.pathlength, h.slot)) + t * n
     q2 = qr * qr + qi * qi
     w2 = lam * q2 / (n * np.pi * qi)
     w = np.sqrt(w2)
@@ -173,10 +164,10 @@ def _footprints(h, wavelength, y_edges, z_edges):
     """How many hits reach a bin centre (within 6 w on both axes)."""
     if len(h) == 0:
         return 0
-    w = _host(h.spotsizeList(wavelength, None))
+    w = support.host(h.spotsizeList(wavelength, None))
     yc, zc = 0.5 * (y_edges[1:] + y_edges[:-1]), 0.5 * (z_edges[1:] + z_edges[:-1])
-    near_y = (np.abs(yc[None, :] - _host(h.yList(None))[:, None]) <= 6 * w[:, None]).any(axis=1)
-    near_z = (np.abs(zc[None, :] - _host(h.zList(None))[:, None]) <= 6 * w[:, None]).any(axis=1)
+    near_y = (np.abs(yc[None, :] - support.host(h.yList(None))[:, None]) <= 6 * w[:, None]).any(axis=1)
+    near_z = (np.abs(zc[None, :] - support.host(h.zList(None))[:, None]) <= 6 * w[:, None]).any(axis=1)
     return int((near_y & near_z).sum())
 
 
@@ -279,9 +270,9 @@ def hand():
     table, mon = oa.OpticalTable(), oa.Monitor([5, 0, 0], 6, 6)
     h = table.record_all(segs, monitors=[mon])[0]
     assert sorted(h.slot.tolist()) == list(range(64)) + [64, 70, 100, 127]
-    spot = _host(h.spotsizeList(WL_HAND, None))
-    assert spot.min() < 0.012 and spot.max() > 19 and (_host(h.qList(None).real) > 0).any() and (_host(h.qList(None).real) < 0).any()
-    assert np.abs(_host(h.tYList(None))).max() <= 0.2 and np.abs(_host(h.tYList(None))).max() > 0.15
+    spot = support.host(h.spotsizeList(WL_HAND, None))
+    assert spot.min() < 0.012 and spot.max() > 19 and (support.host(h.qList(None).real) > 0).any() and (support.host(h.qList(None).real) < 0).any()
+    assert np.abs(support.host(h.tYList(None))).max() <= 0.2 and np.abs(support.host(h.tYList(None))).max() > 0.15
     return table, mon, segs, h
 
 
@@ -299,10 +290,10 @@ def test_hand_built_footprints_from_one_bin_to_the_whole_image(hand, amplitude, 
     # the hit-list form of the same quantities
     q = h.qList(None)
     with np.errstate(divide="ignore"):  # (inf at a waist, on both sides)
-        np.testing.assert_allclose(_host(h.radiusList(None)), _host(q.real**2 + q.imag**2) / _host(q.real), rtol=1e-15)
-    np.testing.assert_allclose(_host(h.gouyList(None)), np.arctan2(_host(q.real), _host(q.imag)), rtol=1e-15)
-    a = _host(h.IList(None)) if amplitude == "linear" else np.sqrt(_host(h.IList(None)))
-    np.testing.assert_allclose(_host(h.amplitudeList(WL_HAND, None, amplitude)), a * np.sqrt(2 / np.pi) / _host(h.spotsizeList(WL_HAND, None)), rtol=1e-14)
+        np.testing.assert_allclose(support.host(h.radiusList(None)), support.host(q.real**2 + q.imag**2) / support.host(q.real), rtol=1e-15)
+    np.testing.assert_allclose(support.host(h.gouyList(None)), np.arctan2(support.host(q.real), support.host(q.imag)), rtol=1e-15)
+    a = support.host(h.IList(None)) if amplitude == "linear" else np.sqrt(support.host(h.IList(None)))
+    np.testing.assert_allclose(support.host(h.amplitudeList(WL_HAND, None, amplitude)), a * np.sqrt(2 / np.pi) / support.host(h.spotsizeList(WL_HAND, None)), rtol=1e-14)
     if gouy:  # the Gouy phase is not nothing here
         plain = _wave_all(table, segs, WL_HAND, bins=(7, 5), monitors=[mon], amplitude=amplitude)[0]
         assert float((plain.field - f.field).abs().max()) > 1e-3 * float(f.field.abs().max())
@@ -391,37 +382,16 @@ def test_closed_form_two_beam_fringes():
 
 
 # -- 4: cfg 2 ---------------------------------------------------------------------------------------------------------------
-def _batch(o, d, seed=7):
-    """cfg 2's rays with per-ray intensities 0.25 + 0.75 u and per-ray waists w0 log-uniform in [0.005, 2] (tests/test_gpu_beam.py)."""
-    rng = np.random.default_rng(seed)
-    intensity = 0.25 + 0.75 * rng.random(len(o))
-    w0 = np.exp(rng.uniform(np.log(0.005), np.log(2.0), len(o)))
-    return RayBatch.from_arrays(o, d, wavelength=scenes.WL, intensity=intensity, q=1j * np.pi * w0**2 / scenes.WL, precision="f64", device="cuda")
-
-
-def _cfg2_table():
-    t = oa.OpticalTable()
-    t.add_components(scenes.cfg2_components(oa))
-    return t
-
-
-def _eight_monitors():
-    """The eight of tests/test_gpu_image.py."""
-    return [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([6.5, 0, 0], 6, 6), oa.Monitor([7.5, 40, 0], 6, 6), oa.Monitor([8.5, 0, 0], 6, 6),
-            oa.Monitor([7.5, 0, 0], 6, 6).RotZ(0.3), oa.Monitor([7.5, 0, 0], 0.5, 0.5), oa.Monitor([7.5, 0, 0], 0.4, 6).RotX(0.5),
-            oa.Monitor([7.5, 0, 0], 2, 2)]
-
-
 @pytest.fixture(scope="module")
 def case4():
     """cfg 2, 5,003 rays, 5 segments, eight monitors: (table, monitors, {layout: (batch, segs, record_all hits)}), traced and
     recorded on first use."""
-    table, mons, made = _cfg2_table(), _eight_monitors(), {}
+    table, mons, made = support.cfg2_table(), support.eight_monitors(), {}
     o, d = scenes.cfg2_rays(5003, 0)
 
     def get(layout):
         if layout not in made:
-            batch = _batch(o, d)
+            batch = support.waisted_batch(o, d)
             segs = table.trace_batch(batch, max_segments=5, layout=layout)
             assert segs.layout == layout and segs.precision == "f64"
             made[layout] = (batch, segs, table.record_all(segs, monitors=mons))
@@ -469,10 +439,10 @@ def test_layouts(case4, layout, monkeypatch):
 def test_global_path_and_accumulation():
     """(80, 80): 6,400 bins, more than the LDS budget — every deposit two global atomics.  And `into=` over the two chunks of a
     batch against the whole batch in one call and against the summed references, on either path; `aliased` accumulates."""
-    table = _cfg2_table()
+    table = support.cfg2_table()
     mon = oa.Monitor([7.5, 0, 0], 2, 2)
     assert wave_plan(1, 80, 80)["path"] == "global" and wave_plan(1, 30, 30)["path"] == "lds"
-    whole = _batch(*scenes.cfg2_rays(2049, 3))
+    whole = support.waisted_batch(*scenes.cfg2_rays(2049, 3))
     segs = table.trace_batch(whole, max_segments=5, layout="slots")
     h = table.record_all(segs, monitors=[mon])[0]
     assert len(h) >= 2049
@@ -554,31 +524,18 @@ def test_one_tree_is_an_interferometer():
 
 
 # -- 7, 8: hits left out, refusals --------------------------------------------------------------------------------------------
-def _tables(mons, nby, nbz):
-    axes = np.array([np.concatenate([m.tangent_Y, m.tangent_Z]) for m in mons], dtype=float)
-    edges = np.array([np.concatenate(image_edges(m, nby, nbz)) for m in mons], dtype=float)
-    return axes, edges
-
-
-class _Out:
+class _Out(support.Sentinel):
     """counts / re / im of M monitors of nby x nbz bins, `skipped` and `aliased` for ot_monitor_wave_many, filled with a sentinel."""
 
-    def __init__(self, M, nby, nbz, fill=-7):
-        self.fill = fill
-        self.counts = torch.full((M, nby, nbz), fill, dtype=torch.int64, device="cuda")
-        self.re = torch.full((M, nby, nbz), float(fill), dtype=torch.float64, device="cuda")
-        self.im = torch.full((M, nby, nbz), float(fill), dtype=torch.float64, device="cuda")
-        self.skipped = torch.full((1,), fill, dtype=torch.int64, device="cuda")
-        self.aliased = torch.full((1,), fill, dtype=torch.int64, device="cuda")
-
-    def untouched(self):
-        return all(bool((t == self.fill).all()) for t in (self.counts, self.re, self.im, self.skipped, self.aliased))
+    def __init__(self, M, nby, nbz):
+        image, one = (torch.float64, (M, nby, nbz)), (torch.int64, (1,))
+        super().__init__(counts=(torch.int64, (M, nby, nbz)), re=image, im=image, skipped=one, aliased=one)
 
 
 def _call(lib, ctx, mons, segs, nby, nbz, out, wavelength=None, n_wavelengths=0, uniform=0.0, mode=0, gouy=0, accumulate=0, source=None, **planes):
     src, n, count, n_rays = segment_source(segs)
     table = (abi.OtMonitor * len(mons))(*[monitor_struct(m) for m in mons])
-    axes, edges = _tables(mons, nby, nbz)
+    axes, edges = support.image_tables(mons, nby, nbz)
     dp = C.POINTER(C.c_double)
     plane = {f: planes.get(f, segs.field(f).data_ptr()) for f in ("intensity", "n", "pathlength", "q_re", "q_im")}
     return lib.ot_monitor_wave_many(ctx, table, len(mons), axes.ctypes.data_as(dp), edges.ctypes.data_as(dp), nby, nbz,
@@ -620,15 +577,6 @@ def test_a_batch_without_q_is_refused(case4):
     assert 0 < known < len(hits[0]) and int(out.skipped.item()) == len(hits[0]) - known and int(out.counts.sum()) == known
 
 
-@pytest.fixture()
-def ctx():
-    lib = abi.load()
-    c = C.c_void_p()
-    assert lib.ot_ctx_create(0, None, C.byref(c)) == 0
-    yield lib, c
-    assert lib.ot_ctx_destroy(c) == 0
-
-
 def test_abi_errors(ctx):
     lib, c = ctx
     y = np.linspace(-2.5, 2.5, 130) + 0.0123
@@ -641,17 +589,7 @@ def test_abi_errors(ctx):
         kw.setdefault("uniform", WL_HAND)
         return _call(lib, c, [mon], segs, 7, 5, out, **kw)
 
-    def expect(status, needle):
-        msg = lib.ot_last_error().decode()
-        assert status == ERR_INVALID and needle in msg, (status, msg, needle)
-
-    src = segment_source(segs)[0]
-
-    def altered(**fields):
-        other = abi.OtSegmentSource.from_buffer_copy(src)
-        for k, v in fields.items():
-            setattr(other, k, v)
-        return other
+    expect, altered = functools.partial(support.expect_invalid, lib), functools.partial(support.altered, segment_source(segs)[0])
 
     expect(call(source=altered(width=2)), "width")
     expect(call(source=altered(width=4)), "double-precision")  # single precision is refused, as for fields

@@ -10,6 +10,7 @@ outside the pupil) must then be EQUAL, and every sum within `bound` of the refer
 of P, t, L, the dot products, the powers and the summation order — derived, not measured.  Coefficients and rms are held to what
 those bounds allow to first order through the solve (coefficient_bound, rms_interval)."""
 import ctypes as C
+import functools
 import math
 import os
 import subprocess
@@ -21,6 +22,7 @@ import torch
 
 import optable_amd as oa
 import scenes
+import support
 import wavefront_cases as cases
 from optable_amd import abi
 from optable_amd import workloads as W
@@ -28,24 +30,21 @@ from optable_amd.batch import RayBatch, SegmentBatch
 from optable_amd.engine import get_engine, segment_source, wavefront_plan
 from optable_amd.table import monitor_struct
 from optable_amd.wavefront import zernike
+from support import ctx  # noqa: F401  (the fixture)
 from wavefront_reference import U, coefficient_bound, gram, rms_interval
 
 pytestmark = pytest.mark.gpu
 
-ERR_INVALID = -1
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _batch(o, d, intensity, precision="f64"):
-    return RayBatch.from_arrays(o, d, wavelength=scenes.WL, intensity=intensity, q=1j * np.pi * scenes.W0**2 / scenes.WL, precision=precision, device="cuda")
+    return RayBatch.from_arrays(o, d, wavelength=scenes.WL, intensity=intensity, q=support.Q, precision=precision, device="cuda")
 
 
 def _records(segs):
     """The valid segment records of a batch, copied from the device: (o, d, length, intensity, n, pathlength) as doubles."""
-    h = segs.to_host(reference_order=False)
-    col = lambda f: np.asarray(h[f], dtype=np.float64)  # noqa: E731
-    return (np.stack([col("ox"), col("oy"), col("oz")], 1), np.stack([col("dx"), col("dy"), col("dz")], 1), col("length"), col("intensity"), col("n"),
-            col("pathlength"))
+    return support.host_records(segs, "n", "pathlength")
 
 
 def _assert_wavefront(wf, ref, terms=(1, 3, 4, 15)):
@@ -80,17 +79,9 @@ def _assert_wavefront(wf, ref, terms=(1, 3, 4, 15)):
 def case1():
     """cfg 2, 5,003 rays, 5 segments — 25,015 slots: 13 workgroups of 2,048 with a ragged tail — traced once per layout:
     (table, get(layout) -> (segs, records))."""
-    table, made = cases.cfg2_table(), {}
+    table = support.cfg2_table()
     o, d, intensity = cases.cfg2_arrays(5003, 0)
-
-    def get(layout):
-        if layout not in made:
-            segs = table.trace_batch(_batch(o, d, intensity), max_segments=5, layout=layout)
-            assert segs.layout == layout and segs.precision == "f64"
-            made[layout] = (segs, _records(segs))
-        return made[layout]
-
-    return table, get
+    return table, support.traced(table, lambda precision: _batch(o, d, intensity, precision), 5, _records)
 
 
 @pytest.mark.parametrize("setup", ["focus", "direction"])
@@ -131,7 +122,7 @@ def test_layouts(case1, layout, setup, monkeypatch):
 @pytest.mark.parametrize("n,K", [(1, 1), (130, 3), (1027, 5)])
 def test_batch_sizes(n, K):
     """1 x 1; 130 x 3 = 390 slots: a partial wave in a partial workgroup; 1,027 x 5 = 5,135: three workgroups, the last one ragged."""
-    table = cases.cfg2_table()
+    table = support.cfg2_table()
     segs = table.trace_batch(_batch(*cases.cfg2_arrays(n, 3)), max_segments=K, layout="slots")
     records = _records(segs)
     for su in cases.SETUPS.values():
@@ -167,7 +158,7 @@ def test_lists_and_trees():
 def test_more_monitors_than_one_group():
     """30 monitors: two launches, 28 + 2."""
     assert wavefront_plan(cases.GROUP_MONITORS) == [(0, 28), (28, 2)]
-    table = cases.cfg2_table()
+    table = support.cfg2_table()
     mons, pupils = cases.group_monitors()
     segs = table.trace_batch(_batch(*cases.cfg2_arrays(1003, 5)), max_segments=5, layout="slots")
     records = _records(segs)
@@ -184,7 +175,7 @@ def test_more_monitors_than_one_group_streamed():
     """The 30 monitors and 1,003 rays above as two chunks of 512 and 491 rays, the second added with `into=`: every launch of the
     second call draws its own ticket, shares the call's partials and adds to what the first call left, with the first call's pistons."""
     assert wavefront_plan(cases.GROUP_MONITORS) == [(0, 28), (28, 2)]
-    table = cases.cfg2_table()
+    table = support.cfg2_table()
     mons, pupils = cases.group_monitors()
     o, d, intensity = cases.cfg2_arrays(1003, 5)
     chunks = [table.trace_batch(_batch(o[part], d[part], intensity[part]), max_segments=5, layout="slots") for part in (slice(0, 512), slice(512, 1003))]
@@ -379,7 +370,7 @@ def test_piston_none_against_an_explicit_piston(case1):
 
 
 def test_single_precision_is_refused():
-    table = cases.cfg2_table()
+    table = support.cfg2_table()
     o, d, intensity = cases.cfg2_arrays(130, 3)
     segs = table.trace_batch(_batch(o, d, intensity, precision="f32"), max_segments=3)
     assert segs.precision == "f32"
@@ -391,7 +382,7 @@ def test_single_precision_is_refused():
 
 
 def test_no_segments():
-    table, eng = cases.cfg2_table(), get_engine()
+    table, eng = support.cfg2_table(), get_engine()
     eng.upload(table.compile())
     none = eng.trace_tree(RayBatch(0, "f64", "cuda"), 5)
     assert none.layout == "list" and none.n_valid == 0
@@ -401,31 +392,11 @@ def test_no_segments():
 
 
 # -- the C ABI -------------------------------------------------------------------------------------------------------------------------
-class _Out:
+class _Out(support.Sentinel):
     """counts / sums of M monitors for ot_monitor_wavefront_many, with a guard region on either side of each."""
-    GUARD = 64
 
-    def __init__(self, M, fill=-7):
-        self.fill, G = fill, self.GUARD
-        self.c = torch.full((2 * M + 2 * G,), fill, dtype=torch.int64, device="cuda")
-        self.s = torch.full((61 * M + 2 * G,), float(fill), dtype=torch.float64, device="cuda")
-        self.counts, self.sums = self.c[G:G + 2 * M].view(M, 2), self.s[G:G + 61 * M].view(M, 61)
-
-    def guards_untouched(self):
-        G = self.GUARD
-        return all(bool((t[:G] == self.fill).all()) and bool((t[-G:] == self.fill).all()) for t in (self.c, self.s))
-
-    def untouched(self):
-        return bool((self.c == self.fill).all()) and bool((self.s == self.fill).all())
-
-
-@pytest.fixture()
-def ctx():
-    lib = abi.load()
-    c = C.c_void_p()
-    assert lib.ot_ctx_create(0, None, C.byref(c)) == 0
-    yield lib, c
-    assert lib.ot_ctx_destroy(c) == 0
+    def __init__(self, M):
+        super().__init__(guard=64, counts=(torch.int64, (M, 2)), sums=(torch.float64, (M, 61)))
 
 
 def test_abi_errors(ctx):
@@ -455,15 +426,7 @@ def test_abi_errors(ctx):
         return lib.ot_monitor_wavefront_many(ctx_, mons, M, ptr(axes), kind, ptr(ref), coords, ptr(pupil), ptr(piston), None if source is None else C.byref(source),
                                              intensity, n_index, pathlength, n_seg, cnt, rays, counts, sums, acc)
 
-    def expect(status, needle):
-        msg = lib.ot_last_error().decode()
-        assert status == ERR_INVALID and needle in msg, (status, msg, needle)
-
-    def altered(**fields):
-        other = abi.OtSegmentSource.from_buffer_copy(src)
-        for k, v in fields.items():
-            setattr(other, k, v)
-        return other
+    expect, altered = functools.partial(support.expect_invalid, lib), functools.partial(support.altered, src)
 
     def with_value(good, at, value):
         a = good.copy()

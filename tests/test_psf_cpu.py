@@ -12,9 +12,9 @@ import pytest
 import torch
 
 import optable_amd as oa
+import support
 from optable_amd import abi, engine
 from optable_amd import psf as psfm
-from optable_amd.batch import SegmentBatch
 from psf_reference import airy, disc_grid, plane_wave_sum, psf_reference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -81,12 +81,6 @@ def test_planner_and_its_constants():
             engine.psf_plan(ny, nz)
 
 
-def _host_segments(n_rays=4, k=2, precision="f64"):
-    segs = SegmentBatch(n_rays * k, precision, "cpu")
-    segs.count, segs.n_rays = torch.full((n_rays,), k, dtype=torch.int32), n_rays
-    return segs
-
-
 class _Recorder:
     """Stands in for the engine: keeps what psf_all hands over."""
     aliased = 0
@@ -111,7 +105,7 @@ def test_refused_before_the_engine_is_asked(monkeypatch):
         raise AssertionError("the engine was asked for")
 
     monkeypatch.setattr(table_module, "_engine", refuse)
-    table, segs = oa.OpticalTable(), _host_segments()
+    table, segs = oa.OpticalTable(), support.host_segments()
     mons = [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([8.5, 0, 0], 6, 6)]
     table.add_monitors(mons)
     good = dict(direction=(1, 0, 0), step=1e-5)
@@ -139,7 +133,7 @@ def test_refused_before_the_engine_is_asked(monkeypatch):
         with pytest.raises(ValueError, match="wavelength"):
             table.psf_all(segs, wavelength, **good)
     with pytest.raises(ValueError, match="double-precision"):
-        table.psf_all(_host_segments(precision="f32"), WL, **good)
+        table.psf_all(support.host_segments(precision="f32"), WL, **good)
     with pytest.raises(AssertionError, match="the engine was asked for"):
         table.psf_all(segs, WL, **good)
     # `into`: the list of ONE earlier call for the same monitors, reference, grid and amplitude
@@ -163,7 +157,7 @@ def test_what_is_handed_over_and_what_comes_back(monkeypatch):
 
     rec = _Recorder()
     monkeypatch.setattr(table_module, "_engine", lambda: rec)
-    table, segs = oa.OpticalTable(), _host_segments()
+    table, segs = oa.OpticalTable(), support.host_segments()
     mons = [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([8.5, 0, 0], 6, 6).RotZ(0.3)]
     table.add_monitors(mons)
     with warnings.catch_warnings():

@@ -1,5 +1,6 @@
 """CPU: the resident-plane token of a SegmentBatch (batch.py), on host tensors — what sets it, what every entry of it is compared
 with, and what ends it.  No engine and no device: `engine` and `stream` are whatever objects the caller compares by."""
+import functools
 import re
 import os
 
@@ -7,8 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+import support
 from optable_amd import abi
-from optable_amd.batch import RayBatch, SegmentBatch
+from optable_amd.batch import RayBatch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RAY, N, I, ALL = abi.RESIDENT_RAY, abi.RESIDENT_N, abi.RESIDENT_INTENSITY, abi.RESIDENT_ALL
@@ -16,13 +18,7 @@ ONE64 = int(np.float64(1.0).view(np.int64))
 ONE32 = int(np.float32(1.0).view(np.int32))
 ENGINE, STREAM = object(), 1234
 n, K = 130, 5
-
-
-def _out(precision="f64", tiled=False):
-    out = SegmentBatch(n * K, precision, "cpu", tiled=tiled)
-    out.count = torch.full((n,), K, dtype=torch.int32)
-    out.n_rays = n
-    return out
+_out = functools.partial(support.host_out, n, K)
 
 
 def _values(one=ONE64):

@@ -10,8 +10,8 @@ import pytest
 import torch
 
 import optable_amd as oa
+import support
 from optable_amd import abi
-from optable_amd.batch import SegmentBatch
 from optable_amd.engine import Engine
 from spots_reference import U, radius_interval, spots_reference
 
@@ -68,12 +68,6 @@ def test_planner_and_its_constant():
             engine.spots_plan(m, j)
 
 
-def _host_segments(n_rays=4, k=2):
-    segs = SegmentBatch(n_rays * k, "f64", "cpu")
-    segs.count, segs.n_rays = torch.full((n_rays,), k, dtype=torch.int32), n_rays
-    return segs
-
-
 class _Recorder:
     """Stands in for the engine: keeps what spots_all hands over."""
 
@@ -92,7 +86,7 @@ def test_refused_before_the_engine_is_asked(monkeypatch):
         raise AssertionError("the engine was asked for")
 
     monkeypatch.setattr(table_module, "_engine", refuse)
-    table, segs = oa.OpticalTable(), _host_segments()
+    table, segs = oa.OpticalTable(), support.host_segments()
     mons = [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([8.5, 0, 0], 6, 6)]
     table.add_monitors(mons)
     for weight in ("power", None, 0, "Intensity"):
@@ -126,7 +120,7 @@ def test_what_is_handed_over_and_what_comes_back(monkeypatch):
 
     rec = _Recorder()
     monkeypatch.setattr(table_module, "_engine", lambda: rec)
-    table, segs = oa.OpticalTable(), _host_segments()
+    table, segs = oa.OpticalTable(), support.host_segments()
     mons = [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([8.5, 0, 0], 6, 6).RotZ(0.3)]
     table.add_monitors(mons)
     spots = table.spots_all(segs)

@@ -5,8 +5,6 @@ oracle reproduces what the reference recorded for every form (tests/golden/g30-g
 package's constructors build the reference's geometry, the reference's own objects compile to the same device tables where
 they can be imported, and each form's batch ray fan is a fair test: it meets the form, does not sit on edges and, through a
 strongly curved cap, does not amplify a last-digit difference beyond what the reference's own roots define."""
-import contextlib
-
 import numpy as np
 import pytest
 
@@ -18,15 +16,6 @@ from optable_amd.batch import RayBatch
 from test_adapter_reference import live_ref  # noqa: F401  (the fixture: the reference package where it can be imported)
 
 Q = 1j * np.pi * FS.W0**2 / FS.WL
-
-
-@contextlib.contextmanager
-def named(form):
-    """Every failure names the form."""
-    try:
-        yield
-    except AssertionError as exc:
-        raise AssertionError(f"surface form {form!r}: {exc}") from exc
 
 
 @pytest.fixture(scope="module")
@@ -137,7 +126,7 @@ def test_form_geometry_matches_reference(name, gold):
     g = FS.sub_fixture(gold[FS.FAMILY[name]], name)
     nodes = table.compile().node_table()
     leaves, groups = nodes[nodes["kind"] == abi.NODE_LEAF], nodes[nodes["kind"] == abi.NODE_GROUP]
-    with named(name):
+    with FS.named(name):
         assert len(leaves) == len(g["leaf_origin"])
         np.testing.assert_allclose(leaves["origin"], g["leaf_origin"], rtol=0, atol=1e-12)
         np.testing.assert_allclose(leaves["M"].reshape(-1, 3, 3), g["leaf_M"], rtol=0, atol=1e-12)
@@ -152,7 +141,7 @@ def test_oracle_reproduces_form_fixture(name, gold, oracle):
     g = FS.sub_fixture(gold[FS.FAMILY[name]], name)
     host, n_classes = helpers.pack_host(sc["rays"])
     assert len(sc["rays"]) <= 40 and 0 < int(g["limit"][0]) <= 12
-    with named(name):
+    with FS.named(name):
         np.testing.assert_allclose(np.stack([host["ox"], host["oy"], host["oz"]], 1), g["in_origin"], atol=1e-15)
         np.testing.assert_allclose(np.stack([host["dx"], host["dy"], host["dz"]], 1), g["in_direction"], atol=1e-15)
         got = oracle.trace(table.compile(), host, max_trace_num=int(g["limit"][0]), n_classes=n_classes)
@@ -171,7 +160,7 @@ def test_reference_objects_of_a_form_compile_to_the_same_tables(name, live_ref):
     if live_ref is None:
         pytest.skip("needs the reference package's own classes, which are not part of the repository")
     mine = helpers.scene_tables(oa.compile_scene(FS.components(oa, name)))
-    with named(name):
+    with FS.named(name):
         helpers.assert_same_tables(helpers.scene_tables(oa.compile_scene(FS.components(live_ref, name))), mine)
 
 
@@ -203,7 +192,7 @@ def test_form_fan_meets_the_form_and_survives_float32_rounding(name, oracle):
     assert form, name
     meets = np.mean([bool(form.intersection(s)) for s in a])
     print(f"{name}: {changed} of {n} rays change their sequence under float32 rounding, {meets:.1%} meet the form")
-    with named(name):
+    with FS.named(name):
         assert changed <= 0.0005 * n, f"{changed} of {n} rays change their surface sequence"
         if name in FS.NEVER_HIT:
             assert meets == 0.0, f"{meets:.1%} of the rays meet a form that no ray can meet"

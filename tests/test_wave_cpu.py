@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import optable_amd as oa
+import support
 from optable_amd import abi
 from optable_amd.batch import RayBatch, SegmentBatch
 from optable_amd.engine import Engine
@@ -96,18 +97,6 @@ def test_budget_and_pass_planner():
             plan(n, nby, nbz)
 
 
-def _host_segments(n_rays=4, k=2, precision="f64"):
-    segs = SegmentBatch(n_rays * k, precision, "cpu")
-    segs.count, segs.n_rays = torch.full((n_rays,), k, dtype=torch.int32), n_rays
-    return segs
-
-
-def _host_rays(n):
-    o = np.zeros((n, 3))
-    d = np.tile([1.0, 0.0, 0.0], (n, 1))
-    return RayBatch.from_arrays(o, d, wavelength=780e-7, q=1.5j, device="cpu")
-
-
 def test_refused_before_the_engine_is_asked(monkeypatch):
     from optable_amd import table as table_module
 
@@ -117,7 +106,7 @@ def test_refused_before_the_engine_is_asked(monkeypatch):
     monkeypatch.setattr(table_module, "_engine", refuse)
     table = oa.OpticalTable()
     mon = oa.Monitor([1, 0, 0], 2, 2)
-    good, rays = _host_segments(), _host_rays(4)
+    good, rays = support.host_segments(), support.host_rays(4, q=1.5j)
     with pytest.raises(ValueError, match=r"wavelength=0\.0: a beam field needs"):
         table.wave_all(good, monitors=[mon])  # the default
     for bad in (0.0, -780e-7, float("nan"), float("inf"), "red", None):
@@ -126,9 +115,9 @@ def test_refused_before_the_engine_is_asked(monkeypatch):
         with pytest.raises(ValueError, match="wavelength"):
             table.wave_batch(mon, good, bad)
     with pytest.raises(ValueError, match="RayBatch of 5 rays"):
-        table.wave_all(good, _host_rays(5), monitors=[mon])
+        table.wave_all(good, support.host_rays(5, q=1.5j), monitors=[mon])
     for value in (0.0, -1.0, float("nan"), float("inf")):
-        dark = _host_rays(4)
+        dark = support.host_rays(4, q=1.5j)
         dark.wavelength[2] = value
         with pytest.raises(ValueError, match="finite wavelength > 0"):
             table.wave_all(good, dark, monitors=[mon])
@@ -149,7 +138,7 @@ def test_refused_before_the_engine_is_asked(monkeypatch):
             table.wave_batch(mon, good, rays, gouy=gouy)
     # single precision is refused with field_all's reasoning, not approximated
     with pytest.raises(ValueError, match="double-precision SegmentBatch.*refused, not approximated"):
-        table.wave_all(_host_segments(precision="f32"), rays, monitors=[mon])
+        table.wave_all(support.host_segments(precision="f32"), rays, monitors=[mon])
     # ... and what is good gets that far
     for kwargs in ({}, {"gouy": True}, {"amplitude": "linear", "gouy": False}):
         with pytest.raises(AssertionError, match="the engine was asked for"):
@@ -184,7 +173,7 @@ def test_what_is_handed_over_and_what_comes_back(monkeypatch):
     monkeypatch.setattr(table_module, "_engine", lambda: rec)
     table = oa.OpticalTable()
     mons = [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([1, 2, 3], 0.3, 1.7).RotZ(0.3)]
-    segs, rays = _host_segments(), _host_rays(4)
+    segs, rays = support.host_segments(), support.host_rays(4, q=1.5j)
     with warnings.catch_warnings():
         warnings.simplefilter("error")  # no aliased hit, no warning
         waves = table.wave_all(segs, 780e-7, bins=(7, 5), monitors=mons)
@@ -276,7 +265,7 @@ def test_into_takes_the_list_of_its_own_mode_only(monkeypatch):
     monkeypatch.setattr(table_module, "_engine", lambda: rec)
     table = oa.OpticalTable()
     mons = [oa.Monitor([7.5, 0, 0], 6, 6), oa.Monitor([1, 2, 3], 0.3, 1.7).RotZ(0.3)]
-    segs = _host_segments()
+    segs = support.host_segments()
     calls = {"image": lambda **kw: table.image_all(segs, bins=(7, 5), monitors=mons, **kw),
              "field": lambda **kw: table.field_all(segs, 780e-7, bins=(7, 5), monitors=mons, **kw),
              "beam": lambda **kw: table.beam_all(segs, 780e-7, bins=(7, 5), monitors=mons, **kw),

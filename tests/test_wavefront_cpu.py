@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import optable_amd as oa
+import support
 import wavefront_cases as cases
 from optable_amd import abi, engine, table as table_module
 from optable_amd import wavefront as wfm
@@ -235,7 +236,7 @@ def test_reference_a_cone_through_a_point_has_a_constant_path():
 def test_the_seeded_gpu_cases_keep_their_margin():
     """The cfg 2 cases of tests/test_gpu_wavefront.py, traced by the C oracle: every decision of the reference is 1e-7 from its
     boundary (cases.reference asserts it), the clipping pupils clip and the empty monitor stays empty."""
-    table = cases.cfg2_table()
+    table = support.cfg2_table()
     for n, seed, K in cases.CFG2_BATCHES:
         records = cases.oracle_records(table, *cases.cfg2_arrays(n, seed), K)
         for name, su in cases.SETUPS.items():

@@ -12,12 +12,6 @@ from wavefront_reference import wavefront_reference
 MARGIN = 1e-7
 
 
-def cfg2_table():
-    t = oa.OpticalTable()
-    t.add_components(scenes.cfg2_components(oa))
-    return t
-
-
 def cfg2_arrays(n, seed):
     """cfg 2's rays with per-ray intensities 0.25 + 0.75 u: (o, d, intensity)."""
     o, d = scenes.cfg2_rays(n, seed)
