@@ -730,6 +730,31 @@ int ot_monitor_spots_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitor
                           int64_t n_segments, const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* sums,
                           int32_t accumulate);
 
+/* Spot statistics per ray group: ot_monitor_spots_many with a GROUP axis on the cells — the moments of every wavelength, field
+ * point or port of one batch from one pass over the segments (chromatic focal shift, field curvature, the power of every port).
+ * A CELL is a triple (monitor m, plane j, group g).  mons, axes, centre, offsets, src, intensity, n_segments, seg_count, n_rays
+ * and accumulate are ot_monitor_spots_many's, and so are the hit test, the coordinates y, z and the weight of a hit: a hit of
+ * slot s is exactly that call's hit.  It belongs to group groups[ray[s]], where ray[s] is the int32 `ray` of the slot (src->ray:
+ * the index of the input ray the segment descends from, in every layout and for every node of a ray tree) and `groups` is a
+ * DEVICE table of n_group_ids int32 ids, one per input ray.
+ * A hit belongs to NO cell — it is counted nowhere and no tally of such hits is kept — when its ray index is outside
+ * 0 .. n_group_ids - 1 (nothing is read out of range) or its id is outside 0 .. n_groups - 1.  That is how rays are masked: id -1.
+ * counts: device, [n_monitors][n_offsets][n_groups] int64.  sums: device, [n_monitors][n_offsets][n_groups][6] double, W, Wy, Wz,
+ * Wyy, Wzz, Wyz as for ot_monitor_spots_many.  All arithmetic is double, whatever the segments' precision.  accumulate as there.
+ * Determinism: as ot_monitor_spots_many — counts exact, sums bit-identical from run to run, no floating-point atomic.  Per pair
+ * (m, j) a wave walks the distinct groups among its hitting lanes, in ascending order of each group's first lane, and sums each
+ * over its lanes by a butterfly in which the other lanes carry 0; rows, workgroups and the last workgroup as there.  With
+ * n_groups = 1 and every id 0 the result is ot_monitor_spots_many's, bit for bit.
+ * Cell groups: the list is [m][j][g] and a launch takes whole pairs (m, j): (256 / n_groups) * n_groups cells, every launch one
+ * pass over the segments.
+ * OT_ERR_INVALID, nothing launched or zeroed: everything ot_monitor_spots_many refuses; groups NULL; n_groups outside
+ * 1 .. OT_SPOT_GROUPS_MAX; n_group_ids < 1 (or >= 2^31); n_monitors * n_offsets * n_groups > 2^20. */
+#define OT_SPOT_GROUPS_MAX 256
+int ot_monitor_spot_groups_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* centre,
+                                const double* offsets, int32_t n_offsets, const int32_t* groups, int64_t n_group_ids,
+                                int32_t n_groups, const ot_segment_source* src, const void* intensity, int64_t n_segments,
+                                const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* sums, int32_t accumulate);
+
 /* Wavefront error: the hits of every monitor reduced to the moments of their optical path difference over a unit pupil, from one
  * pass over the segments with no hit list — what a least-squares fit of Zernike (or any other) polynomials up to radial order 4
  * and the rms wavefront error need.  One cell per monitor; mons, axes, src, n_segments, seg_count, n_rays and accumulate as for

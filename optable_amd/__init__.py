@@ -20,7 +20,7 @@ from .assemblies import (ComponentGroup, GlassSlab, CircleGlassSlab, MLA, MMA, M
                          ASphericParametricLens)
 from .monitors import Monitor
 from .fluence import FluenceMap
-from .spots import MonitorSpots
+from .spots import MonitorSpots, MonitorSpotGroups
 from .wavefront import MonitorWavefront
 from .psf import MonitorPSF
 from .table import OpticalTable

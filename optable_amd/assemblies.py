@@ -14,6 +14,7 @@ from .geometry import pivot_origin
 from .components import (OpticalComponent, BaseRefraciveSurface, SquareMirror, SquareRefractive,
                          CircleRefractive, SphereRefractive, Lens)
 from .shapes import Polygon, ASphere, sag_parametric, sag_exact
+from .materials import Material
 from .slab import solve_normal_to_normal_rotation
 
 _Z = [0, 0, 1]
@@ -390,7 +391,7 @@ class BiConvexLens(ComponentGroup):
             for _ in range(3):  # thick-lens refinement of the lensmaker estimate
                 n = 1 + (1 / EFL) / (1 / R1 - 1 / R2 + (n - 1) * CT / (n * R1 * R2))
         else:
-            assert isinstance(n, (int, float)), "n must be a number"
+            assert isinstance(n, (int, float, Material)), "n must be a number or a Material"  # (a glass: the faces take it as the Doublet's do)
         self.add_component(_spherical_face(0, R1, diameter, 1.0, n, self.origin, kwargs))
         self.add_component(_spherical_face(CT, R2, diameter, n, 1.0, self.origin, kwargs))
 

@@ -249,6 +249,13 @@ class RayBatch:
         out._inherit_uniform(self, tuple(f for f in abi.RAY_FIELDS if f != "wavelength") + ("flags",) + (("id",) if W == 1 else ()))
         return out
 
+    def groups_by_wavelength(self):
+        """(ids, wavelengths): the batch's distinct wavelengths in ascending order (a tensor in the batch's precision) and, per ray,
+        the int32 index of its wavelength among them, on the batch's device — the `groups` of `OpticalTable.spots_grouped_all`
+        that give one spot per wavelength.  A batch from `multiplexed_in_wavelength` comes out group-major: copy w is one group."""
+        wavelengths, ids = torch.unique(self.wavelength, sorted=True, return_inverse=True)
+        return ids.to(torch.int32).contiguous(), wavelengths
+
     def clone(self):
         """Deep copy on the device."""
         out = object.__new__(RayBatch)

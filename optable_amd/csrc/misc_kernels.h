@@ -983,7 +983,18 @@ struct MonSpots {
     int32_t kind, coordinates;           // reference_kind and coordinates of ot_monitor_wavefront_many
     const double *reference, *pupil, *piston;  // [n_monitors][3] F_loc or u_loc, [n_monitors][3] (c_y, c_z, R), [n_monitors]
     const uint8_t *n_index, *pathlength;  // double, addressed like the fields of MonSource
+    // the group mode (below): n_groups > 0, a cell is (monitor, plane, group) and counts / sums are [n_monitors][n_off][n_groups] (x 6)
+    const int32_t* groups;               // [n_group_ids], one id per input ray
+    int32_t n_group_ids, n_groups;       // n_groups = 0: the two other modes
 };
+// Entry k of a host table of the call (axes, centre, offsets: uploaded before the launch, written by no kernel), read through the constant
+// address space: a scalar load whatever else the kernel holds.  Without it the compiler proves "nothing in this kernel writes
+// here" by a bounded search, and with the group mode in the kernel that search gave up: the spot statistics' inner loop read its
+// offset, centre and axes through vector loads and took 3 to 4 % longer.
+__device__ __forceinline__ double mon_table(const double* table, int32_t k) {
+    typedef const __attribute__((address_space(4))) double* ConstPtr;
+    return ((ConstPtr)(uintptr_t)table)[k];
+}
 template <class V> __device__ __forceinline__ V wave_sum(V v) {  // every lane gets the sum, formed in one order
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -1071,6 +1082,66 @@ __device__ __forceinline__ void mon_wavefront_visit(const ot_monitor* __restrict
         if (lane < MON_WAVEFRONT_VALUES) mine[k * MON_WAVEFRONT_VALUES + lane] += v;
     }
 }
+// The group mode of k_mon_spots (ot_monitor_spot_groups_many): the spot statistics' partition, loads, hit test, coordinates,
+// weight, rows, partials, ticket and last workgroup, with a cell per (monitor m, plane j, GROUP g) of the list [m][j][g] — the
+// group of a hit of slot s is groups[ray[s]], the id of the input ray the slot's segment descends from (the ray plane read as
+// mon_wavelength reads it), loaded once per slot at its first hit.  A hit whose ray is outside [0, n_group_ids) (nothing is read
+// out of range) or whose id is outside [0, n_groups) belongs to no cell and is not tallied: id -1 masks a ray.
+// One hit test serves all groups of a pair (m, j).  Where its ballot is not zero the wave walks the DISTINCT groups among its
+// hitting lanes: the id g0 of the lowest lane left in the ballot (v_readlane), the lanes with hit && id == g0, the six butterflies
+// with every other lane carrying 0, lanes 0..6 adding to the wave's own row of cell (m, j, g0), those lanes cleared — in
+// ascending order of each group's first lane, a function of the inputs and their layout alone, so the order of every sum is as
+// fixed as the spot statistics'.  A wave of one group (every wave of a group-major batch in slot or tile layout) does one
+// butterfly set per pair: with n_groups = 1 the inputs of every add are the spot statistics', and so is every bit of the result.
+// A launch takes whole pairs, (MON_SPOT_CELLS / n_groups) * n_groups cells (cell0 and n_cells are multiples of n_groups), so
+// the row of (pair k, group g0) is k * n_groups + g0 < n_cells.
+__device__ __forceinline__ void mon_groups_visit(const ot_monitor* __restrict__ mons, const MonSource& src, const MonSeg& g, int64_t s,
+                                                 const MonSpots& sp, double* mine, int lane) {
+    double w = 1.0;
+    bool have_w = sp.intensity == nullptr;  // intensity and group of a slot are read once, at its first hit
+    int32_t id = -1;
+    bool have_id = false;
+    const int32_t pair0 = sp.cell0 / sp.n_groups;
+    int32_t m = pair0 / sp.n_off, j = pair0 - m * sp.n_off;  // wave-uniform, as in the spot statistics
+    for (int32_t k = 0; k < sp.n_cells; ++m, j = 0) {
+        const MonLocal l = mon_local(mons[m], g.ox, g.oy, g.oz, g.dx, g.dy, g.dz);
+        const double* a = sp.axes + 6 * m;
+        const double cy = mon_table(sp.centre, 2 * m), cz = mon_table(sp.centre, 2 * m + 1);
+        for (; j < sp.n_off && k < sp.n_cells; ++j, k += sp.n_groups) {
+            double Px, Py, Pz, t;
+            const bool hit = g.valid && mon_cross(mons[m], l, l.ox - mon_table(sp.offsets, j), g.len, Px, Py, Pz, t);
+            if (!__ballot(hit)) continue;
+            if (hit && !have_w) {
+                w = mon_real(sp.intensity + mon_at(s, src.tile_stride, src.width), src.width);
+                have_w = true;
+            }
+            if (hit && !have_id) {
+                const int32_t ray = *reinterpret_cast<const int32_t*>(src.ray + mon_at(s, src.ray_stride, 4));
+                if (ray >= 0 && ray < sp.n_group_ids) id = sp.groups[ray];
+                if (id < 0 || id >= sp.n_groups) id = -1;
+                have_id = true;
+            }
+            double W = 0.0, Wy = 0.0, Wz = 0.0, Wyy = 0.0, Wzz = 0.0, Wyz = 0.0;
+            if (hit) {
+                const double y = Px * mon_table(a, 0) + Py * mon_table(a, 1) + Pz * mon_table(a, 2) - cy,
+                             z = Px * mon_table(a, 3) + Py * mon_table(a, 4) + Pz * mon_table(a, 5) - cz;
+                W = w, Wy = w * y, Wz = w * z;
+                Wyy = Wy * y, Wzz = Wz * z, Wyz = Wy * z;
+            }
+            unsigned long long rest = __ballot(hit && id >= 0);
+            while (rest) {
+                const int32_t g0 = __builtin_amdgcn_readlane(id, __ffsll((long long)rest) - 1);
+                const bool in = hit && id == g0;
+                const unsigned long long b = __ballot(in);
+                const double gW = wave_sum(in ? W : 0.0), gWy = wave_sum(in ? Wy : 0.0), gWz = wave_sum(in ? Wz : 0.0),
+                             gWyy = wave_sum(in ? Wyy : 0.0), gWzz = wave_sum(in ? Wzz : 0.0), gWyz = wave_sum(in ? Wyz : 0.0);
+                const double v = lane == 0 ? (double)__popcll(b) : lane == 1 ? gW : lane == 2 ? gWy : lane == 3 ? gWz : lane == 4 ? gWyy : lane == 5 ? gWzz : gWyz;
+                if (lane < MON_SPOT_VALUES) mine[(k + g0) * MON_SPOT_VALUES + lane] += v;
+                rest &= ~b;
+            }
+        }
+    }
+}
 __global__ __launch_bounds__(MON_THREADS) void k_mon_spots(const ot_monitor* __restrict__ mons, MonSource src, int64_t n, int32_t iters,
                                                            const int32_t* __restrict__ seg_count, int64_t n_rays, MonSpots sp) {
     extern __shared__ double spot_rows[];  // [MON_WAVES][n_cells][values]
@@ -1088,7 +1159,9 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_spots(const ot_monitor* __r
         const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
         if (__ballot(g.valid)) mon_wavefront_visit(mons, src, g, s, sp, mine, lane);
     }
-    for (int32_t it = 0; !wavefront && span.has(it); ++it) {
+    // ... and so does the group mode (below the spot statistics' loop), for the same reason
+    const bool grouped = sp.n_groups > 0;  // (uniform for the launch)
+    for (int32_t it = 0; !wavefront && !grouped && span.has(it); ++it) {
         const int64_t s = span.at(it) + threadIdx.x;
         const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
         if (!__ballot(g.valid)) continue;
@@ -1098,10 +1171,10 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_spots(const ot_monitor* __r
         for (int32_t k = 0; k < sp.n_cells; ++m, j = 0) {
             const MonLocal l = mon_local(mons[m], g.ox, g.oy, g.oz, g.dx, g.dy, g.dz);
             const double* a = sp.axes + 6 * m;
-            const double cy = sp.centre[2 * m], cz = sp.centre[2 * m + 1];
+            const double cy = mon_table(sp.centre, 2 * m), cz = mon_table(sp.centre, 2 * m + 1);
             for (; j < sp.n_off && k < sp.n_cells; ++j, ++k) {
                 double Px, Py, Pz, t;
-                const bool hit = g.valid && mon_cross(mons[m], l, l.ox - sp.offsets[j], g.len, Px, Py, Pz, t);
+                const bool hit = g.valid && mon_cross(mons[m], l, l.ox - mon_table(sp.offsets, j), g.len, Px, Py, Pz, t);
                 const unsigned long long b = __ballot(hit);
                 if (!b) continue;
                 if (hit && !have_w) {
@@ -1110,7 +1183,8 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_spots(const ot_monitor* __r
                 }
                 double W = 0.0, Wy = 0.0, Wz = 0.0, Wyy = 0.0, Wzz = 0.0, Wyz = 0.0;
                 if (hit) {
-                    const double y = Px * a[0] + Py * a[1] + Pz * a[2] - cy, z = Px * a[3] + Py * a[4] + Pz * a[5] - cz;
+                    const double y = Px * mon_table(a, 0) + Py * mon_table(a, 1) + Pz * mon_table(a, 2) - cy,
+                                 z = Px * mon_table(a, 3) + Py * mon_table(a, 4) + Pz * mon_table(a, 5) - cz;
                     W = w, Wy = w * y, Wz = w * z;
                     Wyy = Wy * y, Wzz = Wz * z, Wyz = Wy * z;
                 }
@@ -1119,6 +1193,11 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_spots(const ot_monitor* __r
                 if (lane < MON_SPOT_VALUES) mine[k * MON_SPOT_VALUES + lane] += v;
             }
         }
+    }
+    for (int32_t it = 0; grouped && span.has(it); ++it) {
+        const int64_t s = span.at(it) + threadIdx.x;
+        const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
+        if (__ballot(g.valid)) mon_groups_visit(mons, src, g, s, sp, mine, lane);
     }
     __syncthreads();
     double* row = sp.partials + (int64_t)blockIdx.x * nv;

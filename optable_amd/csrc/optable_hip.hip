@@ -1852,7 +1852,7 @@ int ot_fluence_map(ot_ctx* c, const double* axes, const double* u_edges, int32_t
     return 0;
 }
 
-// What the two reductions of k_mon_spots (ot_monitor_spots_many, ot_monitor_wavefront_many; misc_kernels.h) take alike, and what
+// What the reductions of k_mon_spots (ot_monitor_spots_many, ot_monitor_spot_groups_many, ot_monitor_wavefront_many; misc_kernels.h) take alike, and what
 // they refuse of it alike: after their own NULL, size and enum refusals (a size before any array of that size is read), before
 // their own tables' and before anything is zeroed or launched.
 struct ReduceCall {
@@ -1874,7 +1874,7 @@ struct ReduceTable { const double* host; int64_t doubles; const double* MonSpots
 struct ReduceMode { int64_t cells; int32_t cells_a_launch, values; size_t n_counts, n_sums; ReduceTable tables[3]; };
 // The shared half of a checked call: counts and sums zeroed unless they are kept, nothing more for n = 0; else the monitors, axes
 // and tables to the device and one launch per `cells_a_launch` cells, all on the partition of the LDS image passes: at most 1024
-// workgroups, four a CU, which bounds the partials (1024 rows of a launch's values: 14 MB for a full group of either mode) and the
+// workgroups, four a CU, which bounds the partials (1024 rows of a launch's values: 14 MB for a full group of any mode) and the
 // last workgroup's loop over them.  One ticket per launch, zeroed together.  A new mode is a new caller: its checks, its ReduceMode
 // and, in `spots`, its own MonSpots fields by name.
 static int reduce_call(const ReduceCall& a, const ReduceMode& mode, MonSpots spots) {
@@ -1940,6 +1940,35 @@ int ot_monitor_spots_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors,
     MonSpots spots{};
     spots.n_off = n_offsets;
     return reduce_call(a, {cells, MON_SPOT_CELLS, MON_SPOT_VALUES, (size_t)cells, 6 * (size_t)cells,
+                           {{centre, 2 * (int64_t)n_monitors, &MonSpots::centre}, {offsets, n_offsets, &MonSpots::offsets}}}, spots);
+}
+
+// Spot statistics per ray group: k_mon_spots in its group mode, a cell per (monitor, plane, group) of the list [monitor][offset][group],
+// 7 doubles; a launch takes whole (monitor, plane) pairs, (MON_SPOT_CELLS / n_groups) * n_groups cells (optable_amd/engine.py
+// spot_groups_plan).  `groups` stays where it is, on the device.
+int ot_monitor_spot_groups_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, const double* centre,
+                                const double* offsets, int32_t n_offsets, const int32_t* groups, int64_t n_group_ids, int32_t n_groups,
+                                const ot_segment_source* src, const void* intensity, int64_t n, const int32_t* seg_count, int64_t n_rays,
+                                int64_t* counts, double* sums, int32_t accumulate) {
+    static_assert(OT_SPOT_GROUPS_MAX == MON_SPOT_CELLS, "one pair of a launch: every group of it a cell in LDS");
+    if (!c || !mons || !axes || !centre || !offsets || !src || !counts || !sums) return fail(OT_ERR_INVALID, "NULL argument");
+    if (!groups) return fail(OT_ERR_INVALID, "NULL argument: groups");
+    if (n_monitors < 1) return fail(OT_ERR_INVALID, "n_monitors must be at least 1");
+    if (n_offsets < 1) return fail(OT_ERR_INVALID, "n_offsets must be at least 1");
+    if (n_groups < 1 || n_groups > OT_SPOT_GROUPS_MAX) return fail(OT_ERR_INVALID, "n_groups must be 1 .. 256");
+    if (n_group_ids < 1 || n_group_ids > INT32_MAX) return fail(OT_ERR_INVALID, "n_group_ids must be 1 .. 2^31 - 1");
+    const int64_t pairs = (int64_t)n_monitors * n_offsets, cells = pairs * n_groups;
+    if (pairs > (int64_t)1 << 20 || cells > (int64_t)1 << 20) return fail(OT_ERR_INVALID, "n_monitors * n_offsets * n_groups exceeds 2^20 cells");
+    const ReduceCall a{c, mons, n_monitors, axes, src, intensity, n, seg_count, n_rays, counts, sums, accumulate};
+    if (const int rc = check_reduce_call(a)) return rc;
+    for (int64_t k = 0; k < 2 * (int64_t)n_monitors; ++k)
+        if (!std::isfinite(centre[k])) return fail(OT_ERR_INVALID, "centre must be finite");
+    for (int32_t k = 0; k < n_offsets; ++k)
+        if (!std::isfinite(offsets[k])) return fail(OT_ERR_INVALID, "offsets must be finite");
+    MonSpots spots{};
+    spots.n_off = n_offsets;
+    spots.groups = groups, spots.n_group_ids = (int32_t)n_group_ids, spots.n_groups = n_groups;
+    return reduce_call(a, {cells, MON_SPOT_CELLS / n_groups * n_groups, MON_SPOT_VALUES, (size_t)cells, 6 * (size_t)cells,
                            {{centre, 2 * (int64_t)n_monitors, &MonSpots::centre}, {offsets, n_offsets, &MonSpots::offsets}}}, spots);
 }
 

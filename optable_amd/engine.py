@@ -169,7 +169,7 @@ def fluence_plan(nu, nv):
     return {"path": "lds" if nu * nv <= IMAGE_LDS_BINS else "global"}
 
 
-# -- the reductions of k_mon_spots (ot_monitor_spots_many, ot_monitor_wavefront_many) -----------------------------------------------
+# -- the reductions of k_mon_spots (ot_monitor_spots_many, ot_monitor_spot_groups_many, ot_monitor_wavefront_many) -----------------------------------------------
 def _cell_plan(cells, most):
     """How optable_hip.hip reduce_call walks a list of `cells` cells (the same rule): the launches as (first cell, cells), `most`
     at a time — every launch one pass over the segments."""
@@ -188,6 +188,19 @@ def spots_plan(n_monitors, n_offsets):
     if n_monitors < 1 or n_offsets < 1 or n_monitors * n_offsets > SPOT_MAX_CELLS:
         raise ValueError(f"no spot statistics of {n_monitors} monitors x {n_offsets} planes")
     return _cell_plan(n_monitors * n_offsets, SPOT_CELLS)
+
+
+# -- spot statistics per ray group (ot_monitor_spot_groups_many) -------------------------------------------------------------
+SPOT_GROUPS_MAX = 256  # optable_hip.h OT_SPOT_GROUPS_MAX: groups of one call, a pair (monitor, plane) of them the least a launch takes
+
+
+def spot_groups_plan(n_monitors, n_offsets, n_groups):
+    """How ot_monitor_spot_groups_many walks the cells (monitor m, plane j, group g) of the list [m][j][g]: `_cell_plan` with whole
+    pairs (m, j) a launch, (SPOT_CELLS // n_groups) * n_groups cells at a time — one hit test serves all groups of a pair."""
+    n_monitors, n_offsets, n_groups = int(n_monitors), int(n_offsets), int(n_groups)
+    if n_monitors < 1 or n_offsets < 1 or not 1 <= n_groups <= SPOT_GROUPS_MAX or n_monitors * n_offsets * n_groups > SPOT_MAX_CELLS:
+        raise ValueError(f"no spot statistics of {n_monitors} monitors x {n_offsets} planes x {n_groups} groups")
+    return _cell_plan(n_monitors * n_offsets * n_groups, SPOT_CELLS // n_groups * n_groups)
 
 
 # -- wavefront error (ot_monitor_wavefront_many) -----------------------------------------------------------------------------
@@ -995,8 +1008,31 @@ class Engine:
                                  [(torch.int64, (M, J)), (torch.float64, (M, J, 6))], into,
                                  f"into: contiguous int64 counts of shape [{M}, {J}] and float64 sums of shape [{M}, {J}, 6] on {segs.device}")
 
+    def monitor_spot_groups_many(self, monitor_structs, axes, centre, offsets, groups, n_groups, segs: SegmentBatch, weighted=True, into=None):
+        """Spot statistics per ray group (ot_monitor_spot_groups_many): `monitor_spots_many` with a group axis — a hit of a segment
+        of input ray r belongs to group groups[r].  groups: a contiguous int32 vector on the segments' device, one id per input
+        ray; ids outside 0 .. n_groups - 1 (and rays beyond the table) are masked.  Returns (counts, sums): int64 [M, J, G] and
+        float64 [M, J, G, 6] device tensors, zeroed by the call — or `into`, such a pair from an earlier call, with this call's
+        hits added to it.  The sums are the same bits every run."""
+        with self.lock:
+            return self._monitor_spot_groups_many(list(monitor_structs), axes, centre, offsets, groups, int(n_groups), segs, weighted, into)
+
+    def _monitor_spot_groups_many(self, mons, axes, centre, offsets, groups, G, segs, weighted, into):
+        M = len(mons)
+        axes, centre, offsets = _float64_tables(f"axes must be [{M}, 6], centre [{M}, 2] and offsets one-dimensional", (axes, (M, 6)), (centre, (M, 2)),
+                                                (offsets, (None,)))
+        J = len(offsets)
+        spot_groups_plan(max(M, 1), J, G)
+        if (not torch.is_tensor(groups) or groups.dtype != torch.int32 or groups.dim() != 1 or not groups.is_contiguous() or groups.numel() < 1
+                or groups.device.type != segs.device.type):
+            raise ValueError(f"groups: a contiguous int32 vector of one id per input ray on {segs.device}")
+        tables = (_doubles(axes), _doubles(centre), _doubles(offsets), J, groups.data_ptr(), int(groups.numel()), G)
+        return self._reduce_many("ot_monitor_spot_groups_many", mons, tables, segs, weighted, (),
+                                 [(torch.int64, (M, J, G)), (torch.float64, (M, J, G, 6))], into,
+                                 f"into: contiguous int64 counts of shape [{M}, {J}, {G}] and float64 sums of shape [{M}, {J}, {G}, 6] on {segs.device}")
+
     def _reduce_many(self, call, mons, tables, segs, weighted, fields, specs, into, error):
-        """What monitor_spots_many and monitor_wavefront_many do alike once their tables are checked: the outputs of `specs`, and the
+        """What monitor_spots_many, monitor_spot_groups_many and monitor_wavefront_many do alike once their tables are checked: the outputs of `specs`, and the
         library's `call` with the mode's `tables` behind the monitors and its segment `fields` behind the intensity."""
         M = len(mons)
         outs = _outputs(segs.device, specs, into, torch.zeros, error)  # (zeros: the library is not called for nothing)

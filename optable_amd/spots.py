@@ -115,3 +115,90 @@ class MonitorSpots:
     def to_host(self):
         """(counts, sums, offsets) as numpy arrays."""
         return self.counts.cpu().numpy(), self.sums.cpu().numpy(), self.offsets
+
+
+def spot_group_ids(groups, n_rays, n_groups=None, device=None):
+    """`groups` as (the contiguous int32 device tensor the engine takes, G): an integer array or tensor of one id per input ray
+    (`n_rays` of them; None: any length).  n_groups=None: max id + 1.  Ids outside 0 .. G - 1 are kept as they are — such rays are
+    masked (-1 is the way to say so), which is why an `n_groups` below max id + 1 is no error.  ValueError: ids that are no
+    integers, another length, an `n_groups` outside 1 .. 256."""
+    import torch
+
+    from .engine import SPOT_GROUPS_MAX
+
+    if torch.is_tensor(groups):
+        ids = groups
+        if ids.dtype in (torch.bool,) or ids.is_floating_point() or ids.is_complex():
+            raise ValueError(f"groups must be integer ids, not {ids.dtype}")
+    else:
+        try:
+            array = np.asarray(groups)
+        except (TypeError, ValueError):
+            raise ValueError(f"groups must be integer ids, one per ray, not {groups!r}") from None
+        if array.dtype.kind not in "iu":
+            raise ValueError(f"groups must be integer ids, not {array.dtype}")
+        if array.size and (array.min() < -(2**31) or array.max() >= 2**31):
+            raise ValueError("groups: ids must fit 32 bits")
+        ids = torch.from_numpy(np.ascontiguousarray(array.astype(np.int32, copy=False)))
+    if ids.dim() != 1 or ids.numel() < 1 or (n_rays is not None and ids.numel() != int(n_rays)):
+        raise ValueError(f"groups must be one id per input ray ({'any number' if n_rays is None else int(n_rays)}), not of shape {tuple(ids.shape)}")
+    if n_groups is None:
+        n_groups = max(int(ids.max()) + 1, 1)
+    if isinstance(n_groups, bool) or not isinstance(n_groups, (int, np.integer)) or not 1 <= int(n_groups) <= SPOT_GROUPS_MAX:
+        raise ValueError(f"n_groups must be 1 .. {SPOT_GROUPS_MAX}, not {n_groups!r}")
+    ids = ids.to(dtype=torch.int32)
+    if device is not None:
+        ids = ids.to(device)
+    return ids.contiguous(), int(n_groups)
+
+
+class MonitorSpotGroups:
+    """The hits of one monitor as moments, per plane and per RAY GROUP (`OpticalTable.spots_grouped_all`): `counts` (int64, J x G)
+    and `sums` (float64, J x G x 6) are device tensors, `offsets`, `weight` and `centre` as for `MonitorSpots`; `n_groups` = G;
+    `labels`: what the groups stand for, one per group (the wavelengths, say), or None.  A hit belongs to the group of the input
+    ray its segment descends from; rays whose id is outside 0 .. G - 1 are in no group.  `group(g)` is a `MonitorSpots` on views
+    of group g, so everything that class computes is there per group."""
+
+    def __init__(self, monitor, offsets, counts, sums, weight, centre, labels=None, stack=None):
+        self.monitor, self.offsets, self.counts, self.sums, self.weight = monitor, offsets, counts, sums, weight
+        self.centre = (float(centre[0]), float(centre[1]))
+        self.n_groups = int(counts.shape[-1])
+        self.labels = None if labels is None else list(labels)
+        if self.labels is not None and len(self.labels) != self.n_groups:
+            raise ValueError(f"labels: one per group ({self.n_groups}), not {len(self.labels)}")
+        self._stack = stack
+
+    def group(self, g):
+        """Group g as a `MonitorSpots` (views: an `into=` call that adds to this object shows there too)."""
+        g = int(g)
+        if not 0 <= g < self.n_groups:
+            raise IndexError(f"group {g} of {self.n_groups}")
+        return MonitorSpots(self.monitor, self.offsets, self.counts[:, g], self.sums[:, g], self.weight, self.centre)
+
+    def total(self):
+        """All groups together as a `MonitorSpots`: counts exactly, sums in the order of the groups (masked rays are in neither)."""
+        return MonitorSpots(self.monitor, self.offsets, self.counts.sum(dim=1), self.sums.sum(dim=1), self.weight, self.centre)
+
+    def _all(self):
+        return MonitorSpots(self.monitor, self.offsets, self.counts, self.sums, self.weight, self.centre)
+
+    def power(self):
+        """W per plane and group (J x G)."""
+        return self.sums[..., 0]
+
+    def centroid(self):
+        """(y, z) of the weighted centroid per plane and group, `centre` added back (J x G x 2)."""
+        return self._all().centroid()
+
+    def rms_radius(self):
+        """sqrt(var_y + var_z) per plane and group (J x G), NaN where a cell has no hit."""
+        return self._all().rms_radius()
+
+    def best_focus(self):
+        """`MonitorSpots.best_focus` of every group: (offsets, rms radii), two numpy arrays of length G."""
+        found = [self.group(g).best_focus() for g in range(self.n_groups)]
+        return np.array([f[0] for f in found]), np.array([f[1] for f in found])
+
+    def to_host(self):
+        """(counts, sums, offsets) as numpy arrays."""
+        return self.counts.cpu().numpy(), self.sums.cpu().numpy(), self.offsets

@@ -341,6 +341,44 @@ class OpticalTable:
         """One monitor as spot statistics (`spots_all` for it alone): a `MonitorSpots`."""
         return self.spots_all(segs, offsets=offsets, monitors=[monitor], weight=weight, centre=centre)[0]
 
+    def spots_grouped_all(self, segs, groups, n_groups=None, offsets=(0.0,), monitors=None, weight="intensity", centre=None, into=None, labels=None):
+        """`spots_all` PER RAY GROUP: one `MonitorSpotGroups` per monitor, in their order — the count and the six moments of the hits
+        of every (plane, group), from one pass over the segments (ot_monitor_spot_groups_many).  groups: one integer id per INPUT
+        ray of the trace (an array or tensor; `RayBatch.groups_by_wavelength()` gives one group per wavelength); a hit belongs to
+        the group of the ray its segment descends from, whatever the layout and wherever in a ray tree.  n_groups = G, 1 .. 256
+        (None: max id + 1); rays whose id is outside 0 .. G - 1 are in no group, so -1 masks a ray.  offsets, monitors, weight and
+        centre as for `spots_all`; labels: what the groups stand for, one per group, kept on the results.  One trace of a batch
+        multiplexed in wavelength gives the chromatic focal shift (`MonitorSpotGroups.best_focus()`), one of several field points
+        the field curvature.  Counts are exact and the sums the same bits every run.  `into`: the list an earlier call with the
+        same monitors, offsets, weight, centre and G returned; this call's hits are added to it, with this call's `groups` (the
+        chunks of a streamed trace each bring their own table)."""
+        from .spots import MonitorSpotGroups, spot_centres, spot_group_ids, spot_offsets
+
+        check_weight(weight)
+        monitors = list(self.monitors if monitors is None else monitors)
+        offsets, centres = spot_offsets(offsets), spot_centres(centre, len(monitors))
+        ids, G = spot_group_ids(groups, segs.n_rays, n_groups, device=segs.device)
+        if labels is not None and len(labels) != G:
+            raise ValueError(f"labels: one per group ({G}), not {len(labels)}")
+        stack = None
+        if into is not None:
+            into, stack = _into_stack(into, len(monitors), lambda k, sp: isinstance(sp, MonitorSpotGroups) and sp.monitor is monitors[k]
+                                      and sp.weight == weight and sp.centre == tuple(centres[k]) and np.array_equal(sp.offsets, offsets)
+                                      and sp.n_groups == G,
+                                      "into: the list an earlier spots_grouped_all returned for the same monitors, offsets, weight, centre and n_groups")
+            if not monitors:
+                return into
+        counts, sums = _engine().monitor_spot_groups_many([monitor_struct(m) for m in monitors], _monitor_axes(monitors), centres, offsets, ids, G, segs,
+                                                          weighted=weight == "intensity", into=stack)
+        if into is None:
+            into = [MonitorSpotGroups(m, offsets, counts[k], sums[k], weight, centres[k], labels=labels, stack=(counts, sums, k))
+                    for k, m in enumerate(monitors)]
+        return into
+
+    def spots_grouped_batch(self, monitor, segs, groups, n_groups=None, offsets=(0.0,), weight="intensity", centre=None, labels=None):
+        """One monitor as spot statistics per ray group (`spots_grouped_all` for it alone): a `MonitorSpotGroups`."""
+        return self.spots_grouped_all(segs, groups, n_groups=n_groups, offsets=offsets, monitors=[monitor], weight=weight, centre=centre, labels=labels)[0]
+
     def wavefront_all(self, segs, focus=None, direction=None, pupil=None, coordinates=None, monitors=None, weight="intensity", piston=None,
                       into=None):
         """Every monitor of the table (or those given) as a WAVEFRONT: one `MonitorWavefront` per monitor, in their order — the
