@@ -844,6 +844,43 @@ int ot_monitor_psf_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitors,
                         const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* norm, double* re, double* im,
                         int32_t accumulate);
 
+/* Diffraction PSF per ray group: ot_monitor_psf_many with a GROUP axis on the cells — the image of every wavelength, field point
+ * or port of one batch from one pass over the segments.  Fields of different groups are never added: white light adds the
+ * INTENSITIES of its wavelengths, and different field points make different images (the caller sums |U_g|^2 as it needs).
+ * A CELL is a pair (monitor m, group g).  Every argument ot_monitor_psf_many has means what it means there, and so do the hit
+ * test, W, lambda, the amplitude, the samples and the phase of a hit: a hit of slot s is exactly that call's hit.  It belongs to
+ * group groups[ray[s]], where ray[s] is the int32 `ray` of the slot (src->ray: the index of the input ray the segment descends
+ * from, in every layout and for every node of a ray tree) and `groups` is a DEVICE table of n_group_ids int32 ids, one per input ray.
+ * A hit belongs to NO cell when its ray index is outside 0 .. n_group_ids - 1 (nothing is read out of range) or its id is outside
+ * 0 .. n_groups - 1.  That is how rays are masked: id -1.  Such a hit adds to no field, norm or count; it is tallied in
+ * ungrouped[m] (device, [n_monitors] int64, zeroed or kept with the other outputs), so that for every monitor
+ * sum_g (used + skipped) + ungrouped = the hits ot_monitor_record_many finds.
+ * Outputs, all on the device: counts [n_monitors][n_groups][3] int64 (used, skipped, aliased), norm [n_monitors][n_groups] double,
+ * re, im [n_monitors][n_groups][ny][nz] double: U[m][g] is the sum over the usable hits of cell (m, g).  accumulate as there.
+ * How: the hit list of the call is split by group on the device — a stable counting sort in two passes of the PSF kernel with a
+ * scan between them, over tiles of 2048 consecutive hits of one monitor — into a second list in which the hits of cell (m, g) lie
+ * together in the order they had (ascending slots); the sum then runs over the cells as ot_monitor_psf_many's runs over monitors.
+ * Determinism: as ot_monitor_psf_many.  The place of a hit in the second list is a function of the inputs and their layout alone
+ * (no position depends on the order in which an atomic lands; the ungrouped tally is an integer atomic, whose result does not),
+ * the chunks of a cell are a function of its hit count alone, and their partial images are added in ascending order.  So the
+ * result of cell (m, g) is bit for bit that of ot_monitor_psf_many over the segments of group g's rays alone in the same slot
+ * order, and with n_groups = 1 and every id 0, counts, norm, re and im are ot_monitor_psf_many's bit for bit.
+ * Synchronisation: two.  The hit totals per monitor come back to size the lists, as there; then, after the scan, the first hit of
+ * every cell (first_cell, n_monitors * n_groups + 1 words) comes back, because the chunks of a launch and the pairs a launch
+ * takes follow from the cells' hit counts.
+ * Scratch: the hit list twice (80 bytes a hit), 12 bytes per (group, tile) and the partial images of ot_monitor_psf_many.
+ * OT_ERR_INVALID, with nothing launched or zeroed: everything ot_monitor_psf_many refuses; groups or ungrouped NULL; n_groups
+ * outside 1 .. OT_SPOT_GROUPS_MAX; n_group_ids < 1 (or >= 2^31); n_monitors * n_groups > OT_PSF_GROUP_CELLS_MAX;
+ * n_monitors * n_groups * ny * nz > 2^27. */
+#define OT_PSF_GROUP_CELLS_MAX 4096
+int ot_monitor_psf_groups_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitors, const double* axes, int32_t reference_kind,
+                               const double* reference, const double* grid, int32_t ny, int32_t nz, const int32_t* groups,
+                               int64_t n_group_ids, int32_t n_groups, const ot_segment_source* src, const void* intensity,
+                               const void* n_index, const void* pathlength, const double* wavelength, int64_t n_wavelengths,
+                               double wavelength_uniform, int32_t amplitude_mode, int64_t n_segments, const int32_t* seg_count,
+                               int64_t n_rays, int64_t* counts, double* norm, double* re, double* im, int64_t* ungrouped,
+                               int32_t accumulate);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled every trace launch is bracketed by hipEvents on the ctx stream. */
 int ot_timing_enable(ot_ctx* ctx, int enabled);

@@ -22,7 +22,7 @@ from .monitors import Monitor
 from .fluence import FluenceMap
 from .spots import MonitorSpots, MonitorSpotGroups
 from .wavefront import MonitorWavefront
-from .psf import MonitorPSF
+from .psf import MonitorPSF, MonitorPSFGroups
 from .table import OpticalTable
 from .scene import compile_scene, CompiledScene, SceneError
 from .adapter import install

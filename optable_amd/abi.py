@@ -174,6 +174,9 @@ SYMBOLS = {
                                             C.POINTER(C.c_double), C.POINTER(OtSegmentSource), _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32]),
     "ot_monitor_psf_many": (C.c_int, [_vp, C.POINTER(OtMonitor), _i32, C.POINTER(C.c_double), _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32, _i32,
                                       C.POINTER(OtSegmentSource), _vp, _vp, _vp, _vp, _i64, C.c_double, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32]),
+    "ot_monitor_psf_groups_many": (C.c_int, [_vp, C.POINTER(OtMonitor), _i32, C.POINTER(C.c_double), _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32,
+                                             _i32, _vp, _i64, _i32, C.POINTER(OtSegmentSource), _vp, _vp, _vp, _vp, _i64, C.c_double, _i32, _i64, _vp, _i64,
+                                             _vp, _vp, _vp, _vp, _vp, _i32]),
     "ot_timing_enable": (C.c_int, [_vp, C.c_int]),
     "ot_timing_read": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(_i64)]),
     "ot_timing_reset": (C.c_int, [_vp]),

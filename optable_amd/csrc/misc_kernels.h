@@ -1301,7 +1301,104 @@ struct MonPsf {
     long long* counts;                    // [n_monitors][3]: used, skipped, aliased
     int32_t kind, amplitude_mode, ny, nz;
     int32_t pair0, max_chunks;            // the launch: (monitor, tile) pairs from pair0 on, max_chunks workgroups each
+    int32_t mode;                         // 0: the sum; 1, 2: the count and scatter passes of the partition by group (below)
+    const struct MonPsfPartition* pp;     // ... and their arguments, in device memory: the sum's kernel arguments stay what they were
 };
+// Partition of the hit list by group (ot_monitor_psf_groups_many): a STABLE counting sort of every monitor's hits by the key
+// g = groups[ray[hit_index[j]]] (the ray plane read as mon_groups_visit reads it), in two launches with an exclusive_scan between
+// them.  A TILE is MON_PSF_PART_TILE consecutive hits of ONE monitor (the host builds `part` from first[]; a monitor without a
+// hit has one empty tile), so a workgroup meets at most n_groups keys.  The count pass leaves
+// tile_count[base + g * tiles + local]: the entries of cell (m, g) lie together, its tiles in their order, the cells in theirs —
+// so the scan over all of them gives every tile's place in every cell, and cell (m, g) starts at tile_off[base + g * tiles].
+// The scatter pass walks the same tile in rounds of MON_THREADS hits in list order; a hit goes to seen[g] (the tile's place plus the
+// hits of g in its earlier rounds) + the hits of g in the round's lower waves (wcnt, LDS) + those in the wave's lower lanes
+// (the ballot-and-match walk of mon_groups_visit, rank_below).  No place depends on the order in which anything lands.
+// A hit whose ray is outside [0, n_group_ids) (nothing is read out of range) or whose id is outside [0, n_groups) is in no cell: it
+// is not copied, and the count pass tallies it in ungrouped[m] with one integer atomic a wave.
+// The first tile of a monitor writes first_cell[m * n_groups + g] for its groups, workgroup 0 first_cell[n_cells].
+// LDS: wcnt [MON_WAVES][256] int32 and seen [256] int64 lie in the sum's `tab`.  The passes' arguments (MonPsfPartition) lie in device
+// memory behind one pointer of MonPsf: as kernel arguments they cost the sum scalar registers it has no room for.
+static constexpr int MON_PSF_PART_TILE = 2048, MON_PSF_GROUPS_MAX = 256;
+static_assert(MON_PSF_PART_TILE % MON_THREADS == 0 && MON_PSF_PART_TILE <= 2048, "whole rounds, and a tile's count fits any counter");
+struct MonPsfTile {
+    int64_t j0, j1, base;           // its hits [j0, j1) of the list; tile_count index of (group 0, tile 0) of its monitor
+    int32_t monitor, local, tiles;  // its monitor, its place among that monitor's tiles, how many those are
+    int32_t pad;
+};
+struct MonPsfPartition {
+    int32_t n_groups, n_group_ids, n_cells, pad;
+    const int32_t* groups;               // [n_group_ids], one id per input ray
+    const MonPsfTile* part;              // [gridDim.x]: the tile of every workgroup
+    int32_t* tile_count;                 // [n_count + 1], out of the count pass
+    const int64_t* tile_off;             // [n_count + 1], its exclusive scan
+    int64_t n_count;
+    int64_t *first_cell, *to_hit_index;  // out of the scatter pass: [n_cells + 1] and the second hit list
+    double *to_Px, *to_Py, *to_Pz, *to_t;
+    unsigned long long* ungrouped;       // [monitors]
+};
+__device__ __forceinline__ void mon_psf_partition(const MonSource& src, const MonPsf& ps, int32_t* wcnt, int64_t* seen, int tid, int lane, int wave) {
+    const MonPsfPartition pp = *ps.pp;  // (read once, before any store of the pass)
+    const MonPsfTile tl = pp.part[blockIdx.x];
+    const int32_t G = pp.n_groups;
+    const bool scatter = ps.mode == 2;  // (uniform for the launch)
+    for (int32_t g = tid; g < G; g += MON_THREADS) {
+        for (int w = 0; w < MON_WAVES; ++w) wcnt[w * MON_PSF_GROUPS_MAX + g] = 0;
+        if (scatter) {
+            seen[g] = pp.tile_off[tl.base + (int64_t)g * tl.tiles + tl.local];
+            if (tl.local == 0) pp.first_cell[(int64_t)tl.monitor * G + g] = pp.tile_off[tl.base + (int64_t)g * tl.tiles];
+        }
+    }
+    if (blockIdx.x == 0 && tid == 0) {
+        if (scatter) pp.first_cell[pp.n_cells] = pp.tile_off[pp.n_count];
+        else pp.tile_count[pp.n_count] = 0;  // (the scan reads one entry past the counts)
+    }
+    __syncthreads();
+    int32_t none = 0;
+    for (int64_t r0 = tl.j0; r0 < tl.j1; r0 += MON_THREADS) {
+        const int64_t j = r0 + tid;
+        const bool have = j < tl.j1;
+        int32_t id = -1;
+        if (have) {
+            const int32_t ray = *reinterpret_cast<const int32_t*>(src.ray + mon_at(ps.hit_index[j], src.ray_stride, 4));
+            if (ray >= 0 && ray < pp.n_group_ids) id = pp.groups[ray];
+            if (id < 0 || id >= G) id = -1;
+        }
+        none += __popcll(__ballot(have && id < 0));
+        unsigned long long rest = __ballot(id >= 0);
+        int32_t rank = 0;
+        while (rest) {  // the distinct groups of the wave, in ascending order of each one's first lane
+            const int32_t g0 = __builtin_amdgcn_readlane(id, __ffsll((long long)rest) - 1);
+            const bool in = id == g0;
+            const unsigned long long b = __ballot(in);
+            if (in) rank = rank_below(b);
+            if (lane == 0) wcnt[wave * MON_PSF_GROUPS_MAX + g0] += __popcll(b);
+            rest &= ~b;
+        }
+        if (!scatter) continue;  // the count pass keeps adding: wcnt is the wave's count of the whole tile
+        __syncthreads();
+        if (id >= 0) {
+            int64_t d = seen[id] + rank;
+            for (int w = 0; w < wave; ++w) d += wcnt[w * MON_PSF_GROUPS_MAX + id];
+            pp.to_hit_index[d] = ps.hit_index[j];
+            pp.to_Px[d] = ps.Px[j], pp.to_Py[d] = ps.Py[j], pp.to_Pz[d] = ps.Pz[j], pp.to_t[d] = ps.t[j];
+        }
+        __syncthreads();
+        for (int32_t g = tid; g < G; g += MON_THREADS) {
+            int32_t sum = 0;
+            for (int w = 0; w < MON_WAVES; ++w) sum += wcnt[w * MON_PSF_GROUPS_MAX + g], wcnt[w * MON_PSF_GROUPS_MAX + g] = 0;
+            seen[g] += sum;
+        }
+        __syncthreads();
+    }
+    if (scatter) return;
+    if (lane == 0 && none) atomicAdd(pp.ungrouped + tl.monitor, (unsigned long long)none);
+    __syncthreads();
+    for (int32_t g = tid; g < G; g += MON_THREADS) {
+        int32_t sum = 0;
+        for (int w = 0; w < MON_WAVES; ++w) sum += wcnt[w * MON_PSF_GROUPS_MAX + g];
+        pp.tile_count[tl.base + (int64_t)g * tl.tiles + tl.local] = sum;
+    }
+}
 // chunks of a monitor with `hits` hits, and part `i` of the `parts` an axis of `subtiles` is split into: [first, first + count)
 __host__ __device__ inline int32_t mon_psf_chunks(int64_t hits) {
     const int64_t c = (hits + MON_PSF_CHUNK_MIN - 1) / MON_PSF_CHUNK_MIN;
@@ -1314,9 +1411,9 @@ __host__ __device__ inline int32_t mon_psf_part(int32_t samples, int32_t i, int3
     return first;
 }
 typedef double mon_psf_acc __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(MON_THREADS) void k_mon_psf(const ot_monitor* __restrict__ mons, MonSource src, MonPsf ps) {
-    __shared__ double tab[4][MON_PSF_TILE][MON_PSF_STRIDE];
-    __shared__ double par[8][MON_THREADS];  // a c (re, im), gy, gz, cis(gy dy) (re, im), cis(gz dz) (re, im)
+// the sum (mode 0 of k_mon_psf, which owns the LDS: tab, and par: a c (re, im), gy, gz, cis(gy dy) (re, im), cis(gz dz) (re, im))
+__device__ __forceinline__ void mon_psf_sum(const ot_monitor* __restrict__ mons, const MonSource& src, const MonPsf& ps,
+                                            double (&tab)[4][MON_PSF_TILE][MON_PSF_STRIDE], double (&par)[8][MON_THREADS]) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int32_t parts_z = mon_psf_parts(ps.nz), n_tiles = mon_psf_parts(ps.ny) * parts_z;
     const int32_t pair_local = blockIdx.x / ps.max_chunks, chunk = blockIdx.x % ps.max_chunks;
@@ -1495,6 +1592,18 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_psf(const ot_monitor* __res
         if (tid == 0) ps.norm[m] += sum;
         else ps.counts[3 * (int64_t)m + tid - 1] += (long long)sum;
     }
+}
+__global__ __launch_bounds__(MON_THREADS) void k_mon_psf(const ot_monitor* __restrict__ mons, MonSource src, MonPsf ps) {
+    __shared__ double tab[4][MON_PSF_TILE][MON_PSF_STRIDE];
+    __shared__ double par[8][MON_THREADS];
+    if (ps.mode == 0) {  // (uniform for the launch)
+        mon_psf_sum(mons, src, ps, tab, par);
+        return;
+    }
+    // the two passes of the partition by group, behind the sum: its code comes out as it did without them.  The sum's LDS serves them.
+    const int tid = threadIdx.x;
+    int32_t* wcnt = reinterpret_cast<int32_t*>(&tab[0][0][0]);
+    mon_psf_partition(src, ps, wcnt, reinterpret_cast<int64_t*>(wcnt + MON_WAVES * MON_PSF_GROUPS_MAX), tid, tid & 63, __builtin_amdgcn_readfirstlane(tid >> 6));
 }
 
 // ------------------------------------------------------------------------------------------

@@ -2207,12 +2207,19 @@ int ot_monitor_wave_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, 
 // forms on the device.  A launch takes max(1, MON_PSF_PARTIAL_ROWS / (most chunks of a monitor)) (monitor, tile) pairs, so its
 // partials stay within MON_PSF_PARTIAL_ROWS rows of MON_PSF_ROW doubles; the launches of a call follow one another on the stream
 // and share partials and tickets.  optable_amd/engine.py psf_plan says the same.
-int ot_monitor_psf_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, int32_t reference_kind, const double* reference,
-                        const double* grid, int32_t ny, int32_t nz, const ot_segment_source* src, const void* intensity, const void* n_index,
-                        const void* pathlength, const double* wavelength, int64_t n_wavelengths, double wavelength_uniform, int32_t amplitude_mode,
-                        int64_t n, const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* norm, double* re, double* im,
-                        int32_t accumulate) {
+// With groups (ot_monitor_psf_groups_many; `grp` not NULL) the hit list is then split by group — k_mon_psf's count pass over the
+// partition tiles the host cuts from first[], an exclusive_scan, its scatter pass into a second list — and the sum runs over CELLS
+// (m, g) as if they were monitors: monitor, axes, reference and grid of m replicated per group, first_cell in place of first[],
+// the outputs indexed by cell.  first_cell comes back to the host (the second synchronisation) for the cells' chunk counts.
+// optable_amd/engine.py psf_groups_plan says the same.
+struct PsfGroups { const int32_t* ids; int64_t n_ids; int32_t n; int64_t* ungrouped; };
+static int psf_call(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, int32_t reference_kind, const double* reference,
+                    const double* grid, int32_t ny, int32_t nz, const PsfGroups* grp, const ot_segment_source* src, const void* intensity,
+                    const void* n_index, const void* pathlength, const double* wavelength, int64_t n_wavelengths, double wavelength_uniform,
+                    int32_t amplitude_mode, int64_t n, const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* norm, double* re, double* im,
+                    int32_t accumulate) {
     static_assert(MON_PSF_MAX_SAMPLES == OT_PSF_MAX_SAMPLES && MON_PSF_PARTIAL_ROWS * (int64_t)MON_PSF_ROW * 8 == OT_PSF_SCRATCH_BYTES, "the header's constants");
+    static_assert(MON_PSF_GROUPS_MAX == OT_SPOT_GROUPS_MAX, "the partition's LDS holds a counter per group and wave");
     if (!c || !mons || !axes || !reference || !grid || !src || !n_index || !pathlength || !counts || !norm || !re || !im)
         return fail(OT_ERR_INVALID, "NULL argument");
     if (n_monitors < 1 || n_monitors > 1 << 20) return fail(OT_ERR_INVALID, "n_monitors must be 1 .. 2^20");
@@ -2231,24 +2238,36 @@ int ot_monitor_psf_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, c
         if (!std::isfinite(g[0]) || !std::isfinite(g[1]) || !std::isfinite(g[2]) || !std::isfinite(g[3])) return fail(OT_ERR_INVALID, "grid must be finite");
         if (!(g[1] > 0.0) || !(g[3] > 0.0)) return fail(OT_ERR_INVALID, "the steps of a grid must be positive");
     }
+    const int32_t G = grp ? grp->n : 1;
+    if (grp) {
+        if (!grp->ids || !grp->ungrouped) return fail(OT_ERR_INVALID, "NULL argument");
+        if (G < 1 || G > OT_SPOT_GROUPS_MAX) return fail(OT_ERR_INVALID, "n_groups must be 1 .. 256");
+        if (grp->n_ids < 1 || grp->n_ids >= (int64_t)1 << 31) return fail(OT_ERR_INVALID, "n_group_ids must be at least 1 (and below 2^31)");
+        if ((int64_t)n_monitors * G > OT_PSF_GROUP_CELLS_MAX) return fail(OT_ERR_INVALID, "n_monitors * n_groups exceeds 4096 cells");
+        if ((int64_t)n_monitors * G * ny * nz > (int64_t)1 << 27) return fail(OT_ERR_INVALID, "n_monitors * n_groups * ny * nz exceeds 2^27 samples");
+    }
+    const int32_t n_cells = n_monitors * G;  // (a cell is a monitor where there are no groups)
     HIP_TRY(hipSetDevice(c->device));
-    const size_t pixels = (size_t)n_monitors * ny * nz;
+    const size_t pixels = (size_t)n_cells * ny * nz;
     if (!accumulate) {
-        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * 3 * (size_t)n_monitors, c->stream));
-        HIP_TRY(hipMemsetAsync(norm, 0, sizeof(double) * (size_t)n_monitors, c->stream));
+        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * 3 * (size_t)n_cells, c->stream));
+        HIP_TRY(hipMemsetAsync(norm, 0, sizeof(double) * (size_t)n_cells, c->stream));
         HIP_TRY(hipMemsetAsync(re, 0, sizeof(double) * pixels, c->stream));
         HIP_TRY(hipMemsetAsync(im, 0, sizeof(double) * pixels, c->stream));
+        if (grp) HIP_TRY(hipMemsetAsync(grp->ungrouped, 0, sizeof(int64_t) * (size_t)n_monitors, c->stream));
     }
     if (n == 0) return 0;
     ot_monitor* table;
-    int64_t *first, *n_total;
+    int64_t *first, *n_total, *first_cell;
     double *d_axes, *d_reference, *d_grid;
     unsigned int* tickets;
+    MonPsfPartition* d_pp;
     const auto carve = [&](void* base) {
         Carve cv{(uint8_t*)base};
-        table = cv.take<ot_monitor>(n_monitors), first = cv.take<int64_t>((size_t)n_monitors + 1), n_total = cv.take<int64_t>(1);
-        d_axes = cv.take<double>(6 * (size_t)n_monitors), d_reference = cv.take<double>(3 * (size_t)n_monitors), d_grid = cv.take<double>(4 * (size_t)n_monitors);
+        table = cv.take<ot_monitor>(n_cells), first = cv.take<int64_t>((size_t)n_monitors + 1), n_total = cv.take<int64_t>(1);
+        d_axes = cv.take<double>(6 * (size_t)n_cells), d_reference = cv.take<double>(3 * (size_t)n_cells), d_grid = cv.take<double>(4 * (size_t)n_cells);
         tickets = cv.take<unsigned int>(MON_PSF_PARTIAL_ROWS);
+        first_cell = cv.take<int64_t>((size_t)n_cells + 1, grp != nullptr), d_pp = cv.take<MonPsfPartition>(1, grp != nullptr);
         return cv.used;
     };
     if (c->psf.ensure(carve(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of PSF scratch failed");
@@ -2260,25 +2279,59 @@ int ot_monitor_psf_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, c
     HIP_TRY(hipStreamSynchronize(c->stream));
     const int64_t total = host_first[n_monitors];
     if (total == 0) return 0;
-    int32_t max_chunks = 1;
+    int32_t max_chunks = 1;  // (of a monitor: no cell of it has more)
     for (int32_t m = 0; m < n_monitors; ++m) max_chunks = std::max(max_chunks, mon_psf_chunks(host_first[m + 1] - host_first[m]));
-    const int64_t n_pairs = (int64_t)n_monitors * mon_psf_parts(ny) * mon_psf_parts(nz);
-    const int64_t pairs_a_launch = std::min<int64_t>(n_pairs, std::max(1, MON_PSF_PARTIAL_ROWS / max_chunks));
-    int64_t* hit_index;
-    double *Px, *Py, *Pz, *tt, *partials;
+    const int64_t n_pairs = (int64_t)n_cells * mon_psf_parts(ny) * mon_psf_parts(nz);
+    int64_t pairs_a_launch = std::min<int64_t>(n_pairs, std::max(1, MON_PSF_PARTIAL_ROWS / max_chunks));
+    // the partition tiles: MON_PSF_PART_TILE consecutive hits of one monitor each, one empty tile for a monitor without a hit
+    std::vector<MonPsfTile> tiles;
+    for (int32_t m = 0; grp && m < n_monitors; ++m) {
+        const int64_t h0 = host_first[m], h1 = host_first[m + 1], base = (int64_t)G * (int64_t)tiles.size();
+        const int32_t nt = (int32_t)std::max<int64_t>(1, (h1 - h0 + MON_PSF_PART_TILE - 1) / MON_PSF_PART_TILE);
+        for (int32_t k = 0; k < nt; ++k)
+            tiles.push_back({h0 + (int64_t)k * MON_PSF_PART_TILE, std::min(h1, h0 + (int64_t)(k + 1) * MON_PSF_PART_TILE), base, m, k, nt, 0});
+    }
+    const int64_t n_count = (int64_t)G * (int64_t)tiles.size();
+    int64_t *hit_index, *to_hit_index, *tile_off;
+    double *Px, *Py, *Pz, *tt, *to_Px, *to_Py, *to_Pz, *to_t, *partials;
+    MonPsfTile* part;
+    int32_t* tile_count;
+    // the partials: a launch's rows; with groups the cells' chunk counts are not known yet, and no plan of theirs takes more rows
+    // than the monitors' most chunks allow
+    const size_t rows = grp ? (size_t)std::min<int64_t>(n_pairs * max_chunks, MON_PSF_PARTIAL_ROWS) : (size_t)pairs_a_launch * max_chunks;
     const auto carve_hits = [&](void* base) {
         Carve cv{(uint8_t*)base};
         hit_index = cv.take<int64_t>(total), Px = cv.take<double>(total), Py = cv.take<double>(total), Pz = cv.take<double>(total), tt = cv.take<double>(total);
-        partials = cv.take<double>((size_t)pairs_a_launch * max_chunks * MON_PSF_ROW);
+        partials = cv.take<double>(rows * MON_PSF_ROW);
+        const bool g = grp != nullptr;
+        to_hit_index = cv.take<int64_t>(total, g), to_Px = cv.take<double>(total, g), to_Py = cv.take<double>(total, g), to_Pz = cv.take<double>(total, g);
+        to_t = cv.take<double>(total, g);
+        part = cv.take<MonPsfTile>(tiles.size(), g), tile_count = cv.take<int32_t>(n_count + 1, g), tile_off = cv.take<int64_t>(n_count + 1, g);
         return cv.used;
     };
     if (c->psf_hits.ensure(carve_hits(nullptr))) return fail(OT_ERR_HIP, "hipMalloc of the PSF hit list failed");
     carve_hits(c->psf_hits.p);
+    if (grp && c->scan_tmp.ensure(scan_tmp_bytes<int64_t>(n_count + 1) + 256)) return fail(OT_ERR_HIP, "hipMalloc of scan scratch failed");
     if (const int rc = record_passes(c, mons, n_monitors, ms, n, seg_count, n_rays, total, first, hit_index, Px, Py, Pz, tt, n_total)) return rc;
-    HIP_TRY(hipMemcpyAsync(table, mons, sizeof(ot_monitor) * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_axes, axes, sizeof(double) * 6 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_reference, reference, sizeof(double) * 3 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_grid, grid, sizeof(double) * 4 * (size_t)n_monitors, hipMemcpyHostToDevice, c->stream));
+    // the tables of the sum, a row per cell: those of monitor m for each of its groups
+    std::vector<ot_monitor> cell_mons;
+    std::vector<double> cell_tables;
+    if (grp) {
+        cell_mons.resize(n_cells), cell_tables.resize(13 * (size_t)n_cells);
+        double *ca = cell_tables.data(), *cr = ca + 6 * (size_t)n_cells, *cg = cr + 3 * (size_t)n_cells;
+        for (int32_t k = 0; k < n_cells; ++k) {
+            const int32_t m = k / G;
+            cell_mons[k] = mons[m];
+            std::copy(axes + 6 * (size_t)m, axes + 6 * (size_t)m + 6, ca + 6 * (size_t)k);
+            std::copy(reference + 3 * (size_t)m, reference + 3 * (size_t)m + 3, cr + 3 * (size_t)k);
+            std::copy(grid + 4 * (size_t)m, grid + 4 * (size_t)m + 4, cg + 4 * (size_t)k);
+        }
+        mons = cell_mons.data(), axes = ca, reference = cr, grid = cg;
+    }
+    HIP_TRY(hipMemcpyAsync(table, mons, sizeof(ot_monitor) * (size_t)n_cells, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_axes, axes, sizeof(double) * 6 * (size_t)n_cells, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_reference, reference, sizeof(double) * 3 * (size_t)n_cells, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_grid, grid, sizeof(double) * 4 * (size_t)n_cells, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(tickets, 0, sizeof(unsigned int) * MON_PSF_PARTIAL_ROWS, c->stream));
     MonPsf ps{};
     ps.first = first, ps.hit_index = hit_index, ps.Px = Px, ps.Py = Py, ps.Pz = Pz, ps.t = tt;
@@ -2288,6 +2341,28 @@ int ot_monitor_psf_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, c
     ps.partials = partials, ps.ticket = tickets;
     ps.re = re, ps.im = im, ps.norm = norm, ps.counts = (long long*)counts;
     ps.kind = reference_kind, ps.amplitude_mode = amplitude_mode, ps.ny = ny, ps.nz = nz, ps.max_chunks = max_chunks;
+    if (grp) {
+        HIP_TRY(hipMemcpyAsync(part, tiles.data(), sizeof(MonPsfTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
+        const MonPsfPartition pp{G, (int32_t)grp->n_ids, n_cells, 0, grp->ids, part, tile_count, tile_off, n_count, first_cell, to_hit_index,
+                                 to_Px, to_Py, to_Pz, to_t, (unsigned long long*)grp->ungrouped};
+        HIP_TRY(hipMemcpyAsync(d_pp, &pp, sizeof(pp), hipMemcpyHostToDevice, c->stream));
+        ps.pp = d_pp;
+        ps.mode = 1;
+        hipLaunchKernelGGL(k_mon_psf, dim3((unsigned)tiles.size()), dim3(MON_THREADS), 0, c->stream, table, ms, ps);
+        exclusive_scan<int32_t, int64_t>(c->scan_tmp.p, tile_count, tile_off, n_count + 1, c->stream);
+        ps.mode = 2;
+        hipLaunchKernelGGL(k_mon_psf, dim3((unsigned)tiles.size()), dim3(MON_THREADS), 0, c->stream, table, ms, ps);
+        HIP_TRY(hipGetLastError());
+        std::vector<int64_t> host_cell((size_t)n_cells + 1);
+        HIP_TRY(hipMemcpyAsync(host_cell.data(), first_cell, sizeof(int64_t) * host_cell.size(), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (host_cell[n_cells] == 0) return 0;
+        max_chunks = 1;
+        for (int32_t k = 0; k < n_cells; ++k) max_chunks = std::max(max_chunks, mon_psf_chunks(host_cell[k + 1] - host_cell[k]));
+        pairs_a_launch = std::min<int64_t>(n_pairs, std::max(1, MON_PSF_PARTIAL_ROWS / max_chunks));
+        ps.mode = 0, ps.max_chunks = max_chunks;
+        ps.first = first_cell, ps.hit_index = to_hit_index, ps.Px = to_Px, ps.Py = to_Py, ps.Pz = to_Pz, ps.t = to_t;
+    }
     for (int64_t pair0 = 0; pair0 < n_pairs; pair0 += pairs_a_launch) {
         ps.pair0 = (int32_t)pair0;
         const int64_t pairs = std::min(pairs_a_launch, n_pairs - pair0);
@@ -2295,6 +2370,26 @@ int ot_monitor_psf_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, c
     }
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int ot_monitor_psf_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, int32_t reference_kind, const double* reference,
+                        const double* grid, int32_t ny, int32_t nz, const ot_segment_source* src, const void* intensity, const void* n_index,
+                        const void* pathlength, const double* wavelength, int64_t n_wavelengths, double wavelength_uniform, int32_t amplitude_mode,
+                        int64_t n, const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* norm, double* re, double* im,
+                        int32_t accumulate) {
+    return psf_call(c, mons, n_monitors, axes, reference_kind, reference, grid, ny, nz, nullptr, src, intensity, n_index, pathlength, wavelength,
+                    n_wavelengths, wavelength_uniform, amplitude_mode, n, seg_count, n_rays, counts, norm, re, im, accumulate);
+}
+
+int ot_monitor_psf_groups_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, int32_t reference_kind,
+                               const double* reference, const double* grid, int32_t ny, int32_t nz, const int32_t* groups, int64_t n_group_ids,
+                               int32_t n_groups, const ot_segment_source* src, const void* intensity, const void* n_index, const void* pathlength,
+                               const double* wavelength, int64_t n_wavelengths, double wavelength_uniform, int32_t amplitude_mode, int64_t n,
+                               const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* norm, double* re, double* im, int64_t* ungrouped,
+                               int32_t accumulate) {
+    const PsfGroups grp{groups, n_group_ids, n_groups, ungrouped};
+    return psf_call(c, mons, n_monitors, axes, reference_kind, reference, grid, ny, nz, &grp, src, intensity, n_index, pathlength, wavelength,
+                    n_wavelengths, wavelength_uniform, amplitude_mode, n, seg_count, n_rays, counts, norm, re, im, accumulate);
 }
 
 int ot_debug_last_launch(ot_ctx* c, int32_t info[8]) {

@@ -253,6 +253,30 @@ def psf_plan(ny, nz, hits=()):
             "launches": -(-pairs // a_launch) if pairs else 0}
 
 
+# -- diffraction PSF per ray group (ot_monitor_psf_groups_many) ------------------------------------------------------------
+PSF_PART_TILE = 2048          # misc_kernels.h MON_PSF_PART_TILE: consecutive hits of one monitor a workgroup of the partition takes
+PSF_GROUP_CELLS_MAX = 4096    # optable_hip.h OT_PSF_GROUP_CELLS_MAX: n_monitors x n_groups of one call
+PSF_GROUP_SAMPLES_MAX = 1 << 27  # n_monitors x n_groups x ny x nz of one call
+
+
+def psf_groups_plan(ny, nz, cell_hits, tile=PSF_PART_TILE):
+    """How ot_monitor_psf_groups_many walks an image of ny x nz samples whose cells have `cell_hits` hits: an [M][G] nested list
+    (or array) of the GROUPED hits of every cell (monitor, group), masked hits left out (optable_hip.hip, the same rule).
+    {"partition_tiles": per monitor, the workgroups of each of the two partition passes — ceil(hits / tile) over the monitor's
+    hits, 1 for a monitor without a hit (the plan knows the grouped hits only: a monitor with masked hits has ceil((grouped +
+    ungrouped) / tile)); "chunks": per cell [M][G], `psf_plan`'s chunks with the cell in a monitor's place; "pairs_a_launch",
+    "launches": `psf_plan`'s over the M x G cells}."""
+    rows = [[int(h) for h in row] for row in cell_hits]
+    G = len(rows[0]) if rows else 0
+    tile = int(tile)
+    if (any(len(row) != G for row in rows) or (rows and not 1 <= G <= SPOT_GROUPS_MAX) or len(rows) * G > PSF_GROUP_CELLS_MAX
+            or len(rows) * G * int(ny) * int(nz) > PSF_GROUP_SAMPLES_MAX or tile < 1):
+        raise ValueError(f"no PSF of {len(rows)} monitors x {G} groups of {ny} x {nz} samples")
+    plan = psf_plan(ny, nz, [h for row in rows for h in row])
+    return {"partition_tiles": [max(1, -(-sum(row) // tile)) for row in rows], "chunks": [plan["chunks"][m * G:(m + 1) * G] for m in range(len(rows))],
+            "pairs_a_launch": plan["pairs_a_launch"], "launches": plan["launches"]}
+
+
 # -- what the private halves of monitor_*_many and fluence_map share: arguments in, outputs out -------------------------------
 def _doubles(array):
     return array.ctypes.data_as(C.POINTER(C.c_double))
@@ -1080,25 +1104,47 @@ class Engine:
         with self.lock:
             return self._monitor_psf_many(list(monitor_structs), axes, reference_kind, reference, grid, pixels, segs, wavelength, amplitude_mode, into)
 
-    def _monitor_psf_many(self, mons, axes, reference_kind, reference, grid, pixels, segs, wavelength, amplitude_mode, into):
+    def _monitor_psf_many(self, mons, axes, reference_kind, reference, grid, pixels, segs, wavelength, amplitude_mode, into, groups=None):
+        """Both PSF calls: groups None, or (ids, G) — then every output has a group axis behind the monitors' and `ungrouped` follows."""
         dev, M, (ny, nz) = segs.device, len(mons), pixels
         axes, reference, grid = _float64_tables(f"axes must be [{M}, 6], reference [{M}, 3] and grid [{M}, 4]", (axes, (M, 6)), (reference, (M, 3)),
                                                 (grid, (M, 4)))
         if segs.precision != "f64":
             raise ValueError("a PSF needs double-precision segments")
         psf_plan(ny, nz)
+        cell, call, tables, tail, shapes = (M,), "ot_monitor_psf_many", (), [], f"[{M}, 3], float64 norm of shape [{M}] and float64 re, im of shape [{M}, {ny}, {nz}]"
+        if groups is not None:
+            ids, G = groups
+            psf_groups_plan(ny, nz, [[0] * G] * max(M, 1))
+            if (not torch.is_tensor(ids) or ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous() or ids.numel() < 1
+                    or ids.device.type != dev.type):
+                raise ValueError(f"groups: a contiguous int32 vector of one id per input ray on {dev}")
+            cell, call, tables, tail = (M, G), "ot_monitor_psf_groups_many", (ids.data_ptr(), int(ids.numel()), G), [(torch.int64, (M,))]
+            shapes = f"[{M}, {G}, 3], float64 norm of shape [{M}, {G}], float64 re, im of shape [{M}, {G}, {ny}, {nz}] and int64 ungrouped of shape [{M}]"
         wavelength = _wavelength_arg(wavelength, dev)
-        outs = _outputs(dev, [(torch.int64, (M, 3)), (torch.float64, (M,)), (torch.float64, (M, ny, nz)), (torch.float64, (M, ny, nz))], into,
+        outs = _outputs(dev, [(torch.int64, cell + (3,)), (torch.float64, cell), (torch.float64, cell + (ny, nz)), (torch.float64, cell + (ny, nz))] + tail, into,
                         torch.zeros,  # (zeros: the library is not called for nothing)
-                        f"into: contiguous int64 counts of shape [{M}, 3], float64 norm of shape [{M}] and float64 re, im of shape [{M}, {ny}, {nz}] on {dev}")
+                        f"into: contiguous int64 counts of shape {shapes} on {dev}")
         src, n_segments, count, n_rays = segment_source(segs)
         if M == 0 or n_segments == 0:  # (zero-size tensors have no address to hand over; nothing to add)
             return outs
-        abi.check(self.lib.ot_monitor_psf_many(self._ctx, (abi.OtMonitor * M)(*mons), M, _doubles(axes), int(reference_kind), _doubles(reference),
-                                               _doubles(grid), ny, nz, C.byref(src), segs.field("intensity").data_ptr(), segs.field("n").data_ptr(),
-                                               segs.field("pathlength").data_ptr(), *wavelength, int(amplitude_mode), n_segments, _address(count), n_rays,
-                                               *(t.data_ptr() for t in outs), 0 if into is None else 1), self.lib)
+        abi.check(getattr(self.lib, call)(self._ctx, (abi.OtMonitor * M)(*mons), M, _doubles(axes), int(reference_kind), _doubles(reference),
+                                          _doubles(grid), ny, nz, *tables, C.byref(src), segs.field("intensity").data_ptr(), segs.field("n").data_ptr(),
+                                          segs.field("pathlength").data_ptr(), *wavelength, int(amplitude_mode), n_segments, _address(count), n_rays,
+                                          *(t.data_ptr() for t in outs), 0 if into is None else 1), self.lib)
         return outs
+
+    def monitor_psf_groups_many(self, monitor_structs, axes, reference_kind, reference, grid, pixels, groups, n_groups, segs: SegmentBatch, wavelength,
+                                amplitude_mode=0, into=None):
+        """The diffraction PSF per ray group (ot_monitor_psf_groups_many): `monitor_psf_many` with a group axis — a hit of a segment
+        of input ray r belongs to group groups[r], and the fields of different groups are never added.  groups: a contiguous int32
+        vector on the segments' device, one id per input ray; ids outside 0 .. n_groups - 1 (and rays beyond the table) are masked
+        and tallied.  Returns (counts, norm, re, im, ungrouped): int64 [M, G, 3], float64 [M, G], float64 [M, G, ny, nz] twice and
+        int64 [M] (the masked hits) device tensors, zeroed by the call — or `into`, such a tuple from an earlier call, with this
+        call's hits added to it.  The same bits every run; with G = 1 and every id 0, `monitor_psf_many`'s."""
+        with self.lock:
+            return self._monitor_psf_many(list(monitor_structs), axes, reference_kind, reference, grid, pixels, segs, wavelength, amplitude_mode, into,
+                                          groups=(groups, int(n_groups)))
 
     def monitor_field_many(self, monitor_structs, axes, edges, bins, segs: SegmentBatch, wavelength, amplitude_mode=0, into=None):
         """Coherent detector images of a list of monitors over a double-precision SegmentBatch read as it lies

@@ -453,8 +453,8 @@ class OpticalTable:
         (sqrt(intensity): intensity is a power), "linear" or "unit" (every hit 1).  The model: each ray is a plane-wave sample, so
         the result is the diffraction PSF when the rays sample the direction cosines (`focus`) or the pupil positions
         (`direction`) uniformly, with the intensity as weight, and that distribution's weighted sum for any other; no pi on
-        reflection; hits of different wavelengths add coherently; the image repeats with the period wavelength / (n x ray
-        spacing).  Hits whose phase turns more than half a cycle from one sample to the next are summed all the same, counted in
+        reflection; every hit of a monitor adds to ONE field, whatever its wavelength or field point (`psf_grouped_all` keeps a field per
+        group of rays); the image repeats with the period wavelength / (n x ray spacing).  Hits whose phase turns more than half a cycle from one sample to the next are summed all the same, counted in
         `MonitorPSF.aliased` and announced by one RuntimeWarning.  The result is the same bits every run.  `segs` must be double
         precision.  `into`: the list an earlier call with the same monitors, reference, grid and amplitude returned; this call's
         hits are added to it (a field is linear: the chunks of a streamed trace add)."""
@@ -495,6 +495,64 @@ class OpticalTable:
         """One monitor as a diffraction image (`psf_all` for it alone): a `MonitorPSF`."""
         return self.psf_all(segs, wavelength, focus=focus, direction=direction, step=step, pixels=pixels, centre=centre, monitors=[monitor],
                             amplitude=amplitude)[0]
+
+    def psf_grouped_all(self, segs, wavelength, groups, n_groups=None, focus=None, direction=None, step=None, pixels=65, centre=(0.0, 0.0),
+                        monitors=None, amplitude="sqrt", labels=None, into=None):
+        """`psf_all` PER RAY GROUP: one `MonitorPSFGroups` per monitor, in their order — one diffraction image per group of input
+        rays from one trace and one pass over the segments (ot_monitor_psf_groups_many).  The fields of different groups are never
+        added: a batch multiplexed in wavelength gives the image of every wavelength, whose INTENSITIES an instrument adds
+        (`MonitorPSFGroups.intensity()`, `.strehl()`, `.mtf()`: the polychromatic PSF, Strehl ratio and MTF), one of several field
+        points the image of every field point.  groups, n_groups and labels as for `spots_grouped_all`: one integer id per INPUT
+        ray (`RayBatch.groups_by_wavelength()` gives one group per wavelength), G = 1 .. 256 (None: max id + 1), and rays whose id
+        is outside 0 .. G - 1 are in no group — their hits are in no image and are counted in `MonitorPSFGroups.ungrouped`.  A hit
+        belongs to the group of the ray its segment descends from, whatever the layout and wherever in a ray tree.  Every other
+        argument, the model, the aliasing warning and the requirement of double precision are `psf_all`'s; monitors x G may not
+        exceed 4096, monitors x G x samples not 2^27.  Group g of the result is bit for bit `psf_all` of that group's rays traced
+        alone in the same order, the same bits every run.  `into`: the list an earlier call with the same monitors, reference,
+        grid, amplitude and G returned; this call's hits are added to it, with this call's `groups` (the chunks of a streamed trace
+        each bring their own table)."""
+        import warnings
+        from .psf import MonitorPSFGroups, psf_amplitude, psf_grid
+        from .spots import spot_group_ids
+        from .wavefront import wavefront_reference
+
+        monitors = list(self.monitors if monitors is None else monitors)
+        M = len(monitors)
+        kind, lab, local = wavefront_reference(focus, direction, monitors)
+        grid, pixels, step, centres = psf_grid(step, pixels, centre, M)
+        mode = psf_amplitude(amplitude)
+        ids, G = spot_group_ids(groups, segs.n_rays, n_groups, device=segs.device)
+        if labels is not None and len(labels) != G:
+            raise ValueError(f"labels: one per group ({G}), not {len(labels)}")
+        if segs.precision != "f64":
+            raise ValueError("psf_grouped_all needs a double-precision SegmentBatch: a path length in single precision is a hundredth of a wave wrong at table scale")
+        wavelength = _wavelengths_of(wavelength, segs, "a PSF")
+        name = ("focus", "direction")[kind]
+        stack = None
+        if into is not None:
+            into, stack = _into_stack(into, M, lambda k, p: isinstance(p, MonitorPSFGroups) and p.monitor is monitors[k] and p.amplitude == amplitude
+                                      and p.reference == (name, tuple(lab[k])) and p.step == step and p.centre == tuple(centres[k])
+                                      and tuple(p.re.shape) == (G,) + pixels,
+                                      "into: the list an earlier psf_grouped_all returned for the same monitors, reference, grid, amplitude and n_groups")
+            if not monitors:
+                return into
+        before = 0 if stack is None else int(stack[0][:, :, 2].sum().item())
+        counts, norm, re, im, ungrouped = _engine().monitor_psf_groups_many([monitor_struct(m) for m in monitors], _monitor_axes(monitors), kind, local, grid,
+                                                                            pixels, ids, G, segs, wavelength, amplitude_mode=mode, into=stack)
+        if into is None:
+            into = [MonitorPSFGroups(m, counts[k], norm[k], re[k], im[k], ungrouped[k], (name, lab[k]), grid[k], step, centres[k], amplitude, labels=labels,
+                                     stack=(counts, norm, re, im, ungrouped, k)) for k, m in enumerate(monitors)]
+        aliased = (int(counts[:, :, 2].sum().item()) if M else 0) - before
+        if aliased > 0:
+            warnings.warn(f"psf_grouped_all: {aliased} hits are aliased — their phase turns more than half a cycle from one sample to the next, and the "
+                          "sampled image means nothing for them: use a smaller step", RuntimeWarning, stacklevel=2)
+        return into
+
+    def psf_grouped_batch(self, monitor, segs, wavelength, groups, n_groups=None, focus=None, direction=None, step=None, pixels=65, centre=(0.0, 0.0),
+                          amplitude="sqrt", labels=None):
+        """One monitor as diffraction images per ray group (`psf_grouped_all` for it alone): a `MonitorPSFGroups`."""
+        return self.psf_grouped_all(segs, wavelength, groups, n_groups=n_groups, focus=focus, direction=direction, step=step, pixels=pixels, centre=centre,
+                                    monitors=[monitor], amplitude=amplitude, labels=labels)[0]
 
     def field_all(self, segs, wavelength=0.0, bins=30, monitors=None, into=None, amplitude="sqrt"):
         """Every monitor of the table (or those given) as a COHERENT image: one `MonitorField` per monitor, in their order — per
