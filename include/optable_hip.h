@@ -800,6 +800,38 @@ int ot_monitor_wavefront_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_mon
                               int64_t n_segments, const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* sums,
                               int32_t accumulate);
 
+/* Wavefront error per ray group: ot_monitor_wavefront_many with a GROUP axis on the cells — the 61 sums of every wavelength or
+ * field point of one batch from one trace (Zernike coefficients against wavelength and against field).  A CELL is a pair
+ * (monitor m, group g) of the list [m][g].  mons, axes, reference_kind, coordinates, src, intensity, n_index, pathlength,
+ * n_segments, seg_count, n_rays and accumulate are ot_monitor_wavefront_many's, and so are the hit test, W, (p, q), inside,
+ * the weight and the 61 sums of a hit.  The group of a hit of slot s is groups[ray[s]], exactly as for
+ * ot_monitor_spot_groups_many: `groups` is a DEVICE table of n_group_ids int32 ids, one per input ray; a hit whose ray index is
+ * outside 0 .. n_group_ids - 1 (nothing is read out of range) or whose id is outside 0 .. n_groups - 1 belongs to NO cell and no
+ * tally of such hits is kept: id -1 masks a ray.
+ * Every field point has its own image point and its own pupil centre, so reference, pupil and piston are PER CELL, host:
+ * reference[m * n_groups + g] three doubles (F_loc or u_loc in monitor m's frame), pupil[m * n_groups + g] = (c_y, c_z, R),
+ * piston[m * n_groups + g] one double.  axes stay [n_monitors][6].
+ * counts: device, [n_monitors][n_groups][2] int64 (inside, outside).  sums: device, [n_monitors][n_groups][61] double, S, T, Q
+ * in ot_monitor_wavefront_many's order.
+ * Determinism: as ot_monitor_wavefront_many — no floating-point atomic.  Per monitor a wave walks the distinct groups among its
+ * hitting lanes in ascending order of each group's first lane and sums each over its lanes by the same 61 butterflies, the other
+ * lanes carrying 0.
+ *   With n_groups = 1 and every id 0, group 0 of this call equals ot_monitor_wavefront_many with the same reference, pupil and
+ *   piston, bit for bit.
+ *   Group g of this call equals group 0 of the call with n_groups = 1, the ids (id == g ? 0 : -1) and cell (m, g)'s reference,
+ *   pupil and piston for monitor m, bit for bit.
+ * Cell groups: a launch takes OT_WAVEFRONT_MONITORS = 28 consecutive cells of [m][g], which may begin and end inside a monitor; a
+ * call over C cells is ceil(C / 28) passes over the segments.
+ * OT_ERR_INVALID, nothing launched or zeroed: everything ot_monitor_wavefront_many refuses (of reference, pupil and piston: per
+ * cell); groups NULL; n_groups outside 1 .. OT_SPOT_GROUPS_MAX; n_group_ids < 1 (or >= 2^31); n_monitors * n_groups >
+ * OT_WAVEFRONT_GROUP_CELLS_MAX. */
+#define OT_WAVEFRONT_GROUP_CELLS_MAX 4096
+int ot_monitor_wavefront_groups_many(ot_ctx* ctx, const ot_monitor* mons, int32_t n_monitors, const double* axes, int32_t reference_kind,
+                                     const double* reference, int32_t coordinates, const double* pupil, const double* piston,
+                                     const int32_t* groups, int64_t n_group_ids, int32_t n_groups, const ot_segment_source* src,
+                                     const void* intensity, const void* n_index, const void* pathlength, int64_t n_segments,
+                                     const int32_t* seg_count, int64_t n_rays, int64_t* counts, double* sums, int32_t accumulate);
+
 /* Diffraction PSF: the plane waves of every monitor's hits summed over a grid of image samples, on the device.
  * ot_monitor_psf_many uses the hit test of ot_monitor_record_many, unchanged.  A hit of slot s on monitor m gives the local point P,
  * the distance t and the renormalised local direction d.  Further: n = n_index[s]; L = t n + pathlength[s]; the wavelength lambda,

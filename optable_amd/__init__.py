@@ -21,7 +21,7 @@ from .assemblies import (ComponentGroup, GlassSlab, CircleGlassSlab, MLA, MMA, M
 from .monitors import Monitor
 from .fluence import FluenceMap
 from .spots import MonitorSpots, MonitorSpotGroups
-from .wavefront import MonitorWavefront
+from .wavefront import MonitorWavefront, MonitorWavefrontGroups
 from .psf import MonitorPSF, MonitorPSFGroups
 from .table import OpticalTable
 from .scene import compile_scene, CompiledScene, SceneError

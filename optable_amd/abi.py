@@ -172,6 +172,9 @@ SYMBOLS = {
                                               _i32, _vp, _i64, _i32, C.POINTER(OtSegmentSource), _vp, _i64, _vp, _i64, _vp, _vp, _i32]),
     "ot_monitor_wavefront_many": (C.c_int, [_vp, C.POINTER(OtMonitor), _i32, C.POINTER(C.c_double), _i32, C.POINTER(C.c_double), _i32, C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.POINTER(OtSegmentSource), _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32]),
+    "ot_monitor_wavefront_groups_many": (C.c_int, [_vp, C.POINTER(OtMonitor), _i32, C.POINTER(C.c_double), _i32, C.POINTER(C.c_double), _i32,
+                                                   C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, _i64, _i32, C.POINTER(OtSegmentSource), _vp, _vp,
+                                                   _vp, _i64, _vp, _i64, _vp, _vp, _i32]),
     "ot_monitor_psf_many": (C.c_int, [_vp, C.POINTER(OtMonitor), _i32, C.POINTER(C.c_double), _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32, _i32,
                                       C.POINTER(OtSegmentSource), _vp, _vp, _vp, _vp, _i64, C.c_double, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32]),
     "ot_monitor_psf_groups_many": (C.c_int, [_vp, C.POINTER(OtMonitor), _i32, C.POINTER(C.c_double), _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32,

@@ -986,6 +986,8 @@ struct MonSpots {
     // the group mode (below): n_groups > 0, a cell is (monitor, plane, group) and counts / sums are [n_monitors][n_off][n_groups] (x 6)
     const int32_t* groups;               // [n_group_ids], one id per input ray
     int32_t n_group_ids, n_groups;       // n_groups = 0: the two other modes
+    // the wavefront mode's group mode: values = MON_WAVEFRONT_VALUES and n_groups > 0, a cell is (monitor, group); counts / sums are
+    // [n_monitors][n_groups][2] / [61], and reference, pupil and piston [n_monitors][n_groups][3], [..][3], [n_monitors][n_groups]
 };
 // Entry k of a host table of the call (axes, centre, offsets: uploaded before the launch, written by no kernel), read through the constant
 // address space: a scalar load whatever else the kernel holds.  Without it the compiler proves "nothing in this kernel writes
@@ -1015,6 +1017,62 @@ template <class V> __device__ __forceinline__ V wave_sum(V v) {  // every lane g
 // 28 x 63 = 1,764 values, within the 7 x MON_THREADS the last workgroup's threads own.
 static constexpr int MON_WAVEFRONT_CELLS = 28, MON_WAVEFRONT_VALUES = 63, MON_WAVEFRONT_SUMS = 61;
 static_assert(MON_WAVEFRONT_CELLS * MON_WAVEFRONT_VALUES <= MON_SPOT_CELLS * MON_SPOT_VALUES, "a launch's values: seven a thread of the last workgroup");
+// What the wavefront mode and its group mode (below) do alike, as the one source of both: a hit's W, (p, q), inside and W', and
+// the 61 butterflies.  Const: the tables' entries come through mon_table (the group mode, whose cell changes inside a loop over
+// lanes), or through the pointers as they are.
+template <bool Const> __device__ __forceinline__ double mon_entry(const double* table, int32_t k) {
+    if constexpr (Const) return mon_table(table, k);
+    else return table[k];
+}
+// a, f, c, piston: the axes of the monitor and the reference, pupil and piston of the cell.  Returns inside; wi, Wp, p, q are set only then.
+template <bool Const> __device__ __forceinline__ bool mon_wavefront_hit(const MonSpots& sp, const MonSeg& g, const MonLocal& l, const double* a,
+                                                                        const double* f, const double* c, const double* piston, double Px, double Py,
+                                                                        double Pz, double t, double n_index, double pl, double w, double& wi,
+                                                                        double& Wp, double& p, double& q) {
+    const double L = t * n_index + pl;
+    const double Wv = sp.kind == 0 ? L + n_index * ((mon_entry<Const>(f, 0) - Px) * l.dx + (mon_entry<Const>(f, 1) - Py) * l.dy + (mon_entry<Const>(f, 2) - Pz) * l.dz)
+                                   : L - n_index * (Px * mon_entry<Const>(f, 0) + Py * mon_entry<Const>(f, 1) + Pz * mon_entry<Const>(f, 2));
+    const double u = sp.coordinates ? Px * mon_entry<Const>(a, 0) + Py * mon_entry<Const>(a, 1) + Pz * mon_entry<Const>(a, 2)
+                                    : g.dx * mon_entry<Const>(a, 0) + g.dy * mon_entry<Const>(a, 1) + g.dz * mon_entry<Const>(a, 2);
+    const double v = sp.coordinates ? Px * mon_entry<Const>(a, 3) + Py * mon_entry<Const>(a, 4) + Pz * mon_entry<Const>(a, 5)
+                                    : g.dx * mon_entry<Const>(a, 3) + g.dy * mon_entry<Const>(a, 4) + g.dz * mon_entry<Const>(a, 5);
+    const double pp = (u - mon_entry<Const>(c, 0)) / mon_entry<Const>(c, 2), qq = (v - mon_entry<Const>(c, 1)) / mon_entry<Const>(c, 2);
+    const bool inside = pp * pp + qq * qq <= 1.0 && fabs(Wv) < HUGE_VAL;  // (a NaN fails both)
+    if (inside) wi = w, Wp = Wv - mon_entry<Const>(piston, 0), p = pp, q = qq;
+    return inside;
+}
+// the 61 totals of a wave's (wi, Wp, p, q) into v: lane 2 + i keeps total i
+__device__ __forceinline__ void mon_wavefront_sums(double wi, double Wp, double p, double q, int lane, double& v) {
+    double pa[9], qa[9];
+    pa[0] = qa[0] = 1.0;
+#pragma unroll
+    for (int e = 1; e <= 8; ++e) pa[e] = pa[e - 1] * p, qa[e] = qa[e - 1] * q;
+    const double wW = wi * Wp;
+#pragma unroll
+    for (int a = 0; a <= 8; ++a) {  // (by a, so that one w p^a is alive at a time; the place of (a, b) is the header's)
+        const double wa = wi * pa[a];
+#pragma unroll
+        for (int b = 0; a + b <= 8; ++b) {
+            const double total = wave_sum(wa * qa[b]);
+            if (lane == 2 + (a + b) * (a + b + 1) / 2 + b) v = total;
+            asm volatile("" : "+v"(v));         // v takes the total here, not in a chain of selects behind 61 live totals,
+            __builtin_amdgcn_sched_barrier(0);  // and one butterfly at a time: interleaved, their operands take hundreds of registers
+        }
+    }
+#pragma unroll
+    for (int a = 0; a <= 4; ++a) {
+        const double wa = wW * pa[a];
+#pragma unroll
+        for (int b = 0; a + b <= 4; ++b) {
+            const double total = wave_sum(wa * qa[b]);
+            if (lane == 2 + 45 + (a + b) * (a + b + 1) / 2 + b) v = total;
+            asm volatile("" : "+v"(v));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    const double total = wave_sum(wW * Wp);
+    if (lane == 2 + 45 + 15) v = total;
+}
 __device__ __forceinline__ void mon_wavefront_visit(const ot_monitor* __restrict__ mons, const MonSource& src, const MonSeg& g, int64_t s,
                                                     const MonSpots& sp, double* mine, int lane) {
     double w = 1.0, n_index = 0.0, pl = 0.0;
@@ -1032,54 +1090,79 @@ __device__ __forceinline__ void mon_wavefront_visit(const ot_monitor* __restrict
             pl = *reinterpret_cast<const double*>(sp.pathlength + at);
             have = true;
         }
-        const double* a = sp.axes + 6 * m;
-        const double *f = sp.reference + 3 * m, *c = sp.pupil + 3 * m;
         double wi = 0.0, Wp = 0.0, p = 0.0, q = 0.0;
         bool inside = false;
-        if (hit) {
-            const double L = t * n_index + pl;
-            const double Wv = sp.kind == 0 ? L + n_index * ((f[0] - Px) * l.dx + (f[1] - Py) * l.dy + (f[2] - Pz) * l.dz)
-                                           : L - n_index * (Px * f[0] + Py * f[1] + Pz * f[2]);
-            const double u = sp.coordinates ? Px * a[0] + Py * a[1] + Pz * a[2] : g.dx * a[0] + g.dy * a[1] + g.dz * a[2];
-            const double v = sp.coordinates ? Px * a[3] + Py * a[4] + Pz * a[5] : g.dx * a[3] + g.dy * a[4] + g.dz * a[5];
-            const double pp = (u - c[0]) / c[2], qq = (v - c[1]) / c[2];
-            inside = pp * pp + qq * qq <= 1.0 && fabs(Wv) < HUGE_VAL;  // (a NaN fails both)
-            if (inside) wi = w, Wp = Wv - sp.piston[m], p = pp, q = qq;
-        }
+        if (hit)
+            inside = mon_wavefront_hit<false>(sp, g, l, sp.axes + 6 * m, sp.reference + 3 * m, sp.pupil + 3 * m, sp.piston + m, Px, Py, Pz, t, n_index, pl,
+                                              w, wi, Wp, p, q);
         const unsigned long long bi = __ballot(inside), bo = __ballot(hit && !inside);
         double v = lane == 0 ? (double)__popcll(bi) : lane == 1 ? (double)__popcll(bo) : 0.0;
-        if (bi) {
-            double pa[9], qa[9];
-            pa[0] = qa[0] = 1.0;
-#pragma unroll
-            for (int e = 1; e <= 8; ++e) pa[e] = pa[e - 1] * p, qa[e] = qa[e - 1] * q;
-            const double wW = wi * Wp;
-#pragma unroll
-            for (int a = 0; a <= 8; ++a) {  // (by a, so that one w p^a is alive at a time; the place of (a, b) is the header's)
-                const double wa = wi * pa[a];
-#pragma unroll
-                for (int b = 0; a + b <= 8; ++b) {
-                    const double total = wave_sum(wa * qa[b]);
-                    if (lane == 2 + (a + b) * (a + b + 1) / 2 + b) v = total;
-                    asm volatile("" : "+v"(v));         // v takes the total here, not in a chain of selects behind 61 live totals,
-                    __builtin_amdgcn_sched_barrier(0);  // and one butterfly at a time: interleaved, their operands take hundreds of registers
-                }
-            }
-#pragma unroll
-            for (int a = 0; a <= 4; ++a) {
-                const double wa = wW * pa[a];
-#pragma unroll
-                for (int b = 0; a + b <= 4; ++b) {
-                    const double total = wave_sum(wa * qa[b]);
-                    if (lane == 2 + 45 + (a + b) * (a + b + 1) / 2 + b) v = total;
-                    asm volatile("" : "+v"(v));
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            const double total = wave_sum(wW * Wp);
-            if (lane == 2 + 45 + 15) v = total;
-        }
+        if (bi) mon_wavefront_sums(wi, Wp, p, q, lane, v);
         if (lane < MON_WAVEFRONT_VALUES) mine[k * MON_WAVEFRONT_VALUES + lane] += v;
+    }
+}
+// The group mode of the wavefront mode (ot_monitor_wavefront_groups_many; values = MON_WAVEFRONT_VALUES and n_groups > 0): a cell
+// per (monitor m, GROUP g) of the list [m][g], 63 doubles as above, with reference, pupil and piston PER CELL ([m][g][3],
+// [m][g][3], [m][g]: every field point has its own image point and pupil centre); axes stay [m][6].  The group of a hit is
+// groups[ray[s]] as in mon_groups_visit (below): loaded once per slot at its first hit, nothing read out of range, a ray outside
+// [0, n_group_ids) or an id outside [0, n_groups) in no cell and not tallied.
+// A launch takes MON_WAVEFRONT_CELLS consecutive cells, cell0 .. cell0 + n_cells, which may begin and end inside a monitor: the
+// visit walks the monitors cell0 / G .. (cell0 + n_cells - 1) / G with one hit test each, and where its ballot is not zero the
+// DISTINCT groups among the hitting lanes in ascending order of each group's first lane.  Group g0: the cell's tables by scalar
+// loads (mon_table), W, (p, q), inside and W' for the lanes with hit && id == g0 (mon_wavefront_hit, the ungrouped source),
+// every other lane 0, the two popcounts, the 61 butterflies (mon_wavefront_sums, skipped where no lane is inside), lanes 0..62
+// adding to the wave's row of the cell; those lanes cleared.  A group whose cell is outside the launch's window is skipped, its
+// lanes cleared all the same.  With one group of id 0 the inputs of every add are the ungrouped visit's, and so is every bit.
+__device__ __forceinline__ void mon_wavefront_groups_visit(const ot_monitor* __restrict__ mons, const MonSource& src, const MonSeg& g, int64_t s,
+                                                           const MonSpots& sp, double* mine, int lane) {
+    double w = 1.0, n_index = 0.0, pl = 0.0;
+    int32_t id = -1;
+    bool have = false;
+    const int32_t m_last = (sp.cell0 + sp.n_cells - 1) / sp.n_groups;
+    for (int32_t m = sp.cell0 / sp.n_groups; m <= m_last; ++m) {  // wave-uniform
+        double Px, Py, Pz, t;
+        const MonLocal l = mon_local(mons[m], g.ox, g.oy, g.oz, g.dx, g.dy, g.dz);
+        const bool hit = g.valid && mon_cross(mons[m], l, l.ox, g.len, Px, Py, Pz, t);
+        if (!__ballot(hit)) continue;
+        if (hit && !have) {
+            const int64_t at = mon_at(s, src.tile_stride, 8);
+            if (sp.intensity) w = *reinterpret_cast<const double*>(sp.intensity + at);
+            n_index = *reinterpret_cast<const double*>(sp.n_index + at);
+            pl = *reinterpret_cast<const double*>(sp.pathlength + at);
+            const int32_t ray = *reinterpret_cast<const int32_t*>(src.ray + mon_at(s, src.ray_stride, 4));
+            if (ray >= 0 && ray < sp.n_group_ids) id = sp.groups[ray];
+            if (id < 0 || id >= sp.n_groups) id = -1;
+            have = true;
+        }
+        const int32_t row0 = m * sp.n_groups - sp.cell0;  // the row of (m, group 0) in the launch's window: may lie before it
+        unsigned long long rest = __ballot(hit && id >= 0);
+        while (rest) {
+            const int32_t g0 = __builtin_amdgcn_readlane(id, __ffsll((long long)rest) - 1);
+            const bool in = hit && id == g0;
+            rest &= ~__ballot(in);
+            const int32_t k = row0 + g0;
+            if (k < 0 || k >= sp.n_cells) continue;
+            const int32_t cell = sp.cell0 + k;
+            double wi = 0.0, Wp = 0.0, p = 0.0, q = 0.0;
+            bool inside = false;
+            if (in) {
+                // the hit point again, from operands the compiler cannot trace to the test above: kept from there, P, t and the
+                // local direction stay alive through the 61 butterflies of every group, 22 registers more than the ungrouped visit
+                // holds and past four workgroups a CU; formed again they are the same bits
+                double o[6] = {g.ox, g.oy, g.oz, g.dx, g.dy, g.dz};
+#pragma unroll
+                for (int e = 0; e < 6; ++e) asm volatile("" : "+v"(o[e]));
+                double Qx, Qy, Qz, tq;
+                const MonLocal lq = mon_local(mons[m], o[0], o[1], o[2], o[3], o[4], o[5]);
+                (void)mon_cross(mons[m], lq, lq.ox, g.len, Qx, Qy, Qz, tq);
+                inside = mon_wavefront_hit<true>(sp, g, lq, sp.axes + 6 * m, sp.reference + 3 * cell, sp.pupil + 3 * cell, sp.piston + cell, Qx, Qy, Qz, tq,
+                                                 n_index, pl, w, wi, Wp, p, q);
+            }
+            const unsigned long long bi = __ballot(inside), bo = __ballot(in && !inside);
+            double v = lane == 0 ? (double)__popcll(bi) : lane == 1 ? (double)__popcll(bo) : 0.0;
+            if (bi) mon_wavefront_sums(wi, Wp, p, q, lane, v);
+            if (lane < MON_WAVEFRONT_VALUES) mine[k * MON_WAVEFRONT_VALUES + lane] += v;
+        }
     }
 }
 // The group mode of k_mon_spots (ot_monitor_spot_groups_many): the spot statistics' partition, loads, hit test, coordinates,
@@ -1154,13 +1237,13 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_spots(const ot_monitor* __r
     // the wavefront mode walks the span in a loop of its own: one loop for both keeps the scalars of either alive through the
     // other, and the spot statistics' test of every slot against every plane pays for the spills
     const bool wavefront = sp.values == MON_WAVEFRONT_VALUES;  // (uniform for the launch)
-    for (int32_t it = 0; wavefront && span.has(it); ++it) {
+    // ... and so do the two group modes (below the spot statistics' loop), for the same reason
+    const bool grouped = sp.n_groups > 0;  // (uniform for the launch)
+    for (int32_t it = 0; wavefront && !grouped && span.has(it); ++it) {
         const int64_t s = span.at(it) + threadIdx.x;
         const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
         if (__ballot(g.valid)) mon_wavefront_visit(mons, src, g, s, sp, mine, lane);
     }
-    // ... and so does the group mode (below the spot statistics' loop), for the same reason
-    const bool grouped = sp.n_groups > 0;  // (uniform for the launch)
     for (int32_t it = 0; !wavefront && !grouped && span.has(it); ++it) {
         const int64_t s = span.at(it) + threadIdx.x;
         const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
@@ -1194,10 +1277,15 @@ __global__ __launch_bounds__(MON_THREADS) void k_mon_spots(const ot_monitor* __r
             }
         }
     }
-    for (int32_t it = 0; grouped && span.has(it); ++it) {
+    for (int32_t it = 0; !wavefront && grouped && span.has(it); ++it) {
         const int64_t s = span.at(it) + threadIdx.x;
         const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
         if (__ballot(g.valid)) mon_groups_visit(mons, src, g, s, sp, mine, lane);
+    }
+    for (int32_t it = 0; wavefront && grouped && span.has(it); ++it) {
+        const int64_t s = span.at(it) + threadIdx.x;
+        const MonSeg g = mon_load(src, s, n, seg_count, n_rays);
+        if (__ballot(g.valid)) mon_wavefront_groups_visit(mons, src, g, s, sp, mine, lane);
     }
     __syncthreads();
     double* row = sp.partials + (int64_t)blockIdx.x * nv;

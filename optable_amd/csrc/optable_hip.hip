@@ -1852,7 +1852,7 @@ int ot_fluence_map(ot_ctx* c, const double* axes, const double* u_edges, int32_t
     return 0;
 }
 
-// What the reductions of k_mon_spots (ot_monitor_spots_many, ot_monitor_spot_groups_many, ot_monitor_wavefront_many; misc_kernels.h) take alike, and what
+// What the reductions of k_mon_spots (ot_monitor_spots_many, ot_monitor_spot_groups_many, ot_monitor_wavefront_many, ot_monitor_wavefront_groups_many; misc_kernels.h) take alike, and what
 // they refuse of it alike: after their own NULL, size and enum refusals (a size before any array of that size is read), before
 // their own tables' and before anything is zeroed or launched.
 struct ReduceCall {
@@ -2002,6 +2002,44 @@ int ot_monitor_wavefront_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monit
     return reduce_call(a, {n_monitors, MON_WAVEFRONT_CELLS, MON_WAVEFRONT_VALUES, 2 * (size_t)n_monitors, MON_WAVEFRONT_SUMS * (size_t)n_monitors,
                            {{reference, 3 * (int64_t)n_monitors, &MonSpots::reference}, {pupil, 3 * (int64_t)n_monitors, &MonSpots::pupil},
                             {piston, n_monitors, &MonSpots::piston}}}, spots);
+}
+
+// Wavefront error per ray group: k_mon_spots in the wavefront mode's group mode, a cell per (monitor, group) of the list
+// [monitor][group], 63 doubles, MON_WAVEFRONT_CELLS consecutive cells a launch wherever they fall in a monitor
+// (optable_amd/engine.py wavefront_groups_plan); reference, pupil and piston are tables by cell.  `groups` stays on the device.
+int ot_monitor_wavefront_groups_many(ot_ctx* c, const ot_monitor* mons, int32_t n_monitors, const double* axes, int32_t reference_kind,
+                                     const double* reference, int32_t coordinates, const double* pupil, const double* piston,
+                                     const int32_t* groups, int64_t n_group_ids, int32_t n_groups, const ot_segment_source* src,
+                                     const void* intensity, const void* n_index, const void* pathlength, int64_t n, const int32_t* seg_count,
+                                     int64_t n_rays, int64_t* counts, double* sums, int32_t accumulate) {
+    if (!c || !mons || !axes || !reference || !pupil || !piston || !src || !n_index || !pathlength || !counts || !sums)
+        return fail(OT_ERR_INVALID, "NULL argument");
+    if (!groups) return fail(OT_ERR_INVALID, "NULL argument: groups");
+    if (n_monitors < 1 || n_monitors > 1 << 20) return fail(OT_ERR_INVALID, "n_monitors must be 1 .. 2^20");
+    if (n_groups < 1 || n_groups > OT_SPOT_GROUPS_MAX) return fail(OT_ERR_INVALID, "n_groups must be 1 .. 256");
+    if (n_group_ids < 1 || n_group_ids > INT32_MAX) return fail(OT_ERR_INVALID, "n_group_ids must be 1 .. 2^31 - 1");
+    const int64_t cells = (int64_t)n_monitors * n_groups;
+    if (cells > OT_WAVEFRONT_GROUP_CELLS_MAX) return fail(OT_ERR_INVALID, "n_monitors * n_groups exceeds 4096 cells");
+    if (reference_kind != 0 && reference_kind != 1) return fail(OT_ERR_INVALID, "reference_kind must be 0 (focus) or 1 (direction)");
+    if (coordinates != 0 && coordinates != 1) return fail(OT_ERR_INVALID, "coordinates must be 0 (direction) or 1 (position)");
+    const ReduceCall a{c, mons, n_monitors, axes, src, intensity, n, seg_count, n_rays, counts, sums, accumulate};
+    if (const int rc = check_reduce_call(a)) return rc;
+    if (src->width != 8) return fail(OT_ERR_INVALID, "a wavefront needs double-precision segments: width must be 8");
+    for (int64_t k = 0; k < cells; ++k) {
+        const double *r = reference + 3 * k, *p = pupil + 3 * k;
+        if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2])) return fail(OT_ERR_INVALID, "reference must be finite");
+        if (reference_kind == 1 && r[0] == 0.0 && r[1] == 0.0 && r[2] == 0.0) return fail(OT_ERR_INVALID, "the direction of a plane wave must not be zero");
+        if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) return fail(OT_ERR_INVALID, "pupil must be finite");
+        if (!(p[2] > 0.0)) return fail(OT_ERR_INVALID, "the pupil's radius must be positive");
+        if (!std::isfinite(piston[k])) return fail(OT_ERR_INVALID, "piston must be finite");
+    }
+    MonSpots spots{};
+    spots.n_off = 1;
+    spots.kind = reference_kind, spots.coordinates = coordinates;
+    spots.n_index = (const uint8_t*)n_index, spots.pathlength = (const uint8_t*)pathlength;
+    spots.groups = groups, spots.n_group_ids = (int32_t)n_group_ids, spots.n_groups = n_groups;
+    return reduce_call(a, {cells, MON_WAVEFRONT_CELLS, MON_WAVEFRONT_VALUES, 2 * (size_t)cells, MON_WAVEFRONT_SUMS * (size_t)cells,
+                           {{reference, 3 * cells, &MonSpots::reference}, {pupil, 3 * cells, &MonSpots::pupil}, {piston, cells, &MonSpots::piston}}}, spots);
 }
 
 // How the detector-image calls (ot_monitor_image_many / _field_many / _beam_many / _wave_many) walk n_monitors monitors of nby x nbz

@@ -217,6 +217,19 @@ def wavefront_plan(n_monitors):
     return _cell_plan(n_monitors, WAVEFRONT_MONITORS)
 
 
+# -- wavefront error per ray group (ot_monitor_wavefront_groups_many) ----------------------------------------------------------
+WAVEFRONT_GROUP_CELLS_MAX = 4096  # optable_hip.h OT_WAVEFRONT_GROUP_CELLS_MAX: n_monitors * n_groups of one call
+
+
+def wavefront_groups_plan(n_monitors, n_groups):
+    """How ot_monitor_wavefront_groups_many walks the cells (monitor m, group g) of the list [m][g]: `_cell_plan` with
+    WAVEFRONT_MONITORS consecutive cells a launch, wherever in a monitor they begin and end — ceil(M G / 28) passes."""
+    n_monitors, n_groups = int(n_monitors), int(n_groups)
+    if n_monitors < 1 or not 1 <= n_groups <= SPOT_GROUPS_MAX or n_monitors * n_groups > WAVEFRONT_GROUP_CELLS_MAX:
+        raise ValueError(f"no wavefront of {n_monitors} monitors x {n_groups} groups")
+    return _cell_plan(n_monitors * n_groups, WAVEFRONT_MONITORS)
+
+
 # -- diffraction PSF (ot_monitor_psf_many) -------------------------------------------------------------------------------------
 PSF_MAX_SAMPLES = 512             # optable_hip.h OT_PSF_MAX_SAMPLES: ny, nz of one call
 PSF_CHUNK_MIN = 512               # misc_kernels.h MON_PSF_CHUNK_MIN: hits of a chunk before a monitor gets another one
@@ -1091,6 +1104,34 @@ class Engine:
         return self._reduce_many("ot_monitor_wavefront_many", mons, tables, segs, weighted, ("n", "pathlength"),
                                  [(torch.int64, (M, 2)), (torch.float64, (M, WAVEFRONT_SUMS))], into,
                                  f"into: contiguous int64 counts of shape [{M}, 2] and float64 sums of shape [{M}, {WAVEFRONT_SUMS}] on {segs.device}")
+
+    def monitor_wavefront_groups_many(self, monitor_structs, axes, reference_kind, reference, coordinates, pupil, piston, groups, n_groups,
+                                      segs: SegmentBatch, weighted=True, into=None):
+        """The wavefront sums per ray group (ot_monitor_wavefront_groups_many): `monitor_wavefront_many` with a group axis — a hit
+        of a segment of input ray r belongs to group groups[r], and reference [M, G, 3], pupil [M, G, 3] and piston [M, G] are per
+        (monitor, group); axes stay [M, 6].  groups: a contiguous int32 vector on the segments' device, one id per input ray; ids
+        outside 0 .. n_groups - 1 (and rays beyond the table) are masked.  Returns (counts, sums): int64 [M, G, 2] and float64
+        [M, G, 61] device tensors, zeroed by the call — or `into`, such a pair from an earlier call, with this call's hits added
+        to it.  The sums are the same bits every run."""
+        with self.lock:
+            return self._monitor_wavefront_groups_many(list(monitor_structs), axes, reference_kind, reference, coordinates, pupil, piston, groups,
+                                                       int(n_groups), segs, weighted, into)
+
+    def _monitor_wavefront_groups_many(self, mons, axes, reference_kind, reference, coordinates, pupil, piston, groups, G, segs, weighted, into):
+        M = len(mons)
+        wavefront_groups_plan(max(M, 1), G)
+        axes, reference, pupil, piston = _float64_tables(f"axes must be [{M}, 6], reference and pupil [{M}, {G}, 3] and piston [{M}, {G}]", (axes, (M, 6)),
+                                                         (reference, (M, G, 3)), (pupil, (M, G, 3)), (piston, (M, G)))
+        if segs.precision != "f64":
+            raise ValueError("a wavefront needs double-precision segments")
+        if (not torch.is_tensor(groups) or groups.dtype != torch.int32 or groups.dim() != 1 or not groups.is_contiguous() or groups.numel() < 1
+                or groups.device.type != segs.device.type):
+            raise ValueError(f"groups: a contiguous int32 vector of one id per input ray on {segs.device}")
+        tables = (_doubles(axes), int(reference_kind), _doubles(reference), int(coordinates), _doubles(pupil), _doubles(piston), groups.data_ptr(),
+                  int(groups.numel()), G)
+        return self._reduce_many("ot_monitor_wavefront_groups_many", mons, tables, segs, weighted, ("n", "pathlength"),
+                                 [(torch.int64, (M, G, 2)), (torch.float64, (M, G, WAVEFRONT_SUMS))], into,
+                                 f"into: contiguous int64 counts of shape [{M}, {G}, 2] and float64 sums of shape [{M}, {G}, {WAVEFRONT_SUMS}] on {segs.device}")
 
     def monitor_psf_many(self, monitor_structs, axes, reference_kind, reference, grid, pixels, segs: SegmentBatch, wavelength, amplitude_mode=0,
                          into=None):

@@ -439,6 +439,77 @@ class OpticalTable:
         return self.wavefront_all(segs, focus=focus, direction=direction, pupil=pupil, coordinates=coordinates, monitors=[monitor], weight=weight,
                                   piston=piston)[0]
 
+    def wavefront_grouped_all(self, segs, groups, n_groups=None, focus=None, direction=None, pupil=None, coordinates=None, monitors=None,
+                              weight="intensity", piston=None, into=None, labels=None):
+        """`wavefront_all` PER RAY GROUP: one `MonitorWavefrontGroups` per monitor, in their order — the 61 sums, and so the Zernike
+        fit, the rms wavefront error and Marechal's Strehl ratio, of every group of input rays from one trace
+        (ot_monitor_wavefront_groups_many): each colour's defocus from a batch multiplexed in wavelength, each field point's coma and
+        astigmatism from one multiplexed in field.  groups, n_groups (G, 1 .. 256, with monitors x G <= 4096) and labels as for
+        `spots_grouped_all`: one integer id per INPUT ray, a hit belongs to the group of the ray its segment descends from, ids
+        outside 0 .. G - 1 are in no group and in no tally (-1 masks a ray).  Every field point has its own image point and pupil
+        centre, so `focus` / `direction`, `pupil` and `piston` are taken PER (monitor, group), each in one of these shapes: one for
+        all; one per monitor [M, ...]; one per group [G, ...] — only when M != G: a shape that could be either is read as per
+        MONITOR; or [M, G, ...].  coordinates, weight and the meaning of every argument as for `wavefront_all`; `piston=None` is
+        its two-call scheme per cell (the mean of W of every (monitor, group), 0 for an empty one).  A call is ceil(M G / 28) passes
+        over the segments.  Counts are exact and the sums the same bits every run; group g equals `wavefront_all` over the rays of
+        group g alone with that group's reference, pupil and piston, bit for bit.  `into`: the list an earlier call with the same
+        monitors, G, references, pupils, coordinates and weight returned; this call's hits are added to it with ITS pistons and
+        this call's `groups` (the chunks of a streamed trace each bring their own table).  `segs` must be double precision."""
+        from .spots import spot_group_ids
+        from .wavefront import (COORDINATES, MonitorWavefrontGroups, wavefront_coordinates, wavefront_group_piston, wavefront_group_pupil,
+                                wavefront_group_reference)
+
+        check_weight(weight)
+        monitors = list(self.monitors if monitors is None else monitors)
+        M = len(monitors)
+        ids, G = spot_group_ids(groups, segs.n_rays, n_groups, device=segs.device)
+        if labels is not None and len(labels) != G:
+            raise ValueError(f"labels: one per group ({G}), not {len(labels)}")
+        if M:
+            from .engine import wavefront_groups_plan
+
+            wavefront_groups_plan(M, G)
+        kind, lab, local = wavefront_group_reference(focus, direction, monitors, G)
+        pupils, coords = wavefront_group_pupil(pupil, kind, monitors, G), wavefront_coordinates(coordinates, kind)
+        pistons = None if piston is None else wavefront_group_piston(piston, M, G)
+        if segs.precision != "f64":
+            raise ValueError("wavefront_all needs a double-precision SegmentBatch: a path length in single precision is a hundredth of a wave wrong at table scale")
+        name = ("focus", "direction")[kind]
+        stack = None
+        if into is not None:
+            into, stack = _into_stack(into, M, lambda k, wf: isinstance(wf, MonitorWavefrontGroups) and wf.monitor is monitors[k] and wf.weight == weight
+                                      and wf.n_groups == G and wf.reference[0] == name and np.array_equal(wf.reference[1], lab[k])
+                                      and np.array_equal(wf.pupil, pupils[k]) and wf.coordinates == COORDINATES[coords],
+                                      "into: the list an earlier wavefront_grouped_all returned for the same monitors, n_groups, references, pupils, coordinates and weight")
+            if pistons is not None and any(not np.array_equal(wf.piston, row) for wf, row in zip(into, pistons)):
+                raise ValueError("into: piston must be None or the pistons of the earlier call")
+            if not monitors:
+                return into
+            pistons = np.ascontiguousarray(np.array([wf.piston for wf in into], dtype=np.float64).reshape(M, G))
+        axes, structs = _monitor_axes(monitors), [monitor_struct(m) for m in monitors]
+
+        def reduce(p, out):
+            return _engine().monitor_wavefront_groups_many(structs, axes, kind, local, coords, pupils, p, ids, G, segs, weighted=weight == "intensity",
+                                                           into=out)
+
+        if pistons is None:  # the mean of W of every cell with piston 0, then the sums about it
+            _, first = reduce(np.zeros((M, G)), None)
+            first = first.cpu().numpy()
+            with np.errstate(all="ignore"):
+                pistons = np.where(first[..., 0] != 0.0, first[..., 45] / first[..., 0], 0.0)
+            pistons = np.ascontiguousarray(np.where(np.isfinite(pistons), pistons, 0.0)).reshape(M, G)
+        counts, sums = reduce(pistons, stack)
+        if into is None:
+            into = [MonitorWavefrontGroups(m, counts[k, :, 0], counts[k, :, 1], sums[k], (name, lab[k]), pupils[k], COORDINATES[coords], pistons[k], weight,
+                                           labels=labels, stack=(counts, sums, k)) for k, m in enumerate(monitors)]
+        return into
+
+    def wavefront_grouped_batch(self, monitor, segs, groups, n_groups=None, focus=None, direction=None, pupil=None, coordinates=None,
+                                weight="intensity", piston=None, labels=None):
+        """One monitor as a wavefront per ray group (`wavefront_grouped_all` for it alone): a `MonitorWavefrontGroups`."""
+        return self.wavefront_grouped_all(segs, groups, n_groups=n_groups, focus=focus, direction=direction, pupil=pupil, coordinates=coordinates,
+                                          monitors=[monitor], weight=weight, piston=piston, labels=labels)[0]
+
     def psf_all(self, segs, wavelength, focus=None, direction=None, step=None, pixels=65, centre=(0.0, 0.0), monitors=None, amplitude="sqrt",
                 into=None):
         """Every monitor of the table (or those given) as a DIFFRACTION IMAGE: one `MonitorPSF` per monitor, in their order — the

@@ -154,6 +154,73 @@ def wavefront_piston(piston, n_monitors):
     return np.ascontiguousarray(piston)
 
 
+# -- the same arguments per (monitor, group): OpticalTable.wavefront_grouped_all ------------------------------------------------------
+def _cells(value, n_monitors, n_groups, width, what):
+    """`value` as a finite [n_monitors, n_groups, width] float64 table (width 0: [n_monitors, n_groups] of numbers): one entry for
+    all cells, one per monitor [M, ...], one per group [G, ...] — only when M != G: an ambiguous shape is read as per monitor —
+    or one per cell [M, G, ...]."""
+    M, G, tail = n_monitors, n_groups, ((width,) if width else ())
+    entry = f"{width} finite numbers" if width else "a finite number"
+    error = f"{what} must be {entry}: one for all, one per monitor ({M}), one per group ({G}) or [{M}, {G}], not "
+    try:
+        value = np.asarray(value, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(error + repr(value)) from None
+    if value.shape == tail:
+        table = np.broadcast_to(value, (M, G) + tail)
+    elif value.shape == (M,) + tail:
+        table = np.broadcast_to(value.reshape((M, 1) + tail), (M, G) + tail)
+    elif value.shape == (G,) + tail:
+        table = np.broadcast_to(value.reshape((1, G) + tail), (M, G) + tail)
+    elif value.shape == (M, G) + tail:
+        table = value
+    else:
+        raise ValueError(error + f"of shape {value.shape}")
+    if not np.isfinite(table).all():
+        raise ValueError(error + repr(value))
+    return np.ascontiguousarray(table)
+
+
+def wavefront_group_reference(focus, direction, monitors, n_groups):
+    """`wavefront_reference` per (monitor, group): (reference_kind, lab [M, G, 3], local [M, G, 3]).  `focus` / `direction`: one
+    for all, one per monitor [M, 3], one per group [G, 3] (when M == G a [M, 3] table is read as per MONITOR) or [M, G, 3]."""
+    if (focus is None) == (direction is None):
+        raise ValueError("exactly one of focus= (a point) or direction= (a vector) says what the wavefront is measured against")
+    M, G = len(monitors), int(n_groups)
+    kind = 0 if focus is not None else 1
+    lab = _cells(focus if kind == 0 else direction, M, G, 3, ("focus", "direction")[kind])
+    if kind == 1:
+        norm = np.sqrt((lab * lab).sum(axis=-1))
+        if not (norm > 0.0).all() or not np.isfinite(norm).all():
+            raise ValueError(f"direction must not be zero, not {direction!r}")
+        lab = lab / norm[..., None]
+    local = np.empty((M, G, 3))
+    for k, m in enumerate(monitors):
+        R, origin = local_frame(m)
+        for g in range(G):  # (the expressions of wavefront_reference: the same bits for the same vector)
+            local[k, g] = R.T @ (lab[k, g] - origin) if kind == 0 else R.T @ lab[k, g]
+    return kind, np.ascontiguousarray(lab), np.ascontiguousarray(local)
+
+
+def wavefront_group_pupil(pupil, kind, monitors, n_groups):
+    """`wavefront_pupil` per (monitor, group): [M, G, 3] (c_y, c_z, R), R > 0, in the shapes of `wavefront_group_reference`; None
+    with a direction: (0, 0, min(width, height) / 2) of every monitor, for all its groups."""
+    M, G = len(monitors), int(n_groups)
+    if pupil is None:
+        if kind == 0:
+            raise ValueError("pupil=(c_y, c_z, R) is required with focus=: the direction coordinates have no natural extent")
+        pupil = np.array([(0.0, 0.0, min(m.width, m.height) / 2) for m in monitors], dtype=np.float64).reshape(M, 1, 3).repeat(G, axis=1)
+    pupil = _cells(pupil, M, G, 3, "pupil")
+    if not (pupil[..., 2] > 0.0).all():
+        raise ValueError(f"the pupil's radius must be positive, not {pupil[..., 2]!r}")
+    return pupil
+
+
+def wavefront_group_piston(piston, n_monitors, n_groups):
+    """`wavefront_piston` per (monitor, group): [M, G] finite doubles from a number, [M], [G] (read as per monitor when M == G) or [M, G]."""
+    return _cells(piston, n_monitors, int(n_groups), 0, "piston")
+
+
 def hit_wavefront(kind, local, P, t, d, n_index, pathlength):
     """The header's W of hits, hit by hit (torch or numpy alike): P [h, 3] the local hit points, t [h] the distances, d [h, 3] the
     renormalised local directions, n_index and pathlength [h] of the hits' segments; `local` the three numbers of the reference."""
@@ -243,3 +310,77 @@ class MonitorWavefront:
     def to_host(self):
         """(inside, outside, sums): two ints and the 61 sums as a numpy array."""
         return int(self.counts), int(self.outside), self.sums.detach().cpu().numpy()
+
+
+class MonitorWavefrontGroups:
+    """The hits of one monitor as a wavefront per RAY GROUP (`OpticalTable.wavefront_grouped_all`): `counts` and `outside` (int64,
+    [G]) and `sums` (float64, [G, 61]) are device tensors; `n_groups` = G; `labels`: what the groups stand for, one per group (the
+    wavelengths, say), or None.  Every group has its own ideal wave and pupil: `reference` = ("focus" | "direction", the lab
+    vectors [G, 3]), `pupil` [G, 3] (c_y, c_z, R) and `piston` [G] are numpy arrays; `coordinates` and `weight` as for
+    `MonitorWavefront`.  A hit belongs to the group of the input ray its segment descends from; rays whose id is outside
+    0 .. G - 1 are in no group and in no tally.  `group(g)` is a `MonitorWavefront` on views of group g, and every fit here is that
+    class's, group by group; `strehl` is Marechal's approximation per group — wavefronts of different wavelengths are not
+    combined into one (the polychromatic image is `psf_grouped_all`'s)."""
+
+    def __init__(self, monitor, counts, outside, sums, reference, pupil, coordinates, piston, weight, labels=None, stack=None):
+        self.monitor, self.counts, self.outside, self.sums, self.weight, self.coordinates = monitor, counts, outside, sums, weight, coordinates
+        self.n_groups = int(sums.shape[0])
+        G = self.n_groups
+        self.reference = (reference[0], np.array(reference[1], dtype=np.float64).reshape(G, 3))
+        self.pupil, self.piston = np.array(pupil, dtype=np.float64).reshape(G, 3), np.array(piston, dtype=np.float64).reshape(G)
+        self.labels = None if labels is None else list(labels)
+        if self.labels is not None and len(self.labels) != G:
+            raise ValueError(f"labels: one per group ({G}), not {len(self.labels)}")
+        self._stack = stack  # (counts, sums of the whole call, this monitor's place in it): what `into=` adds to
+
+    def group(self, g):
+        """Group g as a `MonitorWavefront` (views: an `into=` call that adds to this object shows there too)."""
+        g = int(g)
+        if not 0 <= g < self.n_groups:
+            raise IndexError(f"group {g} of {self.n_groups}")
+        return MonitorWavefront(self.monitor, self.counts[g], self.outside[g], self.sums[g], (self.reference[0], self.reference[1][g]), self.pupil[g],
+                                self.coordinates, self.piston[g], self.weight)
+
+    def _each(self, what):
+        import torch
+
+        return torch.stack([what(self.group(g)) for g in range(self.n_groups)])
+
+    def power(self):
+        """S[0, 0] of every group ([G])."""
+        return self.sums[:, 0]
+
+    def mean(self):
+        """The weighted mean of W over every group's pupil ([G]), NaN for a group without a hit inside."""
+        return self._each(lambda wf: wf.mean())
+
+    def coefficients(self, terms=TERMS):
+        """`MonitorWavefront.coefficients` of every group: [G, terms], NaN rows where a group's fit is not determined."""
+        return self._each(lambda wf: wf.coefficients(terms))
+
+    def rms(self, terms=1):
+        """`MonitorWavefront.rms` of every group: [G]."""
+        return self._each(lambda wf: wf.rms(terms))
+
+    def strehl(self, wavelength=None, terms=1):
+        """Marechal's Strehl ratio of every group ([G]).  wavelength: a number for all groups, one per group, or None: `labels` are
+        the groups' wavelengths (ValueError if there are none)."""
+        import torch
+
+        if wavelength is None:
+            if self.labels is None:
+                raise ValueError("strehl: wavelength=None takes the groups' labels as their wavelengths, and this result has none")
+            wavelength = self.labels
+        try:
+            lam = np.asarray(wavelength, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"strehl: wavelength must be a number, one per group or None, not {wavelength!r}") from None
+        if lam.ndim == 0:
+            lam = np.full(self.n_groups, float(lam))
+        if lam.shape != (self.n_groups,) or not (np.isfinite(lam) & (lam > 0)).all():
+            raise ValueError(f"strehl: {self.n_groups} finite wavelengths > 0, not {wavelength!r}")
+        return torch.exp(-((2.0 * math.pi / torch.as_tensor(lam, device=self.sums.device)) * self.rms(terms)) ** 2)
+
+    def to_host(self):
+        """(inside, outside, sums): int64 [G] twice and the sums [G, 61], numpy arrays."""
+        return self.counts.cpu().numpy(), self.outside.cpu().numpy(), self.sums.detach().cpu().numpy()
